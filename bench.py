@@ -73,7 +73,12 @@ def parse():
     ap.add_argument("--curve", default="bn254")
     ap.add_argument("--partition", default=os.environ.get("GA_BENCH_PARTITION", "range"), choices=["range", "window"],
                     help="N > 1 Groth16 leg: key sharded by base-point range (partition B) or by scalar windows (partition A, config 4's wording)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the headline MSM's last step returned to DIR/<name>.npy (float64; see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def effective_cores():
@@ -398,6 +403,18 @@ def timed_msm(R, cid, group, n_total, lo, cnt, seed_bases, seed_scalars, steps, 
     res = {"ms_per_step": elapsed * 1e3 / steps, "elapsed_s": elapsed, "value_checked": checked, "stages": stages, "result": result,
            "window_bits": cbits, "windows": nwin, "table_info": ti, "pairs_this_rank": cnt}
     return res, keep
+
+
+def dump_outputs(R, cid, group, res, out_dir):
+    """--dump-outputs DIR: the point the last timed step returned, so that two builds can be compared output for output (the inputs
+    come from fixed seeds).  A Jacobian result is one representative of the sum, not a fixed one (include/gnark_amd.h), so the file
+    holds the affine point a caller gets from it (ga_jac_to_affine: gnark-crypto's Montgomery image, bit-identical across builds and
+    devices): msm_result_affine.npy, the little-endian 64-bit limbs of x then y split into 16-bit pieces -- exact in float64."""
+    from gnark_amd import ecc
+    aff = np.ascontiguousarray(ecc.jac_to_affine(cid, group, res["result"], lib=R.lib), dtype="<u8")
+    pieces = aff.view("<u2").astype(np.float64).reshape(2, -1)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "msm_result_affine.npy"), pieces)
 
 
 def free_keep(keep):
@@ -1325,6 +1342,8 @@ def main():
         out["ranks"] = ranks
     if kept is not None:
         keep, res = kept
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(R, cid, 0, res, args.dump_outputs)
         if rank == 0 and world == 1 and not args.only_headline:
             try:
                 single_gpu_msm_extras(R, out, keep, res)

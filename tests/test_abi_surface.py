@@ -148,25 +148,31 @@ def test_plonk_call_pattern_against_the_emulation_build(tmp_path, emu_lib, curve
     assert r.returncode == 0 and "PLONK_PATTERN_OK" in r.stdout, r.stdout + r.stderr
 
 
+def reference_index():
+    """tools/check_go_idents.py resolving against tests/golden/reference_go_index.json, the committed index of the reference tree"""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import check_go_idents
+    check_go_idents.REF = check_go_idents.IndexReference(check_go_idents.INDEX)
+    return check_go_idents
+
+
 @pytest.mark.parametrize("curve", ["bn254", "bls12-381"])
-def test_plonk_prover_patch_applies_to_the_reference(tmp_path, curve):
+def test_plonk_prover_patch_applies_to_the_reference(curve):
     """go/backend/accelerated/mi355x/plonk/<curve>/prove.patch (the Accelerator hooks wired into backend/plonk/<curve>/prove.go)
-    applies cleanly to the reference's file -- the call sites it names exist as quoted"""
-    import shutil
-    import subprocess
-    ref = "/root/reference/backend/plonk/%s/prove.go" % curve
-    if not os.path.exists(ref):
-        pytest.skip("reference tree not present on this box")
-    shutil.copy(ref, tmp_path / "prove.go")
+    applies cleanly to the reference's file -- every hunk's old lines are the reference's, at the line it names (the committed index
+    holds their SHA-256)"""
+    cgi = reference_index()
     patch = os.path.join(ROOT, "go", "backend", "accelerated", "mi355x", "plonk", curve, "prove.patch")
-    r = subprocess.run(["patch", "-p4", "--dry-run", "-i", patch], cwd=tmp_path, capture_output=True, text=True)
-    assert r.returncode == 0 and "FAILED" not in r.stdout, r.stdout + r.stderr
+    hunks = cgi.patch_hunks(patch)
+    assert len(hunks) == 13 and {h[0] for h in hunks} == {"backend/plonk/%s/prove.go" % curve}
+    assert cgi.check_patch(patch) == []
     src = open(patch).read()
     for hook in ("CommitLagrangeBatch", "CommitBatch", "BuildRatioCopyConstraint", "ComputeQuotientRaw", "s.acc.Open(", "LinearCombination"):
         assert hook in src, hook
 
 
-def test_go_shim_identifiers_resolve():
+def test_go_shim_identifiers_resolve(tmp_path):
     """tools/check_go_idents.py: every `pkg.Ident` of go/** is declared in the reference package it is imported from (or, for the
     gnark-crypto dependency that is not in the tree, used by the reference under the same import path), and every `C.ga_*` call
     matches a prototype of include/gnark_amd.h argument count included.  The Go side has never met a compiler (no toolchain in the
@@ -176,10 +182,8 @@ def test_go_shim_identifiers_resolve():
     import sys
     table = json.load(open(os.path.join(ROOT, "go", "IDENTS.json")))
     assert table["unresolved"] == [] and len(table["resolved"]) > 200
-    if not os.path.isdir("/root/reference"):
-        pytest.skip("reference tree not present on this box: the committed go/IDENTS.json stands")
-    out = os.path.join(ROOT, "tests", "emu", "build", "idents_check.json")
-    os.makedirs(os.path.dirname(out), exist_ok=True)
+    # against tests/golden/reference_go_index.json, what the check reads of the reference tree (--reference DIR reads the tree itself)
+    out = str(tmp_path / "idents_check.json")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_go_idents.py"), "--json", out], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout[-3000:]
     fresh = json.load(open(out))
@@ -187,22 +191,17 @@ def test_go_shim_identifiers_resolve():
 
 
 @pytest.mark.parametrize("curve", ["bn254", "bls12-381"])
-def test_groth16_randomness_hook_patch_applies_to_the_reference(tmp_path, curve):
+def test_groth16_randomness_hook_patch_applies_to_the_reference(curve):
     """go/backend/accelerated/mi355x/internal/fixtures/groth16_rs_<curve>.patch -- the test-only hook that lets gnark's own CPU prover
     take (r, s) and show its solution, so that gen_fixtures_test.go can write golden directories (tests/gnark_fixture.py) -- applies
-    cleanly to backend/groth16/<curve>/prove.go: the lines it names (prove.go:105,171-177) exist as quoted"""
-    import shutil
-    import subprocess
-    ref = "/root/reference/backend/groth16/%s/prove.go" % curve
-    if not os.path.exists(ref):
-        pytest.skip("reference tree not present on this box")
-    dst = tmp_path / "backend" / "groth16" / curve
-    dst.mkdir(parents=True)
-    shutil.copy(ref, dst / "prove.go")
+    cleanly to backend/groth16/<curve>/prove.go: the lines it names (prove.go:105,171-177) exist as quoted (the committed index holds
+    the SHA-256 of the reference's lines every hunk replaces)"""
+    cgi = reference_index()
     fx = os.path.join(ROOT, "go", "backend", "accelerated", "mi355x", "internal", "fixtures")
     patch = os.path.join(fx, "groth16_rs_%s.patch" % curve)
-    r = subprocess.run(["patch", "-p1", "--dry-run", "-i", patch], cwd=tmp_path, capture_output=True, text=True)
-    assert r.returncode == 0 and "FAILED" not in r.stdout, r.stdout + r.stderr
+    hunks = cgi.patch_hunks(patch)
+    assert len(hunks) == 3 and {h[0] for h in hunks} == {"backend/groth16/%s/prove.go" % curve}
+    assert cgi.check_patch(patch) == []
     src = open(patch).read()
     assert "TestingHooks.Randomness" in src and "TestingHooks.Solution(solution)" in src and "SetRandom" in src
     gen = open(os.path.join(fx, "gen_fixtures_test.go")).read()

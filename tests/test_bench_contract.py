@@ -153,6 +153,27 @@ def test_plain_gpus_2_launches_two_ranks(env):
     assert "torch.distributed.run" in r.stderr
 
 
+def test_dump_outputs(env, tmp_path):
+    """--dump-outputs DIR: the affine point the headline MSM's last timed step returned, float64 16-bit pieces of its limbs, the same
+    whatever --steps / --warmup say (fixed seeds: same inputs, same point), and the point the oracle check accepted"""
+    import numpy as np
+    got = []
+    for steps, warmup in (("1", "0"), ("3", "1")):
+        d = str(tmp_path / ("dump_%s" % steps))
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--log-n", "8", "--steps", steps, "--warmup", warmup, "--only-headline",
+                            "--dump-outputs", d], capture_output=True, text=True, env=env, cwd=ROOT, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = _line(r.stdout)
+        assert line["steps"] == int(steps) and line["value_checked"] is True
+        assert os.listdir(d) == ["msm_result_affine.npy"]
+        a = np.load(os.path.join(d, "msm_result_affine.npy"))
+        assert a.dtype == np.float64 and a.shape == (2, 16) and (a >= 0).all() and (a < 65536).all() and (a == np.round(a)).all() and a.any()
+        got.append(a)
+    assert np.array_equal(got[0], got[1])
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--log-n", "8", "--steps", "0"], capture_output=True, text=True, env=env, cwd=ROOT, timeout=120)
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
 def test_world_size_mismatch_is_an_error(env):
     """--gpus is the world the line is ABOUT: a launcher world that disagrees is refused, loudly, with a one-line JSON error and a
     non-zero exit code -- never a silent measurement of another world"""

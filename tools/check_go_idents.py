@@ -3,8 +3,8 @@
 
 For every `alias.Ident` in a .go file whose alias is an import of
   * github.com/consensys/gnark/<path>     -> the identifier must be DECLARED (func / type / const / var, exported) in a non-test
-                                             .go file of /root/reference/<path>, or of go/<path> for the shim's own packages;
-  * github.com/consensys/gnark-crypto/... -> the module is not in /root/reference (go.mod dependency): the same `pkg.Ident`
+                                             .go file of the reference's <path>, or of go/<path> for the shim's own packages;
+  * github.com/consensys/gnark-crypto/... -> the module is not in the reference (go.mod dependency): the same `pkg.Ident`
                                              must be USED somewhere in the reference with the same import path (gnark itself
                                              compiles against it, so the name exists in the pinned version);
   * the standard library                   -> checked against a small allow-list of the packages the shim uses;
@@ -12,18 +12,26 @@ For every `alias.Ident` in a .go file whose alias is an import of
                                              arguments at the call site; `C.GA_*` must be a #define of the header; a handful of
                                              cgo built-ins (C.int, C.GoString, ...) are allowed.
 Methods and struct fields (x.Method() on values) are out of reach of a textual check and are not claimed.
+Every hunk of a patch shipped under go/** (prove.patch, internal/fixtures/groth16_rs_*.patch) must also find the lines it replaces
+exactly where it says, in the reference file it names: the patch applies without offset or fuzz.
 
-  python tools/check_go_idents.py            # prints a report, exit code 1 on any unresolved identifier
+"The reference" is the gnark source tree go/** is written against.  With `--reference DIR` the check reads that tree; without it, it
+reads tests/golden/reference_go_index.json, the part of the tree the check needs (package names, the exported declarations of the
+packages the shim imports, the gnark-crypto identifiers the tree uses, a SHA-256 of the lines every patch hunk replaces), which
+`--reference DIR --write-index tests/golden/reference_go_index.json` regenerates.
+
+  python tools/check_go_idents.py            # prints a report, exit code 1 on any unresolved identifier or stale patch hunk
   python tools/check_go_idents.py --json go/IDENTS.json   # also writes the resolved table (committed, reviewed by the test)
 """
 import argparse
+import hashlib
 import json
 import os
 import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
+INDEX = os.path.join(ROOT, "tests", "golden", "reference_go_index.json")
 GNARK = "github.com/consensys/gnark/"
 CRYPTO = "github.com/consensys/gnark-crypto/"
 SHIM_PREFIX = "backend/accelerated/mi355x"
@@ -83,19 +91,23 @@ def default_alias(path):
     d = None
     if path.startswith(GNARK):
         rel = path[len(GNARK):]
-        for base in (os.path.join(ROOT, "go"), REF):
-            if os.path.isdir(os.path.join(base, rel)):
-                d = os.path.join(base, rel)
-                break
+        if os.path.isdir(os.path.join(ROOT, "go", rel)):
+            d = os.path.join(ROOT, "go", rel)
+        elif REF.package_name(rel):
+            name = REF.package_name(rel)
     if d:
-        for f in sorted(os.listdir(d)):
-            if f.endswith(".go") and not f.endswith("_test.go"):
-                m = re.search(r"^package\s+(\w+)", open(os.path.join(d, f)).read(), flags=re.M)
-                if m:
-                    name = m.group(1)
-                    break
+        name = package_clause(d) or name
     _PKG_NAME_CACHE[path] = name
     return name
+
+
+def package_clause(d):
+    for f in sorted(os.listdir(d)):
+        if f.endswith(".go") and not f.endswith("_test.go"):
+            m = re.search(r"^package\s+(\w+)", open(os.path.join(d, f)).read(), flags=re.M)
+            if m:
+                return m.group(1)
+    return None
 
 
 _DECL_CACHE = {}
@@ -140,31 +152,133 @@ def declared_by_patches():
     return out
 
 
-_REF_USE_CACHE = {}
-
-
 def used_in_reference(import_path, ident):
     """is `<alias>.<ident>` used in a reference file that imports import_path (under whatever alias)?"""
-    key = import_path
-    if key not in _REF_USE_CACHE:
-        uses = set()
-        for f in go_files(REF):
-            try:
-                raw = open(f).read()
-            except OSError:
-                continue
-            if '"%s"' % import_path not in raw:
-                continue
-            src = strip_comments_and_strings_keep_imports(raw)
-            for alias, path in imports_of(raw).items():
-                if path == import_path:
-                    uses |= set(re.findall(r"\b%s\.([A-Z]\w*)" % re.escape(alias), src))
-        _REF_USE_CACHE[key] = uses
-    return ident in _REF_USE_CACHE[key]
+    return ident in REF.crypto_uses(import_path)
 
 
-def strip_comments_and_strings_keep_imports(raw):
-    return strip_comments_and_strings(raw)
+def patch_hunks(path):
+    """(target file, old start line, old line count, the old lines) of every hunk of a unified diff"""
+    out, target, lines = [], None, open(path).read().split("\n")
+    i = 0
+    while i < len(lines):
+        ln = lines[i]
+        if ln.startswith("--- "):
+            target = re.sub(r"^a/", "", ln[4:].split("\t")[0].strip())
+        m = re.match(r"@@ -(\d+)(?:,(\d+))? \+\d+(?:,\d+)? @@", ln)
+        if m:
+            start, count = int(m.group(1)), int(m.group(2) or "1")
+            old, j = [], i + 1
+            while len(old) < count and j < len(lines):
+                if lines[j][:1] in (" ", "-"):
+                    old.append(lines[j][1:])
+                elif lines[j][:1] != "+" and not lines[j].startswith("\\"):
+                    break
+                j += 1
+            out.append((target, start, count, old))
+            i = j
+            continue
+        i += 1
+    return out
+
+
+def text_sha(lines):
+    return hashlib.sha256("\n".join(lines).encode()).hexdigest()
+
+
+class TreeReference:
+    """the reference source tree itself; records what it was asked, which is the index (write_index)"""
+
+    def __init__(self, top):
+        self.top = top
+        self.names, self.decls, self.uses, self.hunks = {}, {}, {}, {}
+
+    def package_name(self, rel):
+        if rel not in self.names:
+            d = os.path.join(self.top, rel)
+            self.names[rel] = package_clause(d) if os.path.isdir(d) else None
+        return self.names[rel]
+
+    def declared(self, pkg):
+        if pkg not in self.decls:
+            self.decls[pkg] = declared_in(os.path.join(self.top, pkg))
+        return self.decls[pkg]
+
+    def crypto_uses(self, import_path):
+        if import_path not in self.uses:
+            uses = set()
+            for f in go_files(self.top):
+                try:
+                    raw = open(f).read()
+                except OSError:
+                    continue
+                if '"%s"' % import_path not in raw:
+                    continue
+                src = strip_comments_and_strings(raw)
+                for alias, path in imports_of(raw).items():
+                    if path == import_path:
+                        uses |= set(re.findall(r"\b%s\.([A-Z]\w*)" % re.escape(alias), src))
+            self.uses[import_path] = uses
+        return self.uses[import_path]
+
+    def hunk_sha(self, target, start, count):
+        """SHA-256 of lines [start, start + count) of the reference file `target` (None if the file is missing or too short)"""
+        key = "%s:%d,%d" % (target, start, count)
+        if key not in self.hunks:
+            f = os.path.join(self.top, target)
+            lines = open(f).read().split("\n") if os.path.isfile(f) else []
+            self.hunks[key] = text_sha(lines[start - 1:start - 1 + count]) if start - 1 + count <= len(lines) else None
+        return self.hunks[key]
+
+    def write_index(self, path):
+        idx = {"package_names": {k: v for k, v in sorted(self.names.items()) if v},
+               "declared": {k: sorted(v) for k, v in sorted(self.decls.items())},
+               "crypto_uses": {k: sorted(v) for k, v in sorted(self.uses.items())},
+               "patch_hunk_sha256": {k: v for k, v in sorted(self.hunks.items()) if v}}
+        with open(path, "w") as f:
+            json.dump(idx, f, indent=0, sort_keys=True)
+            f.write("\n")
+
+
+class IndexReference:
+    """the committed index of the reference tree (tests/golden/reference_go_index.json)"""
+
+    def __init__(self, path):
+        idx = json.load(open(path))
+        self.names, self.hunks = idx["package_names"], idx["patch_hunk_sha256"]
+        self.decls = {k: set(v) for k, v in idx["declared"].items()}
+        self.uses = {k: set(v) for k, v in idx["crypto_uses"].items()}
+
+    def package_name(self, rel):
+        return self.names.get(rel)
+
+    def declared(self, pkg):
+        return self.decls.get(pkg, set())
+
+    def crypto_uses(self, import_path):
+        return self.uses.get(import_path, set())
+
+    def hunk_sha(self, target, start, count):
+        return self.hunks.get("%s:%d,%d" % (target, start, count))
+
+
+REF = None
+
+
+def check_patch(path):
+    """the hunks of one patch whose replaced lines are not where the hunk says in the reference: [(hunk header, reason)]"""
+    bad = []
+    for target, start, count, old in patch_hunks(path):
+        where = "%s @@ -%d,%d" % (target, start, count)
+        if len(old) != count:
+            bad.append((where, "the hunk holds %d old lines, its header says %d" % (len(old), count)))
+            continue
+        want = REF.hunk_sha(target, start, count)
+        if want is None:
+            bad.append((where, "the reference has no such lines"))
+        elif text_sha(old) != want:
+            bad.append((where, "the lines the hunk replaces differ from the reference's"))
+    return bad
 
 
 def header_symbols():
@@ -201,10 +315,19 @@ def call_arity(src, pos):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--json")
+    ap.add_argument("--reference", metavar="DIR", help="the gnark source tree to resolve against (default: the committed index)")
+    ap.add_argument("--write-index", metavar="FILE", help="with --reference: write what the check read from the tree (the committed index)")
     args = ap.parse_args()
-    if not os.path.isdir(REF):
-        print("reference tree not present at %s: nothing to resolve against" % REF)
-        return 2
+    global REF
+    if args.reference:
+        if not os.path.isdir(args.reference):
+            print("reference tree not present at %s: nothing to resolve against" % args.reference)
+            return 2
+        REF = TreeReference(args.reference)
+    elif args.write_index:
+        ap.error("--write-index needs --reference")
+    else:
+        REF = IndexReference(INDEX)
     protos, defines, ctypes = header_symbols()
     patched = declared_by_patches()
     table, bad = [], []
@@ -238,13 +361,15 @@ def main():
             for ident in sorted(idents):
                 if path.startswith(GNARK):
                     pkg = path[len(GNARK):]
-                    d = os.path.join(ROOT, "go", pkg) if pkg.startswith(SHIM_PREFIX) else os.path.join(REF, pkg)
-                    if ident in declared_in(d):
-                        table.append((rel, "%s.%s" % (alias, ident), "declared in %s" % os.path.relpath(d, "/")))
+                    shim = pkg.startswith(SHIM_PREFIX)
+                    if ident in (declared_in(os.path.join(ROOT, "go", pkg)) if shim else REF.declared(pkg)):
+                        # named relative to its tree, so that the table does not depend on where either tree is checked out
+                        where = "go/" + pkg if shim else "the reference's " + pkg
+                        table.append((rel, "%s.%s" % (alias, ident), "declared in %s" % where))
                     elif ident in patched.get(pkg, {}):
                         table.append((rel, "%s.%s" % (alias, ident), "added to %s by %s" % (pkg, patched[pkg][ident])))
                     else:
-                        bad.append((rel, "%s.%s" % (alias, ident), "not declared in %s" % d))
+                        bad.append((rel, "%s.%s" % (alias, ident), "not declared in %s" % ("go/" + pkg if shim else "the reference's " + pkg)))
                 elif path.startswith(CRYPTO):
                     if used_in_reference(path, ident):
                         table.append((rel, "%s.%s" % (alias, ident), "gnark-crypto [EXT]: used by the reference with import %s" % path))
@@ -257,12 +382,20 @@ def main():
                         bad.append((rel, "%s.%s" % (alias, ident), "not in the allow-list for standard package %s" % path))
                 else:
                     bad.append((rel, "%s.%s" % (alias, ident), "import %s is neither gnark, gnark-crypto nor an allow-listed standard package" % path))
+    patches = sorted(os.path.relpath(f, ROOT) for d, _, fs in os.walk(os.path.join(ROOT, "go")) for f in
+                     (os.path.join(d, x) for x in fs if x.endswith(".patch")))
+    stale = [(p,) + b for p in patches for b in check_patch(os.path.join(ROOT, p))]
     print("%d package-qualified identifiers resolved, %d unresolved" % (len(table), len(bad)))
     for r in bad:
         print("UNRESOLVED  %s: %s -- %s" % r)
+    print("%d patches checked against the reference, %d stale hunks" % (len(patches), len(stale)))
+    for r in stale:
+        print("STALE  %s: %s -- %s" % r)
     if args.json:
         json.dump({"resolved": sorted(set(table)), "unresolved": bad}, open(args.json, "w"), indent=0)
-    return 1 if bad else 0
+    if args.write_index:
+        REF.write_index(args.write_index)
+    return 1 if bad or stale else 0
 
 
 if __name__ == "__main__":
