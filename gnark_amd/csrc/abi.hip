@@ -1,6 +1,7 @@
 // extern "C" surface of libgnark_amd.so (include/gnark_amd.h): context, buffers, MSM, NTT, group helpers,
-// profiling.  Groth16 lives in groth16.hip.  Every entry point selects the context's device itself and takes the
-// context mutex (one proof at a time per device, as icicle.go:821-823).
+// profiling.  Groth16 lives in groth16.hip (the prover and its entry points; keys in g16_key.hip.h, key files and proof bytes in
+// g16_io.hip.h).  Every entry point selects the context's device itself and takes the context mutex (one proof at a time per device,
+// as icicle.go:821-823).
 #include <stdarg.h>
 #include <stdlib.h>
 

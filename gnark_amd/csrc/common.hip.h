@@ -242,8 +242,11 @@ struct Ctx {
     // such copies at once share the link at 24 + 24 GB/s where one alone gets 56 (profiles/r06_j_h2d_concurrency.json).  Otherwise
     // they run as they come: two pinned-key proofs in flight LOSE with the turns (122 -> 131 ms per proof, r06_k).
     std::atomic<int> oneshot_inflight{0};
-    // (turns are taken by PRIORITY = the order in which the proof needs the data: W, key A, key B, the solver's A, B, C, key G2.B,
-    // K, Z; equal priorities in arrival order; a copy gives way at 128 MiB boundaries)
+    // (turns are taken by PRIORITY = the order in which the proof needs the data: W 0, key A 1, key B 2, the solver's A, B, C 3, key K 4,
+    // G2.B 5, Z 6 (g16_key.hip.h start_uploader); equal priorities in arrival order; a copy gives way at 128 MiB boundaries.  Deadlock
+    // freedom rests on one invariant: no stream may wait on a copy that has not taken its turn yet (a pageable copy holds the turn
+    // until its host buffer has been consumed; on a stream stuck behind such a wait it would hold it for good).  await_vector keeps
+    // it: the MSM's stream waits on a vector's event only after done[which], set once every chunk of the vector has been issued.)
     struct TurnLock {
         std::mutex mu;
         std::condition_variable cv;
@@ -287,7 +290,7 @@ struct Ctx {
     }
     std::mutex spare_mu;
     Domain* spare_domain = nullptr;   // ntt_domain_give_spare / ntt_domain_take_spare
-    // ... and so do the five vector buffers of the last ONE-SHOT key (groth16.hip): a caller that uploads its key for every proof gets
+    // ... and so do the five vector buffers of the last ONE-SHOT key (g16_key.hip.h): a caller that uploads its key for every proof gets
     // them back instead of 6-9 GiB of hipMalloc / hipFree per proof (5-200 ms, r06_k)
     struct SpareVectors {
         void* p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};

@@ -1,4 +1,5 @@
-// Groth16 prover core: device-resident proving key + one-call proof from the solver's output.
+// Groth16 prover: one-call proof from the solver's output on a device-resident proving key, and the Groth16 entry points of the C
+// ABI.  The key builder is g16_key.hip.h, key files and proof bytes are g16_io.hip.h: one translation unit.
 //
 // Mirrors backend/groth16/bn254/prove.go:130-315 (CPU) and backend/accelerated/icicle/groth16/bn254/icicle.go:784-1360
 // (GPU):  computeH -> filter wire values -> 4 G1 MSMs + 1 G2 MSM -> host epilogue with the caller-supplied randomness
@@ -6,1252 +7,18 @@
 // side is C++ because the reference's host side is compiled Go and no Go toolchain exists in the build image (INTEGRATION.md shows
 // the cgo binding that calls this file's entry points).
 #include <algorithm>
+#include <atomic>
 #include <condition_variable>
 #include <memory>
-#include <new>
-#include <stdexcept>
 #include <string>
-#include <chrono>
 #include <thread>
+#include <vector>
 
+#include "g16_io.hip.h"
+#include "g16_key.hip.h"
 #include "hostops.hip.h"
-#include "keyio.hip.h"
 
 namespace ga {
-
-// dst[idx[i]] = src[i] for elements of `chunks` 16-byte pieces (building the wire-indexed base arrays at pin time)
-static __global__ void g16_scatter_points_kernel(u32x4* __restrict__ dst, const u32x4* __restrict__ src, const uint32_t* __restrict__ idx,
-                                                 uint64_t n, uint32_t chunks) {
-    uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t i = t / chunks, k = t % chunks;
-    if (i >= n) return;
-    dst[(uint64_t)idx[i] * chunks + k] = src[i * chunks + k];
-}
-
-struct G16Pk {
-    Ctx* ctx = nullptr;
-    int curve = 0;
-    uint64_t n = 0;            // domain cardinality
-    uint64_t nb_wires = 0;
-    Domain* dom = nullptr;
-    void *d_a = nullptr, *d_b = nullptr, *d_z = nullptr, *d_k = nullptr, *d_b2 = nullptr;
-    uint64_t len_a = 0, len_b = 0, len_z = 0, len_k = 0, len_b2 = 0;
-    uint32_t *d_idx_a = nullptr, *d_idx_b = nullptr;   // wire indices kept for the A / B MSMs (prove.go:147-168)
-    uint32_t* d_idx_k = nullptr;   // wire indices feeding the K MSM when committed wires are left out (prove.go:231-235); null = W[nbPublic:]
-    uint64_t len_k_remove = 0;
-    std::vector<void*> d_ck_basis, d_ck_sigma;   // pinned pedersen keys (setup.go:260-287, icicle.go:231-261)
-    std::vector<uint64_t> ck_len;
-    // precomputed window-multiple tables (msm.hip.h): a vector with its tab_* flag set points to windows x len points and c_* is the
-    // window width.  Per VECTOR since round 5: when the five tables do not fit the free HBM together (2^26 constraints: 288 GiB), the
-    // ones that pay most per byte are built -- A, B (G1), K (they share one witness sort), then Z, then the twice as large G2.B --
-    // and the rest stay plain affine arrays that run as un-pinned MSMs.
-    bool tables = false;   // any of the five
-    bool tab_a = false, tab_b = false, tab_z = false, tab_k = false, tab_b2 = false;
-    int c_a = 0, c_b = 0, c_z = 0, c_k = 0;
-    // Wire-indexed tables: when a base vector covers (almost) every wire, its table is laid out by WIRE id with (0,0) at the
-    // wires it lacks (infinity entries are skipped by the bucket kernel), so that the digit extraction + radix sort of the whole
-    // witness is done ONCE and shared by the A, B (G1 and G2) and K MSMs instead of once per filtered copy of the witness.
-    bool share_a = false, share_b = false, share_k = false;   // (each implies its tab_* flag)
-    bool share_b2 = false;                                    // G2.B wire-indexed too: it reuses the shared sort (share_b and tab_b2)
-    int c_w = 0;
-    // multi-GPU partition B: this key holds slice [off, off+len) of every base vector (ga_g16_key.shard_index/count)
-    uint32_t shard_index = 0, shard_count = 1;
-    uint64_t off_k = 0, off_z = 0, full_len_k = 0;
-    // multi-GPU partition A (scalar windows, BASELINE config 4's wording): the WHOLE key is pinned on every device and this one
-    // accumulates only share win_index of win_count of the Pippenger windows of every MSM; partial results add up
-    uint32_t win_index = 0, win_count = 1;
-    uint64_t w_lo = 0, w_hi = 0;   // wire range [w_lo, w_hi) the A and B gather lists (and a filtered K list) of this shard touch
-    std::vector<uint8_t> alpha1, beta1, delta1, beta2, delta2;   // affine images (host)
-    // fixed-base tables of delta1 / delta2 for the host epilogue: entry [w*15 + d-1] = d * 2^(4w) * delta (XYZZ images), built on first use
-    std::once_flag delta_tab_once;
-    std::vector<uint8_t> delta1_tab, delta2_tab;
-    // In-flight users: every entry point that takes the key holds one PkUse for its whole duration (the host epilogue included,
-    // which runs outside the device lock); ga_g16_pk_destroy waits for them, so a caller that frees the key from one thread while
-    // another is still proving (Go: `defer pk.FreeGPUResources()` beside a second goroutine's Prove) gets a late free, not a
-    // use-after-free.
-    std::mutex use_mu;
-    std::condition_variable use_cv;
-    int users = 0;
-    bool dying = false;
-    // A key whose base vectors are still ON THEIR WAY (ga_g16_prove_oneshot: the key goes up as plain vectors, is used for ONE proof
-    // and dropped -- the Go package's default, PinToGPU = false): an uploader thread copies them in the order the proof consumes
-    // them (A, B, K, G2.B, Z) while the proof already runs; an MSM waits for ITS vector (await_vector), not for the key.
-    struct Pending {
-        std::mutex mu;
-        std::condition_variable cv;
-        bool done[GA_KEY_NB_VECTORS] = {false, false, false, false, false};
-        size_t bytes[GA_KEY_NB_VECTORS] = {0, 0, 0, 0, 0};   // allocation sizes (the buffers go back to the context's spare set)
-        // recorded on the uploader's stream behind a vector's copies: the consumer's STREAM waits for it (hipStreamWaitEvent), no host
-        // thread does -- a hipStreamSynchronize of the upload stream was seen to return only when another thread's wait for a 54 ms
-        // bucket kernel did (profiles/r06_h_oneshot_timeline.txt)
-        hipEvent_t ev[GA_KEY_NB_VECTORS] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        ~Pending() {
-            for (hipEvent_t e : ev)
-                if (e) hipEventDestroy(e);
-        }
-        int rc = GA_OK;
-        std::string err;
-        std::thread uploader;
-    };
-    std::unique_ptr<Pending> pending;
-};
-
-static void trace_event(const char* what, int arg, double extra_ms);
-// the vector `which` of a key is on the device (always true for a key made by ga_g16_pk_create / the builder / a key file)
-static int await_vector(G16Pk* pk, int which) {
-    G16Pk::Pending* pd = pk->pending.get();
-    if (!pd) return GA_OK;
-    const auto t0 = std::chrono::steady_clock::now();
-    std::unique_lock<std::mutex> g(pd->mu);
-    pd->cv.wait(g, [&] { return pd->done[which] || pd->rc != GA_OK; });
-    trace_event("MSM waited for vector", which, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-    if (pd->rc != GA_OK) {
-        set_error("%s", pd->err.c_str());
-        return pd->rc;
-    }
-    g.unlock();
-    GA_HIP_CHECK(hipStreamWaitEvent(pk->ctx->work_stream(), pd->ev[which], 0));   // the MSM about to be launched on this lane starts behind the copies
-    return GA_OK;
-}
-
-struct PkUse {
-    G16Pk* pk;
-    bool ok = false;
-    explicit PkUse(G16Pk* p) : pk(p) {
-        if (!pk) return;
-        std::lock_guard<std::mutex> g(pk->use_mu);
-        if (pk->dying) return;
-        pk->users++;
-        ok = true;
-    }
-    ~PkUse() {
-        if (!ok) return;
-        std::lock_guard<std::mutex> g(pk->use_mu);
-        if (--pk->users == 0) pk->use_cv.notify_all();
-    }
-    PkUse(const PkUse&) = delete;
-    PkUse& operator=(const PkUse&) = delete;
-};
-#define GA_PK_USE(pk, what)                                                      \
-    PkUse _pk_use(pk);                                                           \
-    if (!_pk_use.ok) {                                                           \
-        set_error(what ": the proving key is being destroyed");                  \
-        return GA_ERR_STATE;                                                     \
-    }
-
-// GA_TRACE_PIN=1, process-wide clock: one line per event of a one-shot proof (uploader, waits) on stderr
-static void trace_event(const char* what, int arg, double extra_ms = -1.0) {
-    static const bool on = getenv("GA_TRACE_PIN") != nullptr;
-    static const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-    if (!on) return;
-    const double t = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (extra_ms >= 0) fprintf(stderr, "[one-shot] %10.2f ms  %s %d (%.2f ms)\n", t, what, arg, extra_ms);
-    else fprintf(stderr, "[one-shot] %10.2f ms  %s %d\n", t, what, arg);
-}
-
-// GA_TRACE_PIN=1: milestones of a key's way to the device on stderr (ms since the first mark of the calling thread) -- tools/exp
-struct PinTrace {
-    bool on;
-    std::chrono::steady_clock::time_point t0;
-    PinTrace() : on(getenv("GA_TRACE_PIN") != nullptr), t0(std::chrono::steady_clock::now()) {}
-    void mark(const char* what) const {
-        if (on) fprintf(stderr, "[pin] %8.2f ms  %s\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), what);
-    }
-};
-
-static int upload(Ctx* ctx, const void* src, size_t bytes, void** dst) {
-    *dst = nullptr;
-    hipError_t e = device_malloc(dst, bytes ? bytes : 16);
-    if (e != hipSuccess) {
-        set_error("proving key upload: device_malloc(%zu) failed: %s", bytes, device_malloc_error(e));
-        return GA_ERR_NOMEM;
-    }
-    if (bytes) GA_HIP_CHECK(hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return GA_OK;
-}
-
-static void pk_free(G16Pk* pk) {
-    if (!pk) return;
-    if (pk->pending && pk->pending->uploader.joinable()) pk->pending->uploader.join();   // (it writes into the buffers freed below)
-    if (pk->pending && pk->ctx && !pk->tables) {   // a one-shot key: its plain vector buffers stay with the context for the next one
-        const char* e = getenv("GA_DOMAIN_SPARE");
-        Ctx* c = pk->ctx;
-        std::lock_guard<std::mutex> g(c->spare_mu);
-        if (!(e && atoi(e) == 0) && !c->spare_vectors.have) {
-            void** slot[GA_KEY_NB_VECTORS] = {&pk->d_a, &pk->d_b, &pk->d_z, &pk->d_k, &pk->d_b2};
-            for (int w = 0; w < GA_KEY_NB_VECTORS; w++) {
-                c->spare_vectors.p[w] = *slot[w];
-                c->spare_vectors.bytes[w] = pk->pending->bytes[w];
-                *slot[w] = nullptr;
-            }
-            c->spare_vectors.have = true;
-        }
-    }
-    if (pk->ctx)
-        for (const void* t : {pk->d_a, pk->d_b, pk->d_z, pk->d_k, pk->d_b2}) pk->ctx->forget_table(t);
-    hipFree(pk->d_a);
-    hipFree(pk->d_b);
-    hipFree(pk->d_z);
-    hipFree(pk->d_k);
-    hipFree(pk->d_b2);
-    hipFree(pk->d_idx_a);
-    hipFree(pk->d_idx_b);
-    hipFree(pk->d_idx_k);
-    for (void* p : pk->d_ck_basis) hipFree(p);
-    for (void* p : pk->d_ck_sigma) hipFree(p);
-    if (pk->dom) ntt_domain_give_spare(pk->ctx, pk->dom);   // (kept for the next key of this size: common.hip.h)
-    delete pk;
-}
-
-// ---- staged key construction (ga_g16_builder_*) -------------------------------------------------------------------------------
-// The proving key reaches the device vector by vector, chunk by chunk: every call takes ONE flat pointer to pointer-free memory
-// and has copied what it needs when it returns.  This is the shape cgo wants (no Go pointer stored inside a C struct, nothing
-// retained after the call) and the shape a streaming reader of the 6-9 GiB key files wants (keyio.hip: ReadDump / ReadFrom feed
-// chunks from a pinned staging buffer).  ga_g16_pk_create(struct) is a thin wrapper over it.
-struct G16Stage {
-    Ctx* ctx = nullptr;
-    int curve = 0;
-    uint64_t n = 0, nb_wires = 0;
-    uint32_t shard_index = 0, shard_count = 1;
-    uint32_t win_index = 0, win_count = 1;
-    struct Vec {
-        void* d = nullptr;
-        uint64_t total = 0, lo = 0, cnt = 0, seen = 0;
-        bool reserved = false;
-    } v[GA_KEY_NB_VECTORS];
-    std::vector<uint8_t> inf[2];                 // InfinityA, InfinityB (Go []bool images)
-    bool have_inf[2] = {false, false};
-    // the wire ids each mask keeps, ascending (the gather lists of prove.go:147-168): built by a helper thread as soon as a mask is
-    // set -- beside the uploads of the vectors, which keep the calling thread busy for 19 ms per GiB -- and joined by stage_finish
-    struct WireList {
-        std::unique_ptr<uint32_t[]> ids;
-        uint64_t size = 0;
-        std::thread job;
-    } lists[2];
-    void start_list(int which) {
-        WireList& L = lists[which];
-        if (L.job.joinable()) L.job.join();
-        L.ids.reset(new uint32_t[inf[which].size() + 8]);   // (uninitialised on purpose: 64 MiB at 2^24 wires)
-        L.size = 0;
-        const uint8_t* m = inf[which].data();
-        const uint64_t nw = inf[which].size();
-        uint32_t* out = L.ids.get();
-        uint64_t* size = &L.size;
-        L.job = std::thread([m, nw, out, size]() {
-            uint32_t* p = out;
-            uint64_t i = 0;
-            for (; i + 8 <= nw; i += 8) {   // masks are zero almost everywhere: eight wires per test
-                uint64_t w;
-                memcpy(&w, m + i, 8);
-                if (w == 0) {
-                    for (int k = 0; k < 8; k++) p[k] = (uint32_t)(i + k);
-                    p += 8;
-                } else {
-                    for (int k = 0; k < 8; k++)
-                        if (!m[i + k]) *p++ = (uint32_t)(i + k);
-                }
-            }
-            for (; i < nw; i++)
-                if (!m[i]) *p++ = (uint32_t)i;
-            *size = (uint64_t)(p - out);
-        });
-    }
-    std::vector<uint8_t> pts[GA_KEY_NB_POINTS];  // alpha1, beta1, delta1, beta2, delta2
-    std::vector<void*> d_ck_basis, d_ck_sigma;
-    std::vector<uint64_t> ck_len;
-    std::vector<uint64_t> k_remove;
-    std::thread* early_uploader = nullptr;       // one-shot keys: the thread already filling the vectors' buffers (pk_create_from_struct)
-    ~G16Stage() {
-        for (auto& L : lists)
-            if (L.job.joinable()) L.job.join();
-        for (auto& x : v) hipFree(x.d);
-        for (void* p : d_ck_basis) hipFree(p);
-        for (void* p : d_ck_sigma) hipFree(p);
-    }
-};
-
-static size_t stage_point_bytes(int curve, int which) {
-    const size_t fp = curve == GA_BN254 ? 32 : 48;
-    return which == GA_KEY_G2_B ? 4 * fp : 2 * fp;
-}
-
-static int stage_reserve(G16Stage* st, int which, uint64_t total) {
-    if (which < 0 || which >= GA_KEY_NB_VECTORS) {
-        set_error("proving key: unknown vector id %d", which);
-        return GA_ERR_INVALID;
-    }
-    G16Stage::Vec& x = st->v[which];
-    if (x.reserved) {
-        set_error("proving key: vector %d reserved twice", which);
-        return GA_ERR_STATE;
-    }
-    const uint64_t base = total / st->shard_count, rem = total % st->shard_count, k = st->shard_index;   // same split as multigpu.shard_range
-    x.total = total;
-    x.lo = k * base + (k < rem ? k : rem);
-    x.cnt = base + (k < rem ? 1 : 0);
-    const size_t bytes = x.cnt * stage_point_bytes(st->curve, which);
-    hipError_t e = device_malloc(&x.d, bytes ? bytes : 16);
-    if (e != hipSuccess) {
-        set_error("proving key upload: device_malloc(%zu) failed: %s", bytes, device_malloc_error(e));
-        return GA_ERR_NOMEM;
-    }
-    x.reserved = true;
-    return GA_OK;
-}
-
-// points [seen, seen + count) of the full vector; only the part inside this shard's range is copied.  `pinned`: the source is
-// page-locked memory owned by the caller for the duration of the call (keyio's staging buffers) -- the copy is then truly
-// asynchronous and the caller synchronises; otherwise the stream is drained before returning.
-static int stage_append(G16Stage* st, int which, const void* points, uint64_t count, bool pinned = false) {
-    if (which < 0 || which >= GA_KEY_NB_VECTORS || !st->v[which].reserved) {
-        set_error("proving key: append to vector %d before ga_g16_builder_reserve", which);
-        return GA_ERR_STATE;
-    }
-    G16Stage::Vec& x = st->v[which];
-    if (x.seen + count > x.total) {
-        set_error("proving key: vector %d overflows its reserved length %llu", which, (unsigned long long)x.total);
-        return GA_ERR_INVALID;
-    }
-    const size_t psz = stage_point_bytes(st->curve, which);
-    const uint64_t b0 = x.seen > x.lo ? x.seen : x.lo;
-    const uint64_t e0 = x.seen + count < x.lo + x.cnt ? x.seen + count : x.lo + x.cnt;
-    if (e0 > b0) {
-        GA_HIP_CHECK(hipMemcpyAsync((char*)x.d + (b0 - x.lo) * psz, (const char*)points + (b0 - x.seen) * psz, (e0 - b0) * psz,
-                                    hipMemcpyHostToDevice, st->ctx->stream));
-        if (!pinned) GA_HIP_CHECK(hipStreamSynchronize(st->ctx->stream));   // no host pointer survives this call
-    }
-    x.seen += count;
-    return GA_OK;
-}
-
-template <class C>
-static int stage_finish(G16Stage* st, int precompute, G16Pk** out) {
-    typedef Fe<typename C::FpP> F1;
-    typedef Fe2<typename C::FpP> F2;
-    Ctx* ctx = st->ctx;
-    const size_t s1 = sizeof(Affine<F1>), s2 = sizeof(Affine<F2>);
-    for (int w = 0; w < GA_KEY_NB_VECTORS; w++)
-        if (!st->v[w].reserved || st->v[w].seen != st->v[w].total) {
-            set_error("proving key: vector %d incomplete (%llu of %llu points)", w, (unsigned long long)st->v[w].seen,
-                      (unsigned long long)st->v[w].total);
-            return GA_ERR_STATE;
-        }
-    for (int q = 0; q < GA_KEY_NB_POINTS; q++)
-        if (st->pts[q].empty()) {
-            set_error("proving key: point %d (alpha1, beta1, delta1, beta2, delta2) not set", q);
-            return GA_ERR_STATE;
-        }
-    if (!st->have_inf[0] || !st->have_inf[1]) {
-        set_error("proving key: InfinityA / InfinityB not set");
-        return GA_ERR_STATE;
-    }
-    const uint64_t len_a = st->v[GA_KEY_G1_A].total, len_b = st->v[GA_KEY_G1_B].total, len_z = st->v[GA_KEY_G1_Z].total,
-                   len_k = st->v[GA_KEY_G1_K].total, len_b2 = st->v[GA_KEY_G2_B].total;
-    if (len_z + 1 != st->n) {
-        set_error("proving key: len(G1.Z)=%llu but domain cardinality is %llu (expected n-1, setup.go:248-249)",
-                  (unsigned long long)len_z, (unsigned long long)st->n);
-        return GA_ERR_INVALID;
-    }
-    if (st->nb_wires >= (1ull << 32)) {
-        set_error("proving key: %llu wires exceed the 32-bit wire index space", (unsigned long long)st->nb_wires);
-        return GA_ERR_INVALID;
-    }
-    if (len_a > st->nb_wires || len_b > st->nb_wires || len_k > st->nb_wires || st->k_remove.size() > st->nb_wires ||
-        len_k + st->k_remove.size() > st->nb_wires) {   // (nbWires - len(K) - len(k_remove) = nbPublic >= 0; the wire-indexed layouts rely on it)
-        set_error("proving key: len(A) %llu, len(B) %llu, len(K) %llu + %zu removed wires do not fit %llu wires", (unsigned long long)len_a,
-                  (unsigned long long)len_b, (unsigned long long)len_k, st->k_remove.size(), (unsigned long long)st->nb_wires);
-        return GA_ERR_INVALID;
-    }
-    if (st->inf[0].size() != st->nb_wires || st->inf[1].size() != st->nb_wires) {
-        set_error("proving key: InfinityA / InfinityB must have one entry per wire");
-        return GA_ERR_INVALID;
-    }
-    if (st->win_count > 1 && (st->shard_count > 1 || st->win_index >= st->win_count)) {
-        set_error("proving key: window sharding (%u of %u) cannot be combined with base-range sharding, and the index must be below the count",
-                  st->win_index, st->win_count);
-        return GA_ERR_INVALID;
-    }
-    PinTrace tr;
-    for (int k = 0; k < 2; k++) {
-        if (!st->lists[k].job.joinable()) st->start_list(k);   // (a caller that set the mask through a path without the early start)
-        st->lists[k].job.join();
-    }
-    const uint32_t *ia = st->lists[0].ids.get(), *ib = st->lists[1].ids.get();
-    if (st->lists[0].size != len_a || st->lists[1].size != len_b || len_b2 != len_b) {
-        set_error("proving key: InfinityA/B masks disagree with len(A)/len(B), or len(G2.B) != len(G1.B)");
-        return GA_ERR_INVALID;
-    }
-    G16Pk* pk = new G16Pk();
-    pk->ctx = ctx;
-    pk->curve = C::ID;
-    pk->n = st->n;
-    pk->nb_wires = st->nb_wires;
-    pk->shard_count = st->shard_count;
-    pk->shard_index = st->shard_index;
-    pk->win_count = st->win_count ? st->win_count : 1;
-    pk->win_index = st->win_index;
-    auto take = [&](int which, void** slot, uint64_t* len) {   // the device buffer changes owner
-        *slot = st->v[which].d;
-        *len = st->v[which].cnt;
-        st->v[which].d = nullptr;
-    };
-    take(GA_KEY_G1_A, &pk->d_a, &pk->len_a);
-    take(GA_KEY_G1_B, &pk->d_b, &pk->len_b);
-    take(GA_KEY_G1_Z, &pk->d_z, &pk->len_z);
-    take(GA_KEY_G1_K, &pk->d_k, &pk->len_k);
-    take(GA_KEY_G2_B, &pk->d_b2, &pk->len_b2);
-    const uint64_t lo_a = st->v[GA_KEY_G1_A].lo, lo_b = st->v[GA_KEY_G1_B].lo, lo_k = st->v[GA_KEY_G1_K].lo;
-    pk->off_k = lo_k;
-    pk->off_z = st->v[GA_KEY_G1_Z].lo;
-    pk->full_len_k = len_k;
-    {   // wire range of this shard: the sorted gather lists are sliced contiguously, so min/max are the slice ends
-        uint64_t lo = st->nb_wires, hi = 0;
-        auto span = [&](const uint32_t* v, uint64_t off, uint64_t cnt) {
-            if (cnt == 0) return;
-            lo = lo < v[off] ? lo : v[off];
-            hi = hi > (uint64_t)v[off + cnt - 1] + 1 ? hi : (uint64_t)v[off + cnt - 1] + 1;
-        };
-        span(ia, lo_a, pk->len_a);
-        span(ib, lo_b, pk->len_b);
-        pk->w_lo = st->shard_count == 1 ? 0 : lo;
-        pk->w_hi = st->shard_count == 1 ? st->nb_wires : hi;
-    }
-    tr.mark("finish: gather lists built on the host");
-    int rc = GA_OK;
-    pk->dom = ntt_domain_take_spare(ctx, C::ID, pk->n);   // the domain of the key this context freed last, when it has this size
-    if (!pk->dom) rc = ntt_domain_new<C>(ctx, pk->n, &pk->dom);
-    tr.mark("finish: ntt_domain_new returned");
-    if (rc == GA_OK) rc = upload(ctx, ia + lo_a, pk->len_a * 4, (void**)&pk->d_idx_a);
-    if (rc == GA_OK) rc = upload(ctx, ib + lo_b, pk->len_b * 4, (void**)&pk->d_idx_b);
-    // K filter with commitments: wireValues[nbPublic:] minus the private committed and commitment wires (prove.go:231-235)
-    std::vector<uint32_t> ik;
-    pk->len_k_remove = st->k_remove.size();
-    if (rc == GA_OK && pk->len_k_remove) {
-        const uint64_t nrem = st->k_remove.size();
-        if (len_k + nrem > st->nb_wires) {
-            set_error("proving key: len(K)+len(k_remove) > nbWires");
-            rc = GA_ERR_INVALID;
-        } else {
-            const uint64_t nb_public = st->nb_wires - len_k - nrem;
-            ik.reserve(len_k);
-            uint64_t j = 0;
-            bool ok = true;
-            for (uint64_t i = 0; i < nrem; i++)
-                ok = ok && st->k_remove[i] >= nb_public && st->k_remove[i] < st->nb_wires && (i == 0 || st->k_remove[i] > st->k_remove[i - 1]);
-            for (uint64_t i = nb_public; ok && i < st->nb_wires; i++) {
-                if (j < nrem && st->k_remove[j] == i) j++;
-                else ik.push_back((uint32_t)i);
-            }
-            if (!ok || ik.size() != len_k) {
-                set_error("proving key: k_remove must be strictly increasing wire ids in [nbPublic, nbWires)");
-                rc = GA_ERR_INVALID;
-            }
-        }
-        if (rc == GA_OK) rc = upload(ctx, ik.data() + lo_k, pk->len_k * 4, (void**)&pk->d_idx_k);
-        if (rc == GA_OK && pk->len_k && st->shard_count > 1) {
-            pk->w_lo = pk->w_lo < ik[lo_k] ? pk->w_lo : ik[lo_k];
-            pk->w_hi = pk->w_hi > (uint64_t)ik[lo_k + pk->len_k - 1] + 1 ? pk->w_hi : (uint64_t)ik[lo_k + pk->len_k - 1] + 1;
-        }
-    }
-    pk->d_ck_basis.swap(st->d_ck_basis);
-    pk->d_ck_sigma.swap(st->d_ck_sigma);
-    pk->ck_len = st->ck_len;
-    if (rc == GA_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) {   // no host pointer survives this call
-        set_error("proving key upload: stream synchronize failed");
-        rc = GA_ERR_HIP;
-    }
-    tr.mark("finish: gather lists uploaded, stream drained");
-    // ---- optional precomputation: [2^(c*w)]P for every window (one shared bucket set per MSM afterwards) ----------
-    if (rc == GA_OK && precompute >= 0) {
-        {   // a key that is here to stay: the buffers kept for one-shot keys (6-9 GiB) go back to the device before the tables are sized
-            std::lock_guard<std::mutex> g(ctx->spare_mu);
-            for (void*& q : ctx->spare_vectors.p) {
-                hipFree(q);
-                q = nullptr;
-            }
-            ctx->spare_vectors.have = false;
-        }
-        int nw = 0;
-        const size_t t1 = msm_table_point_bytes<C, GA_G1>(), t2 = msm_table_point_bytes<C, GA_G2>();
-        // share the witness sort between the vectors that cover at least GA_G16_SHARE_MIN_PCT % of the wires (default 90: a
-        // sparse vector would make the lanes of the bucket kernel idle on its missing wires, and waste table memory)
-        const int share_pct = ctx->tun.g16_share_min_pct;
-        auto dense = [&](uint64_t len) {
-            return pk->shard_count == 1 && pk->nb_wires < (1ull << 27) && len > 0 && (double)len * 100.0 >= (double)pk->nb_wires * share_pct;
-        };
-        pk->share_a = dense(pk->len_a);
-        pk->share_b = dense(pk->len_b);
-        pk->share_k = dense(pk->len_k);
-        bool plan_ok = msm_plan_table<C>(pk->nb_wires, &pk->c_w, &nw) == GA_OK;
-        const uint64_t wide = (uint64_t)nw * pk->nb_wires;
-        plan_ok = msm_plan_table<C>(pk->len_a, &pk->c_a, &nw) == GA_OK && plan_ok;
-        plan_ok = msm_plan_table<C>(pk->len_b, &pk->c_b, &nw) == GA_OK && plan_ok;
-        plan_ok = msm_plan_table<C>(pk->len_z, &pk->c_z, &nw) == GA_OK && plan_ok;
-        plan_ok = msm_plan_table<C>(pk->len_k, &pk->c_k, &nw) == GA_OK && plan_ok;
-        if (!plan_ok && precompute > 0) rc = GA_ERR_INVALID;   // vectors beyond the table index space: the caller asked for tables explicitly
-        size_t free_b = 0, total_b = 0;
-        hipMemGetInfo(&free_b, &total_b);
-        // Which vectors get a table.  precompute > 0: all five (the caller insists; a table that does not fit fails the call).
-        // precompute == 0: as many as fit the free HBM next to the per-proof scratch, in the order of what a table buys per byte:
-        // A, B1, K (48 GiB each at 2^26 BN254; with all three the witness is sorted once instead of three times), Z, and last G2.B
-        // (twice the bytes for the smallest relative gain).
-        // (a vector the planner refused -- beyond the 2^31 pair space, or a forced GA_TABLE_C too narrow -- has c_* = 0: no table, no size)
-        auto nwin_of = [](int cbits) -> uint64_t { return cbits > 0 ? (uint64_t)(C::FrP::BITS / cbits + 1) : 0; };
-        const uint64_t bytes_a = !plan_ok ? 0 : pk->share_a ? wide * t1 : nwin_of(pk->c_a) * pk->len_a * t1;
-        const uint64_t bytes_b = !plan_ok ? 0 : pk->share_b ? wide * t1 : nwin_of(pk->c_b) * pk->len_b * t1;
-        const uint64_t bytes_b2 = !plan_ok ? 0 : pk->share_b ? wide * t2 : nwin_of(pk->c_b) * pk->len_b * t2;
-        const uint64_t bytes_z = !plan_ok ? 0 : nwin_of(pk->c_z) * pk->len_z * t1;
-        const uint64_t bytes_k = !plan_ok ? 0 : pk->share_k ? wide * t1 : nwin_of(pk->c_k) * pk->len_k * t1;
-        if (rc == GA_OK && plan_ok) {
-            if (precompute > 0) {
-                pk->tab_a = pk->tab_b = pk->tab_k = pk->tab_z = pk->tab_b2 = true;
-            } else {
-                // What the tables may take = free HBM - what a single caller's proof will allocate on this context (measured: 1.15 KB per
-                // constraint at 2^26 with three tables -- sort pairs, task lists, hat-domain copies of the plain vectors, input slots, NTT
-                // tables --, 1.25 KB allowed, + 10 %) - 4 GiB.  At 2^26 BN254 on an empty device: 244 - 88 - 4 = 152 GiB -> A, B, K (144).
-                // Scratch this context already holds (an earlier proof of this size) is credited against the allowance: it is not free
-                // any more, but it is exactly what the allowance was for.
-                uint64_t held = 0;
-                {
-                    std::lock_guard<std::mutex> g(ctx->scratch_mu);
-                    for (const auto& kv : ctx->scratch) held += kv.second.second;
-                }
-                const double per_proof = (double)pk->n * 1280.0;
-                const double allowance = per_proof > (double)held ? per_proof - (double)held : 0.0;
-                double budget = (double)free_b - 1.1 * allowance - 4.0 * 1073741824.0;
-                if (const uint64_t pct = ctx->tun.g16_table_budget_pct)   // GA_G16_TABLE_BUDGET_PCT (tests: partial tables on small keys)
-                    budget = (double)pct / 100.0 * (double)(bytes_a + bytes_b + bytes_k + bytes_z + bytes_b2);
-                struct Cand { bool* flag; uint64_t bytes; } order[5] = {{&pk->tab_a, bytes_a}, {&pk->tab_b, bytes_b}, {&pk->tab_k, bytes_k},
-                                                                       {&pk->tab_z, bytes_z}, {&pk->tab_b2, bytes_b2}};
-                for (auto& cnd : order) {
-                    // (the plain array it replaces is freed once the table stands; while it is built both are resident)
-                    if ((double)cnd.bytes <= budget) {
-                        *cnd.flag = true;
-                        budget -= (double)cnd.bytes;
-                    }
-                }
-            }
-        }
-        pk->share_a = pk->share_a && pk->tab_a;
-        pk->share_b = pk->share_b && pk->tab_b;
-        pk->share_k = pk->share_k && pk->tab_k;
-        pk->share_b2 = pk->share_b && pk->tab_b2;
-        pk->tables = pk->tab_a || pk->tab_b || pk->tab_k || pk->tab_z || pk->tab_b2;
-        if (rc == GA_OK && pk->tables) {
-            auto make = [&](void** slot, uint64_t len, int c, size_t psz, auto build) -> int {
-                if (len == 0) return GA_OK;
-                const int nwin = C::FrP::BITS / c + 1;
-                void* t = nullptr;
-                if (device_malloc(&t, (uint64_t)nwin * len * psz) != hipSuccess) {
-                    set_error("proving key: hipMalloc of a %llu-byte window table failed", (unsigned long long)((uint64_t)nwin * len * psz));
-                    return GA_ERR_NOMEM;
-                }
-                int r = build(*slot, len, c, t);
-                if (r == GA_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) r = GA_ERR_HIP;
-                hipFree(*slot);
-                *slot = t;
-                return r;
-            };
-            auto b1 = [&](const void* src, uint64_t len, int c, void* t) { return msm_table_build<C, GA_G1>(ctx, src, len, c, t); };
-            auto b2 = [&](const void* src, uint64_t len, int c, void* t) { return msm_table_build<C, GA_G2>(ctx, src, len, c, t); };
-            // compact base array -> wire-indexed array with (0,0) at the missing wires
-            auto widen = [&](void** slot, uint64_t len, const uint32_t* d_idx, size_t psz) -> int {
-                void* wide_arr = nullptr;
-                if (device_malloc(&wide_arr, pk->nb_wires * psz) != hipSuccess) {
-                    set_error("proving key: hipMalloc of a wire-indexed base array failed");
-                    return GA_ERR_NOMEM;
-                }
-                hipError_t we = hipMemsetAsync(wide_arr, 0, pk->nb_wires * psz, ctx->stream);
-                const uint32_t chunks = (uint32_t)(psz / 16);
-                const uint64_t threads = len * chunks;
-                if (we == hipSuccess) {
-                    hipLaunchKernelGGL(g16_scatter_points_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream,
-                                       (u32x4*)wide_arr, (const u32x4*)*slot, d_idx, len, chunks);
-                    we = hipGetLastError();
-                }
-                if (we == hipSuccess) we = hipStreamSynchronize(ctx->stream);
-                if (we != hipSuccess) {
-                    set_error("proving key: building a wire-indexed base array failed: %s", hipGetErrorString(we));
-                    hipFree(wide_arr);
-                    return GA_ERR_HIP;
-                }
-                hipFree(*slot);
-                *slot = wide_arr;
-                return GA_OK;
-            };
-            uint32_t* d_ik = pk->d_idx_k;   // wire ids of K's entries: the remove-list gather, or nbPublic + i
-            if (pk->share_k && !d_ik) {
-                const uint64_t nbp = pk->nb_wires - pk->len_k;
-                std::vector<uint32_t> ikk(pk->len_k);
-                for (uint64_t i = 0; i < pk->len_k; i++) ikk[i] = (uint32_t)(nbp + i);
-                rc = upload(ctx, ikk.data(), pk->len_k * 4, (void**)&d_ik);
-                if (rc == GA_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = GA_ERR_HIP;
-            }
-            if (rc == GA_OK && pk->share_a) rc = widen(&pk->d_a, pk->len_a, pk->d_idx_a, s1);
-            if (rc == GA_OK && pk->share_b) rc = widen(&pk->d_b, pk->len_b, pk->d_idx_b, s1);
-            if (rc == GA_OK && pk->share_b2) rc = widen(&pk->d_b2, pk->len_b2, pk->d_idx_b, s2);
-            if (rc == GA_OK && pk->share_k) rc = widen(&pk->d_k, pk->len_k, d_ik, s1);
-            if (d_ik && d_ik != pk->d_idx_k) hipFree(d_ik);
-            const uint64_t nwr = pk->nb_wires;
-            if (rc == GA_OK && pk->tab_a) rc = pk->share_a ? make(&pk->d_a, nwr, pk->c_w, t1, b1) : make(&pk->d_a, pk->len_a, pk->c_a, t1, b1);
-            if (rc == GA_OK && pk->tab_b) rc = pk->share_b ? make(&pk->d_b, nwr, pk->c_w, t1, b1) : make(&pk->d_b, pk->len_b, pk->c_b, t1, b1);
-            if (rc == GA_OK && pk->tab_z) rc = make(&pk->d_z, pk->len_z, pk->c_z, t1, b1);
-            if (rc == GA_OK && pk->tab_k) rc = pk->share_k ? make(&pk->d_k, nwr, pk->c_w, t1, b1) : make(&pk->d_k, pk->len_k, pk->c_k, t1, b1);
-            if (rc == GA_OK && pk->tab_b2) rc = pk->share_b2 ? make(&pk->d_b2, nwr, pk->c_w, t2, b2) : make(&pk->d_b2, pk->len_b2, pk->c_b, t2, b2);
-            if (rc != GA_OK) pk->tables = false;
-        }
-    }
-    if (!pk->tables) {
-        pk->share_a = pk->share_b = pk->share_k = pk->share_b2 = false;
-        pk->tab_a = pk->tab_b = pk->tab_k = pk->tab_z = pk->tab_b2 = false;
-    }
-    if (rc != GA_OK) {
-        if (st->early_uploader && st->early_uploader->joinable()) st->early_uploader->join();   // (it writes into the buffers pk_free frees)
-        pk_free(pk);
-        return rc;
-    }
-    pk->alpha1 = st->pts[GA_KEY_G1_ALPHA];
-    pk->beta1 = st->pts[GA_KEY_G1_BETA];
-    pk->delta1 = st->pts[GA_KEY_G1_DELTA];
-    pk->beta2 = st->pts[GA_KEY_G2_BETA];
-    pk->delta2 = st->pts[GA_KEY_G2_DELTA];
-    (void)s2;
-    *out = pk;
-    return GA_OK;
-}
-
-static int stage_set_point(G16Stage* st, int which, const void* affine) {
-    if (which < 0 || which >= GA_KEY_NB_POINTS || !affine) {
-        set_error("proving key: bad point id %d or null pointer", which);
-        return GA_ERR_INVALID;
-    }
-    const size_t fp = st->curve == GA_BN254 ? 32 : 48;
-    const size_t bytes = (which == GA_KEY_G2_BETA || which == GA_KEY_G2_DELTA) ? 4 * fp : 2 * fp;
-    st->pts[which].assign((const uint8_t*)affine, (const uint8_t*)affine + bytes);
-    return GA_OK;
-}
-
-static int stage_add_commitment_key(G16Stage* st, const void* basis, const void* sigma, uint64_t len) {
-    if (len && (!basis || !sigma)) {
-        set_error("proving key: null commitment key basis");
-        return GA_ERR_INVALID;
-    }
-    const size_t s1 = stage_point_bytes(st->curve, GA_KEY_G1_A);
-    void *db = nullptr, *ds = nullptr;
-    int rc = upload(st->ctx, basis, len * s1, &db);
-    if (rc == GA_OK) rc = upload(st->ctx, sigma, len * s1, &ds);
-    if (rc == GA_OK && hipStreamSynchronize(st->ctx->stream) != hipSuccess) rc = GA_ERR_HIP;
-    if (rc != GA_OK) {
-        hipFree(db);
-        hipFree(ds);
-        return rc;
-    }
-    st->d_ck_basis.push_back(db);
-    st->d_ck_sigma.push_back(ds);
-    st->ck_len.push_back(len);
-    return GA_OK;
-}
-
-// ga_g16_pk_create: the struct-of-pointers form of the same thing (C and ctypes callers; from Go only with runtime.Pinner)
-// defer_uploads (ga_g16_prove_oneshot): the five base vectors get their device buffers here but are copied by an uploader thread
-// that this function starts before it returns -- plain vectors only (no tables), the whole key on one device; the caller must keep
-// the host vectors alive until the thread has been joined (pk_free does).
-static int pk_create_from_struct(Ctx* ctx, const ga_g16_key* key, G16Pk** out, bool defer_uploads = false) {
-    if (!key->g1_alpha || !key->g1_beta || !key->g1_delta || !key->g2_beta || !key->g2_delta || !key->infinity_a || !key->infinity_b ||
-        (key->len_a && !key->g1_a) || (key->len_b && !key->g1_b) || (key->len_z && !key->g1_z) || (key->len_k && !key->g1_k) ||
-        (key->len_b2 && !key->g2_b)) {
-        set_error("ga_g16_pk_create: null pointer inside ga_g16_key");
-        return GA_ERR_INVALID;
-    }
-    if (key->len_a + key->nb_infinity_a != key->nb_wires || key->len_b + key->nb_infinity_b != key->nb_wires) {
-        set_error("proving key: len(A)+NbInfinityA, len(B)+NbInfinityB must equal nbWires and len(G2.B)==len(G1.B)");
-        return GA_ERR_INVALID;
-    }
-    if (key->nb_commitments && (!key->ck_basis || !key->ck_basis_exp_sigma || !key->ck_len)) {
-        set_error("proving key: nb_commitments > 0 but the commitment key arrays are null");
-        return GA_ERR_INVALID;
-    }
-    if (key->len_k_remove && !key->k_remove) {
-        set_error("proving key: k_remove missing");
-        return GA_ERR_INVALID;
-    }
-    PinTrace tr;
-    G16Stage st;
-    st.ctx = ctx;
-    st.curve = key->curve;
-    st.n = key->domain_cardinality;
-    st.nb_wires = key->nb_wires;
-    st.shard_count = key->shard_count ? key->shard_count : 1;
-    st.shard_index = key->shard_index;
-    if (st.shard_index >= st.shard_count) {
-        set_error("proving key: shard_index %u >= shard_count %u", st.shard_index, st.shard_count);
-        return GA_ERR_INVALID;
-    }
-    st.win_count = key->window_shard_count ? key->window_shard_count : 1;
-    st.win_index = key->window_shard_index;
-    // the masks first: their gather lists are built by helper threads while this thread is busy with the 6-9 GiB of uploads below
-    st.inf[0].assign(key->infinity_a, key->infinity_a + key->nb_wires);
-    st.inf[1].assign(key->infinity_b, key->infinity_b + key->nb_wires);
-    st.have_inf[0] = st.have_inf[1] = true;
-    st.start_list(0);
-    st.start_list(1);
-    const void* vec[GA_KEY_NB_VECTORS] = {key->g1_a, key->g1_b, key->g1_z, key->g1_k, key->g2_b};
-    const uint64_t len[GA_KEY_NB_VECTORS] = {key->len_a, key->len_b, key->len_z, key->len_k, key->len_b2};
-    if (defer_uploads && (st.shard_count != 1 || st.win_count != 1)) {
-        set_error("ga_g16_prove_oneshot: the key must be whole (no base-range or window sharding)");
-        return GA_ERR_INVALID;
-    }
-    size_t alloc_bytes[GA_KEY_NB_VECTORS];
-    for (int w = 0; w < GA_KEY_NB_VECTORS; w++) alloc_bytes[w] = len[w] ? (size_t)len[w] * stage_point_bytes(key->curve, w) : 16;
-    if (defer_uploads) {   // the buffers of the previous one-shot key, when they have the sizes this one needs
-        std::lock_guard<std::mutex> g(ctx->spare_mu);
-        Ctx::SpareVectors& sp = ctx->spare_vectors;
-        if (sp.have) {
-            bool fits = true;
-            for (int w = 0; w < GA_KEY_NB_VECTORS; w++) fits = fits && sp.bytes[w] == alloc_bytes[w];
-            for (int w = 0; w < GA_KEY_NB_VECTORS; w++) {
-                if (fits) {
-                    G16Stage::Vec& x = st.v[w];
-                    x.d = sp.p[w];
-                    x.total = x.cnt = len[w];
-                    x.lo = 0;
-                    x.reserved = true;
-                } else {
-                    hipFree(sp.p[w]);
-                }
-                sp.p[w] = nullptr;
-            }
-            sp.have = false;
-        }
-    }
-    for (int w = 0; w < GA_KEY_NB_VECTORS; w++) {
-        if (!st.v[w].reserved) GA_CHECK(stage_reserve(&st, w, len[w]));
-        if (defer_uploads) st.v[w].seen = st.v[w].total;   // (the uploader below fills the buffer)
-        else GA_CHECK(stage_append(&st, w, vec[w], len[w], /*pinned=*/true));   // one drain below instead of five
-        tr.mark("vector reserved + appended");
-    }
-    GA_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    tr.mark("uploads drained");
-    // one-shot: the uploader starts NOW, on the buffers just reserved -- the masks, gather lists and domain below (30-40 ms at 2^24)
-    // are built while the first vector is already on its way
-    std::unique_ptr<G16Pk::Pending> pending;
-    struct JoinOnError {   // an error return below must not free the buffers (G16Stage's destructor) under a running uploader
-        G16Pk::Pending* pd = nullptr;
-        ~JoinOnError() {
-            if (pd && pd->uploader.joinable()) pd->uploader.join();
-        }
-    } join_on_error;
-    if (defer_uploads) {
-        pending.reset(new G16Pk::Pending());
-        G16Pk::Pending* pd = pending.get();
-        join_on_error.pd = pd;
-        st.early_uploader = &pd->uploader;
-        for (int w = 0; w < GA_KEY_NB_VECTORS; w++) {
-            pd->bytes[w] = alloc_bytes[w];
-            GA_HIP_CHECK(hipEventCreateWithFlags(&pd->ev[w], hipEventDisableTiming));
-        }
-        // in the order the proof consumes them: A, B, K (G1), B (G2) on the witness lane, Z last (it waits for h anyway)
-        struct Job { int which; void* dst; const void* src; size_t bytes; int prio; };
-        std::vector<Job> jobs;
-        void* const dst[GA_KEY_NB_VECTORS] = {st.v[GA_KEY_G1_A].d, st.v[GA_KEY_G1_B].d, st.v[GA_KEY_G1_Z].d, st.v[GA_KEY_G1_K].d, st.v[GA_KEY_G2_B].d};
-        int order = 0;
-        for (int w : {GA_KEY_G1_A, GA_KEY_G1_B, GA_KEY_G1_K, GA_KEY_G2_B, GA_KEY_G1_Z}) {
-            // turn priorities (common.hip.h): W 0 | A 1, B 2 | the solver's A, B, C 3 | K 4, G2.B 5, Z 6.  (K before G2.B, and its MSM
-            // before G2.B's in witness_msms: copies make little progress while the G2 bucket kernel runs -- 2 GiB in 72 ms where
-            // they take 38 -- so as much as possible is on the device before that kernel starts)
-            static const int prio[5] = {1, 2, 4, 5, 6};
-            jobs.push_back(Job{w, dst[w], vec[w], (size_t)len[w] * stage_point_bytes(key->curve, w), prio[order++]});
-        }
-        const int device = ctx->device;
-        pd->uploader = std::thread([pd, jobs, device, ctx]() {
-            int rc = GA_OK;
-            std::string err;
-            hipStream_t up = nullptr;
-            try {
-                if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&up, hipStreamNonBlocking) != hipSuccess) {
-                    rc = GA_ERR_HIP;
-                    err = "one-shot key upload: no stream";
-                }
-                for (const Job& j : jobs) {
-                    if (rc != GA_OK) break;
-                    hipError_t e = j.bytes ? ctx->h2d_pageable(j.dst, j.src, j.bytes, up, j.prio) : hipSuccess;
-                    if (e == hipSuccess) e = hipEventRecord(pd->ev[j.which], up);
-                    std::lock_guard<std::mutex> g(pd->mu);
-                    if (e != hipSuccess) {
-                        rc = GA_ERR_HIP;
-                        err = std::string("one-shot key upload: ") + hipGetErrorString(e);
-                    } else {
-                        pd->done[j.which] = true;
-                        pd->cv.notify_all();
-                        trace_event("uploaded vector", j.which);
-                    }
-                }
-            } catch (...) {   // (an exception leaving a thread function terminates the process)
-                rc = GA_ERR_STATE;
-                err = "one-shot key upload: exception in the uploader thread";
-            }
-            if (up) {   // the host vectors may be released once this thread has been joined: every copy must have left them
-                if (hipStreamSynchronize(up) != hipSuccess && rc == GA_OK) {
-                    rc = GA_ERR_HIP;
-                    err = "one-shot key upload: stream synchronize failed";
-                }
-                hipStreamDestroy(up);
-            }
-            if (rc != GA_OK) {
-                std::lock_guard<std::mutex> g(pd->mu);
-                pd->rc = rc;
-                pd->err = err;
-                pd->cv.notify_all();
-            }
-        });
-    }
-
-    const void* pt[GA_KEY_NB_POINTS] = {key->g1_alpha, key->g1_beta, key->g1_delta, key->g2_beta, key->g2_delta};
-    for (int q = 0; q < GA_KEY_NB_POINTS; q++) GA_CHECK(stage_set_point(&st, q, pt[q]));
-    for (uint32_t i = 0; i < key->nb_commitments; i++) GA_CHECK(stage_add_commitment_key(&st, key->ck_basis[i], key->ck_basis_exp_sigma[i], key->ck_len[i]));
-    if (key->len_k_remove) st.k_remove.assign(key->k_remove, key->k_remove + key->len_k_remove);
-    tr.mark("points, infinity masks, commitment keys staged");
-    G16Pk* pk = nullptr;
-    GA_DISPATCH_CURVE(key->curve, GA_CHECK(stage_finish<C>(&st, defer_uploads ? -1 : key->precompute, &pk)));
-    tr.mark("stage_finish");
-    if (defer_uploads) {
-        pk->pending = std::move(pending);   // (the key now owns the uploader: pk_free joins it)
-        join_on_error.pd = nullptr;
-    }
-    *out = pk;
-    return GA_OK;
-}
-
-
-// ---- key files -> staged key (keyio.hip.h has the formats) --------------------------------------------------------------------------
-// `count` encoded points of group G from `src`: decoded on the device, the part inside [keep_lo, keep_lo + keep_cnt) lands at d_dst
-template <class C, int G>
-static int decode_stream(Ctx* ctx, Staging& sg, ByteSource& src, uint64_t count, bool compressed, void* d_dst, uint64_t keep_lo,
-                         uint64_t keep_cnt) {
-    typedef typename GroupField<C, G>::F F;
-    const size_t enc = compressed ? sizeof(F) : 2 * sizeof(F), psz = sizeof(Affine<F>);
-    const uint64_t per_chunk = Staging::BYTES / enc;
-    GA_HIP_CHECK(hipMemsetAsync(sg.d_bad, 0, 4, ctx->stream));
-    int k = 0;
-    for (uint64_t done = 0; done < count; k ^= 1) {
-        const uint64_t cn = count - done < per_chunk ? count - done : per_chunk;
-        GA_HIP_CHECK(hipEventSynchronize(sg.ev[k]));   // the previous copy out of this staging buffer has finished
-        GA_CHECK(src.read(sg.h[k], cn * enc));
-        GA_HIP_CHECK(hipMemcpyAsync(sg.d_bytes, sg.h[k], cn * enc, hipMemcpyHostToDevice, ctx->stream));
-        GA_HIP_CHECK(hipEventRecord(sg.ev[k], ctx->stream));
-        hipLaunchKernelGGL((key_decode_kernel<C, G>), dim3((unsigned)((cn + 63) / 64)), dim3(64), 0, ctx->stream, (const uint8_t*)sg.d_bytes, cn,
-                           compressed ? 1 : 0, sg.d_points, sg.d_bad);
-        GA_KERNEL_CHECK();
-        const uint64_t b0 = done > keep_lo ? done : keep_lo;
-        const uint64_t e0 = done + cn < keep_lo + keep_cnt ? done + cn : keep_lo + keep_cnt;
-        if (e0 > b0)
-            GA_HIP_CHECK(hipMemcpyAsync((char*)d_dst + (b0 - keep_lo) * psz, (const char*)sg.d_points + (b0 - done) * psz, (e0 - b0) * psz,
-                                        hipMemcpyDeviceToDevice, ctx->stream));
-        done += cn;
-    }
-    uint32_t bad = 0;
-    GA_HIP_CHECK(hipMemcpyAsync(&bad, sg.d_bad, 4, hipMemcpyDeviceToHost, ctx->stream));
-    GA_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if (bad) {
-        set_error("key file: %u of %llu points do not decode (bad flag bits, coordinate >= p, or not on the curve)", bad,
-                  (unsigned long long)count);
-        return GA_ERR_INVALID;
-    }
-    return GA_OK;
-}
-
-// a []G1Affine / []G2Affine of the Encoder: u32 BE length, then the points (all compressed or all uncompressed)
-// mode: the encoding of the STREAM (1 compressed, 0 raw), fixed once from [alpha]1 -- which is never infinity -- by pk_read; -1 =
-// unknown, guess from the first byte of the vector (a vector that starts with a point at infinity is then ambiguous on BN254,
-// whose infinity flag is the same in both encodings)
-template <class C, int G>
-static int read_encoded_vector(G16Stage* st, Staging& sg, ByteSource& src, int which, void** d_plain, uint64_t* len_out, int mode = -1) {
-    typedef typename GroupField<C, G>::F F;
-    uint32_t len = 0;
-    GA_CHECK(src.u32be(&len));
-    bool compressed = mode != 0;
-    if (len && mode < 0) {
-        uint8_t b0;
-        GA_CHECK(src.peek(&b0, 1));
-        PointFlags f;
-        if (!point_flags<C>(b0, &f)) {
-            set_error("key file: malformed flag bits 0x%02x at the head of a point vector", b0);
-            return GA_ERR_INVALID;
-        }
-        compressed = f.compressed || (f.infinity && C::ID == GA_BLS12_381 && (b0 & 0x80));
-    }
-    if (len_out) *len_out = len;
-    GA_CHECK(src.expect(len, compressed ? sizeof(Affine<F>) / 2 : sizeof(Affine<F>), "a point vector"));   // before any allocation
-    if (which >= 0) {
-        GA_CHECK(stage_reserve(st, which, len));
-        G16Stage::Vec& x = st->v[which];
-        GA_CHECK((decode_stream<C, G>(st->ctx, sg, src, len, compressed, x.d, x.lo, x.cnt)));
-        x.seen = len;
-        return GA_OK;
-    }
-    *d_plain = nullptr;   // a commitment basis: kept whole
-    hipError_t e = device_malloc(d_plain, len ? (size_t)len * sizeof(Affine<F>) : 16);
-    if (e != hipSuccess) {
-        set_error("key file: hipMalloc of a commitment basis failed: %s", hipGetErrorString(e));
-        return GA_ERR_NOMEM;
-    }
-    return decode_stream<C, G>(st->ctx, sg, src, len, compressed, *d_plain, 0, len);
-}
-
-// a slice of unsafe.WriteSlice: u64 LE length + gnark's own memory image; no arithmetic, file -> pinned buffer -> HBM
-template <class C, int G>
-static int read_dumped_vector(G16Stage* st, Staging& sg, ByteSource& src, int which, void** d_plain, uint64_t* len_out) {
-    typedef typename GroupField<C, G>::F F;
-    const size_t psz = sizeof(Affine<F>);
-    uint64_t len = 0;
-    GA_CHECK(src.u64le(&len));
-    if (len >= (1ull << 40)) {
-        set_error("key dump: implausible slice length %llu", (unsigned long long)len);
-        return GA_ERR_INVALID;
-    }
-    if (len_out) *len_out = len;
-    GA_CHECK(src.expect(len, psz, "a dumped slice"));   // before any allocation
-    char* plain = nullptr;
-    if (which >= 0) GA_CHECK(stage_reserve(st, which, len));
-    else {
-        hipError_t e = device_malloc((void**)&plain, len ? len * psz : 16);
-        if (e != hipSuccess) {
-            set_error("key dump: hipMalloc of a commitment basis failed: %s", hipGetErrorString(e));
-            return GA_ERR_NOMEM;
-        }
-        *d_plain = plain;
-    }
-    const uint64_t per_chunk = Staging::BYTES / psz;
-    int k = 0;
-    for (uint64_t done = 0; done < len; k ^= 1) {
-        const uint64_t cn = len - done < per_chunk ? len - done : per_chunk;
-        GA_HIP_CHECK(hipEventSynchronize(sg.ev[k]));
-        GA_CHECK(src.read(sg.h[k], cn * psz));
-        if (which >= 0) GA_CHECK(stage_append(st, which, sg.h[k], cn, /*pinned=*/true));
-        else GA_HIP_CHECK(hipMemcpyAsync(plain + done * psz, sg.h[k], cn * psz, hipMemcpyHostToDevice, st->ctx->stream));
-        GA_HIP_CHECK(hipEventRecord(sg.ev[k], st->ctx->stream));
-        done += cn;
-    }
-    GA_HIP_CHECK(hipStreamSynchronize(st->ctx->stream));
-    return GA_OK;
-}
-
-// one point of the header (alpha, beta, delta): host arithmetic; advances the source by its encoded length
-// *mode: -1 = not known yet, 0 = the stream holds uncompressed points, 1 = compressed; set by the first finite point.  BN254 has
-// one flag value (0b01) for infinity in both modes, so an infinity point takes the size of the stream's mode (compressed when the
-// mode is still unknown -- the size gnark-crypto's SetBytes consumes for it).
-template <class C, int G>
-static int read_header_point(ByteSource& src, std::vector<uint8_t>* out_image, int* mode = nullptr) {
-    typedef typename GroupField<C, G>::F F;
-    uint8_t buf[2 * sizeof(F)];
-    GA_CHECK(src.peek(buf, 1));
-    PointFlags f;
-    if (!point_flags<C>(buf[0], &f)) {
-        set_error("key file: malformed flag bits 0x%02x", buf[0]);
-        return GA_ERR_INVALID;
-    }
-    bool compressed = f.compressed;
-    if (f.infinity && C::ID == GA_BN254) compressed = !(mode && *mode == 0);
-    if (!f.infinity && mode && *mode < 0) *mode = f.compressed ? 1 : 0;
-    const size_t len = compressed ? sizeof(F) : 2 * sizeof(F);
-    GA_CHECK(src.read(buf, len));
-    Affine<F> p;
-    if (!point_decode<C, G>(buf, f.compressed, &p)) {
-        set_error("key file: header point does not decode");
-        return GA_ERR_INVALID;
-    }
-    out_image->assign(reinterpret_cast<const uint8_t*>(&p), reinterpret_cast<const uint8_t*>(&p) + sizeof(p));
-    return GA_OK;
-}
-
-// fft.Domain.WriteTo: cardinality + five fr elements (+ the withPrecompute byte of newer gnark-crypto versions, detected by
-// trying to decode [alpha]1 right after it)
-template <class C>
-static int read_domain(ByteSource& src, uint64_t* cardinality) {
-    typedef Fe<typename C::FpP> F1;
-    GA_CHECK(src.u64be(cardinality));
-    uint8_t skip[5 * 32];
-    GA_CHECK(src.read(skip, sizeof skip));
-    if (*cardinality == 0 || (*cardinality & (*cardinality - 1)) || *cardinality > (1ull << C::FrP::ADICITY)) {
-        set_error("key file: domain cardinality %llu is not a power of two within the field's 2-adicity", (unsigned long long)*cardinality);
-        return GA_ERR_INVALID;
-    }
-    uint8_t win[1 + 2 * sizeof(F1)];
-    GA_CHECK(src.peek(win, sizeof win));
-    auto decodes = [&](const uint8_t* b) {
-        PointFlags f;
-        Affine<F1> p;
-        return point_flags<C>(b[0], &f) && !f.infinity && point_decode<C, GA_G1>(b, f.compressed, &p);
-    };
-    if (win[0] <= 1 && decodes(win + 1)) {
-        uint8_t flag;
-        return src.read(&flag, 1);   // withPrecompute
-    }
-    if (decodes(win)) return GA_OK;
-    set_error("key file: [alpha]1 does not decode after the domain block (neither with nor without the withPrecompute byte)");
-    return GA_ERR_INVALID;
-}
-
-static bool source_is_dump(ByteSource& src) {
-    uint8_t m[8];
-    static const uint8_t marker[8] = {0xef, 0xbe, 0xad, 0xde, 0, 0, 0, 0};   // uint64(0xdeadbeef) as this (little-endian) platform stores it
-    return src.peek(m, 8) == GA_OK && memcmp(m, marker, 8) == 0;
-}
-
-template <class C>
-static int pk_read(Ctx* ctx, ByteSource& src, int32_t precompute, uint32_t shard_index, uint32_t shard_count, const uint64_t* k_remove,
-                   uint64_t len_k_remove, G16Pk** out) {
-    G16Stage st;
-    st.ctx = ctx;
-    st.curve = C::ID;
-    st.shard_index = shard_index;
-    st.shard_count = shard_count ? shard_count : 1;
-    if (st.shard_index >= st.shard_count) {
-        set_error("proving key: shard_index %u >= shard_count %u", st.shard_index, st.shard_count);
-        return GA_ERR_INVALID;
-    }
-    Staging sg;
-    GA_CHECK(sg.init());
-    const bool dump = source_is_dump(src);
-    if (dump) {
-        uint8_t m[8];
-        GA_CHECK(src.read(m, 8));
-    }
-    GA_CHECK(read_domain<C>(src, &st.n));
-    auto header_tail = [&]() -> int {   // nbWires, NbInfinityA, NbInfinityB, InfinityA, InfinityB, nbCommitments (marshal.go:263-270,335-349)
-        uint64_t nb_wires, nia, nib;
-        GA_CHECK(src.u64be(&nb_wires));
-        GA_CHECK(src.u64be(&nia));
-        GA_CHECK(src.u64be(&nib));
-        if (nb_wires >= (1ull << 32)) {
-            set_error("key file: %llu wires", (unsigned long long)nb_wires);
-            return GA_ERR_INVALID;
-        }
-        if (nia > nb_wires || nib > nb_wires) {
-            set_error("key file: %llu / %llu infinity entries for %llu wires", (unsigned long long)nia, (unsigned long long)nib, (unsigned long long)nb_wires);
-            return GA_ERR_INVALID;
-        }
-        if (src.fd < 0 && 2 * nb_wires > src.mem_len - src.mem_pos) {   // (never size a buffer from an untrusted count alone)
-            set_error("key image: unexpected end of input (%llu wires announced, %zu bytes left)", (unsigned long long)nb_wires, src.mem_len - src.mem_pos);
-            return GA_ERR_INVALID;
-        }
-        st.nb_wires = nb_wires;
-        for (int k = 0; k < 2; k++) {
-            st.inf[k].clear();
-            for (uint64_t done = 0; done < nb_wires;) {   // grown as the bytes really arrive
-                const uint64_t cn = nb_wires - done < (1u << 20) ? nb_wires - done : (1u << 20);
-                st.inf[k].resize(done + cn);
-                GA_CHECK(src.read(st.inf[k].data() + done, cn));
-                done += cn;
-            }
-            st.have_inf[k] = true;
-            uint64_t ones = 0;
-            for (uint8_t b : st.inf[k]) ones += b != 0;
-            if (ones != (k == 0 ? nia : nib)) {
-                set_error("key file: Infinity%c holds %llu set entries, the header says %llu", k == 0 ? 'A' : 'B', (unsigned long long)ones,
-                          (unsigned long long)(k == 0 ? nia : nib));
-                return GA_ERR_INVALID;
-            }
-        }
-        return GA_OK;
-    };
-    uint32_t nb_commitments = 0;
-    int mode = -1;   // compressed (1) or raw (0) stream: taken from [alpha]1, the first point, which is never infinity
-    if (!dump) {   // ReadFrom order, marshal.go:316-330
-        GA_CHECK((read_header_point<C, GA_G1>(src, &st.pts[GA_KEY_G1_ALPHA], &mode)));
-        GA_CHECK((read_header_point<C, GA_G1>(src, &st.pts[GA_KEY_G1_BETA], &mode)));
-        GA_CHECK((read_header_point<C, GA_G1>(src, &st.pts[GA_KEY_G1_DELTA], &mode)));
-        for (int w : {GA_KEY_G1_A, GA_KEY_G1_B, GA_KEY_G1_Z, GA_KEY_G1_K}) GA_CHECK((read_encoded_vector<C, GA_G1>(&st, sg, src, w, nullptr, nullptr, mode)));
-        GA_CHECK((read_header_point<C, GA_G2>(src, &st.pts[GA_KEY_G2_BETA], &mode)));
-        GA_CHECK((read_header_point<C, GA_G2>(src, &st.pts[GA_KEY_G2_DELTA], &mode)));
-        GA_CHECK((read_encoded_vector<C, GA_G2>(&st, sg, src, GA_KEY_G2_B, nullptr, nullptr, mode)));
-        GA_CHECK(header_tail());
-        GA_CHECK(src.u32be(&nb_commitments));
-    } else {       // ReadDump order, marshal.go:459-478
-        GA_CHECK((read_header_point<C, GA_G1>(src, &st.pts[GA_KEY_G1_ALPHA])));
-        GA_CHECK((read_header_point<C, GA_G1>(src, &st.pts[GA_KEY_G1_BETA])));
-        GA_CHECK((read_header_point<C, GA_G1>(src, &st.pts[GA_KEY_G1_DELTA])));
-        GA_CHECK((read_header_point<C, GA_G2>(src, &st.pts[GA_KEY_G2_BETA])));
-        GA_CHECK((read_header_point<C, GA_G2>(src, &st.pts[GA_KEY_G2_DELTA])));
-        GA_CHECK(header_tail());
-        GA_CHECK(src.u32be(&nb_commitments));
-        for (int w : {GA_KEY_G1_A, GA_KEY_G1_B, GA_KEY_G1_Z, GA_KEY_G1_K}) GA_CHECK((read_dumped_vector<C, GA_G1>(&st, sg, src, w, nullptr, nullptr)));
-        GA_CHECK((read_dumped_vector<C, GA_G2>(&st, sg, src, GA_KEY_G2_B, nullptr, nullptr)));
-    }
-    if (nb_commitments > 4096) {
-        set_error("key file: implausible number of commitment keys %u", nb_commitments);
-        return GA_ERR_INVALID;
-    }
-    for (uint32_t i = 0; i < nb_commitments; i++) {   // pedersen.ProvingKey: Basis, BasisExpSigma
-        void *db = nullptr, *ds = nullptr;
-        uint64_t lb = 0, ls = 0;
-        int rc = dump ? read_dumped_vector<C, GA_G1>(&st, sg, src, -1, &db, &lb) : read_encoded_vector<C, GA_G1>(&st, sg, src, -1, &db, &lb, mode);
-        if (rc == GA_OK) rc = dump ? read_dumped_vector<C, GA_G1>(&st, sg, src, -1, &ds, &ls) : read_encoded_vector<C, GA_G1>(&st, sg, src, -1, &ds, &ls, mode);
-        if (rc == GA_OK && lb != ls) {
-            set_error("key file: commitment key %u has %llu basis points and %llu sigma points", i, (unsigned long long)lb, (unsigned long long)ls);
-            rc = GA_ERR_INVALID;
-        }
-        if (rc != GA_OK) {
-            hipFree(db);
-            hipFree(ds);
-            return rc;
-        }
-        st.d_ck_basis.push_back(db);
-        st.d_ck_sigma.push_back(ds);
-        st.ck_len.push_back(lb);
-    }
-    if (len_k_remove) st.k_remove.assign(k_remove, k_remove + len_k_remove);
-    return stage_finish<C>(&st, precompute, out);
-}
-
-// ---- key writers: the host description (ga_g16_key) -> WriteTo / WriteRawTo / WriteDump bytes ------------------------------------------
-template <class C, int G>
-static int write_encoded_vector(Ctx* ctx, Staging& sg, ByteSink& dst, const void* pts, uint64_t len, bool compressed) {
-    typedef typename GroupField<C, G>::F F;
-    if (len >= (1ull << 32)) {
-        set_error("key writer: a vector of %llu points does not fit the u32 length prefix", (unsigned long long)len);
-        return GA_ERR_INVALID;
-    }
-    GA_CHECK(dst.u32be((uint32_t)len));
-    const size_t enc = compressed ? sizeof(F) : 2 * sizeof(F), psz = sizeof(Affine<F>);
-    const uint64_t per_chunk = Staging::BYTES / psz;
-    for (uint64_t done = 0; done < len;) {
-        const uint64_t cn = len - done < per_chunk ? len - done : per_chunk;
-        GA_HIP_CHECK(hipMemcpyAsync(sg.d_points, (const char*)pts + done * psz, cn * psz, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL((key_encode_kernel<C, G>), dim3((unsigned)((cn + 63) / 64)), dim3(64), 0, ctx->stream, (const void*)sg.d_points, cn,
-                           compressed ? 1 : 0, sg.d_bytes);
-        GA_KERNEL_CHECK();
-        GA_HIP_CHECK(hipMemcpyAsync(sg.h[0], sg.d_bytes, cn * enc, hipMemcpyDeviceToHost, ctx->stream));
-        GA_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        GA_CHECK(dst.write(sg.h[0], cn * enc));
-        done += cn;
-    }
-    return GA_OK;
-}
-template <class C, int G>
-static int write_header_point(ByteSink& dst, const void* affine, bool compressed) {
-    typedef typename GroupField<C, G>::F F;
-    Affine<F> p;
-    memcpy(&p, affine, sizeof p);
-    uint8_t buf[2 * sizeof(F)];
-    point_encode<C, G>(p, compressed, buf);
-    return dst.write(buf, compressed ? sizeof(F) : 2 * sizeof(F));
-}
-template <class C>
-static int write_domain(ByteSink& dst, uint64_t n) {
-    typedef typename C::FrP FrP;
-    typedef Fe<FrP> F;
-    const int logn = ilog2_u64(n);
-    if ((1ull << logn) != n || logn > FrP::ADICITY) {
-        set_error("key writer: domain cardinality %llu", (unsigned long long)n);
-        return GA_ERR_INVALID;
-    }
-    F w = fe_const<FrP>(FrP::ROOT), wi = fe_const<FrP>(FrP::ROOT_INV);
-    for (int k = 0; k < FrP::ADICITY - logn; k++) {
-        w = sqr(w);
-        wi = sqr(wi);
-    }
-    F card = fe_zero<FrP>();
-    card.l[0] = (uint32_t)n;
-    card.l[1] = (uint32_t)(n >> 32);
-    const F elems[5] = {inv(to_mont(card)), w, wi, fe_const<FrP>(FrP::GEN), fe_const<FrP>(FrP::GEN_INV)};
-    GA_CHECK(dst.u64be(n));
-    for (const F& e : elems) {
-        uint8_t b[32];
-        fe_to_be_bytes(e, b);
-        GA_CHECK(dst.write(b, 32));
-    }
-    const uint8_t with_precompute = 1;
-    return dst.write(&with_precompute, 1);
-}
-template <class C>
-static int key_write(Ctx* ctx, const ga_g16_key* key, int format, ByteSink& dst) {
-    typedef Fe<typename C::FpP> F1;
-    typedef Fe2<typename C::FpP> F2;
-    const bool dump = format == GA_KEY_FORMAT_DUMP, compressed = format == GA_KEY_FORMAT_COMPRESSED;
-    Staging sg;
-    GA_CHECK(sg.init());
-    if (dump) GA_CHECK(dst.u64le(0xdeadbeefull));
-    GA_CHECK(write_domain<C>(dst, key->domain_cardinality));
-    const bool hc = compressed;   // header points follow the encoder's mode (raw for the dump)
-    auto tail = [&]() -> int {
-        GA_CHECK(dst.u64be(key->nb_wires));
-        GA_CHECK(dst.u64be(key->nb_infinity_a));
-        GA_CHECK(dst.u64be(key->nb_infinity_b));
-        GA_CHECK(dst.write(key->infinity_a, key->nb_wires));
-        GA_CHECK(dst.write(key->infinity_b, key->nb_wires));
-        return dst.u32be(key->nb_commitments);
-    };
-    auto slice = [&](const void* p, uint64_t len, size_t psz) -> int {
-        GA_CHECK(dst.u64le(len));
-        return dst.write(p, len * psz);
-    };
-    GA_CHECK((write_header_point<C, GA_G1>(dst, key->g1_alpha, hc)));
-    GA_CHECK((write_header_point<C, GA_G1>(dst, key->g1_beta, hc)));
-    GA_CHECK((write_header_point<C, GA_G1>(dst, key->g1_delta, hc)));
-    if (!dump) {
-        GA_CHECK((write_encoded_vector<C, GA_G1>(ctx, sg, dst, key->g1_a, key->len_a, compressed)));
-        GA_CHECK((write_encoded_vector<C, GA_G1>(ctx, sg, dst, key->g1_b, key->len_b, compressed)));
-        GA_CHECK((write_encoded_vector<C, GA_G1>(ctx, sg, dst, key->g1_z, key->len_z, compressed)));
-        GA_CHECK((write_encoded_vector<C, GA_G1>(ctx, sg, dst, key->g1_k, key->len_k, compressed)));
-    }
-    GA_CHECK((write_header_point<C, GA_G2>(dst, key->g2_beta, hc)));
-    GA_CHECK((write_header_point<C, GA_G2>(dst, key->g2_delta, hc)));
-    if (!dump) GA_CHECK((write_encoded_vector<C, GA_G2>(ctx, sg, dst, key->g2_b, key->len_b2, compressed)));
-    GA_CHECK(tail());
-    if (dump) {
-        GA_CHECK(slice(key->g1_a, key->len_a, sizeof(Affine<F1>)));
-        GA_CHECK(slice(key->g1_b, key->len_b, sizeof(Affine<F1>)));
-        GA_CHECK(slice(key->g1_z, key->len_z, sizeof(Affine<F1>)));
-        GA_CHECK(slice(key->g1_k, key->len_k, sizeof(Affine<F1>)));
-        GA_CHECK(slice(key->g2_b, key->len_b2, sizeof(Affine<F2>)));
-    }
-    for (uint32_t i = 0; i < key->nb_commitments; i++) {
-        if (dump) {
-            GA_CHECK(slice(key->ck_basis[i], key->ck_len[i], sizeof(Affine<F1>)));
-            GA_CHECK(slice(key->ck_basis_exp_sigma[i], key->ck_len[i], sizeof(Affine<F1>)));
-        } else {
-            GA_CHECK((write_encoded_vector<C, GA_G1>(ctx, sg, dst, key->ck_basis[i], key->ck_len[i], compressed)));
-            GA_CHECK((write_encoded_vector<C, GA_G1>(ctx, sg, dst, key->ck_basis_exp_sigma[i], key->ck_len[i], compressed)));
-        }
-    }
-    return GA_OK;
-}
-
-// Proof.ReadFrom (marshal.go:62-86): Ar | Bs | Krs | u32 n | n commitments | CommitmentPok, compressed or uncompressed points
-template <class C>
-static int proof_unmarshal(const uint8_t* data, size_t len, void* proof_out, void* commitments_out, uint32_t max_commitments,
-                           uint32_t* n_commitments, void* pok_out, size_t* consumed) {
-    typedef Fe<typename C::FpP> F1;
-    typedef Fe2<typename C::FpP> F2;
-    ByteSource src;
-    src.mem = data;
-    src.mem_len = len;
-    std::vector<uint8_t> img;
-    int mode = -1;
-    char* o = reinterpret_cast<char*>(proof_out);
-    GA_CHECK((read_header_point<C, GA_G1>(src, &img, &mode)));
-    memcpy(o, img.data(), sizeof(Affine<F1>));
-    GA_CHECK((read_header_point<C, GA_G2>(src, &img, &mode)));
-    memcpy(o + sizeof(Affine<F1>), img.data(), sizeof(Affine<F2>));
-    GA_CHECK((read_header_point<C, GA_G1>(src, &img, &mode)));
-    memcpy(o + sizeof(Affine<F1>) + sizeof(Affine<F2>), img.data(), sizeof(Affine<F1>));
-    uint32_t n = 0;
-    GA_CHECK(src.u32be(&n));
-    if (n > max_commitments || (n && !commitments_out)) {
-        set_error("proof: %u commitments, room for %u", n, max_commitments);
-        return GA_ERR_INVALID;
-    }
-    for (uint32_t i = 0; i < n; i++) {
-        GA_CHECK((read_header_point<C, GA_G1>(src, &img, &mode)));
-        memcpy(reinterpret_cast<char*>(commitments_out) + (size_t)i * sizeof(Affine<F1>), img.data(), sizeof(Affine<F1>));
-    }
-    GA_CHECK((read_header_point<C, GA_G1>(src, &img, &mode)));
-    if (pok_out) memcpy(pok_out, img.data(), sizeof(Affine<F1>));
-    if (n_commitments) *n_commitments = n;
-    if (consumed) *consumed = src.mem_pos;
-    return GA_OK;
-}
 
 // ---- the device part of a proof, in pieces (a multi-GPU proof runs them on different devices) ----------------------------------
 // witness_msms : upload W (only the wire range this shard's bases cover), filter, MSM A, B (G1 + G2), K      prove.go:147-237,283
@@ -1285,6 +52,30 @@ static int witness_upload(G16Pk* pk, const SlotLease& slot, const void* w, uint6
     if (hi > lo) GA_HIP_CHECK(ctx->h2d_pageable((char*)d_w + lo * 32, (const char*)w + lo * 32, (hi - lo) * 32, up_stream, /*prio=*/0));
     return GA_OK;
 }
+
+// The four partial sums of a proof before randomisation -- Ar, Bs1, Krs in G1, Bs2 in G2 -- which add up across shards.
+// store / load: the ABI's partials image (include/gnark_amd.h, ga_g16_prove_partial): three G1 Jacobians, then one G2 Jacobian.
+template <class C>
+struct G16Partials {
+    typedef Fe<typename C::FpP> F1;
+    typedef Fe2<typename C::FpP> F2;
+    XYZZ<F1> ar = xyzz_inf<F1>(), bs1 = xyzz_inf<F1>(), krs = xyzz_inf<F1>();
+    XYZZ<F2> bs2 = xyzz_inf<F2>();
+    void store(void* out) const {
+        char* o = reinterpret_cast<char*>(out);
+        host_store_jac<F1>(o, ar);
+        host_store_jac<F1>(o + sizeof(Jac<F1>), bs1);
+        host_store_jac<F1>(o + 2 * sizeof(Jac<F1>), krs);
+        host_store_jac<F2>(o + 3 * sizeof(Jac<F1>), bs2);
+    }
+    void load(const void* in) {
+        const char* i = reinterpret_cast<const char*>(in);
+        ar = host_load_jac<F1>(i);
+        bs1 = host_load_jac<F1>(i + sizeof(Jac<F1>));
+        krs = host_load_jac<F1>(i + 2 * sizeof(Jac<F1>));
+        bs2 = host_load_jac<F2>(i + 3 * sizeof(Jac<F1>));
+    }
+};
 
 // What the two halves of a split proof share (prove_partial): the sort of the whole witness, made once on the lane of the
 // witness MSMs, and the K MSM, which goes to whichever lane gets to it first.
@@ -1372,11 +163,11 @@ static int k_msm(G16Pk* pk, uint64_t nb_public, WitnessShared& sh, XYZZ<Fe<typen
     return host_msm<C, GA_G1>(ctx, pk->d_k, d_wk, pk->len_k, true, out, pk->win_index, pk->win_count);
 }
 
-// The witness MSMs A, B (G1 and G2) and -- unless the partner lane claims it first -- K, on the calling thread's lane.
-// `sh` is posted as soon as the shared witness sort has been launched; o_k is written only when *did_k comes back true.
+// The witness MSMs A, B (G1 and G2) and -- unless the partner lane claims it first -- K, on the calling thread's lane, into
+// out->ar, bs1, bs2 and (the K sum alone) krs.  `sh` is posted as soon as the shared witness sort has been launched; out->krs is
+// written only when *did_k comes back true.
 template <class C>
-static int witness_msms(G16Pk* pk, const SlotLease& slot, uint64_t nb_public, WitnessShared& sh, XYZZ<Fe<typename C::FpP>>* o_ar,
-                        XYZZ<Fe<typename C::FpP>>* o_bs1, XYZZ<Fe<typename C::FpP>>* o_k, XYZZ<Fe2<typename C::FpP>>* o_bs2, bool* did_k) {
+static int witness_msms(G16Pk* pk, const SlotLease& slot, uint64_t nb_public, WitnessShared& sh, G16Partials<C>* out, bool* did_k) {
     typedef Fe<typename C::FpP> F1;
     typedef Fe2<typename C::FpP> F2;
     Ctx* ctx = pk->ctx;
@@ -1415,8 +206,9 @@ static int witness_msms(G16Pk* pk, const SlotLease& slot, uint64_t nb_public, Wi
     if (!pk->share_a) GA_CHECK(util_gather_fr<C>(ctx, d_wa, d_w, pk->d_idx_a, pk->len_a));
     if (!pk->share_b || !pk->share_b2) GA_CHECK(util_gather_fr<C>(ctx, d_wb, d_w, pk->d_idx_b, pk->len_b));   // (G2.B may be plain beside a wire-indexed G1.B)
     // ---- the witness MSMs (prove.go:194,207,237,283) ---------------------------------------------------
-    XYZZ<F1> ar, bs1;
-    XYZZ<F2> bs2;
+    XYZZ<F1>& ar = out->ar;
+    XYZZ<F1>& bs1 = out->bs1;
+    XYZZ<F2>& bs2 = out->bs2;
     {   // every vector on its own kind of path: wire-indexed table over the shared sort, compact table with its own digits + sort, or
         // plain bases (no table: un-pinned MSM, one bucket set per window + Horner)
         MsmPrepared prep;
@@ -1448,7 +240,7 @@ static int witness_msms(G16Pk* pk, const SlotLease& slot, uint64_t nb_public, Wi
             const bool k_fits = pk->share_k && !ctx->is_degenerate(pk->d_k);
             if (nt + (k_fits ? 1 : 0) >= 2) {
                 if (k_fits && sh.claim_k(current_lane())) {
-                    want(true, pk->d_k, o_k);
+                    want(true, pk->d_k, &out->krs);
                     *did_k = true;
                 }
                 if (nt >= 2) {
@@ -1478,7 +270,7 @@ static int witness_msms(G16Pk* pk, const SlotLease& slot, uint64_t nb_public, Wi
             GA_CHECK((host_msm<C, GA_G1>(ctx, pk->d_b, d_wb, pk->len_b, true, &bs1, pk->win_index, pk->win_count)));
         }
         if (pk->pending && !*did_k && sh.claim_k(current_lane())) {   // a key still on its way: K's MSM before G2.B's (upload order)
-            GA_CHECK(k_msm<C>(pk, nb_public, sh, o_k));
+            GA_CHECK(k_msm<C>(pk, nb_public, sh, &out->krs));
             *did_k = true;
         }
         if (pk->share_b2) {   // G2.B wire-indexed: the shared witness sort again
@@ -1498,11 +290,8 @@ static int witness_msms(G16Pk* pk, const SlotLease& slot, uint64_t nb_public, Wi
             GA_CHECK((host_msm<C, GA_G2>(ctx, pk->d_b2, d_wb, pk->len_b2, true, &bs2, pk->win_index, pk->win_count)));
         }
     }
-    *o_ar = ar;
-    *o_bs1 = bs1;
-    *o_bs2 = bs2;
     if (!*did_k && sh.claim_k(current_lane())) {
-        GA_CHECK(k_msm<C>(pk, nb_public, sh, o_k));
+        GA_CHECK(k_msm<C>(pk, nb_public, sh, &out->krs));
         *did_k = true;
     }
     return GA_OK;
@@ -1590,8 +379,7 @@ static int preload_solution(G16Pk* pk, const SlotLease& slot, const void* w, con
 // as in round 2.  Everything is joined before this function returns, so no host pointer outlives the call.
 template <class C>
 static int prove_partial(G16Pk* pk, const SlotLease& slot, bool preloaded, const void* w, const void* a, const void* b, const void* c,
-                         uint64_t n_constraints, uint64_t nb_public, XYZZ<Fe<typename C::FpP>>* o_ar, XYZZ<Fe<typename C::FpP>>* o_bs1,
-                         XYZZ<Fe<typename C::FpP>>* o_krs, XYZZ<Fe2<typename C::FpP>>* o_bs2) {
+                         uint64_t n_constraints, uint64_t nb_public, G16Partials<C>* out) {
     typedef Fe<typename C::FpP> F1;
     Ctx* ctx = pk->ctx;
     const uint64_t n = pk->n;
@@ -1611,7 +399,7 @@ static int prove_partial(G16Pk* pk, const SlotLease& slot, bool preloaded, const
     for (int k = 0; k < 3; k++) GA_HIP_CHECK(hipEventCreateWithFlags(&ev[k].ev, hipEventDisableTiming));
     // W first: the witness MSMs only need W, and the (PCIe-competing) upload of A, B, C starts when this one has been handed over
     if (!preloaded) GA_CHECK(witness_upload(pk, slot, w, nb_public));
-    XYZZ<F1> k_part = xyzz_inf<F1>(), k_part_h = xyzz_inf<F1>(), z_part = xyzz_inf<F1>();
+    XYZZ<F1> k_part_h = xyzz_inf<F1>(), z_part = xyzz_inf<F1>();
     bool split = false, h_did_k = false;
     int h_rc = GA_OK;
     std::string h_err;
@@ -1691,7 +479,7 @@ static int prove_partial(G16Pk* pk, const SlotLease& slot, bool preloaded, const
         });
     ThreadJoiner joiner{helper};
     bool did_k = false;
-    const int w_rc = witness_msms<C>(pk, slot, nb_public, sh, o_ar, o_bs1, &k_part, o_bs2, &did_k);
+    const int w_rc = witness_msms<C>(pk, slot, nb_public, sh, out, &did_k);
     if (helper.joinable()) helper.join();
     if (w_rc != GA_OK) {
         hipStreamSynchronize(ctx->work_stream());
@@ -1711,7 +499,7 @@ static int prove_partial(G16Pk* pk, const SlotLease& slot, bool preloaded, const
         set_error("prove: the K MSM was claimed by no lane");
         return GA_ERR_STATE;
     }
-    *o_krs = add(did_k ? k_part : k_part_h, z_part);
+    out->krs = add(did_k ? out->krs : k_part_h, z_part);
     return GA_OK;
 }
 
@@ -1743,8 +531,7 @@ static XYZZ<F> fixed_base_mul(const std::vector<uint8_t>& blob, const uint32_t* 
 
 // Host epilogue with the prover's randomness (prove.go:171-185,199-200,212-214,241-269,287-292) on the SUMMED partials.
 template <class C>
-static int finish(G16Pk* pk, XYZZ<Fe<typename C::FpP>> ar, XYZZ<Fe<typename C::FpP>> bs1, XYZZ<Fe<typename C::FpP>> krs,
-                  XYZZ<Fe2<typename C::FpP>> bs2, const void* r_mont, const void* s_mont, void* proof_out) {
+static int finish(G16Pk* pk, G16Partials<C> p, const void* r_mont, const void* s_mont, void* proof_out) {
     typedef typename C::FrP FrP;
     typedef Fe<typename C::FpP> F1;
     typedef Fe2<typename C::FpP> F2;
@@ -1761,15 +548,15 @@ static int finish(G16Pk* pk, XYZZ<Fe<typename C::FpP>> ar, XYZZ<Fe<typename C::F
         fixed_base_table<F2>(host_load_affine<F2>(pk->delta2.data()), pk->delta2_tab);
     });
     XYZZ<F1> d_r = fixed_base_mul<F1>(pk->delta1_tab, rc.l), d_s = fixed_base_mul<F1>(pk->delta1_tab, sc.l), d_kr = fixed_base_mul<F1>(pk->delta1_tab, krc.l);
-    bs1 = add(add(bs1, host_load_affine<F1>(pk->beta1.data())), d_s);
-    ar = add(add(ar, host_load_affine<F1>(pk->alpha1.data())), d_r);
-    krs = add(krs, d_kr);
-    krs = add(krs, scalar_mul2(ar, sc.l, bs1, rc.l, 8));   // s*Ar + r*Bs1 on one doubling chain
-    bs2 = add(add(bs2, fixed_base_mul<F2>(pk->delta2_tab, sc.l)), host_load_affine<F2>(pk->beta2.data()));
+    p.bs1 = add(add(p.bs1, host_load_affine<F1>(pk->beta1.data())), d_s);
+    p.ar = add(add(p.ar, host_load_affine<F1>(pk->alpha1.data())), d_r);
+    p.krs = add(p.krs, d_kr);
+    p.krs = add(p.krs, scalar_mul2(p.ar, sc.l, p.bs1, rc.l, 8));   // s*Ar + r*Bs1 on one doubling chain
+    p.bs2 = add(add(p.bs2, fixed_base_mul<F2>(pk->delta2_tab, sc.l)), host_load_affine<F2>(pk->beta2.data()));
     char* o = reinterpret_cast<char*>(proof_out);
-    host_store_affine<F1>(o, ar);
-    host_store_affine<F2>(o + sizeof(Affine<F1>), bs2);
-    host_store_affine<F1>(o + sizeof(Affine<F1>) + sizeof(Affine<F2>), krs);
+    host_store_affine<F1>(o, p.ar);
+    host_store_affine<F2>(o + sizeof(Affine<F1>), p.bs2);
+    host_store_affine<F1>(o + sizeof(Affine<F1>) + sizeof(Affine<F2>), p.krs);
     return GA_OK;
 }
 
@@ -1811,134 +598,6 @@ static int fold_pok(const void* poks, uint64_t n, const void* challenge_mont, vo
     host_store_affine<F1>(out, acc);
     return GA_OK;
 }
-
-// ---- compressed point encoding (marshal.go:33-58 via gnark-crypto's encoder [EXT]) ---------
-template <class P>
-static bool lex_largest(const Fe<P>& y_mont) {
-    // y > (p-1)/2 on the canonical value
-    Fe<P> y = from_mont(y_mont);
-    uint32_t half[P::N];
-    for (int i = 0; i < P::N; i++) half[i] = (P::MOD[i] >> 1) | (i + 1 < P::N ? (P::MOD[i + 1] << 31) : 0);
-    for (int i = P::N - 1; i >= 0; i--) {
-        if (y.l[i] > half[i]) return true;
-        if (y.l[i] < half[i]) return false;
-    }
-    return false;
-}
-template <class P>
-static void be_bytes(const Fe<P>& x_mont, uint8_t* out) {
-    Fe<P> x = from_mont(x_mont);
-    for (int i = 0; i < P::N; i++) {
-        uint32_t v = x.l[P::N - 1 - i];
-        out[4 * i] = v >> 24;
-        out[4 * i + 1] = v >> 16;
-        out[4 * i + 2] = v >> 8;
-        out[4 * i + 3] = v;
-    }
-}
-template <class C>
-static void flag_bytes(uint8_t* out, bool inf, bool largest) {
-    if (C::ID == GA_BN254) out[0] |= inf ? 0x40 : (largest ? 0xC0 : 0x80);
-    else out[0] |= inf ? 0xC0 : (0x80 | (largest ? 0x20 : 0));
-}
-template <class C>
-static size_t compress_g1(const void* aff, uint8_t* out) {
-    typedef typename C::FpP P;
-    Affine<Fe<P>> a;
-    memcpy(&a, aff, sizeof(a));
-    const size_t nb = P::N * 4;
-    memset(out, 0, nb);
-    if (is_inf(a)) {
-        flag_bytes<C>(out, true, false);
-        return nb;
-    }
-    be_bytes<P>(a.x, out);
-    flag_bytes<C>(out, false, lex_largest<P>(a.y));
-    return nb;
-}
-template <class C>
-static size_t compress_g2(const void* aff, uint8_t* out) {
-    typedef typename C::FpP P;
-    Affine<Fe2<P>> a;
-    memcpy(&a, aff, sizeof(a));
-    const size_t nb = P::N * 4;
-    memset(out, 0, 2 * nb);
-    if (is_inf(a)) {
-        flag_bytes<C>(out, true, false);
-        return 2 * nb;
-    }
-    be_bytes<P>(a.x.c1, out);        // A1 || A0
-    be_bytes<P>(a.x.c0, out + nb);
-    bool largest = is_zero(a.y.c1) ? lex_largest<P>(a.y.c0) : lex_largest<P>(a.y.c1);
-    flag_bytes<C>(out, false, largest);
-    return 2 * nb;
-}
-
-// uncompressed encodings (curve.RawEncoding(), Proof.WriteRawTo marshal.go:25-30): x | y big-endian, G2 coordinates A1 | A0;
-// infinity = flag byte 0x40 followed by zeros
-template <class C>
-static size_t raw_g1(const void* aff, uint8_t* out) {
-    typedef typename C::FpP P;
-    Affine<Fe<P>> a;
-    memcpy(&a, aff, sizeof(a));
-    const size_t nb = P::N * 4;
-    memset(out, 0, 2 * nb);
-    if (is_inf(a)) {
-        out[0] = 0x40;
-        return 2 * nb;
-    }
-    be_bytes<P>(a.x, out);
-    be_bytes<P>(a.y, out + nb);
-    return 2 * nb;
-}
-template <class C>
-static size_t raw_g2(const void* aff, uint8_t* out) {
-    typedef typename C::FpP P;
-    Affine<Fe2<P>> a;
-    memcpy(&a, aff, sizeof(a));
-    const size_t nb = P::N * 4;
-    memset(out, 0, 4 * nb);
-    if (is_inf(a)) {
-        out[0] = 0x40;
-        return 4 * nb;
-    }
-    be_bytes<P>(a.x.c1, out);
-    be_bytes<P>(a.x.c0, out + nb);
-    be_bytes<P>(a.y.c1, out + 2 * nb);
-    be_bytes<P>(a.y.c0, out + 3 * nb);
-    return 4 * nb;
-}
-
-template <class C>
-static int marshal(const void* proof, const void* commitments, uint32_t ncom, const void* pok, uint8_t* out, size_t cap, size_t* len,
-                   bool raw = false) {
-    typedef Fe<typename C::FpP> F1;
-    typedef Fe2<typename C::FpP> F2;
-    const size_t nb = C::FpP::N * 4;
-    const size_t need = (raw ? 2 : 1) * (nb + 2 * nb + nb + (size_t)ncom * nb + nb) + 4;
-    if (cap < need) {
-        set_error("proof marshal: buffer too small (%zu < %zu)", cap, need);
-        return GA_ERR_INVALID;
-    }
-    const char* p = reinterpret_cast<const char*>(proof);
-    size_t o = 0;
-    auto g1 = [&](const void* a, uint8_t* dst) { return raw ? raw_g1<C>(a, dst) : compress_g1<C>(a, dst); };
-    o += g1(p, out + o);
-    o += raw ? raw_g2<C>(p + sizeof(Affine<F1>), out + o) : compress_g2<C>(p + sizeof(Affine<F1>), out + o);
-    o += g1(p + sizeof(Affine<F1>) + sizeof(Affine<F2>), out + o);
-    out[o] = ncom >> 24;   // uint32 big-endian number of commitments (the slice encoder's length prefix)
-    out[o + 1] = ncom >> 16;
-    out[o + 2] = ncom >> 8;
-    out[o + 3] = ncom;
-    o += 4;
-    for (uint32_t i = 0; i < ncom; i++) o += g1((const char*)commitments + i * sizeof(Affine<F1>), out + o);
-    Affine<F1> inf;
-    memset(&inf, 0, sizeof(inf));
-    o += g1(pok ? pok : &inf, out + o);   // CommitmentPok (infinity without commitments)
-    *len = o;
-    return GA_OK;
-}
-
 // One proof over several devices from ONE process: keys[i] = shard i of n of the same proving key, each in a context on its own
 // device.  One host thread per device for the MSMs plus one for the H side (second lane of the context); the three chains of computeH
 // run on the first three devices beside their witness MSMs (with n >= 3 every device uploads 1/n of A, B, C over its own PCIe link and
@@ -1973,12 +632,7 @@ template <class C>
 static int prove_multi(G16Pk* const* pks, uint32_t n, const void* w, const void* a, const void* b, const void* c, uint64_t n_constraints,
                        uint64_t nb_public, const void* r, const void* s, void* proof_out) {
     typedef Fe<typename C::FpP> F1;
-    typedef Fe2<typename C::FpP> F2;
-    struct Part {
-        XYZZ<F1> ar, bs1, k, z;
-        XYZZ<F2> bs2;
-    };
-    std::vector<Part> parts(n);
+    std::vector<G16Partials<C>> parts(n);   // per device; the Z sum is added into krs
     const uint64_t N = pks[0]->n;
     // which device runs which chain: a on 0, b on 1 (or 0), c on 2 (or 0)
     const uint32_t owner[3] = {0, n >= 2 ? 1u : 0u, n >= 3 ? 2u : 0u};
@@ -2086,7 +740,7 @@ static int prove_multi(G16Pk* const* pks, uint32_t n, const void* w, const void*
             WitnessShared wsh;
             bool did_k = false;
             if (hipEventCreateWithFlags(&wsh.w_ev, hipEventDisableTiming) != hipSuccess ||
-                witness_msms<C>(pk, slot, nb_public, wsh, &parts[t].ar, &parts[t].bs1, &parts[t].k, &parts[t].bs2, &did_k) != GA_OK) {
+                witness_msms<C>(pk, slot, nb_public, wsh, &parts[t], &did_k) != GA_OK) {
                 bail("multi-device prove: witness MSMs");
                 ok = false;
             }
@@ -2111,7 +765,9 @@ static int prove_multi(G16Pk* const* pks, uint32_t n, const void* w, const void*
             h_slice[0] = (char*)dev0_buf[0] + pk->off_z * 32;
         }
         if (!sh.barrier(2)) return;
-        if (z_msm<C>(pk, h_slice[t], &parts[t].z) != GA_OK) bail("multi-device prove: Z MSM");
+        XYZZ<F1> z;
+        if (z_msm<C>(pk, h_slice[t], &z) != GA_OK) bail("multi-device prove: Z MSM");
+        else parts[t].krs = add(parts[t].krs, z);
         sh.barrier(3);
     };
     std::vector<std::thread> threads;
@@ -2122,15 +778,14 @@ static int prove_multi(G16Pk* const* pks, uint32_t n, const void* w, const void*
         set_error("%s", sh.err.c_str());
         return GA_ERR_HIP;
     }
-    XYZZ<F1> ar = xyzz_inf<F1>(), bs1 = xyzz_inf<F1>(), krs = xyzz_inf<F1>();
-    XYZZ<F2> bs2 = xyzz_inf<F2>();
-    for (uint32_t t = 0; t < n; t++) {
-        ar = add(ar, parts[t].ar);
-        bs1 = add(bs1, parts[t].bs1);
-        krs = add(krs, add(parts[t].k, parts[t].z));
-        bs2 = add(bs2, parts[t].bs2);
+    G16Partials<C> sum;
+    for (const G16Partials<C>& q : parts) {
+        sum.ar = add(sum.ar, q.ar);
+        sum.bs1 = add(sum.bs1, q.bs1);
+        sum.krs = add(sum.krs, q.krs);
+        sum.bs2 = add(sum.bs2, q.bs2);
     }
-    return finish<C>(pks[0], ar, bs1, krs, bs2, r, s, proof_out);
+    return finish<C>(pks[0], sum, r, s, proof_out);
 }
 
 }  // namespace ga
@@ -2139,6 +794,7 @@ using namespace ga;
 
 extern "C" {
 
+// ---- proving keys (g16_key.hip.h) ------------------------------------------------------------------------------------------------
 int ga_g16_pk_create(ga_ctx* h, const ga_g16_key* key, ga_g16_pk** out) try {
     GA_ABI_ENTRY();
     Ctx* ctx = reinterpret_cast<Ctx*>(h);
@@ -2277,10 +933,8 @@ int ga_g16_builder_finish(ga_g16_builder* b, int32_t precompute, ga_g16_pk** out
     {
         CtxLock g(st->ctx);
         G16Pk* pk = nullptr;
-        rc = GA_ERR_INVALID;
         try {
-            if (st->curve == GA_BN254) rc = stage_finish<Bn254>(st, precompute, &pk);
-            else if (st->curve == GA_BLS12_381) rc = stage_finish<Bls12381>(st, precompute, &pk);
+            rc = stage_finish_any(st, precompute, &pk);
         } catch (const std::exception& e) {   // (host allocations sized by the key: no exception crosses the C ABI)
             set_error("ga_g16_builder_finish: %s", e.what());
             rc = GA_ERR_NOMEM;
@@ -2301,157 +955,12 @@ void ga_g16_builder_destroy(ga_g16_builder* b) try {
     delete st;
 } GA_ABI_CATCH_VOID
 
-static void pk_destroy_impl(G16Pk* pk) {
-    if (!pk) return;
-    {   // wait for every entry point still working on this key (provers on other lanes, epilogues outside the device lock)
-        std::unique_lock<std::mutex> u(pk->use_mu);
-        pk->dying = true;
-        pk->use_cv.wait(u, [&] { return pk->users == 0; });
-    }
-    CtxLock g(pk->ctx);
-    for (int l = 0; l < GA_NUM_LANES; l++) hipStreamSynchronize(pk->ctx->lane_stream[l]);
-    pk_free(pk);
-}
-
 void ga_g16_pk_destroy(ga_g16_pk* p) try {
     GA_ABI_ENTRY();
     pk_destroy_impl(reinterpret_cast<G16Pk*>(p));
 } GA_ABI_CATCH_VOID
 
-static int g16_prove_impl(ga_g16_pk* p, const void* w, const void* a, const void* b, const void* c, uint64_t n_constraints,
-                 uint64_t nb_public, const void* r, const void* s, void* proof_out) {
-    G16Pk* pk = reinterpret_cast<G16Pk*>(p);
-    if (!pk || !w || !a || !b || !c || !r || !s || !proof_out) {
-        set_error("ga_g16_prove: null argument");
-        return GA_ERR_INVALID;
-    }
-    GA_PK_USE(pk, "ga_g16_prove");
-    if (pk->shard_count != 1 || pk->win_count != 1) {
-        set_error("ga_g16_prove: this key holds one share of a sharded key (base range %u/%u, windows %u/%u); use ga_g16_prove_multi or "
-                  "ga_g16_prove_partial + ga_g16_finish", pk->shard_index, pk->shard_count, pk->win_index, pk->win_count);
-        return GA_ERR_STATE;
-    }
-    // Two callers may be inside at once (two goroutines proving on one device).  The first holds the device lock and works on
-    // lanes 0/1 (witness MSMs / H side, prove_partial).  The second finds the device busy and computes its proof on lanes 2/3 --
-    // own streams, own scratch namespaces -- so the two proofs run CONCURRENTLY: uploads hide behind the other proof's kernels
-    // and the kernels interleave.  When lane 2 is taken as well, or while the profiler records stages, or with GA_G16_LANES=1,
-    // the caller stages its solution in its input slot and queues for the device.  The host epilogue always runs outside the
-    // device lock.  ga_g16_lane_stats reports how the calls of a context were scheduled.
-    // A lane-2 proof that cannot get its scratch (precompute = 0 fills HBM with tables beside ONE caller's scratch: at 2^26 a second
-    // caller's 77 GiB are not there) gives back what lanes 2/3 hold and queues for the device like a third caller would -- a proof
-    // is slower then, never failed.
-    Ctx* ctx = pk->ctx;
-    SlotLease slot(ctx);
-    std::unique_lock<std::mutex> dev(ctx->mu, std::try_to_lock);
-    std::unique_lock<std::mutex> lane2(ctx->lane_mu[2], std::defer_lock);
-    hipSetDevice(ctx->device);
-    for (int attempt = 0;; attempt++) {
-        bool preloaded = false;
-        int lane = 0;
-        if (!dev.owns_lock()) {
-            if (attempt == 0 && !ctx->profiling && ctx->tun.g16_lanes > 1 && lane2.try_lock()) {
-                lane = 2;
-                ctx->stat_lane2++;
-            } else {
-                GA_CHECK(preload_solution(pk, slot, w, a, b, c, n_constraints, nb_public));
-                preloaded = true;
-                dev.lock();
-                ctx->stat_queued++;
-            }
-        }
-        if (lane == 0 && !preloaded) ctx->stat_lane0++;
-        int partial_rc = GA_OK;
-        {
-            LaneScope on_lane(lane);
-            if (lane == 0) ctx->tun.read_env();
-            GA_DISPATCH_CURVE(pk->curve, {
-                XYZZ<Fe<typename C::FpP>> ar, bs1, krs;
-                XYZZ<Fe2<typename C::FpP>> bs2;
-                partial_rc = prove_partial<C>(pk, slot, preloaded, w, a, b, c, n_constraints, nb_public, &ar, &bs1, &krs, &bs2);
-                if (partial_rc == GA_OK) {
-                    const bool profiling = ctx->profiling;
-                    if (lane == 0 && !profiling) dev.unlock();   // the stage list of the profiler is guarded by the device lock
-                    if (lane == 2) lane2.unlock();
-                    return finish<C>(pk, ar, bs1, krs, bs2, r, s, proof_out);
-                }
-            });
-        }
-        if (partial_rc != GA_ERR_NOMEM || lane != 2) return partial_rc;
-        // (everything prove_partial started on lanes 2/3 has joined; hipFree synchronises with what their streams still hold)
-        ctx->scratch_free_lanes(2);
-        ctx->stat_lane2--;
-        lane2.unlock();
-    }
-}
-
-// out[0..3] = ga_g16_prove calls of this context that ran on lanes 0/1, on lanes 2/3 beside another proof, that staged their
-// inputs and queued for the device, and proofs whose H side ran on a partner lane (any entry point); out[4..5] = device bytes
-// of scratch held by lanes 0/1 and by lanes 2/3
-int ga_g16_lane_stats(ga_ctx* h, uint64_t* out6) try {
-    GA_ABI_ENTRY();
-    Ctx* ctx = reinterpret_cast<Ctx*>(h);
-    if (!ctx || !out6) {
-        set_error("ga_g16_lane_stats: null argument");
-        return GA_ERR_INVALID;
-    }
-    out6[0] = ctx->stat_lane0;
-    out6[1] = ctx->stat_lane2;
-    out6[2] = ctx->stat_queued;
-    out6[3] = ctx->stat_split;
-    out6[4] = out6[5] = 0;
-    std::lock_guard<std::mutex> g(ctx->scratch_mu);
-    for (const auto& kv : ctx->scratch) {
-        const size_t at = kv.first.rfind('@');
-        const int lane = at == std::string::npos ? 0 : atoi(kv.first.c_str() + at + 1);
-        out6[lane < 2 ? 4 : 5] += kv.second.second;
-    }
-    return GA_OK;
-} GA_ABI_CATCH
-
-static int g16_prove_partial_impl(ga_g16_pk* p, const void* w, const void* a, const void* b, const void* c, uint64_t n_constraints,
-                         uint64_t nb_public, void* partials_out) {
-    G16Pk* pk = reinterpret_cast<G16Pk*>(p);
-    if (!pk || !w || !a || !b || !c || !partials_out) {
-        set_error("ga_g16_prove_partial: null argument");
-        return GA_ERR_INVALID;
-    }
-    GA_PK_USE(pk, "ga_g16_prove_partial");
-    SlotLease slot(pk->ctx);   // always slot first, device lock second (ga_g16_prove's order)
-    CtxLock g(pk->ctx);
-    GA_DISPATCH_CURVE(pk->curve, {
-        typedef Fe<typename C::FpP> F1;
-        typedef Fe2<typename C::FpP> F2;
-        XYZZ<F1> ar, bs1, krs;
-        XYZZ<F2> bs2;
-        GA_CHECK(prove_partial<C>(pk, slot, false, w, a, b, c, n_constraints, nb_public, &ar, &bs1, &krs, &bs2));
-        char* o = reinterpret_cast<char*>(partials_out);
-        host_store_jac<F1>(o, ar);
-        host_store_jac<F1>(o + sizeof(Jac<F1>), bs1);
-        host_store_jac<F1>(o + 2 * sizeof(Jac<F1>), krs);
-        host_store_jac<F2>(o + 3 * sizeof(Jac<F1>), bs2);
-    });
-    return GA_OK;
-}
-
-int ga_g16_finish(ga_g16_pk* p, const void* partials_sum, const void* r, const void* s, void* proof_out) try {
-    GA_ABI_ENTRY();
-    G16Pk* pk = reinterpret_cast<G16Pk*>(p);
-    if (!pk || !partials_sum || !r || !s || !proof_out) {
-        set_error("ga_g16_finish: null argument");
-        return GA_ERR_INVALID;
-    }
-    GA_PK_USE(pk, "ga_g16_finish");
-    GA_DISPATCH_CURVE(pk->curve, {
-        typedef Fe<typename C::FpP> F1;
-        typedef Fe2<typename C::FpP> F2;
-        const char* i = reinterpret_cast<const char*>(partials_sum);
-        return finish<C>(pk, host_load_jac<F1>(i), host_load_jac<F1>(i + sizeof(Jac<F1>)), host_load_jac<F1>(i + 2 * sizeof(Jac<F1>)),
-                         host_load_jac<F2>(i + 3 * sizeof(Jac<F1>)), r, s, proof_out);
-    });
-    return GA_OK;
-} GA_ABI_CATCH
-
-// ---- pieces of a sharded proof (multi-GPU orchestration by the caller: gnark_amd/multigpu.py over RCCL, or ga_g16_prove_multi) ----
+// what a key holds, for callers that orchestrate a sharded proof themselves (gnark_amd/multigpu.py)
 int ga_g16_shard_layout(ga_g16_pk* p, uint64_t* out6) try {
     GA_ABI_ENTRY();
     G16Pk* pk = reinterpret_cast<G16Pk*>(p);
@@ -2485,165 +994,7 @@ int ga_g16_table_layout(ga_g16_pk* p, uint64_t* out2) try {
     return GA_OK;
 } GA_ABI_CATCH
 
-static int g16_witness_partial_impl(ga_g16_pk* p, const void* w, uint64_t nb_public, void* partials_out) {
-    G16Pk* pk = reinterpret_cast<G16Pk*>(p);
-    if (!pk || !w || !partials_out) {
-        set_error("ga_g16_witness_partial: null argument");
-        return GA_ERR_INVALID;
-    }
-    GA_PK_USE(pk, "ga_g16_witness_partial");
-    SlotLease slot(pk->ctx);
-    CtxLock g(pk->ctx);
-    GA_DISPATCH_CURVE(pk->curve, {
-        typedef Fe<typename C::FpP> F1;
-        typedef Fe2<typename C::FpP> F2;
-        XYZZ<F1> ar, bs1, krs;
-        XYZZ<F2> bs2;
-        GA_CHECK(witness_upload(pk, slot, w, nb_public));
-        WitnessShared sh;
-        GA_HIP_CHECK(hipEventCreateWithFlags(&sh.w_ev, hipEventDisableTiming));
-        bool did_k = false;
-        GA_CHECK(witness_msms<C>(pk, slot, nb_public, sh, &ar, &bs1, &krs, &bs2, &did_k));
-        char* o = reinterpret_cast<char*>(partials_out);
-        host_store_jac<F1>(o, ar);
-        host_store_jac<F1>(o + sizeof(Jac<F1>), bs1);
-        host_store_jac<F1>(o + 2 * sizeof(Jac<F1>), krs);
-        host_store_jac<F2>(o + 3 * sizeof(Jac<F1>), bs2);
-    });
-    return GA_OK;
-}
-
-int ga_g16_h_chain(ga_g16_pk* p, const void* v, uint64_t n_constraints, void* out_dev) try {
-    GA_ABI_ENTRY();
-    G16Pk* pk = reinterpret_cast<G16Pk*>(p);
-    if (!pk || !v || !out_dev) {
-        set_error("ga_g16_h_chain: null argument");
-        return GA_ERR_INVALID;
-    }
-    GA_PK_USE(pk, "ga_g16_h_chain");
-    LaneLock g(pk->ctx);   // beside the witness MSMs of the same shard when the caller runs them from another thread
-    GA_CHECK(h_upload(pk, v, n_constraints, out_dev, pk->ctx->work_stream()));
-    GA_DISPATCH_CURVE(pk->curve, GA_CHECK(ntt_domain_h_chain<C>(pk->dom, out_dev)));
-    GA_HIP_CHECK(hipStreamSynchronize(pk->ctx->work_stream()));   // the buffer is handed to another stream / device next
-    return GA_OK;
-} GA_ABI_CATCH
-
-int ga_g16_h_chain_dev(ga_g16_pk* p, void* buf_dev, uint64_t n_constraints) try {
-    GA_ABI_ENTRY();
-    G16Pk* pk = reinterpret_cast<G16Pk*>(p);
-    if (!pk || !buf_dev) {
-        set_error("ga_g16_h_chain_dev: null argument");
-        return GA_ERR_INVALID;
-    }
-    GA_PK_USE(pk, "ga_g16_h_chain_dev");
-    if (n_constraints > pk->n) {
-        set_error("ga_g16_h_chain_dev: %llu constraints exceed the domain cardinality %llu", (unsigned long long)n_constraints,
-                  (unsigned long long)pk->n);
-        return GA_ERR_INVALID;
-    }
-    LaneLock g(pk->ctx);
-    hipStream_t st = pk->ctx->work_stream();
-    if (pk->n > n_constraints)   // computeH pads to the domain size (prove.go:356-359)
-        GA_HIP_CHECK(hipMemsetAsync((char*)buf_dev + n_constraints * 32, 0, (pk->n - n_constraints) * 32, st));
-    GA_DISPATCH_CURVE(pk->curve, GA_CHECK(ntt_domain_h_chain<C>(pk->dom, buf_dev)));
-    GA_HIP_CHECK(hipStreamSynchronize(st));
-    return GA_OK;
-} GA_ABI_CATCH
-
-int ga_g16_h_combine(ga_g16_pk* p, void* a_dev, const void* b_dev, const void* c_dev) try {
-    GA_ABI_ENTRY();
-    G16Pk* pk = reinterpret_cast<G16Pk*>(p);
-    if (!pk || !a_dev || !b_dev || !c_dev) {
-        set_error("ga_g16_h_combine: null argument");
-        return GA_ERR_INVALID;
-    }
-    GA_PK_USE(pk, "ga_g16_h_combine");
-    LaneLock g(pk->ctx);
-    GA_DISPATCH_CURVE(pk->curve, GA_CHECK(ntt_domain_h_combine<C>(pk->dom, a_dev, b_dev, c_dev)));
-    GA_HIP_CHECK(hipStreamSynchronize(pk->ctx->work_stream()));
-    return GA_OK;
-} GA_ABI_CATCH
-
-int ga_g16_z_partial(ga_g16_pk* p, const void* h_slice_dev, void* partial_out) try {
-    GA_ABI_ENTRY();
-    G16Pk* pk = reinterpret_cast<G16Pk*>(p);
-    if (!pk || (!h_slice_dev && pk->len_z) || !partial_out) {
-        set_error("ga_g16_z_partial: null argument");
-        return GA_ERR_INVALID;
-    }
-    GA_PK_USE(pk, "ga_g16_z_partial");
-    CtxLock g(pk->ctx);
-    GA_DISPATCH_CURVE(pk->curve, {
-        typedef Fe<typename C::FpP> F1;
-        XYZZ<F1> z;
-        GA_CHECK(z_msm<C>(pk, h_slice_dev, &z));
-        host_store_jac<F1>(partial_out, z);
-    });
-    return GA_OK;
-} GA_ABI_CATCH
-
-static int g16_prove_multi_impl(ga_g16_pk* const* keys, uint32_t n, const void* w, const void* a, const void* b, const void* c,
-                       uint64_t n_constraints, uint64_t nb_public, const void* r, const void* s, void* proof_out) {
-    if (!keys || n == 0 || n > 64 || !w || !a || !b || !c || !r || !s || !proof_out) {
-        set_error("ga_g16_prove_multi: null argument or unsupported device count");
-        return GA_ERR_INVALID;
-    }
-    G16Pk* const* pks = reinterpret_cast<G16Pk* const*>(keys);
-    for (uint32_t t = 0; t < n; t++) {
-        const bool by_range = pks[t] && pks[t]->shard_count == n && pks[t]->shard_index == t && pks[t]->win_count == 1;
-        const bool by_window = pks[t] && pks[t]->win_count == n && pks[t]->win_index == t && pks[t]->shard_count == 1;
-        if (!pks[t] || pks[t]->curve != pks[0]->curve || pks[t]->n != pks[0]->n || pks[t]->nb_wires != pks[0]->nb_wires ||
-            !(n == 1 || by_range || by_window) || (pks[t]->win_count > 1) != (pks[0]->win_count > 1)) {
-            set_error("ga_g16_prove_multi: keys[%u] must be shard %u of %u of the same proving key (all by base range or all by windows)", t, t, n);
-            return GA_ERR_INVALID;
-        }
-        for (uint32_t q = 0; q < t; q++)
-            if (pks[q]->ctx == pks[t]->ctx) {
-                set_error("ga_g16_prove_multi: keys[%u] and keys[%u] share a context; one context per shard", q, t);
-                return GA_ERR_INVALID;
-            }
-    }
-    if (n == 1) return ga_g16_prove(keys[0], w, a, b, c, n_constraints, nb_public, r, s, proof_out);
-    std::vector<std::unique_ptr<PkUse>> uses;
-    for (uint32_t t = 0; t < n; t++) {
-        uses.emplace_back(new PkUse(pks[t]));
-        if (!uses.back()->ok) {
-            set_error("ga_g16_prove_multi: keys[%u] is being destroyed", t);
-            return GA_ERR_STATE;
-        }
-    }
-    // One multi-device proof at a time per process: every worker thread holds its device's lock while it waits for the others at
-    // the barriers, so two calls over the same devices could each hold one lock the other needs (A holds dev0 and waits for its
-    // worker on dev1, B holds dev1 and waits for its worker on dev0).  A sharded proof occupies all its devices anyway.
-    static std::mutex multi_mu;
-    std::lock_guard<std::mutex> multi_guard(multi_mu);
-    for (uint32_t t = 0; t < n; t++)   // peer access both ways between device 0 and the others (errors = already enabled / same device)
-        for (uint32_t q = 0; q < n; q++)
-            if (q != t && (t == 0 || q == 0) && pks[t]->ctx->device != pks[q]->ctx->device) {
-                hipSetDevice(pks[t]->ctx->device);
-                (void)hipDeviceEnablePeerAccess(pks[q]->ctx->device, 0);
-                (void)hipGetLastError();
-            }
-    GA_DISPATCH_CURVE(pks[0]->curve, return (prove_multi<C>(pks, n, w, a, b, c, n_constraints, nb_public, r, s, proof_out)));
-    return GA_OK;
-}
-
 // ---- key files and proof bytes ------------------------------------------------------------------------------------------------
-static int pk_read_any(ga_ctx* h, int curve, ByteSource& src, int32_t precompute, uint32_t shard_index, uint32_t shard_count,
-                       const uint64_t* k_remove, uint64_t len_k_remove, ga_g16_pk** out, uint64_t* bytes_read) {
-    Ctx* ctx = reinterpret_cast<Ctx*>(h);
-    if (!ctx || !out || (len_k_remove && !k_remove)) {
-        set_error("ga_g16_pk_read: null argument");
-        return GA_ERR_INVALID;
-    }
-    CtxLock g(ctx);
-    G16Pk* pk = nullptr;
-    GA_DISPATCH_CURVE(curve, GA_CHECK(pk_read<C>(ctx, src, precompute, shard_index, shard_count, k_remove, len_k_remove, &pk)));
-    *out = reinterpret_cast<ga_g16_pk*>(pk);
-    if (bytes_read) *bytes_read = src.consumed;
-    return GA_OK;
-}
-
 int ga_g16_pk_read_mem(ga_ctx* h, int curve, const uint8_t* data, size_t len, int32_t precompute, uint32_t shard_index, uint32_t shard_count,
                        const uint64_t* k_remove, uint64_t len_k_remove, ga_g16_pk** out, uint64_t* bytes_read) try {
     GA_ABI_ENTRY();
@@ -2763,26 +1114,278 @@ int ga_g1_marshal_uncompressed(int curve, const void* affine, uint8_t* out, size
         return GA_ERR_INVALID;
     }
     GA_DISPATCH_CURVE(curve, {
-        typedef typename C::FpP P;
-        const size_t nb = P::N * 4;
-        if (cap < 2 * nb) {
+        if (cap < 2 * sizeof(Fe<typename C::FpP>)) {
             set_error("ga_g1_marshal_uncompressed: buffer too small");
             return GA_ERR_INVALID;
         }
-        Affine<Fe<P>> a;
-        memcpy(&a, affine, sizeof(a));
-        memset(out, 0, 2 * nb);
-        if (is_inf(a)) {
-            out[0] = C::ID == GA_BN254 ? 0x40 : 0x40;   // mUncompressedInfinity: 0b01<<6 (BN254), 0b010<<5 (BLS12-381)
-        } else {
-            be_bytes<P>(a.x, out);
-            be_bytes<P>(a.y, out + nb);
-        }
-        *len = 2 * nb;
+        *len = encode_point<C, GA_G1>(affine, false, out);
     });
     return GA_OK;
 } GA_ABI_CATCH
 
+// ---- proofs ----------------------------------------------------------------------------------------------------------------------
+static int g16_prove_impl(ga_g16_pk* p, const void* w, const void* a, const void* b, const void* c, uint64_t n_constraints,
+                 uint64_t nb_public, const void* r, const void* s, void* proof_out) {
+    G16Pk* pk = reinterpret_cast<G16Pk*>(p);
+    if (!pk || !w || !a || !b || !c || !r || !s || !proof_out) {
+        set_error("ga_g16_prove: null argument");
+        return GA_ERR_INVALID;
+    }
+    GA_PK_USE(pk, "ga_g16_prove");
+    if (pk->shard_count != 1 || pk->win_count != 1) {
+        set_error("ga_g16_prove: this key holds one share of a sharded key (base range %u/%u, windows %u/%u); use ga_g16_prove_multi or "
+                  "ga_g16_prove_partial + ga_g16_finish", pk->shard_index, pk->shard_count, pk->win_index, pk->win_count);
+        return GA_ERR_STATE;
+    }
+    // Two callers may be inside at once (two goroutines proving on one device).  The first holds the device lock and works on
+    // lanes 0/1 (witness MSMs / H side, prove_partial).  The second finds the device busy and computes its proof on lanes 2/3 --
+    // own streams, own scratch namespaces -- so the two proofs run CONCURRENTLY: uploads hide behind the other proof's kernels
+    // and the kernels interleave.  When lane 2 is taken as well, or while the profiler records stages, or with GA_G16_LANES=1,
+    // the caller stages its solution in its input slot and queues for the device.  The host epilogue always runs outside the
+    // device lock.  ga_g16_lane_stats reports how the calls of a context were scheduled.
+    // A lane-2 proof that cannot get its scratch (precompute = 0 fills HBM with tables beside ONE caller's scratch: at 2^26 a second
+    // caller's 77 GiB are not there) gives back what lanes 2/3 hold and queues for the device like a third caller would -- a proof
+    // is slower then, never failed.
+    Ctx* ctx = pk->ctx;
+    SlotLease slot(ctx);
+    std::unique_lock<std::mutex> dev(ctx->mu, std::try_to_lock);
+    std::unique_lock<std::mutex> lane2(ctx->lane_mu[2], std::defer_lock);
+    hipSetDevice(ctx->device);
+    for (int attempt = 0;; attempt++) {
+        bool preloaded = false;
+        int lane = 0;
+        if (!dev.owns_lock()) {
+            if (attempt == 0 && !ctx->profiling && ctx->tun.g16_lanes > 1 && lane2.try_lock()) {
+                lane = 2;
+                ctx->stat_lane2++;
+            } else {
+                GA_CHECK(preload_solution(pk, slot, w, a, b, c, n_constraints, nb_public));
+                preloaded = true;
+                dev.lock();
+                ctx->stat_queued++;
+            }
+        }
+        if (lane == 0 && !preloaded) ctx->stat_lane0++;
+        int partial_rc = GA_OK;
+        {
+            LaneScope on_lane(lane);
+            if (lane == 0) ctx->tun.read_env();
+            GA_DISPATCH_CURVE(pk->curve, {
+                G16Partials<C> part;
+                partial_rc = prove_partial<C>(pk, slot, preloaded, w, a, b, c, n_constraints, nb_public, &part);
+                if (partial_rc == GA_OK) {
+                    const bool profiling = ctx->profiling;
+                    if (lane == 0 && !profiling) dev.unlock();   // the stage list of the profiler is guarded by the device lock
+                    if (lane == 2) lane2.unlock();
+                    return finish<C>(pk, part, r, s, proof_out);
+                }
+            });
+        }
+        if (partial_rc != GA_ERR_NOMEM || lane != 2) return partial_rc;
+        // (everything prove_partial started on lanes 2/3 has joined; hipFree synchronises with what their streams still hold)
+        ctx->scratch_free_lanes(2);
+        ctx->stat_lane2--;
+        lane2.unlock();
+    }
+}
+
+// out[0..3] = ga_g16_prove calls of this context that ran on lanes 0/1, on lanes 2/3 beside another proof, that staged their
+// inputs and queued for the device, and proofs whose H side ran on a partner lane (any entry point); out[4..5] = device bytes
+// of scratch held by lanes 0/1 and by lanes 2/3
+int ga_g16_lane_stats(ga_ctx* h, uint64_t* out6) try {
+    GA_ABI_ENTRY();
+    Ctx* ctx = reinterpret_cast<Ctx*>(h);
+    if (!ctx || !out6) {
+        set_error("ga_g16_lane_stats: null argument");
+        return GA_ERR_INVALID;
+    }
+    out6[0] = ctx->stat_lane0;
+    out6[1] = ctx->stat_lane2;
+    out6[2] = ctx->stat_queued;
+    out6[3] = ctx->stat_split;
+    out6[4] = out6[5] = 0;
+    std::lock_guard<std::mutex> g(ctx->scratch_mu);
+    for (const auto& kv : ctx->scratch) {
+        const size_t at = kv.first.rfind('@');
+        const int lane = at == std::string::npos ? 0 : atoi(kv.first.c_str() + at + 1);
+        out6[lane < 2 ? 4 : 5] += kv.second.second;
+    }
+    return GA_OK;
+} GA_ABI_CATCH
+
+int ga_g16_prove_partial(ga_g16_pk* p, const void* w, const void* a, const void* b, const void* c, uint64_t n_constraints,
+                         uint64_t nb_public, void* partials_out) try {
+    GA_ABI_ENTRY();
+    G16Pk* pk = reinterpret_cast<G16Pk*>(p);
+    if (!pk || !w || !a || !b || !c || !partials_out) {
+        set_error("ga_g16_prove_partial: null argument");
+        return GA_ERR_INVALID;
+    }
+    GA_PK_USE(pk, "ga_g16_prove_partial");
+    SlotLease slot(pk->ctx);   // always slot first, device lock second (ga_g16_prove's order)
+    CtxLock g(pk->ctx);
+    GA_DISPATCH_CURVE(pk->curve, {
+        G16Partials<C> part;
+        GA_CHECK(prove_partial<C>(pk, slot, false, w, a, b, c, n_constraints, nb_public, &part));
+        part.store(partials_out);
+    });
+    return GA_OK;
+} GA_ABI_CATCH
+
+int ga_g16_finish(ga_g16_pk* p, const void* partials_sum, const void* r, const void* s, void* proof_out) try {
+    GA_ABI_ENTRY();
+    G16Pk* pk = reinterpret_cast<G16Pk*>(p);
+    if (!pk || !partials_sum || !r || !s || !proof_out) {
+        set_error("ga_g16_finish: null argument");
+        return GA_ERR_INVALID;
+    }
+    GA_PK_USE(pk, "ga_g16_finish");
+    GA_DISPATCH_CURVE(pk->curve, {
+        G16Partials<C> sum;
+        sum.load(partials_sum);
+        return finish<C>(pk, sum, r, s, proof_out);
+    });
+    return GA_OK;
+} GA_ABI_CATCH
+
+// ---- pieces of a sharded proof (multi-GPU orchestration by the caller: gnark_amd/multigpu.py over RCCL, or ga_g16_prove_multi) ----
+int ga_g16_witness_partial(ga_g16_pk* p, const void* w, uint64_t nb_public, void* partials_out) try {
+    GA_ABI_ENTRY();
+    G16Pk* pk = reinterpret_cast<G16Pk*>(p);
+    if (!pk || !w || !partials_out) {
+        set_error("ga_g16_witness_partial: null argument");
+        return GA_ERR_INVALID;
+    }
+    GA_PK_USE(pk, "ga_g16_witness_partial");
+    SlotLease slot(pk->ctx);
+    CtxLock g(pk->ctx);
+    GA_DISPATCH_CURVE(pk->curve, {
+        G16Partials<C> part;
+        GA_CHECK(witness_upload(pk, slot, w, nb_public));
+        WitnessShared sh;
+        GA_HIP_CHECK(hipEventCreateWithFlags(&sh.w_ev, hipEventDisableTiming));
+        bool did_k = false;
+        GA_CHECK(witness_msms<C>(pk, slot, nb_public, sh, &part, &did_k));
+        part.store(partials_out);
+    });
+    return GA_OK;
+} GA_ABI_CATCH
+
+int ga_g16_h_chain(ga_g16_pk* p, const void* v, uint64_t n_constraints, void* out_dev) try {
+    GA_ABI_ENTRY();
+    G16Pk* pk = reinterpret_cast<G16Pk*>(p);
+    if (!pk || !v || !out_dev) {
+        set_error("ga_g16_h_chain: null argument");
+        return GA_ERR_INVALID;
+    }
+    GA_PK_USE(pk, "ga_g16_h_chain");
+    LaneLock g(pk->ctx);   // beside the witness MSMs of the same shard when the caller runs them from another thread
+    GA_CHECK(h_upload(pk, v, n_constraints, out_dev, pk->ctx->work_stream()));
+    GA_DISPATCH_CURVE(pk->curve, GA_CHECK(ntt_domain_h_chain<C>(pk->dom, out_dev)));
+    GA_HIP_CHECK(hipStreamSynchronize(pk->ctx->work_stream()));   // the buffer is handed to another stream / device next
+    return GA_OK;
+} GA_ABI_CATCH
+
+int ga_g16_h_chain_dev(ga_g16_pk* p, void* buf_dev, uint64_t n_constraints) try {
+    GA_ABI_ENTRY();
+    G16Pk* pk = reinterpret_cast<G16Pk*>(p);
+    if (!pk || !buf_dev) {
+        set_error("ga_g16_h_chain_dev: null argument");
+        return GA_ERR_INVALID;
+    }
+    GA_PK_USE(pk, "ga_g16_h_chain_dev");
+    if (n_constraints > pk->n) {
+        set_error("ga_g16_h_chain_dev: %llu constraints exceed the domain cardinality %llu", (unsigned long long)n_constraints,
+                  (unsigned long long)pk->n);
+        return GA_ERR_INVALID;
+    }
+    LaneLock g(pk->ctx);
+    hipStream_t st = pk->ctx->work_stream();
+    if (pk->n > n_constraints)   // computeH pads to the domain size (prove.go:356-359)
+        GA_HIP_CHECK(hipMemsetAsync((char*)buf_dev + n_constraints * 32, 0, (pk->n - n_constraints) * 32, st));
+    GA_DISPATCH_CURVE(pk->curve, GA_CHECK(ntt_domain_h_chain<C>(pk->dom, buf_dev)));
+    GA_HIP_CHECK(hipStreamSynchronize(st));
+    return GA_OK;
+} GA_ABI_CATCH
+
+int ga_g16_h_combine(ga_g16_pk* p, void* a_dev, const void* b_dev, const void* c_dev) try {
+    GA_ABI_ENTRY();
+    G16Pk* pk = reinterpret_cast<G16Pk*>(p);
+    if (!pk || !a_dev || !b_dev || !c_dev) {
+        set_error("ga_g16_h_combine: null argument");
+        return GA_ERR_INVALID;
+    }
+    GA_PK_USE(pk, "ga_g16_h_combine");
+    LaneLock g(pk->ctx);
+    GA_DISPATCH_CURVE(pk->curve, GA_CHECK(ntt_domain_h_combine<C>(pk->dom, a_dev, b_dev, c_dev)));
+    GA_HIP_CHECK(hipStreamSynchronize(pk->ctx->work_stream()));
+    return GA_OK;
+} GA_ABI_CATCH
+
+int ga_g16_z_partial(ga_g16_pk* p, const void* h_slice_dev, void* partial_out) try {
+    GA_ABI_ENTRY();
+    G16Pk* pk = reinterpret_cast<G16Pk*>(p);
+    if (!pk || (!h_slice_dev && pk->len_z) || !partial_out) {
+        set_error("ga_g16_z_partial: null argument");
+        return GA_ERR_INVALID;
+    }
+    GA_PK_USE(pk, "ga_g16_z_partial");
+    CtxLock g(pk->ctx);
+    GA_DISPATCH_CURVE(pk->curve, {
+        typedef Fe<typename C::FpP> F1;
+        XYZZ<F1> z;
+        GA_CHECK(z_msm<C>(pk, h_slice_dev, &z));
+        host_store_jac<F1>(partial_out, z);
+    });
+    return GA_OK;
+} GA_ABI_CATCH
+
+int ga_g16_prove_multi(ga_g16_pk* const* keys, uint32_t n, const void* w, const void* a, const void* b, const void* c,
+                       uint64_t n_constraints, uint64_t nb_public, const void* r, const void* s, void* proof_out) try {
+    GA_ABI_ENTRY();
+    if (!keys || n == 0 || n > 64 || !w || !a || !b || !c || !r || !s || !proof_out) {
+        set_error("ga_g16_prove_multi: null argument or unsupported device count");
+        return GA_ERR_INVALID;
+    }
+    G16Pk* const* pks = reinterpret_cast<G16Pk* const*>(keys);
+    for (uint32_t t = 0; t < n; t++) {
+        const bool by_range = pks[t] && pks[t]->shard_count == n && pks[t]->shard_index == t && pks[t]->win_count == 1;
+        const bool by_window = pks[t] && pks[t]->win_count == n && pks[t]->win_index == t && pks[t]->shard_count == 1;
+        if (!pks[t] || pks[t]->curve != pks[0]->curve || pks[t]->n != pks[0]->n || pks[t]->nb_wires != pks[0]->nb_wires ||
+            !(n == 1 || by_range || by_window) || (pks[t]->win_count > 1) != (pks[0]->win_count > 1)) {
+            set_error("ga_g16_prove_multi: keys[%u] must be shard %u of %u of the same proving key (all by base range or all by windows)", t, t, n);
+            return GA_ERR_INVALID;
+        }
+        for (uint32_t q = 0; q < t; q++)
+            if (pks[q]->ctx == pks[t]->ctx) {
+                set_error("ga_g16_prove_multi: keys[%u] and keys[%u] share a context; one context per shard", q, t);
+                return GA_ERR_INVALID;
+            }
+    }
+    if (n == 1) return ga_g16_prove(keys[0], w, a, b, c, n_constraints, nb_public, r, s, proof_out);
+    std::vector<std::unique_ptr<PkUse>> uses;
+    for (uint32_t t = 0; t < n; t++) {
+        uses.emplace_back(new PkUse(pks[t]));
+        if (!uses.back()->ok) {
+            set_error("ga_g16_prove_multi: keys[%u] is being destroyed", t);
+            return GA_ERR_STATE;
+        }
+    }
+    // One multi-device proof at a time per process: every worker thread holds its device's lock while it waits for the others at
+    // the barriers, so two calls over the same devices could each hold one lock the other needs (A holds dev0 and waits for its
+    // worker on dev1, B holds dev1 and waits for its worker on dev0).  A sharded proof occupies all its devices anyway.
+    static std::mutex multi_mu;
+    std::lock_guard<std::mutex> multi_guard(multi_mu);
+    for (uint32_t t = 0; t < n; t++)   // peer access both ways between device 0 and the others (errors = already enabled / same device)
+        for (uint32_t q = 0; q < n; q++)
+            if (q != t && (t == 0 || q == 0) && pks[t]->ctx->device != pks[q]->ctx->device) {
+                hipSetDevice(pks[t]->ctx->device);
+                (void)hipDeviceEnablePeerAccess(pks[q]->ctx->device, 0);
+                (void)hipGetLastError();
+            }
+    GA_DISPATCH_CURVE(pks[0]->curve, return (prove_multi<C>(pks, n, w, a, b, c, n_constraints, nb_public, r, s, proof_out)));
+    return GA_OK;
+} GA_ABI_CATCH
 int ga_g16_commit(ga_g16_pk* p, uint32_t index, const void* values, uint64_t n_values, void* commitment_out, void* pok_out) try {
     GA_ABI_ENTRY();
     G16Pk* pk = reinterpret_cast<G16Pk*>(p);
@@ -2806,12 +1409,12 @@ int ga_g16_fold_pok(int curve, const void* poks, uint64_t n, const void* challen
     return GA_OK;
 } GA_ABI_CATCH
 
-
 int ga_g16_prove(ga_g16_pk* p, const void* w, const void* a, const void* b, const void* c, uint64_t n_constraints,
                  uint64_t nb_public, const void* r, const void* s, void* proof_out) try {
     GA_ABI_ENTRY();
     return g16_prove_impl(p, w, a, b, c, n_constraints, nb_public, r, s, proof_out);
 } GA_ABI_CATCH
+
 // One proof on a key that is NOT kept on the device (the Go package's default, PinToGPU = false, as icicle.go:797-805): the key
 // goes up as plain vectors WHILE the proof runs -- the uploader thread of pk_create_from_struct copies A, B, K, G2.B, Z in the order
 // the MSMs consume them, every MSM waits for its own vector only -- and is dropped afterwards.  Same proof bytes as
@@ -2848,18 +1451,6 @@ int ga_g16_prove_oneshot(ga_ctx* h, const ga_g16_key* key, const void* w, const 
     trace_event("proof done", rc);
     return rc;
 } GA_ABI_CATCH
-int ga_g16_prove_partial(ga_g16_pk* p, const void* w, const void* a, const void* b, const void* c, uint64_t n_constraints,
-                         uint64_t nb_public, void* partials_out) try {
-    GA_ABI_ENTRY();
-    return g16_prove_partial_impl(p, w, a, b, c, n_constraints, nb_public, partials_out);
-} GA_ABI_CATCH
-int ga_g16_witness_partial(ga_g16_pk* p, const void* w, uint64_t nb_public, void* partials_out) try {
-    GA_ABI_ENTRY();
-    return g16_witness_partial_impl(p, w, nb_public, partials_out);
-} GA_ABI_CATCH
-int ga_g16_prove_multi(ga_g16_pk* const* keys, uint32_t n, const void* w, const void* a, const void* b, const void* c,
-                       uint64_t n_constraints, uint64_t nb_public, const void* r, const void* s, void* proof_out) try {
-    GA_ABI_ENTRY();
-    return g16_prove_multi_impl(keys, n, w, a, b, c, n_constraints, nb_public, r, s, proof_out);
-} GA_ABI_CATCH
+
 }  // extern "C"
+

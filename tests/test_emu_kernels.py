@@ -1766,6 +1766,8 @@ def test_emu_proof_unmarshal(emu_ctx, c):
             assert p.WriteTo() == pyref.proof_bytes(c, ar, bs, krs, coms, pok)      # and back out through the marshaller
     with pytest.raises(Exception, match="does not decode|end of input|malformed"):
         groth16.ParseProof(c.name, b"\x00" * 20, lib=lib)
+    # G1Affine.Marshal of infinity: the uncompressed infinity flag, then zeros (both curves)
+    assert groth16.MarshalG1(c.name, np.zeros(2 * c.fp_limbs, dtype=np.uint64), lib=lib) == b"\x40" + bytes(2 * c.fp_bytes - 1)
     # the reference's own serialized keys: alpha1 beta1 beta2 gamma2 delta1 delta2, u32 4, 4 x K  (marshal.go:99-125)
     name = "bn254" if c.cid == 0 else "bls12381"
     raw = open(os.path.join(os.path.dirname(__file__), "golden", f"vk_blank_groth16_{name}_nocommit.bin"), "rb").read()

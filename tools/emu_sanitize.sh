@@ -15,14 +15,18 @@ mkdir -p $OUT
 if [ "$KIND" = "asan" ]; then SANF="-fsanitize=address,undefined -fno-omit-frame-pointer"; else SANF="-fsanitize=undefined -fno-sanitize-recover=undefined"; fi
 FLAGS="-O1 -g -std=c++17 -fPIC -I$HERE/include -I$SRC -I$ROOT/include -w $SANF"
 pids=()
-for f in abi groth16 hash_to_field plonk_bn254 plonk_bls12381 ntt_domain msm_bn254_g1 msm_bn254_g2 msm_bls12381_g1 msm_bls12381_g2 ntt_bn254 ntt_bls12381 util_bn254 util_bls12381; do
+objs=("$OUT/emu_impl.o")
+for s in "$SRC"/*.hip; do
+  f=$(basename "$s" .hip)
+  [ "$f" = microbench ] && continue   # (as tests/emu/build_emu.sh)
+  objs+=("$OUT/$f.o")
   g++ $FLAGS -x c++ -c "$SRC/$f.hip" -o "$OUT/$f.o" &
   pids+=($!)
 done
 g++ $FLAGS -c "$HERE/emu_impl.cpp" -o "$OUT/emu_impl.o" &
 pids+=($!)
 for p in "${pids[@]}"; do wait $p; done
-g++ -shared $SANF -o $WORK/libgnark_amd_emu_$KIND.so "$OUT"/*.o -lpthread
+g++ -shared $SANF -o $WORK/libgnark_amd_emu_$KIND.so "${objs[@]}" -lpthread
 export GA_EMU_LIB_PATH=$WORK/libgnark_amd_emu_$KIND.so
 if [ "$KIND" = "asan" ]; then
   export LD_PRELOAD=$(g++ -print-file-name=libasan.so)
