@@ -2,10 +2,18 @@
 """bench.py -- headline benchmark of the MI355X prover backend (driver contract: ONE compact JSON line from rank 0, < 8 KB, ending in
 "summary"; `--detail-file PATH` additionally writes the verbose object with every leg's explanation).
 
+Two kinds of run at N = 1.  A PLAIN run (`bench.py --gpus 1 --steps K --warmup W`, what is typed several times for every change) does
+what the headline figure needs and nothing else: set up, warm up, time the K steps, write --dump-outputs, print the line -- `metric`,
+`value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, `config`, the roofline object and stage table of the timed launches (they
+come from the hipEvents of the timed steps themselves), `value_checked` null.  `--full` adds every other leg below: the oracle check of
+the headline result, the counter passes, the MSM variants, Groth16, PLONK, BLS12-381, the RCCL self-test and the CPU baselines (about
+100 s beside the steps); the --no-* options leave single legs of a full run out.  A multi-rank line (N > 1) is a scaling record, not
+a per-change run, and always carries all its legs.
+
 Workload (BASELINE.json `metric`: "G1 MSM Mscalar-mul/s + Groth16 proofs/s, BN254 2^24 constraints, 1/2/4/8 GPU"):
   * a "step" = ONE BN254 G1 Pippenger MSM over 2^24 (scalar, base) pairs, bases (a pinned window table) and scalars resident in HBM
     when the timed region starts (SURVEY 8d config 2/3 shapes: uniform Montgomery scalars, distinct known-dlog bases generated on
-    device).  `value` = scalar-muls/s of the whole job in Mscalar-mul/s, checked against [sum s_i k_i]G outside the timed region.
+    device).  `value` = scalar-muls/s of the whole job in Mscalar-mul/s, checked (--full) against [sum s_i k_i]G outside the timed region.
   * N = 1: the whole problem on one GPU.  N > 1: the SAME 2^24-pair problem sharded by base-point range over the N ranks (SURVEY 8e
     partitioning B: rank g owns pairs [g n/N, (g+1) n/N) and contributes one Jacobian point; the exchange step is an all_gather of
     the partials + a local add) -- `"scaling": "strong"`, the fixed 2^24 problem BASELINE quotes at 1/2/4/8 GPUs.  The weak-scaling
@@ -60,13 +68,17 @@ def parse():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--log-n", type=int, default=int(os.environ.get("GA_BENCH_LOGN", "24")))
     ap.add_argument("--groth16-proofs", type=int, default=int(os.environ.get("GA_BENCH_PROOFS", "5")))
-    ap.add_argument("--no-check", action="store_true", help="skip the oracle checks of the Groth16 / PLONK legs (outside the timed regions)")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: beside the headline MSM, run everything else the line can carry -- the oracle check of the headline result, the rocprofv3 counter "
+                         "passes, the MSM variants, Groth16, PLONK, BLS12-381, the RCCL self-test, the CPU baselines (about 100 s beside the steps).  Without it a "
+                         "run sets up, warms up, times the steps and prints the line.  N > 1 always runs all its legs")
+    ap.add_argument("--no-check", action="store_true", help="--full: skip the oracle checks of the MSM / Groth16 / PLONK legs (outside the timed regions)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pipelined", action="store_true", help="skip the two-caller Groth16 leg (rocprofv3 passes: concurrent proofs stretch per-kernel durations)")
     ap.add_argument("--plonk-log-n", type=int, default=int(os.environ.get("GA_BENCH_PLONK_LOGN", "22")), help="0 disables the PLONK leg")
     ap.add_argument("--no-bls", action="store_true", help="N = 1: leave the BLS12-381 legs (config 4's curve) out")
     ap.add_argument("--no-selftest", action="store_true", help="N = 1: skip the one-rank RCCL self-test")
-    ap.add_argument("--only-headline", action="store_true", help="the headline MSM leg alone (what the in-run rocprofv3 counter passes execute)")
+    ap.add_argument("--only-headline", action="store_true", help="--full or N > 1: the headline MSM leg alone, with its oracle check")
     ap.add_argument("--no-pmc", action="store_true", help="N = 1: do not spawn the two rocprofv3 --pmc child passes for roofline.traffic (the committed figure is used)")
     ap.add_argument("--detail-file", default=os.environ.get("GA_BENCH_DETAIL", ""), help="also write the verbose result object (every leg with its prose) to this path; stdout carries the compact line")
     ap.add_argument("--replica-proofs", type=int, default=int(os.environ.get("GA_BENCH_REPLICA_PROOFS", "5")), help="N > 1: proofs per rank in the replica-throughput leg (0 = skip)")
@@ -78,6 +90,9 @@ def parse():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    args.plain = args.gpus == 1 and not args.full
+    if args.plain:   # the headline leg alone, unchecked, without child passes: what --full --only-headline --no-check --no-pmc runs
+        args.only_headline = args.no_check = args.no_pmc = True
     return args
 
 
@@ -262,7 +277,7 @@ def pmc_traffic(kernel_key, curve, log_n):
 def pmc_traffic_live(args):
     """HBM bytes per launch of the dominant kernel MEASURED IN THIS RUN: two child processes -- `rocprofv3 --pmc FETCH_SIZE
     --kernel-trace` and the same for WRITE_SIZE, separate passes as the profiling guide prescribes (the two counters do not fit one
-    pass; --pmc is never combined with anything but --kernel-trace) -- over `bench.py --only-headline --steps 3`.  Returns (bytes per
+    pass; --pmc is never combined with anything but --kernel-trace) -- over a plain `bench.py --steps 3`.  Returns (bytes per
     launch or None, source text, detail dict).  rocprofv3 reports both counters in KiB per dispatch."""
     import shutil
     import sqlite3
@@ -282,8 +297,8 @@ def pmc_traffic_live(args):
         env = dict(os.environ, TMPDIR="/tmp")
         for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
             env.pop(k, None)
-        cmd = [exe, "--pmc", ctr, "--kernel-trace", "-d", d, "-o", "p", "--", sys.executable, os.path.abspath(__file__), "--only-headline", "--steps", "3",
-               "--warmup", "1", "--log-n", str(args.log_n), "--curve", args.curve, "--no-check", "--no-pmc"]
+        cmd = [exe, "--pmc", ctr, "--kernel-trace", "-d", d, "-o", "p", "--", sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", "3",
+               "--warmup", "1", "--log-n", str(args.log_n), "--curve", args.curve]
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd="/tmp", timeout=int(os.environ.get("GA_BENCH_PMC_TIMEOUT_S", "240")))
             dbs = [os.path.join(dp, f) for dp, _, fs in os.walk(d) for f in fs if f.endswith("_results.db")]
@@ -306,7 +321,7 @@ def pmc_traffic_live(args):
     detail["seconds"] = round(time.perf_counter() - t0, 1)
     if len(vals) == 2:
         return vals["FETCH_SIZE"] + vals["WRITE_SIZE"], ("this run: rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE child passes (--kernel-trace only) over "
-                                                            "bench.py --only-headline --steps 3; KiB x 1024 per dispatch, uncorrected"), detail
+                                                            "a plain bench.py --steps 3; KiB x 1024 per dispatch, uncorrected"), detail
     return None, "the in-run rocprofv3 passes failed: " + json.dumps(detail)[:200], detail
 
 
@@ -462,7 +477,7 @@ def headline_leg(R):
     acc = res["stages"].get("msm_accumulate")
     traffic, tsrc = (None, None)
     if R.world == 1 and not R.emu:
-        live = (None, "in-run counter passes switched off (%s)" % ("--only-headline" if args.only_headline else "--no-pmc"), {})
+        live = (None, "in-run counter passes switched off (%s)" % ("a plain run: --full measures them" if args.plain else "--only-headline" if args.only_headline else "--no-pmc"), {})
         if not args.no_pmc and not args.only_headline:
             live = pmc_traffic_live(args)
             out["pmc_passes"] = live[2]

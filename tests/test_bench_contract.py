@@ -1,6 +1,7 @@
 """bench.py's contract, exercised against the CPU emulation build (GA_BENCH_EMU=1: tiny sizes, the JSON line says "data": "emulation"
 -- a dry run of the script's control flow, never a measurement): one JSON line with the fields the driver reads, the self-checks of
-the Groth16 / PLONK / BLS12-381 legs, the one-rank collective self-test, and the N > 1 path (two gloo ranks: the strong-scaling
+the Groth16 / PLONK / BLS12-381 legs, the one-rank collective self-test (all behind --full at N = 1; a plain run is the headline leg
+alone), and the N > 1 path (two gloo ranks: the strong-scaling
 headline -- ONE MSM problem sharded over the ranks --, the weak-scaling figure beside it, the sharded proof), and what happens when a
 rank fails: every rank skips the leg and the line carries the error -- in seconds, not after a collective timeout."""
 import json
@@ -35,7 +36,7 @@ def _check_compact(line_text, d):
 
 def test_single_rank_line(env, tmp_path):
     detail = str(tmp_path / "detail.json")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--log-n", "8", "--steps", "2", "--warmup", "1", "--groth16-proofs", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--log-n", "8", "--steps", "2", "--warmup", "1", "--groth16-proofs", "2",
                         "--plonk-log-n", "6", "--detail-file", detail], capture_output=True, text=True, env=env, cwd=ROOT, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     line = _line(r.stdout)
@@ -84,6 +85,31 @@ def test_single_rank_line(env, tmp_path):
     st = d["nccl_selftest_detail"]
     assert st["sharded_proof_same_bytes"] is True and st["msm_all_gather"] is True
     assert all(st["collectives"][k] is True for k in ("all_gather", "gather", "scatter", "broadcast", "all_reduce"))
+
+
+def test_plain_run_is_the_headline_alone(env, tmp_path):
+    """without --full a run sets up, warms up, times its steps and prints the line: the fields the driver reads mean what they mean in
+    a full run, and nothing that takes a run, a child process or the CPU oracle beside the steps is in it"""
+    detail = str(tmp_path / "detail.json")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--log-n", "8", "--detail-file", detail],
+                       capture_output=True, text=True, env=env, cwd=ROOT, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = _line(r.stdout)
+    sm = _check_compact([l for l in r.stdout.splitlines() if l.startswith("{")][0], line)
+    assert line["metric"].startswith("G1 MSM throughput, BN254, 2^8 scalar-muls on one GPU") and line["unit"] == "Mscalar-mul/s" and line["higher_is_better"] is True
+    assert "v_mad_u64_u32" in line["dtype"] and line["n_gpus"] == 1 and line["steps"] == 2 and line["warmup"] == 1 and line["scaling"] == "strong"
+    # value is the scalar-muls of the timed steps over their wall time, ms_per_step that time per step: one figure, two readings
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and abs(line["value"] * line["ms_per_step"] / (256 / 1e3) - 1) < 0.02
+    assert line["value_checked"] is None                      # the oracle check of the result belongs to --full
+    rf = line["roofline"]                                        # from the hipEvents of the timed launches: no run of its own
+    assert rf["bound"] == "hbm" and rf["launches_timed"] == 2 and rf["algorithmic_bytes_per_launch"] == 96.0 * 256 and "int_mad_frac" in rf
+    assert "pmc_passes" not in line and line["stages_ms"]["msm_accumulate"] >= 0
+    moved = ("cpu_baseline", "config2_msm_2p20_unpinned", "plain_msm_no_tables", "msm_with_scalar_h2d", "groth16", "plonk", "msm_bls12_381", "groth16_bls12_381",
+             "nccl_selftest", "nccl_selftest_detail")
+    d = json.load(open(detail))
+    assert not [k for k in moved if k in line or k in d]
+    assert list(line["legs_seconds"]) == ["headline_msm"] and sm["msm_Mscalar_mul_per_s"] == line["value"] and sm["msm_ms"] == line["ms_per_step"]
+    assert not [k for k in sm if k.startswith(("groth16", "plonk", "cpu_", "msm_bls"))]
 
 
 def _two_ranks(env, port, extra_env=None, timeout=900):
@@ -155,16 +181,17 @@ def test_plain_gpus_2_launches_two_ranks(env):
 
 def test_dump_outputs(env, tmp_path):
     """--dump-outputs DIR: the affine point the headline MSM's last timed step returned, float64 16-bit pieces of its limbs, the same
-    whatever --steps / --warmup say (fixed seeds: same inputs, same point), and the point the oracle check accepted"""
+    whatever --steps / --warmup say (fixed seeds: same inputs, same point), from a plain run as from a full one, and the point the
+    oracle check (--full) accepted"""
     import numpy as np
     got = []
-    for steps, warmup in (("1", "0"), ("3", "1")):
+    for steps, warmup, mode, checked in (("1", "0", [], None), ("3", "1", ["--full", "--only-headline"], True)):
         d = str(tmp_path / ("dump_%s" % steps))
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--log-n", "8", "--steps", steps, "--warmup", warmup, "--only-headline",
-                            "--dump-outputs", d], capture_output=True, text=True, env=env, cwd=ROOT, timeout=900)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--log-n", "8", "--steps", steps, "--warmup", warmup, "--dump-outputs", d] + mode,
+                           capture_output=True, text=True, env=env, cwd=ROOT, timeout=900)
         assert r.returncode == 0, r.stderr[-3000:]
         line = _line(r.stdout)
-        assert line["steps"] == int(steps) and line["value_checked"] is True
+        assert line["steps"] == int(steps) and line["value_checked"] is checked
         assert os.listdir(d) == ["msm_result_affine.npy"]
         a = np.load(os.path.join(d, "msm_result_affine.npy"))
         assert a.dtype == np.float64 and a.shape == (2, 16) and (a >= 0).all() and (a < 65536).all() and (a == np.round(a)).all() and a.any()

@@ -7,7 +7,7 @@
 # apply that patch (or add your own #ifdef) first; a -D that no #if in gnark_amd/csrc tests is refused below, because such a
 # variant would silently equal the default build.
 # -> gnark_amd/variants/libgnark_amd_<name>.so (git-ignored; it travels to the GPU box with gpurun), used with
-#   GA_LIB_PATH=$PWD/gnark_amd/variants/libgnark_amd_pad3.so python bench.py --no-cpu-baseline --no-check
+#   GA_LIB_PATH=$PWD/gnark_amd/variants/libgnark_amd_pad3.so python bench.py
 # --only: the knob touches just these translation units; every other object is taken from the shipped build (gnark_amd/csrc/build,
 # which must be up to date) instead of being recompiled.
 set -e

@@ -6,9 +6,9 @@
 #   tests[:<pytest -k expression>]   the -m gpu suite (or a selection)
 #   smoke                            __graft_entry__.smoke()
 #   micro                            ga_microbench: instruction issue rates (burst and sustained), dependency distance x occupancy
-#   bench[:<extra bench.py args>]    python bench.py -> ${TAG}_bench.json  (":--curve bls12-381" etc.; spaces as '+')
+#   bench[:<extra bench.py args>]    python bench.py --full (every leg) -> ${TAG}_bench.json  (":--curve bls12-381" etc.; spaces as '+')
 #   bench2                           `python bench.py --gpus 2` as the driver would type it (bench.py launches its ranks): two ranks share this box's GPU, collectives over gloo
-#   stats[:<bench args>]             rocprofv3 --kernel-trace --stats of the headline leg (bench.py --only-headline) -> ${TAG}_kernel_stats.txt
+#   stats[:<bench args>]             rocprofv3 --kernel-trace --stats of the headline leg (a plain bench.py run) -> ${TAG}_kernel_stats.txt
 #   stats_proof                      the same over a short bench WITH a Groth16 proof (multi-table launches included) -> ${TAG}_kernel_stats_proof.txt
 #   hbm[:<bench args>]               FETCH_SIZE / WRITE_SIZE passes of the headline leg (separate, kernel-trace only) -> ${TAG}_pmc_{FETCH,WRITE}_SIZE.txt
 #   sq:<name>:<driver>               the SQ issue accounting + the wait split (LDS / VMEM / instruction cache) of <driver>:
@@ -27,7 +27,7 @@ TAG=${TAG:-r04}
 OUT=gpurun_out
 mkdir -p $OUT
 export TMPDIR=/tmp
-SHORT_BENCH="--steps 3 --warmup 1 --no-cpu-baseline --no-check --groth16-proofs 1 --no-pipelined --plonk-log-n 0 --no-bls --no-selftest --no-pmc"
+SHORT_BENCH="--full --steps 3 --warmup 1 --no-cpu-baseline --no-check --groth16-proofs 1 --no-pipelined --plonk-log-n 0 --no-bls --no-selftest --no-pmc"
 
 driver_cmd() {
   case "$1" in
@@ -72,7 +72,7 @@ for step in "$@"; do
       tail -2 $OUT/${TAG}_microbench.err; cat $OUT/${TAG}_microbench.json ;;
     bench)
       sfx=$(echo "$arg" | tr -cd 'a-z0-9' | cut -c1-24)
-      (time timeout 2400 python bench.py --detail-file $OUT/${TAG}_bench${sfx:+_$sfx}_detail.json $arg) > $OUT/${TAG}_bench${sfx:+_$sfx}.json 2> $OUT/${TAG}_bench${sfx:+_$sfx}.err
+      (time timeout 2400 python bench.py --full --detail-file $OUT/${TAG}_bench${sfx:+_$sfx}_detail.json $arg) > $OUT/${TAG}_bench${sfx:+_$sfx}.json 2> $OUT/${TAG}_bench${sfx:+_$sfx}.err
       tail -4 $OUT/${TAG}_bench${sfx:+_$sfx}.err
       python tools/bench_digest.py $OUT/${TAG}_bench${sfx:+_$sfx}.json ;;
     bench2)
@@ -84,7 +84,7 @@ for step in "$@"; do
       d=$OUT/stats_tmp_$$
       # the HEADLINE leg alone (20 MSM steps): since round 6 a proof launches the bucket kernel once for THREE tables (A, B1, K), so a
       # profile of the whole short bench would average single- and triple-table launches under one kernel name
-      timeout 900 rocprofv3 --kernel-trace --stats -d $d -o k -- python bench.py --only-headline --steps 20 --warmup 2 ${arg:-} > $OUT/${TAG}_stats.log 2>&1
+      timeout 900 rocprofv3 --kernel-trace --stats -d $d -o k -- python bench.py --steps 20 --warmup 2 ${arg:-} > $OUT/${TAG}_stats.log 2>&1
       python tools/prof_summary.py $d/k_results.db > $OUT/${TAG}_kernel_stats.txt 2>/dev/null
       rm -rf $d
       head -12 $OUT/${TAG}_kernel_stats.txt | cut -c1-200 ;;
@@ -97,7 +97,7 @@ for step in "$@"; do
     hbm)
       for ctr in FETCH_SIZE WRITE_SIZE; do
         rm -f $OUT/${TAG}_pmc_${ctr}.txt
-        pmc_pass $OUT/${TAG}_pmc_${ctr}.txt $ctr -- python bench.py --only-headline --steps 10 --warmup 2 ${arg:-}
+        pmc_pass $OUT/${TAG}_pmc_${ctr}.txt $ctr -- python bench.py --steps 10 --warmup 2 ${arg:-}
         head -5 $OUT/${TAG}_pmc_${ctr}.txt | cut -c1-170
       done ;;
     sq)
