@@ -177,12 +177,12 @@ struct Tunables {
     std::atomic<int> table_c{0};
     std::atomic<uint64_t> msm_min_seg{256};
     std::atomic<int> msm_exact_redo{0};
-    std::atomic<uint64_t> msm_fuse_min{1ull << 21};   // pairs from which the digits are fused with the first sort pass (msm.hip.h 1b)
+    std::atomic<uint64_t> msm_fuse_min{1ull << 21};   // pairs from which the digits are fused with the first sort pass (msm_sort.hip.h 1b)
     std::atomic<int> msm_group{0};                   // buckets per running-sum group of the window reduction (0 = MSM_GROUP)
     std::atomic<uint64_t> fault_throw{0};            // FNV-1a of GA_FAULT_THROW (0 = unset): the entry point under which scratch_get throws (tests)
     std::atomic<int> fault_lane2_nomem{0};           // GA_FAULT_LANE2_NOMEM (tests): scratch requests of lanes 2/3 fail as if HBM were exhausted
     std::atomic<uint64_t> msm_p1_grid{512};         // blocks of the first sort level (a block walks several tiles)
-    std::atomic<uint64_t> msm_task_exact_min{1ull << 25};   // pairs from which the task list is sorted on exact lengths (msm.hip.h 3)
+    std::atomic<uint64_t> msm_task_exact_min{1ull << 25};   // pairs from which the task list is sorted on exact lengths (msm_tasks.hip.h 3)
     std::atomic<int> msm_xcd{3};                     // fused sort placement: bit 0 per-XCD slices of the first level's groups, bit 1 XCD swizzle of the second level's segments
     void read_env();
 };
@@ -302,7 +302,7 @@ struct Ctx {
     // reusable device scratch, grown on demand (keyed by purpose)
     std::map<std::string, std::pair<void*, size_t>> scratch;
 
-    // base tables on which the fast bucket loop flagged most of its tasks (all bases equal: a DummySetup key); msm.hip.h
+    // base tables on which the fast bucket loop flagged most of its tasks (all bases equal: a DummySetup key); msm_bucket.hip.h
     std::mutex degenerate_mu;
     std::set<const void*> degenerate;
     bool is_degenerate(const void* table) {
@@ -320,7 +320,7 @@ struct Ctx {
     }
     // tables whose SMALL shared bucket set turned out mostly empty on the previous call (a witness of zeros and ones puts nearly
     // every (scalar, window) pair into the skip bucket): the lazy window reduction flags most groups there, so the next call takes
-    // the exact kernel again (msm.hip.h, dense_set)
+    // the exact kernel again (msm_reduce.hip.h, dense_set)
     // The verdict is re-examined: every 16th call on such a table takes the lazy pass again and note_sparse_set renews or drops it
     // (one 0/1-heavy witness must not send a table to the slow exact kernel for the rest of its life).
     std::map<const void*, uint32_t> sparse_sets;   // table -> calls since the verdict

@@ -319,7 +319,7 @@ GA_HD F29<P> f29_reduce_3p(const F29<P>& a) {
 }
 
 // exact test v == 0 (mod p) of a lazy value (normalized limbs, any v < 2^(NL*L)): one Barrett step to [0, 3p), then the three
-// candidates 0, p, 2p.  Used only where the addition law needs it (the complete variant of the bucket loop, msm.hip.h).
+// candidates 0, p, 2p.  Used only where the addition law needs it (the complete variant of the bucket loop, msm_bucket.hip.h).
 template <class P>
 GA_HD bool f29_is_zero_mod_p(const F29<P>& a) {
     typedef Radix<P> R;

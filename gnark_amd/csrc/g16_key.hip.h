@@ -36,7 +36,7 @@ struct G16Pk {
     uint64_t len_k_remove = 0;
     std::vector<void*> d_ck_basis, d_ck_sigma;   // pinned pedersen keys (setup.go:260-287, icicle.go:231-261)
     std::vector<uint64_t> ck_len;
-    // precomputed window-multiple tables (msm.hip.h): a vector with its tab_* flag set points to windows x len points and c_* is the
+    // precomputed window-multiple tables (msm_bucket.hip.h): a vector with its tab_* flag set points to windows x len points and c_* is the
     // window width.  Per VECTOR since round 5: when the five tables do not fit the free HBM together (2^26 constraints: 288 GiB), the
     // ones that pay most per byte are built -- A, B (G1), K (they share one witness sort), then Z, then the twice as large G2.B --
     // and the rest stay plain affine arrays that run as un-pinned MSMs.

@@ -179,7 +179,7 @@ def test_msm_degenerate_bases_exact_kernel(gpu_ctx, monkeypatch):
 @pytest.mark.parametrize("c,group,n,table_c", [(BN254, 0, 1 << 20, 22), (BLS12_381, 1, 1 << 18, 20), (BN254, 1, (1 << 16) + 77, 16)],
                          ids=["bn254-G1-2^20-c22", "bls12-381-G2-2^18-c20", "bn254-G2-ragged-c16"])
 def test_msm_fused_first_sort_pass(gpu_ctx, monkeypatch, c, group, n, table_c, xcd):
-    """the digit extraction fused with the first level of the sort (msm.hip.h 1b; the default from 2^21 pairs, forced here on smaller
+    """the digit extraction fused with the first level of the sort (msm_sort.hip.h 1b; the default from 2^21 pairs, forced here on smaller
     inputs; with and without the XCD placement of round 5) == the plain digits + two-pass sort sequence == [sum s_i k_i]G: production shape (c = 22, 12 windows), 13 windows,
     16 windows with partial tiles and a ragged length; hot / zero / canonical scalars, window ranges; the same inputs as a raw-bases
     MSM in ranges of 16 windows (one bucket set per window)"""

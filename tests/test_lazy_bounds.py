@@ -19,7 +19,7 @@ def test_bounds_hold_with_headroom(curve, fp2):
 
 
 def test_constants_match_the_kernels():
-    src = open(os.path.join(ROOT, "gnark_amd", "csrc", "msm.hip.h")).read()
+    src = open(os.path.join(ROOT, "gnark_amd", "csrc", "msm_bucket.hip.h")).read()
     g1 = src[src.index("__device__ __forceinline__ void madd29(const LdsAcc29<Fe<P>>"):src.index("__device__ __forceinline__ void madd29(const LdsAcc29<Fe2<P>>")]
     g2 = src[src.index("__device__ __forceinline__ void madd29(const LdsAcc29<Fe2<P>>"):src.index("// acc = 2*(qx, qy) for an affine q")]
     dbl = src[src.index("__device__ __forceinline__ void mdbl29("):src.index("// acc += q with the exceptional cases")]
@@ -45,14 +45,14 @@ def test_constants_match_the_kernels():
 @pytest.mark.parametrize("curve", ["bn254", "bls12-381"])
 @pytest.mark.parametrize("fp2", [False, True], ids=["G1", "G2"])
 def test_general_addition_bounds(curve, fp2):
-    """msm.hip.h::add29 (lazy window reduction): fixed point of the bounds when both operands are earlier sums"""
+    """msm_lazy.hip.h::add29 (lazy window reduction): fixed point of the bounds when both operands are earlier sums"""
     out = lazy_bounds.check_add(curve, fp2)
     assert max(out["X"], out["Y"], out["P"], out["R"]) < out["limit"] - 2.5
 
 
 def test_general_addition_constants_match_the_kernel():
-    src = open(os.path.join(ROOT, "gnark_amd", "csrc", "msm.hip.h")).read()
-    body = src[src.index("__device__ __forceinline__ void add29(Lazy4<F>& a"):src.index("msm_reduce_groups29_kernel(")]
+    src = open(os.path.join(ROOT, "gnark_amd", "csrc", "msm_lazy.hip.h")).read()
+    body = src[src.index("__device__ __forceinline__ void add29(Lazy4<F>& a"):src.index("// 2 P for a general XYZZ point")]
     subs = [int(x) for x in re.findall(r"f29_sub<(\d+)>", body)]
     for k in (lazy_bounds.ADD_G1, lazy_bounds.ADD_G2):
         assert subs == [k["KP"], k["KR"], k["K3"], k["Kq"]]
@@ -63,7 +63,7 @@ def test_general_addition_constants_match_the_kernel():
 @pytest.mark.parametrize("curve", sorted(lazy_bounds.CURVES))
 @pytest.mark.parametrize("fp2", [False, True], ids=["G1", "G2"])
 def test_affine_doubling_into_the_accumulator(curve, fp2):
-    """msm.hip.h::mdbl29 (the doubling case of the complete bucket loop): its own subtraction constants and Fp2 operand bounds,
+    """msm_bucket.hip.h::mdbl29 (the doubling case of the complete bucket loop): its own subtraction constants and Fp2 operand bounds,
     and the mixed additions that follow still satisfy theirs when the accumulator starts from a doubling's output"""
     out = lazy_bounds.check_mdbl(curve, fp2)
     limit = lazy_bounds.CURVES[curve][1] * lazy_bounds.CURVES[curve][2]
@@ -73,14 +73,14 @@ def test_affine_doubling_into_the_accumulator(curve, fp2):
 @pytest.mark.parametrize("curve", sorted(lazy_bounds.CURVES))
 @pytest.mark.parametrize("fp2", [False, True], ids=["G1", "G2"])
 def test_repeated_doubling_bounds(curve, fp2):
-    """msm.hip.h::dbl29 (the doubling chain of the window-table build): fixed point of the bounds, with headroom"""
+    """msm_lazy.hip.h::dbl29 (the doubling chain of the window-table build): fixed point of the bounds, with headroom"""
     out = lazy_bounds.check_dbl(curve, fp2)
     assert all(v < out["limit"] - 2 for k, v in out.items() if k != "limit")
 
 
 def test_doubling_constants_match_the_kernel():
-    src = open(os.path.join(ROOT, "gnark_amd", "csrc", "msm.hip.h")).read()
-    d = src[src.index("__device__ __forceinline__ void dbl29("):src.index("// A lane carries TableBatch<F>::K points")]
+    src = open(os.path.join(ROOT, "gnark_amd", "csrc", "msm_lazy.hip.h")).read()
+    d = src[src.index("__device__ __forceinline__ void dbl29("):src.index("// ---- block-wide sums of XYZZ points")]
     assert [int(x) for x in re.findall(r"f29_sub<(\d+)>", d)] == [4, 8] and "KMS = Lazy<F>::FP2 ? P::FP2Z_K : 8" in d
 
 

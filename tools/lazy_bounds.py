@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Interval analysis behind the lazy (unreduced) arithmetic of gnark_amd/csrc/field29.hip.h + msm.hip.h::madd29.
+"""Interval analysis behind the lazy (unreduced) arithmetic of gnark_amd/csrc/field29.hip.h + msm_bucket.hip.h::madd29.
 
 Every value is tracked by an upper bound.  The representation needs (NL limbs of L bits, R' = 2^(NL*L)):
   * values < R' (the top limb must stay below 2^L so that column sums of 2*NL products fit 64 bits);
@@ -13,7 +13,7 @@ BN254_P = 0x30644E72E131A029B85045B68181585D97816A916871CA8D3C208C16D87CFD47
 BLS12_381_P = 0x1A0111EA397FE69A4B1BA7B6434BACD764774B84F38512BF6730D2A0F6B0F6241EABFFFEB153FFFFB9FEFFFFFFFFAAAB
 CURVES = {"bn254": (BN254_P, 29, 9, 254), "bls12-381": (BLS12_381_P, 28, 14, 381)}
 
-# constants used by msm.hip.h::madd29 (G1) and its Fp2 overload (G2), and by field29.hip.h's Fp2 product / square
+# constants used by msm_bucket.hip.h::madd29 (G1) and its Fp2 overload (G2), and by field29.hip.h's Fp2 product / square
 G1 = dict(Kx=8, Ky=8, K3=4, Kq=8, Ky3=2)
 G2 = dict(Kx=4, Ky=4, K3=4, Kq=8, Ky3=8, KQ=8, partial_reduce=("X",))
 
@@ -113,14 +113,14 @@ def check(curve: str, fp2: bool, verbose=False, init=None):
     return out
 
 
-# ---- general XYZZ + XYZZ addition in the lazy representation (msm.hip.h::add29, window reduction) -------------------------
+# ---- general XYZZ + XYZZ addition in the lazy representation (msm_lazy.hip.h::add29, window reduction) -------------------------
 ADD_G1 = dict(KP=4, KR=4, K3=4, Kq=8, Kms=8, partial_reduce=())
 ADD_G2 = dict(KP=4, KR=4, K3=4, Kq=8, Kms=16, partial_reduce=("X",))
 
 
 def check_add(curve: str, fp2: bool, verbose=False):
     """Fixed point of the coordinate bounds under a = add29(a, b) when both operands are earlier results (running sums added
-    into running sums); every subtraction constant and every Fp2 operand bound of msm.hip.h::add29 is asserted."""
+    into running sums); every subtraction constant and every Fp2 operand bound of msm_lazy.hip.h::add29 is asserted."""
     p, L, NL, bits = CURVES[curve]
     R = 1 << (L * NL)
     unit = 1 << (L * (NL - 1))
@@ -199,7 +199,7 @@ def check_add(curve: str, fp2: bool, verbose=False):
     return out
 
 
-# ---- affine doubling into the lazy accumulator (msm.hip.h::mdbl29, the complete variant of the bucket loop) ---------------------
+# ---- affine doubling into the lazy accumulator (msm_bucket.hip.h::mdbl29, the complete variant of the bucket loop) ---------------------
 def check_mdbl(curve: str, fp2: bool, verbose=False):
     """acc = 2*(qx, qy) for a table point (qx canonical, qy canonical or negated = 2p - y): every subtraction constant and Fp2
     operand bound of mdbl29, and the outputs must not exceed the accumulator bounds madd29 was analysed with (check())."""
@@ -274,7 +274,7 @@ def check_mdbl(curve: str, fp2: bool, verbose=False):
     return out
 
 
-# ---- repeated doubling of a general XYZZ point (msm.hip.h::dbl29, the window-table build) ----------------------------------------
+# ---- repeated doubling of a general XYZZ point (msm_lazy.hip.h::dbl29, the window-table build) ----------------------------------------
 def check_dbl(curve: str, fp2: bool, verbose=False):
     """fixed point of the coordinate bounds under a = dbl29(a), starting from an affine point with canonical coordinates"""
     p, L, NL, bits = CURVES[curve]
