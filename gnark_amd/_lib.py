@@ -15,6 +15,7 @@ GA_OK = 0
 BN254, BLS12_381 = 0, 1
 G1, G2 = 0, 1
 BASES_ON_DEVICE, SCALARS_ON_DEVICE, SCALARS_MONTGOMERY, TABLE_BATCHED = 0x1, 0x2, 0x4, 0x10
+RESULT_ON_DEVICE, RESULT_BITREVERSED = 0x20, 0x40
 FFT_FORWARD, FFT_INVERSE = 0, 1
 DIF, DIT = 0, 1
 
@@ -75,6 +76,8 @@ _PROTOS = {
                                  C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ga_msm_plan": (C.c_int, [C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ga_msm_combine_windows": (C.c_int, [C.c_int, C.c_int, _P, C.c_int, C.c_int, _P]),
+    "ga_batch_scalar_mul": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_size_t, C.c_uint, _P]),
+    "ga_batch_scalar_mul_plan": (C.c_int, [C.c_int, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ga_msm_table_create": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_size_t, C.c_uint, C.POINTER(_P)]),
     "ga_msm_table_destroy": (None, [_P]),
     "ga_msm_table_run": (C.c_int, [_P, _P, C.c_uint, _P]),

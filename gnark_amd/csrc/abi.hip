@@ -202,6 +202,25 @@ void Tunables::read_env() {
 
 typedef CtxLock Lock;
 
+// fixed-base batch scalar multiplication (fixed_base.hip.h; instantiated in fixed_base_<curve>_g<k>.hip): out[i] = [scalars[i]] base.
+// h_base: one affine point on the host; scalars / out: host or device per flags; forced_c / forced_chunk: the knobs below (0 = planned)
+template <class C, int G>
+int fixed_base_run(Ctx* ctx, const void* h_base, const void* scalars, size_t n, unsigned flags, void* out, int forced_c, uint64_t forced_chunk);
+template <class C>
+int fixed_base_plan_abi(size_t n, int forced_c, int* c, int* nwin);
+// The two run-time knobs of the fixed-base entry points.  They are NOT part of Tunables (no other code reads them): each of the two
+// entry points reads them from the environment itself, once per call, before any launch:
+//   GA_FIXED_BASE_C      force the window width (2 .. 20; 0 or anything else = planned, 4 .. 18; tests run several widths at small n)
+//   GA_FIXED_BASE_CHUNK  scalars per pass (0 = 2^22, at most 2^30; tests force a small chunk)
+static int fixed_base_forced_c() {
+    const char* e = getenv("GA_FIXED_BASE_C");
+    return e ? atoi(e) : 0;
+}
+static uint64_t fixed_base_forced_chunk() {
+    const char* e = getenv("GA_FIXED_BASE_CHUNK");
+    return e ? strtoull(e, nullptr, 10) : 0;
+}
+
 // Bring inputs to the device when they are host pointers.
 struct Staged {
     Ctx* ctx;
@@ -462,6 +481,42 @@ int ga_msm_windows(ga_ctx* h, int curve, int group, const void* bases, const voi
     Lock l(c);
     GA_DISPATCH_CURVE(curve, GA_DISPATCH_GROUP(group, return (msm_impl<C, G>(c, bases, scalars, n, flags, win_lo, win_hi, out_windows,
                                                                             window_bits, num_windows, true))));
+    return GA_OK;
+} GA_ABI_CATCH
+
+// ---- fixed-base batch scalar multiplication (fixed_base.hip.h) ---------------------------------------------
+int ga_batch_scalar_mul(ga_ctx* h, int curve, int group, const void* base_affine, const void* scalars, size_t n, unsigned flags,
+                        void* out_affine) try {
+    GA_ABI_ENTRY();
+    Ctx* c = reinterpret_cast<Ctx*>(h);
+    if ((curve != GA_BN254 && curve != GA_BLS12_381) || (group != GA_G1 && group != GA_G2)) {
+        set_error("ga_batch_scalar_mul: unknown curve id %d or group id %d", curve, group);
+        return GA_ERR_INVALID;
+    }
+    if (n == 0) return GA_OK;
+    if (!c || !base_affine || !scalars || !out_affine) {
+        set_error("ga_batch_scalar_mul: null argument");
+        return GA_ERR_INVALID;
+    }
+    if ((flags & GA_RESULT_BITREVERSED) && (n & (n - 1)) != 0) {
+        set_error("ga_batch_scalar_mul: GA_RESULT_BITREVERSED needs a power-of-two n (got %zu)", n);
+        return GA_ERR_INVALID;
+    }
+    Lock l(c);
+    const int forced_c = fixed_base_forced_c();
+    const uint64_t forced_chunk = fixed_base_forced_chunk();
+    GA_DISPATCH_CURVE(curve, GA_DISPATCH_GROUP(group, return (fixed_base_run<C, G>(c, base_affine, scalars, n, flags, out_affine, forced_c, forced_chunk))));
+    return GA_OK;
+} GA_ABI_CATCH
+
+int ga_batch_scalar_mul_plan(int curve, size_t n, int* window_bits, int* num_windows) try {
+    GA_ABI_ENTRY();
+    if (!window_bits || !num_windows) {
+        set_error("ga_batch_scalar_mul_plan: null argument");
+        return GA_ERR_INVALID;
+    }
+    const int forced_c = fixed_base_forced_c();
+    GA_DISPATCH_CURVE(curve, return fixed_base_plan_abi<C>(n, forced_c, window_bits, num_windows));
     return GA_OK;
 } GA_ABI_CATCH
 

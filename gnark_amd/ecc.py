@@ -50,6 +50,48 @@ def MultiExp(ctx: Context, curve, group: int, points, scalars, n: int | None = N
     return out
 
 
+def BatchScalarMultiplication(ctx: Context, curve, group: int, base, scalars, n: int | None = None, montgomery: bool = False,
+                              bitreversed: bool = False, out_device: bool = False):
+    """[scalars[i]] base for ONE base point -- curve.BatchScalarMultiplicationG1 / G2 as groth16.Setup calls them
+    (backend/groth16/bn254/setup.go:233,302) and kzg.NewSRS over the powers of tau.
+
+    base    : one G1Affine / G2Affine image (host array; any point on the curve, (0,0) = infinity)
+    scalars : (n, 4) uint64 array or a DeviceBuffer of n elements; canonical integers as gnark's setup passes them, fr.Element
+              images with montgomery=True
+    bitreversed: result i lands at index bitrev(i, log2 n) (setup.go:247 on the Z points); n must be a power of two
+    Returns an (n, affine_words) array, or with out_device=True a DeviceBuffer of n affine points (the caller frees it).
+    """
+    cid = curve_id(curve)
+    wa = affine_words(cid, group)
+    base = as_u64(np.asarray(base).reshape(1, -1), wa)
+    if not isinstance(scalars, (DeviceBuffer, int)):
+        scalars = as_u64(scalars, 4)
+        n = scalars.shape[0]
+    if n is None:
+        raise ValueError("n is required for device-resident scalars")
+    sp, f = _arg(scalars, _lib.SCALARS_ON_DEVICE)
+    flags = f | (_lib.SCALARS_MONTGOMERY if montgomery else 0) | (_lib.RESULT_BITREVERSED if bitreversed else 0)
+    if out_device:
+        buf = ctx.malloc(max(n, 1) * wa * 8)
+        try:
+            ctx.lib.check(ctx.lib.ga_batch_scalar_mul(ctx.handle, cid, group, _ptr(base), sp, n, flags | _lib.RESULT_ON_DEVICE, C.c_void_p(buf.ptr)))
+        except Exception:
+            buf.free()
+            raise
+        return buf
+    out = np.zeros((n, wa), dtype=np.uint64)
+    ctx.lib.check(ctx.lib.ga_batch_scalar_mul(ctx.handle, cid, group, _ptr(base), sp, n, flags, _ptr(out)))
+    return out
+
+
+def batch_scalar_mul_plan(curve, n: int, lib=None):
+    """(window_bits, windows) BatchScalarMultiplication uses for n scalars (ga_batch_scalar_mul_plan)"""
+    lib = lib or _lib.load()
+    c, nw = C.c_int(), C.c_int()
+    lib.check(lib.ga_batch_scalar_mul_plan(curve_id(curve), n, C.byref(c), C.byref(nw)))
+    return c.value, nw.value
+
+
 class PrecomputedBases:
     """Bases pinned on the device together with [2^(c*w)]P for every Pippenger window w (ga_msm_table_*): the GPU analogue of
     keeping `pk.G1.A` etc. resident ("PinToGPU", provingkey.go:37-42) with ICICLE's PrecomputeFactor."""

@@ -49,6 +49,8 @@ const (
 	BasesOnDevice     = uint(C.GA_BASES_ON_DEVICE)
 	ScalarsOnDevice   = uint(C.GA_SCALARS_ON_DEVICE)
 	ScalarsMontgomery = uint(C.GA_SCALARS_MONTGOMERY)
+	ResultOnDevice    = uint(C.GA_RESULT_ON_DEVICE)
+	ResultBitReversed = uint(C.GA_RESULT_BITREVERSED)
 )
 
 // Vector / point selectors of the staged key builder.
@@ -394,6 +396,22 @@ func (c *Context) MSM(curve Curve, group int, bases, scalars unsafe.Pointer, n u
 	return call("ga_msm", func() C.int {
 		return C.ga_msm(c.h, C.int(curve), C.int(group), bases, scalars, C.size_t(n), C.uint(flags), outJac)
 	})
+}
+
+// BatchScalarMul computes out[i] = [scalars[i]]base for ONE affine base point (curve.BatchScalarMultiplicationG1 / G2 as groth16.Setup
+// and kzg.NewSRS call them): n affine points out, in gnark's memory image.  scalars are canonical integers ([]fr.Element after
+// BigInt, 4 little-endian words) unless flags carries ScalarsMontgomery; ResultBitReversed writes result i at bitrev(i, log2 n).
+func (c *Context) BatchScalarMul(curve Curve, group int, base, scalars unsafe.Pointer, n uint64, flags uint, outAffine unsafe.Pointer) error {
+	return call("ga_batch_scalar_mul", func() C.int {
+		return C.ga_batch_scalar_mul(c.h, C.int(curve), C.int(group), base, scalars, C.size_t(n), C.uint(flags), outAffine)
+	})
+}
+
+// BatchScalarMulPlan reports the window width and window count BatchScalarMul uses for n scalars.
+func BatchScalarMulPlan(curve Curve, n uint64) (windowBits, windows int, err error) {
+	var c, nw C.int
+	err = call("ga_batch_scalar_mul_plan", func() C.int { return C.ga_batch_scalar_mul_plan(C.int(curve), C.size_t(n), &c, &nw) })
+	return int(c), int(nw), err
 }
 
 // Table is a pinned base vector with its window multiples (ga_msm_table_*): the KZG SRS of a PLONK key.

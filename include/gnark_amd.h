@@ -64,6 +64,8 @@ extern "C" {
 #define GA_SCALARS_MONTGOMERY 0x4u     /* scalars are fr.Element images (Montgomery); else canonical LE integers
                                           (ICICLE's AreScalarsMontgomeryForm, icicle.go:861-863,1232) */
 #define GA_RESULT_WINDOW_SUMS 0x8u     /* multi-GPU window sharding: see ga_msm_windows */
+#define GA_RESULT_ON_DEVICE 0x20u      /* ga_batch_scalar_mul: `out_affine` is a device pointer */
+#define GA_RESULT_BITREVERSED 0x40u    /* ga_batch_scalar_mul: result i is written at index bitrev(i, log2 n) */
 
 /* NTT direction / ordering, mirroring gnark-crypto fft.Domain.FFT / FFTInverse (prove.go:362-386) */
 #define GA_FFT_FORWARD 0
@@ -121,6 +123,24 @@ int ga_msm_plan(int curve, int group, size_t n, int* window_bits, int* num_windo
 /* result = sum_j 2^(window_bits*j) * windows[j]   (host arithmetic; windows are Jacobian, Montgomery) */
 int ga_msm_combine_windows(int curve, int group, const void* windows, int num_windows, int window_bits,
                            void* out_jac);
+
+/* ---- fixed-base batch scalar multiplication --------------------------------------------------------------
+ * replaces: curve.BatchScalarMultiplicationG1 / G2 -- all the curve work of groth16.Setup (backend/groth16/bn254/setup.go:233,302)
+ * -- and the same primitive over the powers of tau in kzg.NewSRS.  out[i] = [scalars[i]] base.
+ *   base    : ONE affine point (Montgomery, (0,0) = infinity), host pointer; any point ON the curve, subgroup or not
+ *   scalars : n fr elements; canonical LE 4x64 (< r) as gnark's setup passes them, Montgomery with GA_SCALARS_MONTGOMERY;
+ *             host, or device with GA_SCALARS_ON_DEVICE
+ *   out     : n affine points in gnark's memory image ((0,0) for a zero scalar or an infinite result);
+ *             host, or device with GA_RESULT_ON_DEVICE
+ *   GA_RESULT_BITREVERSED : out[bitrev(i, log2 n)] = [scalars[i]] base (setup.go:247 on the Z points); n must be a power of two
+ * GA_ERR_INVALID: unknown curve or group, a null pointer with n > 0, a base that is not on the curve, GA_RESULT_BITREVERSED with
+ * n not a power of two.  n = 0 is GA_OK and touches nothing.  The window width is deterministic in (curve, n); the environment
+ * knobs GA_FIXED_BASE_C (2 .. 20) / GA_FIXED_BASE_CHUNK (at most 2^30) force the width and the number of scalars per pass (tests). */
+int ga_batch_scalar_mul(ga_ctx* ctx, int curve, int group, const void* base_affine, const void* scalars, size_t n,
+                        unsigned flags, void* out_affine);
+/* window width / number of windows ga_batch_scalar_mul will use for n scalars: deterministic in (curve, n), the same for both groups;
+ * GA_FIXED_BASE_C, when set, is what it reports */
+int ga_batch_scalar_mul_plan(int curve, size_t n, int* window_bits, int* num_windows);
 
 /* ---- MSM over pinned bases with precomputed window multiples ---------------------------------------------
  * (ICICLE's MSMConfig.PrecomputeFactor / precompute-bases, icicle.go:507-525.)  ga_msm_table_create uploads (or takes
