@@ -176,7 +176,6 @@ void Tunables::read_env() {
     put64(g16_table_budget_pct, num("GA_G16_TABLE_BUDGET_PCT", 0));
     put(g16_split, (int)num("GA_G16_SPLIT", 1));
     put(g16_batch_tables, (int)num("GA_G16_BATCH_TABLES", 1));
-    put(ntt_coset_fold, (int)num("GA_NTT_COSET_FOLD", 1));
     put(ntt_wave_local, (int)num("GA_NTT_WAVE_LOCAL", 1));
     put(ntt_direct, (int)num("GA_NTT_DIRECT", 1));
     put(table_c, (int)num("GA_TABLE_C", 0));
@@ -838,42 +837,6 @@ int ga_fft(ga_domain* dh, void* data, int direction, int decimation, int on_cose
     return GA_OK;
 } GA_ABI_CATCH
 
-int ga_plonk_quotient(ga_domain* dh0, ga_domain* dh1, const ga_plonk_quotient_in* in, void* h_out) try {
-    GA_ABI_ENTRY();
-    Domain *d0 = reinterpret_cast<Domain*>(dh0), *d1 = reinterpret_cast<Domain*>(dh1);
-    if (!d0 || !d1 || !in || !h_out || !in->l || !in->r || !in->o || !in->z || !in->ql || !in->qr || !in->qm || !in->qo || !in->qk ||
-        !in->s1 || !in->s2 || !in->s3 || !in->bl || !in->br || !in->bo || !in->bz || !in->alpha || !in->beta || !in->gamma ||
-        (in->nb_bsb && (!in->qcp || !in->pi2))) {
-        set_error("ga_plonk_quotient: null argument");
-        return GA_ERR_INVALID;
-    }
-    if (in->nb_bsb > (uint32_t)PLONK_MAX_BSB || ntt_domain_curve(d0) != ntt_domain_curve(d1) || ntt_domain_ctx(d0) != ntt_domain_ctx(d1)) {
-        set_error("ga_plonk_quotient: more than %d BSB22 gates, or the two domains differ in curve/context", PLONK_MAX_BSB);
-        return GA_ERR_INVALID;
-    }
-    Ctx* c = ntt_domain_ctx(d0);
-    Lock l(c);
-    PlonkQuotientArgs a;
-    memset(&a, 0, sizeof(a));
-    a.nb_bsb = in->nb_bsb;
-    const void* fixed[PLONK_NB_FIXED] = {in->l, in->r, in->o, in->z, in->ql, in->qr, in->qm, in->qo, in->qk, in->s1, in->s2, in->s3};
-    for (int k = 0; k < PLONK_NB_FIXED; k++) a.polys[k] = fixed[k];
-    for (uint32_t k = 0; k < in->nb_bsb; k++) {
-        if (!in->qcp[k] || !in->pi2[k]) {
-            set_error("ga_plonk_quotient: null Qcp / Pi2 polynomial %u", k);
-            return GA_ERR_INVALID;
-        }
-        a.polys[PLONK_NB_FIXED + 2 * k] = in->qcp[k];
-        a.polys[PLONK_NB_FIXED + 2 * k + 1] = in->pi2[k];
-    }
-    a.lagrange_mask = in->lagrange_mask;
-    a.on_device = (in->flags & GA_PLONK_ON_DEVICE) != 0;
-    a.bl = in->bl; a.br = in->br; a.bo = in->bo; a.bz = in->bz;
-    a.alpha = in->alpha; a.beta = in->beta; a.gamma = in->gamma;
-    GA_DISPATCH_CURVE(ntt_domain_curve(d0), GA_CHECK(plonk_domain_quotient<C>(d0, d1, a, h_out)));
-    return GA_OK;
-} GA_ABI_CATCH
-
 static int plonk_args_from(const ga_plonk_quotient_in* in, bool need_fixed, bool need_var, PlonkQuotientArgs* a) {
     memset(a, 0, sizeof(*a));
     if (in->nb_bsb > (uint32_t)PLONK_MAX_BSB) {
@@ -908,6 +871,21 @@ static int plonk_args_from(const ga_plonk_quotient_in* in, bool need_fixed, bool
     a->alpha = in->alpha; a->beta = in->beta; a->gamma = in->gamma;
     return GA_OK;
 }
+
+int ga_plonk_quotient(ga_domain* dh0, ga_domain* dh1, const ga_plonk_quotient_in* in, void* h_out) try {
+    GA_ABI_ENTRY();
+    Domain *d0 = reinterpret_cast<Domain*>(dh0), *d1 = reinterpret_cast<Domain*>(dh1);
+    if (!d0 || !d1 || !in || !h_out || ntt_domain_curve(d0) != ntt_domain_curve(d1) || ntt_domain_ctx(d0) != ntt_domain_ctx(d1)) {
+        set_error("ga_plonk_quotient: null argument, or the two domains differ in curve/context");
+        return GA_ERR_INVALID;
+    }
+    Ctx* c = ntt_domain_ctx(d0);
+    Lock l(c);
+    PlonkQuotientArgs a;
+    GA_CHECK(plonk_args_from(in, true, true, &a));
+    GA_DISPATCH_CURVE(ntt_domain_curve(d0), GA_CHECK(plonk_domain_quotient<C>(d0, d1, a, h_out)));
+    return GA_OK;
+} GA_ABI_CATCH
 
 int ga_plonk_pk_create(ga_domain* dh0, ga_domain* dh1, const ga_plonk_quotient_in* in, ga_plonk_pk** out) try {
     GA_ABI_ENTRY();

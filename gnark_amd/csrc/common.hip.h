@@ -158,7 +158,6 @@ struct StageRec {
 //   GA_TABLE_C            force the window width of precomputed tables built from now on (experiments; 0 = planned)
 //   GA_G16_LANES          1: a second concurrent ga_g16_prove caller queues for the device instead of proving on its own lanes
 //   GA_G16_SPLIT          0: a proof keeps its H side (computeH, Z MSM) on the lane of its witness MSMs instead of a partner lane
-//   GA_NTT_COSET_FOLD     0: coset FFTs scale their input by the coset powers (round 2) instead of running over a coset twiddle table
 //   GA_NTT_WAVE_LOCAL     0: every round of an NTT pass ends in a workgroup barrier (round 3) instead of wave-local exchanges
 //   GA_NTT_DIRECT         0: the first / last round of an NTT pass goes through LDS instead of moving its quads to / from HBM itself
 // (GA_HBM_RESERVE_MB is read once per process by device_malloc: see there.)
@@ -171,7 +170,6 @@ struct Tunables {
     std::atomic<int> g16_lanes{2};
     std::atomic<int> g16_split{1};
     std::atomic<int> g16_batch_tables{1};            // 1: the wire-indexed G1 tables of a proof (A, B1, K) in one pass of every MSM kernel
-    std::atomic<int> ntt_coset_fold{1};
     std::atomic<int> ntt_wave_local{1};
     std::atomic<int> ntt_direct{1};
     std::atomic<int> table_c{0};

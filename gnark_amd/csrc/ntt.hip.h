@@ -6,15 +6,19 @@
 //   inverse includes 1/n;  OnCoset: forward pre-scales coefficient i by g^i, inverse post-scales by g^-i.
 //
 // Design (HBM-bound shape: 64 B algorithmic traffic per element per transform):
-//   * log2(n) butterfly stages are split into passes; one pass = one kernel = one HBM round trip.  A pass owns
-//     K consecutive stages [s_lo, s_lo+K); a workgroup stages a tile of 2^K strided rows x 2^lc contiguous
-//     columns (x 2^g independent groups) in LDS, runs the K stages out of LDS and writes the tile back.
-//   * global traffic is 16 B per lane, lanes walking consecutive 16-byte halves of consecutive elements
-//     (2^lc * 32 B contiguous per row), so every pass streams at full width even for the strided top stages.
-//   * LDS layout is two planes of uint4 (low / high 16 bytes of each element): a butterfly's ds_read_b128 /
-//     ds_write_b128 are conflict-free for unit-stride lanes.
-//   * coset scaling and the 1/n factor are fused into the first / last pass (two small power tables:
-//     g^k for k < 2^12 and g^(k*2^12)), so OnCoset transforms cost no extra HBM pass.
+//   * log2(n) butterfly stages are split into passes (ntt_plan); one pass = one launch of ntt_pass29r4_kernel = one HBM round
+//     trip.  A pass owns K consecutive stages [s_lo, s_lo+K); a workgroup stages a tile of 2^K strided rows x 2^lc contiguous
+//     columns (x 2^g independent groups) in LDS, runs the K stages there, two at a time (radix-4 rounds, a radix-2 round when K
+//     is odd), and writes the tile back.
+//   * elements stay in gnark's Montgomery form in HBM; inside a pass they are nine lazy 29-bit limbs (field29.hip.h), reduced
+//     once at the store.  The LDS tile is [NL][tile] words, one plane per limb.
+//   * twiddles come from per-domain tables of hat(w) = w * 2^261, laid out so that each stage reads them densely: TS (stacked
+//     per stage) for bit-reversed -> natural transforms, TB (bit-reversed) for natural -> bit-reversed ones, each for w and 1/w.
+//   * a forward bit-reversed -> natural transform on a coset runs over TSg, a TS with the coset shift folded into its entries
+//     (ntt_coset_table: the domain's g, one more per coset of the PLONK quotient), and scales nothing.  The other coset transforms
+//     multiply by g^i in their first pass (forward) or by g^-i / n in their last (inverse) from two small power tables (g^k for
+//     k < 2^12, g^(k * 2^12)); a plain inverse multiplies by 1/n in its last pass.  No transform costs an extra HBM pass.
+// Representation, butterflies, table layouts and the measurements behind them: the comment above ntt_pass29r4_kernel.
 #pragma once
 #include "common.hip.h"
 #include "field29.hip.h"
@@ -59,22 +63,6 @@ __device__ __forceinline__ uint64_t bitrev64(uint64_t i, int logn) {
     uint32_t lo = __brev((uint32_t)i), hi = __brev((uint32_t)(i >> 32));
     uint64_t r = ((uint64_t)lo << 32) | hi;
     return r >> (64 - logn);
-}
-
-template <class FrP>
-__device__ __forceinline__ Fe<FrP> ntt_scale_factor(const NttScale& sc, uint64_t i, int logn) {
-    if (sc.mode == 1) {
-        Fe<FrP> f;
-#pragma unroll
-        for (int k = 0; k < 8; k++) f.l[k] = sc.cst[k];
-        return f;
-    }
-    uint64_t idx = sc.bitrev ? bitrev64(i, logn) : i;
-    Fe<FrP> a = load_fe_plain<FrP>(sc.lo + (idx & ((1ull << sc.lo_bits) - 1)) * 8);
-    uint64_t h = idx >> sc.lo_bits;
-    if (h == 0 && logn <= sc.lo_bits) return a;
-    Fe<FrP> b = load_fe_plain<FrP>(sc.hi + h * 8);
-    return mul(a, b);
 }
 
 // ---- one pass over stages [s_lo, s_lo+K) in the lazy unpacked representation (field29.hip.h) ----------------------------------
@@ -442,8 +430,10 @@ struct Domain {
     uint32_t* d_g_hi = nullptr;
     uint32_t* d_gi_lo = nullptr;    // g^-k / n
     uint32_t* d_gi_hi = nullptr;
-    static constexpr bool lazy = true;   // twiddle / scale tables are kept in the hat domain (w * 2^261) for the lazy passes
-    uint32_t ninv[8];               // 1/n (Montgomery; hat-packed when lazy)
+    // twiddle and scale tables and ninv are kept in the hat domain (w * 2^261) for the lazy passes
+    uint32_t ninv[8];               // hat(1/n): the scale factor of a plain inverse transform
+    uint32_t ninv_mont[8];          // 1/n (Montgomery)
+    uint32_t w[8];                  // generator of the domain (Montgomery)
     uint32_t den[8];                // (g^n - 1)^-1 (Montgomery), prove.go:370-373
     std::vector<NttPass> passes;    // ascending stage order
 };
@@ -574,9 +564,9 @@ int ntt_fft(Domain* d, uint32_t* d_data, int direction, int decimation, int on_c
     bool dit = decimation == GA_DIT;
     NttScale pre = scale_none(), post = scale_none();
     if (!inverse) {
-        if (on_coset && dit && d->d_ts_g && d->ctx->tun.ntt_coset_fold)   // the coset lives in the twiddle table: no scaling pass
+        if (on_coset && dit)   // the coset lives in the twiddle table: no scaling pass
             return ntt_run<FrP>(d, d_data, false, true, pre, post, nullptr, d->d_ts_g);
-        if (on_coset) pre = scale_pow(d->d_g_lo, d->d_g_hi, /*bitrev=*/dit);
+        if (on_coset) pre = scale_pow(d->d_g_lo, d->d_g_hi, /*bitrev=*/false);
     } else {
         if (on_coset) post = scale_pow(d->d_gi_lo, d->d_gi_hi, /*bitrev=*/!dit);
         else post = scale_const(d->ninv);
@@ -594,8 +584,6 @@ int ntt_compute_h_chain(Domain* d, uint32_t* d_v) {
     // n * FFT_coset(iFFT(v)) without a single scaling multiplication: the inverse transform leaves its 1/n out (the point-wise step
     // of ntt_compute_h_combine absorbs it: the chains are only ever consumed there) and the forward one runs over the coset table
     GA_CHECK(ntt_run<FrP>(d, d_v, /*inverse=*/true, /*dit=*/false, scale_none(), scale_none()));
-    if (!d->ctx->tun.ntt_coset_fold)   // (A/B: the round-2 form, coset powers and 1/n applied to the input of the forward transform; x n to match)
-        return ntt_run<FrP>(d, d_v, /*inverse=*/false, /*dit=*/true, scale_pow(d->d_g_lo, d->d_g_hi, true), scale_none());
     return ntt_run<FrP>(d, d_v, /*inverse=*/false, /*dit=*/true, scale_none(), scale_none(), nullptr, d->d_ts_g);
 }
 
@@ -664,6 +652,40 @@ int ntt_coset_table(Domain* d, const Fe<FrP>& shift, const uint32_t** out) {
     return GA_OK;
 }
 
+// generator of the subgroup of order 2^logn (or its inverse): ROOT^(2^(adicity - logn))
+template <class FrP>
+Fe<FrP> ntt_root_of_unity(int logn, bool inverse = false) {
+    Fe<FrP> w = fe_const<FrP>(inverse ? FrP::ROOT_INV : FrP::ROOT);
+    for (int k = 0; k < FrP::ADICITY - logn; k++) w = sqr(w);
+    return w;
+}
+
+// Host words of the two-level power table of `base` with first factor c0 that covers exponents below n: 2^NTT_POW_LO_BITS entries
+// lo[k] = c0 * base^k, then max(n >> NTT_POW_LO_BITS, 1) entries hi[k] = base^(k << NTT_POW_LO_BITS).  hat: entries in the hat
+// domain (scale tables of the pass kernels: NttScale), else in plain Montgomery form (plonk_point)
+template <class FrP>
+std::vector<uint32_t> ntt_pow_table_host(const Fe<FrP>& base, const Fe<FrP>& c0, uint64_t n, bool hat) {
+    typedef Fe<FrP> F;
+    const uint64_t nlo = 1ull << NTT_POW_LO_BITS;
+    const uint64_t nhi = (n >> NTT_POW_LO_BITS) ? (n >> NTT_POW_LO_BITS) : 1;
+    std::vector<uint32_t> buf((nlo + nhi) * 8);
+    F acc = c0;
+    for (uint64_t k = 0; k < nlo; k++) {
+        F st = hat ? f29_hat_packed(acc) : acc;
+        memcpy(&buf[k * 8], st.l, 32);
+        acc = mul(acc, base);
+    }
+    F step = base;
+    for (int k = 0; k < NTT_POW_LO_BITS; k++) step = sqr(step);
+    acc = fe_one<FrP>();
+    for (uint64_t k = 0; k < nhi; k++) {
+        F st = hat ? f29_hat_packed(acc) : acc;
+        memcpy(&buf[(nlo + k) * 8], st.l, 32);
+        acc = mul(acc, step);
+    }
+    return buf;
+}
+
 template <class FrP>
 int domain_init(Ctx* ctx, Domain* d, int curve, uint64_t n) {
     typedef Fe<FrP> F;
@@ -676,22 +698,17 @@ int domain_init(Ctx* ctx, Domain* d, int curve, uint64_t n) {
         return GA_ERR_INVALID;
     }
     d->passes = ntt_plan(d->logn);
-    // host: w = ROOT^(2^(adicity-logn)), inverse likewise; tables of w^(2^k)
-    F w = fe_const<FrP>(FrP::ROOT), wi = fe_const<FrP>(FrP::ROOT_INV);
-    for (int k = 0; k < FrP::ADICITY - d->logn; k++) {
-        w = sqr(w);
-        wi = sqr(wi);
-    }
+    const F w = ntt_root_of_unity<FrP>(d->logn), wi = ntt_root_of_unity<FrP>(d->logn, /*inverse=*/true);
+    memcpy(d->w, w.l, 32);
     F g = fe_const<FrP>(FrP::GEN), gi = fe_const<FrP>(FrP::GEN_INV);
     // 1/n = (1/2)^logn
     F two = add(fe_one<FrP>(), fe_one<FrP>());
     F half = inv(two);
     F ninv = fe_one<FrP>();
     for (int k = 0; k < d->logn; k++) ninv = mul(ninv, half);
-    {
-        F nv = d->lazy ? f29_hat_packed(ninv) : ninv;   // used as a scale factor by the pass kernels
-        memcpy(d->ninv, nv.l, 32);
-    }
+    memcpy(d->ninv_mont, ninv.l, 32);
+    const F nv = f29_hat_packed(ninv);   // used as a scale factor by the pass kernels
+    memcpy(d->ninv, nv.l, 32);
     // den = (g^n - 1)^-1
     F gn = g;
     for (int k = 0; k < d->logn; k++) gn = sqr(gn);
@@ -732,30 +749,13 @@ int domain_init(Ctx* ctx, Domain* d, int curve, uint64_t n) {
         d->d_ts_g = const_cast<uint32_t*>(tg);
     }
     // coset power tables (host-computed: <= 2^12 + n/2^12 entries each)
-    uint64_t nlo = 1ull << NTT_POW_LO_BITS;
-    uint64_t nhi = (n >> NTT_POW_LO_BITS) ? (n >> NTT_POW_LO_BITS) : 1;
     auto build = [&](const F& base, const F& c0, uint32_t** dlo, uint32_t** dhi) -> int {
-        std::vector<uint32_t> lo(nlo * 8), hi(nhi * 8);
-        F acc = c0;
-        for (uint64_t k = 0; k < nlo; k++) {
-            F st = d->lazy ? f29_hat_packed(acc) : acc;
-            memcpy(&lo[k * 8], st.l, 32);
-            acc = mul(acc, base);
-        }
-        F step = base;
-        for (int k = 0; k < NTT_POW_LO_BITS; k++) step = sqr(step);
-        acc = fe_one<FrP>();
-        for (uint64_t k = 0; k < nhi; k++) {
-            F st = d->lazy ? f29_hat_packed(acc) : acc;
-            memcpy(&hi[k * 8], st.l, 32);
-            acc = mul(acc, step);
-        }
-        GA_HIP_CHECK(device_malloc((void**)dlo, nlo * 32));
-        GA_HIP_CHECK(hipMemcpy(*dlo, lo.data(), nlo * 32, hipMemcpyHostToDevice));
-        if (dhi) {
-            GA_HIP_CHECK(device_malloc((void**)dhi, nhi * 32));
-            GA_HIP_CHECK(hipMemcpy(*dhi, hi.data(), nhi * 32, hipMemcpyHostToDevice));
-        }
+        const std::vector<uint32_t> tab = ntt_pow_table_host<FrP>(base, c0, n, /*hat=*/true);
+        const size_t lo_bytes = (size_t)32 << NTT_POW_LO_BITS, hi_bytes = tab.size() * 4 - lo_bytes;
+        GA_HIP_CHECK(device_malloc((void**)dlo, lo_bytes));
+        GA_HIP_CHECK(hipMemcpy(*dlo, tab.data(), lo_bytes, hipMemcpyHostToDevice));
+        GA_HIP_CHECK(device_malloc((void**)dhi, hi_bytes));
+        GA_HIP_CHECK(hipMemcpy(*dhi, tab.data() + lo_bytes / 4, hi_bytes, hipMemcpyHostToDevice));
         return GA_OK;
     };
     GA_CHECK(build(g, fe_one<FrP>(), &d->d_g_lo, &d->d_g_hi));

@@ -5,13 +5,16 @@
 // coset_i = g*w1^i, converts every polynomial back to canonical form, rescales it and runs a forward FFT (two FFTs per
 // polynomial and coset, prove.go:1033-1058: "we do **a lot** of FFT here").  Here the canonical coefficients stay resident
 // in HBM in bit-reversed order (one inverse DIF per polynomial, once), each coset costs ONE out-of-place coset DIT per
-// polynomial with the coset scaling fused into its first pass, the pointwise constraint (gate + alpha*ordering +
+// polynomial over a twiddle table that carries the coset shift (ntt_coset_table), the pointwise constraint (gate + alpha*ordering +
 // alpha^2*(Z-1)*L1, blinding included) is one kernel that also applies divideByZH's 1/(X^n-1) factor and writes the result
 // at its bit-reversed slot, and the final inverse coset transform of size rho*n produces h in canonical order.
 // 1/(x-1) for L1 comes from a batched Montgomery-trick inversion kernel (the reference's batchInvert, prove.go:1134-1147).
 // Field elements are mathematically unique, so the coefficients equal the reference's bit for bit.
 #pragma once
 #include "ntt.hip.h"
+#include <algorithm>
+#include <iterator>
+#include <memory>
 
 namespace ga {
 
@@ -293,35 +296,17 @@ __global__ void fr_chunk_apply_kernel(const uint32_t* __restrict__ num, const ui
 
 // ---- host side -----------------------------------------------------------------------------------------------------
 
-// two-level power table of `base` with first factor c0 (plain Montgomery form): lo[k] = c0*base^k, hi[k] = base^(k << LO)
+// two-level power table of `base` with first factor c0 in plain Montgomery form (ntt_pow_table_host), uploaded into scratch `key`
 template <class FrP>
-int plonk_pow_tables(Ctx* ctx, const char* key, const Fe<FrP>& base, const Fe<FrP>& c0, uint64_t n, bool hat, uint32_t** d_lo,
-                     uint32_t** d_hi) {
-    typedef Fe<FrP> F;
-    const uint64_t nlo = 1ull << NTT_POW_LO_BITS;
-    const uint64_t nhi = (n >> NTT_POW_LO_BITS) ? (n >> NTT_POW_LO_BITS) : 1;
-    std::vector<uint32_t> buf((nlo + nhi) * 8);
-    F acc = c0;
-    for (uint64_t k = 0; k < nlo; k++) {
-        F st = hat ? f29_hat_packed(acc) : acc;
-        memcpy(&buf[k * 8], st.l, 32);
-        acc = mul(acc, base);
-    }
-    F step = base;
-    for (int k = 0; k < NTT_POW_LO_BITS; k++) step = sqr(step);
-    acc = fe_one<FrP>();
-    for (uint64_t k = 0; k < nhi; k++) {
-        F st = hat ? f29_hat_packed(acc) : acc;
-        memcpy(&buf[(nlo + k) * 8], st.l, 32);
-        acc = mul(acc, step);
-    }
+int plonk_pow_tables(Ctx* ctx, const char* key, const Fe<FrP>& base, const Fe<FrP>& c0, uint64_t n, uint32_t** d_lo, uint32_t** d_hi) {
+    const std::vector<uint32_t> buf = ntt_pow_table_host<FrP>(base, c0, n, /*hat=*/false);
     void* d;
     GA_CHECK(ctx->scratch_get(key, buf.size() * 4, &d));
     // the staging vector dies at return: synchronous copy (pageable memory)
     GA_HIP_CHECK(hipMemcpyAsync(d, buf.data(), buf.size() * 4, hipMemcpyHostToDevice, ctx->stream));
     GA_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     *d_lo = (uint32_t*)d;
-    *d_hi = (uint32_t*)d + nlo * 8;
+    *d_hi = (uint32_t*)d + ((size_t)8 << NTT_POW_LO_BITS);
     return GA_OK;
 }
 
@@ -336,11 +321,16 @@ Fe<FrP> plonk_host_pow(Fe<FrP> a, uint64_t e) {
     return r;
 }
 
+// element k of a host array of field elements (Montgomery images) / its words into a kernel argument
 template <class FrP>
-Fe<FrP> plonk_root_of_unity(int logn) {
-    Fe<FrP> w = fe_const<FrP>(FrP::ROOT);
-    for (int k = 0; k < FrP::ADICITY - logn; k++) w = sqr(w);
-    return w;
+Fe<FrP> plonk_ld(const void* p, int k = 0) {
+    Fe<FrP> f;
+    memcpy(f.l, (const char*)p + 32 * k, 32);
+    return f;
+}
+template <class FrP>
+void plonk_put(uint32_t* dst, const Fe<FrP>& v) {
+    memcpy(dst, v.l, 32);
 }
 
 // Circuit-constant part of the quotient, pinned in HBM (the "huge memory footprint" precomputation prove.go:1030-1034 decides
@@ -348,204 +338,236 @@ Fe<FrP> plonk_root_of_unity(int logn) {
 // each coset -- (7 + k + 1) * rho * n * 32 B, 4.3 GB at n = 2^22.  Per proof only L, R, O, Z, Qk and the BSB22 commitment
 // polynomials are transformed: 6 + 4*6 + 1 transforms instead of 12 + 4*12 + 1.
 struct PlonkFixed {
-    Ctx* ctx = nullptr;
     Domain *d0 = nullptr, *d1 = nullptr;
     uint32_t nb_bsb = 0;
     int nslots = 0;
     int slot[PLONK_NB_FIXED + 2 * PLONK_MAX_BSB];   // -1: per-proof polynomial; else index into evals
     uint32_t* evals = nullptr;     // [rho][nslots][n] fr
     uint32_t* inv_xm1 = nullptr;   // [rho][n] fr
+    uint32_t* evals_of(uint64_t coset, int p) const { return evals + ((size_t)(coset * nslots + slot[p])) * d0->n * 8; }
+    uint32_t* inv_xm1_of(uint64_t coset) const { return inv_xm1 + (size_t)coset * d0->n * 8; }
 };
-inline bool plonk_is_fixed(int p) {
-    if (p >= PLONK_NB_FIXED) return ((p - PLONK_NB_FIXED) & 1) == 0;               // Qcp_i fixed, Pi2_i per proof
-    return p == PX_QL || p == PX_QR || p == PX_QM || p == PX_QO || p == PX_S1 || p == PX_S2 || p == PX_S3;
-}
-
-// mode 0: everything per call; mode 1: build `fx` from the fixed polynomials of A (no quotient); mode 2: quotient with `fx`
-template <class FrP>
-int plonk_quotient(Domain* d0, Domain* d1, const PlonkQuotientArgs& A, void* h_out, int mode = 0, PlonkFixed* fx = nullptr) {
-    typedef Fe<FrP> F;
-    Ctx* ctx = d0->ctx;
-    const uint64_t n = d0->n, N = d1->n;
-    const int logn = d0->logn;
-    if (n < 2 || N < n || N % n != 0 || A.nb_bsb > (uint32_t)PLONK_MAX_BSB || d1->ctx != ctx) {
-        set_error("plonk quotient: need n >= 2, |domain1| a multiple of |domain0|, at most %d BSB22 gates", PLONK_MAX_BSB);
-        return GA_ERR_INVALID;
-    }
-    if (mode == 2 && (fx->nb_bsb != A.nb_bsb || fx->d0 != d0 || fx->d1 != d1)) {
-        set_error("plonk quotient: the pinned key was built for %u BSB22 gates / other domains", fx->nb_bsb);
-        return GA_ERR_INVALID;
-    }
-    const uint64_t rho = N / n;
-    const int logrho = ilog2_u64(rho);
-    const int np = PLONK_NB_FIXED + 2 * (int)A.nb_bsb;
-    hipStream_t st = ctx->stream;
-    uint32_t *canon, *work, *invb, *tmpb, *cres;
-    GA_CHECK(ctx->scratch_get("plonk_canon", (size_t)np * n * 32, (void**)&canon));
-    GA_CHECK(ctx->scratch_get("plonk_work", (size_t)np * n * 32, (void**)&work));
-    GA_CHECK(ctx->scratch_get("plonk_inv", n * 32, (void**)&invb));
-    GA_CHECK(ctx->scratch_get("plonk_tmp", n * 32, (void**)&tmpb));
-    GA_CHECK(ctx->scratch_get("plonk_cres", N * 32, (void**)&cres));
-    const unsigned blocks = (unsigned)((n + 255) / 256);
-    auto skip = [&](int p) { return mode == 1 ? !plonk_is_fixed(p) : (mode == 2 && plonk_is_fixed(p)); };
-    // ---- canonical coefficients in bit-reversed order, once ---------------------------------------------------------
-    for (int p = 0; p < np; p++) {
-        if (skip(p)) continue;
-        uint32_t* dst = canon + (size_t)p * n * 8;
-        uint32_t* stage = work + (size_t)p * n * 8;
-        const bool lag = (A.lagrange_mask >> p) & 1;
-        {
-            StageTimer tm(ctx, "plonk_h2d");
-            GA_HIP_CHECK(hipMemcpyAsync(lag ? dst : stage, A.polys[p], n * 32, A.on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-        }
-        if (lag) {
-            // Lagrange regular -> canonical bit-reversed: inverse DIF with the 1/n (p.ToCanonical, prove.go:1036)
-            GA_CHECK(ntt_run<FrP>(d0, dst, /*inverse=*/true, /*dit=*/false, scale_none(), scale_const(d0->ninv)));
-        } else {
-            StageTimer tm(ctx, "plonk_bitrev");
-            hipLaunchKernelGGL((fr_bitrev_copy_kernel<FrP>), dim3(blocks), dim3(256), 0, st, dst, stage, n, logn);
-            GA_KERNEL_CHECK();
-        }
-    }
-    // ---- constants ------------------------------------------------------------------------------------------------------
-    auto ld = [](const void* p, int k = 0) {
-        F f;
-        memcpy(f.l, (const char*)p + 32 * k, 32);
-        return f;
-    };
-    const F g = fe_const<FrP>(FrP::GEN);
-    const F w0 = plonk_root_of_unity<FrP>(logn), w1 = plonk_root_of_unity<FrP>(d1->logn);
-    F ninv = fe_one<FrP>();
-    {
-        F half = inv(add(fe_one<FrP>(), fe_one<FrP>()));
-        for (int k = 0; k < logn; k++) ninv = mul(ninv, half);
-    }
-    PlonkConsts K;
-    auto put = [](uint32_t* dst, const F& v) { memcpy(dst, v.l, 32); };
-    memset(&K, 0, sizeof(K));
-    if (mode != 1) {
-        put(K.alpha, ld(A.alpha));
-        put(K.beta, ld(A.beta));
-        put(K.gamma, ld(A.gamma));
-    }
-    put(K.cs, g);              // prove.go:891-893
-    put(K.css, sqr(g));
-    put(K.omega, w0);
-    PlonkPtrs P;
-    memset(&P, 0, sizeof(P));
-    P.nb_bsb = (int)A.nb_bsb;
-    F coset = fe_one<FrP>();
-    for (uint64_t i = 0; i < rho; i++) {
-        for (int p = 0; p < np; p++)
-            P.p[p] = (mode == 2 && plonk_is_fixed(p)) ? fx->evals + ((size_t)(i * fx->nslots + fx->slot[p])) * n * 8 : work + (size_t)p * n * 8;
-        coset = mul(coset, i == 0 ? g : w1);                       // shifters, prove.go:936-941,998
-        const F cexp = sub(plonk_host_pow<FrP>(coset, n), fe_one<FrP>());   // (coset^n - 1), prove.go:999-1000
-        if (mode != 1)
-        for (int k = 0; k < 2; k++) {
-            put(K.bl[k], mul(ld(A.bl, k), cexp));
-            put(K.br[k], mul(ld(A.br, k), cexp));
-            put(K.bo[k], mul(ld(A.bo, k), cexp));
-        }
-        if (mode != 1)
-            for (int k = 0; k < 3; k++) put(K.bz[k], mul(ld(A.bz, k), cexp));
-        put(K.lone, mul(cexp, ninv));
-        put(K.zh_inv, inv(cexp));
-        {   // 32 c mod r of the constants the lazy constraint kernel multiplies by (five modular doublings each, host)
-            auto sh5 = [&](const uint32_t* c) {
-                F v = ld(c);
-                for (int k = 0; k < 5; k++) v = add(v, v);
-                return v;
-            };
-            const uint32_t* src[11] = {K.omega, K.bl[1], K.br[1], K.bo[1], K.bz[2], K.beta, K.cs, K.css, K.lone, K.alpha, K.zh_inv};
-            for (int q = 0; q < 11; q++) put(K.sh[q], sh5(src[q]));   // (index = PSH_*)
-        }
-        // evaluations on coset*H: forward DIT with the coset powers fused into the first pass (prove.go:1033-1058)
-        // (round 3: the coset lives in the twiddle table -- ntt_coset_table, built once per domain and coset and kept -- instead of
-        // a scaling of the input by coset^i: two products per element and transform less)
-        uint32_t *x_lo, *x_hi, *s_lo = nullptr, *s_hi = nullptr;
-        const uint32_t* coset_tw = nullptr;
-        const bool fold = ctx->tun.ntt_coset_fold != 0;
-        if (fold) GA_CHECK(ntt_coset_table<FrP>(d0, coset, &coset_tw));
-        else GA_CHECK(plonk_pow_tables<FrP>(ctx, "plonk_scale_tab", coset, fe_one<FrP>(), n, d0->lazy, &s_lo, &s_hi));
-        GA_CHECK(plonk_pow_tables<FrP>(ctx, "plonk_x_tab", w0, coset, n, false, &x_lo, &x_hi));
-        for (int p = 0; p < np; p++) {
-            if (skip(p)) continue;
-            uint32_t* dst = mode == 1 ? fx->evals + ((size_t)(i * fx->nslots + fx->slot[p])) * n * 8 : work + (size_t)p * n * 8;
-            if (fold) GA_CHECK(ntt_run<FrP>(d0, dst, /*inverse=*/false, /*dit=*/true, scale_none(), scale_none(), canon + (size_t)p * n * 8, coset_tw));
-            else GA_CHECK(ntt_run<FrP>(d0, dst, /*inverse=*/false, /*dit=*/true, scale_pow(s_lo, s_hi, /*bitrev=*/true), scale_none(), canon + (size_t)p * n * 8));
-        }
-        uint32_t* inv_i = mode == 0 ? invb : fx->inv_xm1 + (size_t)i * n * 8;
-        if (mode != 2) {
-            StageTimer tm(ctx, "plonk_batch_inverse");
-            hipLaunchKernelGGL((plonk_x_minus_one_kernel<FrP>), dim3(blocks), dim3(256), 0, st, inv_i, x_lo, x_hi, NTT_POW_LO_BITS, n);
-            const uint64_t threads = n < 65536 ? (n + 63) / 64 : n / 64;   // >= 64 elements per thread amortise the inversion
-            const unsigned ib = (unsigned)((threads + 63) / 64);
-            hipLaunchKernelGGL((fr_batch_inverse_kernel<FrP>), dim3(ib), dim3(64), 0, st, inv_i, tmpb, n);
-            GA_KERNEL_CHECK();
-        }
-        if (mode != 1) {
-            StageTimer tm(ctx, "plonk_constraints");
-            uint64_t block = 0;   // bitrev_N(rho*j + i) = bitrev_rho(i)*n + bitrev_n(j)
-            for (int b = 0; b < logrho; b++) block |= ((i >> b) & 1) << (logrho - 1 - b);
-            if constexpr (Radix<FrP>::NL * Radix<FrP>::L - FrP::BITS >= 7)   // (BN254: lazy representation; BLS12-381's 255-bit Fr leaves 6 spare bits: packed)
-                hipLaunchKernelGGL((plonk_constraints29_kernel<FrP>), dim3((unsigned)((n + 127) / 128)), dim3(128), 0, st, P, K, x_lo, x_hi,
-                                   NTT_POW_LO_BITS, inv_i, cres + block * n * 8, n, logn);
-            else
-                hipLaunchKernelGGL((plonk_constraints_kernel<FrP>), dim3((unsigned)((n + 127) / 128)), dim3(128), 0, st, P, K, x_lo, x_hi,
-                                   NTT_POW_LO_BITS, inv_i, cres + block * n * 8, n, logn);
-            GA_KERNEL_CHECK();
-        }
-    }
-    if (mode == 1) {
-        GA_HIP_CHECK(hipStreamSynchronize(st));
-        return GA_OK;
-    }
-    // ---- a.ToCanonical(bigDomain).ToRegular() from LagrangeCoset/BitReverse (prove.go:1319): inverse DIT on the coset ----
-    GA_CHECK(ntt_fft<FrP>(d1, cres, GA_FFT_INVERSE, GA_DIT, 1));
-    {
-        StageTimer tm(ctx, "plonk_d2h");
-        GA_HIP_CHECK(hipMemcpyAsync(h_out, cres, N * 32, A.on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
-    }
-    GA_HIP_CHECK(hipStreamSynchronize(st));
-    return GA_OK;
-}
-
-template <class FrP>
-int plonk_fixed_create(Domain* d0, Domain* d1, const PlonkQuotientArgs& A, PlonkFixed** out) {
-    const uint64_t n = d0->n, rho = d1->n / (d0->n ? d0->n : 1);
-    if (n < 2 || d1->n % n != 0 || A.nb_bsb > (uint32_t)PLONK_MAX_BSB || d1->ctx != d0->ctx) {
-        set_error("plonk key: need n >= 2, |domain1| a multiple of |domain0|, at most %d BSB22 gates", PLONK_MAX_BSB);
-        return GA_ERR_INVALID;
-    }
-    PlonkFixed* fx = new PlonkFixed();
-    fx->ctx = d0->ctx;
-    fx->d0 = d0;
-    fx->d1 = d1;
-    fx->nb_bsb = A.nb_bsb;
-    const int np = PLONK_NB_FIXED + 2 * (int)A.nb_bsb;
-    for (int p = 0; p < PLONK_NB_FIXED + 2 * PLONK_MAX_BSB; p++) fx->slot[p] = (p < np && plonk_is_fixed(p)) ? fx->nslots++ : -1;
-    const size_t ev = (size_t)rho * fx->nslots * n * 32, iv = (size_t)rho * n * 32;
-    if (device_malloc((void**)&fx->evals, ev) != hipSuccess || device_malloc((void**)&fx->inv_xm1, iv) != hipSuccess) {
-        set_error("plonk key: hipMalloc of %zu bytes failed", ev + iv);
-        hipFree(fx->evals);
-        delete fx;
-        return GA_ERR_NOMEM;
-    }
-    int rc = plonk_quotient<FrP>(d0, d1, A, nullptr, 1, fx);
-    if (rc != GA_OK) {
-        hipFree(fx->evals);
-        hipFree(fx->inv_xm1);
-        delete fx;
-        return rc;
-    }
-    *out = fx;
-    return GA_OK;
-}
 inline void plonk_fixed_destroy(PlonkFixed* fx) {
     if (!fx) return;
     hipFree(fx->evals);
     hipFree(fx->inv_xm1);
     delete fx;
+}
+inline bool plonk_is_fixed(int p) {
+    if (p >= PLONK_NB_FIXED) return ((p - PLONK_NB_FIXED) & 1) == 0;               // Qcp_i fixed, Pi2_i per proof
+    return p == PX_QL || p == PX_QR || p == PX_QM || p == PX_QO || p == PX_S1 || p == PX_S2 || p == PX_S3;
+}
+// the ids below np that are (not) circuit constants
+inline std::vector<int> plonk_ids(int np, bool fixed) {
+    std::vector<int> ids;
+    for (int p = 0; p < np; p++)
+        if (plonk_is_fixed(p) == fixed) ids.push_back(p);
+    return ids;
+}
+
+// One call of a driver below: the checked shape, the scratch buffers, the coset being worked on, and the stages as members.  A
+// driver calls begin once, to_canonical per polynomial it owns, then per coset begin_coset followed by the stages it needs (every
+// launch of a coset reads the coset's tables: x_lo / x_hi live in one scratch buffer that the next begin_coset overwrites after
+// its synchronisation).
+template <class FrP>
+struct PlonkRun {
+    typedef Fe<FrP> F;
+    Ctx* ctx;
+    Domain *d0, *d1;
+    hipStream_t st;
+    uint64_t n, rho;
+    int np;
+    unsigned blocks;                               // of 256 threads over n
+    uint32_t *canon, *work, *invb, *tmpb, *cres;   // [np][n] canonical bit-reversed, [np][n] coset evaluations, [n], [n], [rho*n]
+    F coset, cexp;                                 // the current coset: its shift g * w1^i and coset^n - 1,
+    const uint32_t* coset_tw;                      // the ntt_coset_table of the shift,
+    uint32_t *x_lo, *x_hi;                         // the power table of its points coset * w0^j,
+    PlonkConsts K;                                 // the constants
+    PlonkPtrs P;                                   // and where the constraint kernel reads each polynomial: work_of(p) unless a driver says otherwise
+    uint32_t* canon_of(int p) const { return canon + (size_t)p * n * 8; }
+    uint32_t* work_of(int p) const { return work + (size_t)p * n * 8; }
+
+    int begin(Domain* dom0, Domain* dom1, uint32_t nb_bsb) {
+        d0 = dom0, d1 = dom1, ctx = d0->ctx, st = ctx->stream, n = d0->n;
+        if (n < 2 || d1->n < n || d1->n % n != 0 || nb_bsb > (uint32_t)PLONK_MAX_BSB || d1->ctx != ctx) {
+            set_error("plonk: need n >= 2, |domain1| a multiple of |domain0|, at most %d BSB22 gates", PLONK_MAX_BSB);
+            return GA_ERR_INVALID;
+        }
+        rho = d1->n / n;
+        np = PLONK_NB_FIXED + 2 * (int)nb_bsb;
+        blocks = (unsigned)((n + 255) / 256);
+        GA_CHECK(ctx->scratch_get("plonk_canon", (size_t)np * n * 32, (void**)&canon));
+        GA_CHECK(ctx->scratch_get("plonk_work", (size_t)np * n * 32, (void**)&work));
+        GA_CHECK(ctx->scratch_get("plonk_inv", n * 32, (void**)&invb));
+        GA_CHECK(ctx->scratch_get("plonk_tmp", n * 32, (void**)&tmpb));
+        GA_CHECK(ctx->scratch_get("plonk_cres", d1->n * 32, (void**)&cres));
+        coset = fe_one<FrP>();
+        memset(&K, 0, sizeof(K));
+        memset(&P, 0, sizeof(P));
+        P.nb_bsb = (int)nb_bsb;
+        for (int p = 0; p < np; p++) P.p[p] = work_of(p);
+        return GA_OK;
+    }
+
+    // polynomial p of A to canonical coefficients in bit-reversed order (canon_of(p)), once per driver call
+    int to_canonical(const PlonkQuotientArgs& A, int p) {
+        uint32_t *dst = canon_of(p), *stage = work_of(p);
+        const bool lag = (A.lagrange_mask >> p) & 1;
+        {
+            StageTimer tm(ctx, "plonk_h2d");
+            GA_HIP_CHECK(hipMemcpyAsync(lag ? dst : stage, A.polys[p], n * 32, A.on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+        }
+        if (lag)   // Lagrange regular -> canonical bit-reversed: inverse DIF with the 1/n (p.ToCanonical, prove.go:1036)
+            return ntt_run<FrP>(d0, dst, /*inverse=*/true, /*dit=*/false, scale_none(), scale_const(d0->ninv));
+        StageTimer tm(ctx, "plonk_bitrev");
+        hipLaunchKernelGGL((fr_bitrev_copy_kernel<FrP>), dim3(blocks), dim3(256), 0, st, dst, stage, n, d0->logn);
+        GA_KERNEL_CHECK();
+        return GA_OK;
+    }
+
+    // Coset i (cosets are begun in order): the shift g * w1^i (shifters, prove.go:936-941,998), its twiddle table -- kept per domain
+    // and coset, so a forward transform scales nothing (prove.go:1033-1058) -- the table of its points, uploaded synchronously,
+    // and the proof-independent constants cs, css, omega, lone, zh_inv
+    int begin_coset(uint64_t i) {
+        const F g = fe_const<FrP>(FrP::GEN);
+        coset = mul(coset, i == 0 ? g : plonk_ld<FrP>(d1->w));
+        cexp = sub(plonk_host_pow<FrP>(coset, n), fe_one<FrP>());   // (coset^n - 1), prove.go:999-1000
+        plonk_put(K.cs, g);   // prove.go:891-893
+        plonk_put(K.css, sqr(g));
+        memcpy(K.omega, d0->w, 32);
+        plonk_put(K.lone, mul(cexp, plonk_ld<FrP>(d0->ninv_mont)));
+        plonk_put(K.zh_inv, inv(cexp));
+        GA_CHECK(ntt_coset_table<FrP>(d0, coset, &coset_tw));
+        return plonk_pow_tables<FrP>(ctx, "plonk_x_tab", plonk_ld<FrP>(d0->w), coset, n, &x_lo, &x_hi);
+    }
+
+    // the proof's constants on the current coset, after begin_coset: the challenges, the blinding coefficients times (coset^n - 1),
+    // and the images sh[] of the constants the lazy constraint kernel multiplies by
+    void proof_consts(const PlonkQuotientArgs& A) {
+        plonk_put(K.alpha, plonk_ld<FrP>(A.alpha));
+        plonk_put(K.beta, plonk_ld<FrP>(A.beta));
+        plonk_put(K.gamma, plonk_ld<FrP>(A.gamma));
+        for (int k = 0; k < 2; k++) {
+            plonk_put(K.bl[k], mul(plonk_ld<FrP>(A.bl, k), cexp));
+            plonk_put(K.br[k], mul(plonk_ld<FrP>(A.br, k), cexp));
+            plonk_put(K.bo[k], mul(plonk_ld<FrP>(A.bo, k), cexp));
+        }
+        for (int k = 0; k < 3; k++) plonk_put(K.bz[k], mul(plonk_ld<FrP>(A.bz, k), cexp));
+        const uint32_t* src[11] = {K.omega, K.bl[1], K.br[1], K.bo[1], K.bz[2], K.beta, K.cs, K.css, K.lone, K.alpha, K.zh_inv};   // (index = PSH_*)
+        for (int q = 0; q < 11; q++) {   // 32 c mod r: five modular doublings each
+            F v = plonk_ld<FrP>(src[q]);
+            for (int k = 0; k < 5; k++) v = add(v, v);
+            plonk_put(K.sh[q], v);
+        }
+    }
+
+    // dst = evaluations of polynomial p on the current coset: one out-of-place forward DIT over the coset's twiddle table
+    int eval_on_coset(int p, uint32_t* dst) {
+        return ntt_run<FrP>(d0, dst, /*inverse=*/false, /*dit=*/true, scale_none(), scale_none(), canon_of(p), coset_tw);
+    }
+
+    // out[j] = 1 / (x_j - 1) over the current coset
+    int inv_x_minus_one(uint32_t* out) {
+        StageTimer tm(ctx, "plonk_batch_inverse");
+        hipLaunchKernelGGL((plonk_x_minus_one_kernel<FrP>), dim3(blocks), dim3(256), 0, st, out, x_lo, x_hi, NTT_POW_LO_BITS, n);
+        const uint64_t threads = n < 65536 ? (n + 63) / 64 : n / 64;   // >= 64 elements per thread amortise the inversion
+        hipLaunchKernelGGL((fr_batch_inverse_kernel<FrP>), dim3((unsigned)((threads + 63) / 64)), dim3(64), 0, st, out, tmpb, n);
+        GA_KERNEL_CHECK();
+        return GA_OK;
+    }
+
+    // the constraints of coset i, from the evaluations P and 1/(x-1), into their block of cres
+    int constraints(const uint32_t* inv_xm1, uint64_t i) {
+        StageTimer tm(ctx, "plonk_constraints");
+        const int logrho = ilog2_u64(rho);
+        uint64_t block = 0;   // bitrev_N(rho*j + i) = bitrev_rho(i)*n + bitrev_n(j)
+        for (int b = 0; b < logrho; b++) block |= ((i >> b) & 1) << (logrho - 1 - b);
+        auto kernel = [] {   // BN254: lazy representation; BLS12-381's 255-bit Fr leaves 6 spare bits: packed
+            if constexpr (Radix<FrP>::NL * Radix<FrP>::L - FrP::BITS >= 7) return plonk_constraints29_kernel<FrP>;
+            else return plonk_constraints_kernel<FrP>;
+        }();
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, st, P, K, x_lo, x_hi, NTT_POW_LO_BITS, inv_xm1,
+                           cres + block * n * 8, n, d0->logn);
+        GA_KERNEL_CHECK();
+        return GA_OK;
+    }
+
+    // a.ToCanonical(bigDomain).ToRegular() from LagrangeCoset/BitReverse (prove.go:1319): inverse DIT on the coset, then h leaves
+    int finish(const PlonkQuotientArgs& A, void* h_out) {
+        GA_CHECK(ntt_fft<FrP>(d1, cres, GA_FFT_INVERSE, GA_DIT, 1));
+        {
+            StageTimer tm(ctx, "plonk_d2h");
+            GA_HIP_CHECK(hipMemcpyAsync(h_out, cres, d1->n * 32, A.on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+        }
+        GA_HIP_CHECK(hipStreamSynchronize(st));
+        return GA_OK;
+    }
+};
+
+// ---- the three drivers -------------------------------------------------------------------------------------------------
+// Every polynomial per call.
+template <class FrP>
+int plonk_quotient(Domain* d0, Domain* d1, const PlonkQuotientArgs& A, void* h_out) {
+    PlonkRun<FrP> R;
+    GA_CHECK(R.begin(d0, d1, A.nb_bsb));
+    for (int p = 0; p < R.np; p++) GA_CHECK(R.to_canonical(A, p));
+    for (uint64_t i = 0; i < R.rho; i++) {
+        GA_CHECK(R.begin_coset(i));
+        R.proof_consts(A);
+        for (int p = 0; p < R.np; p++) GA_CHECK(R.eval_on_coset(p, R.work_of(p)));
+        GA_CHECK(R.inv_x_minus_one(R.invb));
+        GA_CHECK(R.constraints(R.invb, i));
+    }
+    return R.finish(A, h_out);
+}
+
+// The key: the circuit constants of A on every coset and 1/(x-1) per coset; no quotient.
+template <class FrP>
+int plonk_fixed_create(Domain* d0, Domain* d1, const PlonkQuotientArgs& A, PlonkFixed** out) {
+    PlonkRun<FrP> R;
+    GA_CHECK(R.begin(d0, d1, A.nb_bsb));
+    const std::vector<int> fixed = plonk_ids(R.np, true);
+    std::unique_ptr<PlonkFixed, void (*)(PlonkFixed*)> fx(new PlonkFixed(), plonk_fixed_destroy);
+    fx->d0 = d0;
+    fx->d1 = d1;
+    fx->nb_bsb = A.nb_bsb;
+    std::fill(std::begin(fx->slot), std::end(fx->slot), -1);
+    for (int p : fixed) fx->slot[p] = fx->nslots++;
+    const size_t ev = (size_t)R.rho * fx->nslots * R.n * 32, iv = (size_t)R.rho * R.n * 32;
+    if (device_malloc((void**)&fx->evals, ev) != hipSuccess || device_malloc((void**)&fx->inv_xm1, iv) != hipSuccess) {
+        set_error("plonk key: hipMalloc of %zu bytes failed", ev + iv);
+        return GA_ERR_NOMEM;
+    }
+    for (int p : fixed) GA_CHECK(R.to_canonical(A, p));
+    for (uint64_t i = 0; i < R.rho; i++) {
+        GA_CHECK(R.begin_coset(i));
+        for (int p : fixed) GA_CHECK(R.eval_on_coset(p, fx->evals_of(i, p)));
+        GA_CHECK(R.inv_x_minus_one(fx->inv_xm1_of(i)));
+    }
+    GA_HIP_CHECK(hipStreamSynchronize(R.st));
+    *out = fx.release();
+    return GA_OK;
+}
+
+// The per-proof polynomials only; the constraints read the circuit constants and 1/(x-1) from the key.
+template <class FrP>
+int plonk_quotient_pinned(PlonkFixed* fx, const PlonkQuotientArgs& A, void* h_out) {
+    PlonkRun<FrP> R;
+    GA_CHECK(R.begin(fx->d0, fx->d1, A.nb_bsb));
+    if (fx->nb_bsb != A.nb_bsb) {
+        set_error("plonk quotient: the pinned key was built for %u BSB22 gates", fx->nb_bsb);
+        return GA_ERR_INVALID;
+    }
+    const std::vector<int> fixed = plonk_ids(R.np, true), proof = plonk_ids(R.np, false);
+    for (int p : proof) GA_CHECK(R.to_canonical(A, p));
+    for (uint64_t i = 0; i < R.rho; i++) {
+        GA_CHECK(R.begin_coset(i));
+        R.proof_consts(A);
+        for (int p : proof) GA_CHECK(R.eval_on_coset(p, R.work_of(p)));
+        for (int p : fixed) R.P.p[p] = fx->evals_of(i, p);
+        GA_CHECK(R.constraints(fx->inv_xm1_of(i), i));
+    }
+    return R.finish(A, h_out);
 }
 
 // ---- kzg.Open: p(z) and the coefficients of (p(X) - p(z)) / (X - z) -----------------------------------------------------
@@ -629,7 +651,7 @@ int kzg_divide_by_linear(Ctx* ctx, const uint32_t* d_poly, uint64_t n, const voi
     const unsigned blocks = (unsigned)((n + 255) / 256), cb = (unsigned)((nchunks + 63) / 64);
     uint32_t *lo, *hi;
     StageTimer tm(ctx, "kzg_divide");
-    GA_CHECK(plonk_pow_tables<FrP>(ctx, "plonk_x_tab", z, fe_one<FrP>(), n, false, &lo, &hi));
+    GA_CHECK(plonk_pow_tables<FrP>(ctx, "plonk_x_tab", z, fe_one<FrP>(), n, &lo, &hi));
     hipLaunchKernelGGL((kzg_scale_kernel<FrP>), dim3(blocks), dim3(256), 0, st, d_poly, t, lo, hi, NTT_POW_LO_BITS, n, (uint64_t)0);
     hipLaunchKernelGGL((fr_chunk_sum_kernel<FrP>), dim3(cb), dim3(64), 0, st, t, cs, n);
     hipLaunchKernelGGL((fr_chunk_suffix_scan_kernel<FrP>), dim3(1), dim3(256), 0, st, cs, nchunks);
@@ -643,7 +665,7 @@ int kzg_divide_by_linear(Ctx* ctx, const uint32_t* d_poly, uint64_t n, const voi
             GA_HIP_CHECK(hipMemcpyAsync(d_quot, d_poly + 8, (n - 1) * 32, hipMemcpyDeviceToDevice, st));
         } else {
             // q_k = S_{k+1} * z^-(k+1): table of zinv^j, element i of the output reads index i+1
-            GA_CHECK(plonk_pow_tables<FrP>(ctx, "plonk_scale_tab", inv(z), fe_one<FrP>(), n, false, &lo, &hi));
+            GA_CHECK(plonk_pow_tables<FrP>(ctx, "plonk_scale_tab", inv(z), fe_one<FrP>(), n, &lo, &hi));
             hipLaunchKernelGGL((kzg_scale_kernel<FrP>), dim3((unsigned)((n - 1 + 255) / 256)), dim3(256), 0, st, t, d_quot, lo, hi,
                                NTT_POW_LO_BITS, n - 1, (uint64_t)1);
             GA_KERNEL_CHECK();
@@ -776,7 +798,7 @@ int plonk_build_z(Domain* d0, const void* L, const void* R, const void* O, const
     F gg = sqr(g);
     memcpy(K.css, gg.l, 32);
     uint32_t *w_lo, *w_hi;
-    GA_CHECK(plonk_pow_tables<FrP>(ctx, "plonk_x_tab", plonk_root_of_unity<FrP>(d0->logn), fe_one<FrP>(), n, false, &w_lo, &w_hi));
+    GA_CHECK(plonk_pow_tables<FrP>(ctx, "plonk_x_tab", plonk_ld<FrP>(d0->w), fe_one<FrP>(), n, &w_lo, &w_hi));
     const unsigned blocks = (unsigned)((n + 255) / 256);
     {
         StageTimer tm(ctx, "plonk_z_terms");

@@ -11,7 +11,7 @@ int plonk_domain_fixed_create<Bls12381>(Domain* d0, Domain* d1, const PlonkQuoti
 }
 template <>
 int plonk_domain_quotient_pinned<Bls12381>(PlonkFixed* fx, const PlonkQuotientArgs& args, void* h_out) {
-    return plonk_quotient<Bls12381::FrP>(fx->d0, fx->d1, args, h_out, 2, fx);
+    return plonk_quotient_pinned<Bls12381::FrP>(fx, args, h_out);
 }
 template <>
 int plonk_domain_build_z<Bls12381>(Domain* d0, const void* L, const void* R, const void* O, const int64_t* perm, const void* beta,

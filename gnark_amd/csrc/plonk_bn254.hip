@@ -11,7 +11,7 @@ int plonk_domain_fixed_create<Bn254>(Domain* d0, Domain* d1, const PlonkQuotient
 }
 template <>
 int plonk_domain_quotient_pinned<Bn254>(PlonkFixed* fx, const PlonkQuotientArgs& args, void* h_out) {
-    return plonk_quotient<Bn254::FrP>(fx->d0, fx->d1, args, h_out, 2, fx);
+    return plonk_quotient_pinned<Bn254::FrP>(fx, args, h_out);
 }
 template <>
 int plonk_domain_build_z<Bn254>(Domain* d0, const void* L, const void* R, const void* O, const int64_t* perm, const void* beta,

@@ -494,6 +494,57 @@ def test_emu_plonk_quotient(emu_ctx, c, n, nb_bsb, seed=11):
         d1.close()
 
 
+def test_emu_plonk_null_arguments(emu_ctx):
+    """ga_plonk_quotient, ga_plonk_pk_create and ga_plonk_quotient_pinned answer GA_ERR_INVALID when exactly one of the pointers
+    they need is null -- the struct, the output, a polynomial, the Qcp / Pi2 array or an entry of it, a blinding polynomial, a
+    challenge -- and for more BSB22 gates than PLONK_MAX_BSB; the complete input is accepted by all three (n = 4, one gate)"""
+    import ctypes as C
+    from gnark_amd import _lib
+    c, n, lib, GA_ERR_INVALID, MAX_BSB = BN254, 4, emu_ctx.lib, -1, 16
+    d0, d1 = fft.Domain(emu_ctx, c.name, n), fft.Domain(emu_ctx, c.name, plonk.Rho(n) * n)
+    poly = np.zeros((n, 4), dtype=np.uint64)
+    arrays = (C.c_void_p * (MAX_BSB + 1))(*[poly.ctypes.data] * (MAX_BSB + 1))
+    holed = (C.c_void_p * 1)(None)
+    out = np.zeros((plonk.Rho(n) * n, 4), dtype=np.uint64)
+    fixed, proof = ("ql", "qr", "qm", "qo", "s1", "s2", "s3"), ("l", "r", "o", "z", "qk")
+    rest = ("bl", "br", "bo", "bz", "alpha", "beta", "gamma")
+
+    def make(**changes):
+        a = _lib.PlonkQuotientIn()
+        a.nb_bsb = 1
+        for k in fixed + proof + rest:
+            setattr(a, k, poly.ctypes.data)
+        a.qcp = a.pi2 = arrays
+        for k, v in changes.items():
+            setattr(a, k, v)
+        return C.byref(a)
+
+    nothing = C.POINTER(C.c_void_p)()
+    key, key2 = C.c_void_p(), C.c_void_p()   # the pinned calls' key; what the pk_create calls write (one of them succeeds)
+    try:
+        assert lib.ga_plonk_pk_create(d0.handle, d1.handle, make(), C.byref(key)) == 0
+        calls = {
+            "quotient": (lambda a, o=out.ctypes.data: lib.ga_plonk_quotient(d0.handle, d1.handle, a, o),
+                         [{k: None} for k in fixed + proof + rest] + [{"qcp": nothing}, {"pi2": nothing}, {"qcp": holed}, {"pi2": holed}]),
+            "pk_create": (lambda a, o=C.byref(key2): lib.ga_plonk_pk_create(d0.handle, d1.handle, a, o),
+                          [{k: None} for k in fixed] + [{"qcp": nothing}, {"qcp": holed}]),
+            "pinned": (lambda a, o=out.ctypes.data: lib.ga_plonk_quotient_pinned(key, a, o),
+                       [{k: None} for k in proof + rest] + [{"pi2": nothing}, {"pi2": holed}]),
+        }
+        for name, (call, holes) in calls.items():
+            assert call(make()) == 0, name
+            assert call(None) == GA_ERR_INVALID and call(make(), None) == GA_ERR_INVALID, name
+            for changes in holes + [{"nb_bsb": MAX_BSB + 1}]:
+                assert call(make(**changes)) == GA_ERR_INVALID, (name, changes)
+        assert lib.ga_plonk_quotient_pinned(None, make(), out.ctypes.data) == GA_ERR_INVALID
+    finally:
+        for k in (key, key2):
+            if k:
+                lib.ga_plonk_pk_destroy(k)
+        d0.close()
+        d1.close()
+
+
 @pytest.mark.parametrize("c", CURVES, ids=lambda c: c.name)
 @pytest.mark.parametrize("n", [2, 8, 512, 1000])
 def test_emu_plonk_build_z_and_batch_invert(emu_ctx, c, n):

@@ -436,6 +436,10 @@ def test_plonk_quotient_vs_oracle(gpu_ctx, c, n, nb_bsb):
     cases.test_emu_plonk_quotient(gpu_ctx, c, n, nb_bsb, seed=77 + n)
 
 
+def test_plonk_null_arguments(gpu_ctx):
+    cases.test_emu_plonk_null_arguments(gpu_ctx)
+
+
 @pytest.mark.parametrize("c", CURVES, ids=lambda c: c.name)
 @pytest.mark.parametrize("n", [2, 8, 512, 1000, 4096])
 def test_plonk_build_z_and_batch_invert(gpu_ctx, c, n):
