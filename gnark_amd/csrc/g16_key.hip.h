@@ -1,8 +1,10 @@
-// Groth16 proving key construction, part of the groth16.hip translation unit: the device-resident key (G16Pk) and the guard that
-// counts its users (PkUse), the staged builder (G16Stage -> stage_finish -> G16Pk, with the optional window tables), the one-shot key
-// of ga_g16_prove_oneshot (its uploader thread) and the key's lifetime.  Key files are read into the same builder by g16_io.hip.h;
-// the entry points (ga_g16_pk_create, ga_g16_builder_*, ...) are in groth16.hip with the rest of the Groth16 ABI.
+// Groth16 proving key construction, part of the groth16.hip translation unit: the device-resident key (G16Pk: one G16Vec record per base
+// vector, indexed by GA_KEY_*, whose `layout` names the path of its MSM) and the guard that counts its users (PkUse); the staged builder
+// (G16Stage -> stage_finish -> G16Pk: check, move, domain, gather lists, plan_layouts, build_tables, points); the one-shot key of
+// ga_g16_prove_oneshot (its uploader thread) and the key's lifetime.  Key files are read into the same builder by g16_io.hip.h; the
+// entry points (ga_g16_pk_create, ga_g16_builder_*, ...) are in groth16.hip with the rest of the Groth16 ABI.
 #pragma once
+#include <algorithm>
 #include <chrono>
 #include <condition_variable>
 #include <memory>
@@ -23,35 +25,46 @@ static __global__ void g16_scatter_points_kernel(u32x4* __restrict__ dst, const 
     dst[(uint64_t)idx[i] * chunks + k] = src[i * chunks + k];
 }
 
+// One base vector of a key (G1.A, G1.B, G1.Z, G1.K, G2.B: G16Pk::vec[GA_KEY_*]) and the path its MSM takes (vector_msm, groth16.hip).
+// Which vectors get a table is decided per vector: when the five tables do not fit the free HBM together (2^26 constraints: 288 GiB),
+// the ones that pay most per byte are built -- A, B (G1), K (they share one witness sort), then Z, then the twice as large G2.B -- and
+// the rest stay plain (plan_layouts).
+struct G16Vec {
+    enum Layout {
+        PLAIN,           // d = len affine points: an un-pinned MSM (one bucket set per window + Horner)
+        COMPACT_TABLE,   // d = windows x len precomputed window multiples (msm_bucket.hip.h): an MSM with its own digits + sort
+        // d = windows x nb_wires, laid out by WIRE id with (0,0) at the wires the vector lacks (infinity entries are skipped by the
+        // bucket kernel): for a vector that covers (almost) every wire, so that the digit extraction + radix sort of the whole
+        // witness is done ONCE and shared by the A, B (G1 and G2) and K MSMs instead of once per filtered copy of the witness
+        WIRE_TABLE
+    };
+    void* d = nullptr;
+    uint64_t len = 0, off = 0;       // this key holds points [off, off + len) of the full vector (everything unless sharded by base range)
+    // wire id of every point, on the device (the gather lists of prove.go:147-168 for A and B; G2.B refers to G1.B's); K has one only
+    // when committed wires are left out (prove.go:231-235; null = W[nbPublic:]), Z none.  The key owns the lists of A, B and K.
+    const uint32_t* idx = nullptr;
+    int c = 0;                       // window width of the table: the key's c_w when wire-indexed; G2.B's compact table has G1.B's
+    Layout layout = PLAIN;
+    bool has_table() const { return layout != PLAIN; }
+    bool wire_indexed() const { return layout == WIRE_TABLE; }
+};
+
 struct G16Pk {
     Ctx* ctx = nullptr;
     int curve = 0;
     uint64_t n = 0;            // domain cardinality
     uint64_t nb_wires = 0;
     Domain* dom = nullptr;
-    void *d_a = nullptr, *d_b = nullptr, *d_z = nullptr, *d_k = nullptr, *d_b2 = nullptr;
-    uint64_t len_a = 0, len_b = 0, len_z = 0, len_k = 0, len_b2 = 0;
-    uint32_t *d_idx_a = nullptr, *d_idx_b = nullptr;   // wire indices kept for the A / B MSMs (prove.go:147-168)
-    uint32_t* d_idx_k = nullptr;   // wire indices feeding the K MSM when committed wires are left out (prove.go:231-235); null = W[nbPublic:]
+    G16Vec vec[GA_KEY_NB_VECTORS];
+    bool any_table() const { return std::any_of(vec, vec + GA_KEY_NB_VECTORS, [](const G16Vec& v) { return v.has_table(); }); }
+    bool any_wire_indexed() const { return std::any_of(vec, vec + GA_KEY_NB_VECTORS, [](const G16Vec& v) { return v.wire_indexed(); }); }
     uint64_t len_k_remove = 0;
     std::vector<void*> d_ck_basis, d_ck_sigma;   // pinned pedersen keys (setup.go:260-287, icicle.go:231-261)
     std::vector<uint64_t> ck_len;
-    // precomputed window-multiple tables (msm_bucket.hip.h): a vector with its tab_* flag set points to windows x len points and c_* is the
-    // window width.  Per VECTOR since round 5: when the five tables do not fit the free HBM together (2^26 constraints: 288 GiB), the
-    // ones that pay most per byte are built -- A, B (G1), K (they share one witness sort), then Z, then the twice as large G2.B --
-    // and the rest stay plain affine arrays that run as un-pinned MSMs.
-    bool tables = false;   // any of the five
-    bool tab_a = false, tab_b = false, tab_z = false, tab_k = false, tab_b2 = false;
-    int c_a = 0, c_b = 0, c_z = 0, c_k = 0;
-    // Wire-indexed tables: when a base vector covers (almost) every wire, its table is laid out by WIRE id with (0,0) at the
-    // wires it lacks (infinity entries are skipped by the bucket kernel), so that the digit extraction + radix sort of the whole
-    // witness is done ONCE and shared by the A, B (G1 and G2) and K MSMs instead of once per filtered copy of the witness.
-    bool share_a = false, share_b = false, share_k = false;   // (each implies its tab_* flag)
-    bool share_b2 = false;                                    // G2.B wire-indexed too: it reuses the shared sort (share_b and tab_b2)
-    int c_w = 0;
+    int c_w = 0;   // window width of the wire-indexed tables (one sort of the whole witness serves them all)
     // multi-GPU partition B: this key holds slice [off, off+len) of every base vector (ga_g16_key.shard_index/count)
     uint32_t shard_index = 0, shard_count = 1;
-    uint64_t off_k = 0, off_z = 0, full_len_k = 0;
+    uint64_t full_len_k = 0;
     // multi-GPU partition A (scalar windows, BASELINE config 4's wording): the WHOLE key is pinned on every device and this one
     // accumulates only share win_index of win_count of the Pippenger windows of every MSM; partial results add up
     uint32_t win_index = 0, win_count = 1;
@@ -234,30 +247,23 @@ static int upload(Ctx* ctx, const void* src, size_t bytes, void** dst) {
 static void pk_free(G16Pk* pk) {
     if (!pk) return;
     if (pk->pending && pk->pending->uploader.joinable()) pk->pending->uploader.join();   // (it writes into the buffers freed below)
-    if (pk->pending && pk->ctx && !pk->tables) {   // a one-shot key: its plain vector buffers stay with the context for the next one
+    if (pk->pending && pk->ctx && !pk->any_table()) {   // a one-shot key: its plain vector buffers stay with the context for the next one
         const char* e = getenv("GA_DOMAIN_SPARE");
         Ctx* c = pk->ctx;
         std::lock_guard<std::mutex> g(c->spare_mu);
         if (!(e && atoi(e) == 0) && !c->spare_vectors.have) {
-            void** slot[GA_KEY_NB_VECTORS] = {&pk->d_a, &pk->d_b, &pk->d_z, &pk->d_k, &pk->d_b2};
             for (int w = 0; w < GA_KEY_NB_VECTORS; w++) {
-                c->spare_vectors.p[w] = *slot[w];
+                c->spare_vectors.p[w] = pk->vec[w].d;
                 c->spare_vectors.bytes[w] = pk->pending->bytes[w];
-                *slot[w] = nullptr;
+                pk->vec[w].d = nullptr;
             }
             c->spare_vectors.have = true;
         }
     }
     if (pk->ctx)
-        for (const void* t : {pk->d_a, pk->d_b, pk->d_z, pk->d_k, pk->d_b2}) pk->ctx->forget_table(t);
-    hipFree(pk->d_a);
-    hipFree(pk->d_b);
-    hipFree(pk->d_z);
-    hipFree(pk->d_k);
-    hipFree(pk->d_b2);
-    hipFree(pk->d_idx_a);
-    hipFree(pk->d_idx_b);
-    hipFree(pk->d_idx_k);
+        for (const G16Vec& v : pk->vec) pk->ctx->forget_table(v.d);
+    for (const G16Vec& v : pk->vec) hipFree(v.d);
+    for (int w : {GA_KEY_G1_A, GA_KEY_G1_B, GA_KEY_G1_K}) hipFree(const_cast<uint32_t*>(pk->vec[w].idx));   // (G2.B's is G1.B's)
     for (void* p : pk->d_ck_basis) hipFree(p);
     for (void* p : pk->d_ck_sigma) hipFree(p);
     if (pk->dom) ntt_domain_give_spare(pk->ctx, pk->dom);   // (kept for the next key of this size: common.hip.h)
@@ -336,12 +342,9 @@ static int stage_append(G16Stage* st, int which, const void* points, uint64_t co
     return GA_OK;
 }
 
-template <class C>
-static int stage_finish(G16Stage* st, int precompute, G16Pk** out) {
-    typedef Fe<typename C::FpP> F1;
-    typedef Fe2<typename C::FpP> F2;
-    Ctx* ctx = st->ctx;
-    const size_t s1 = sizeof(Affine<F1>), s2 = sizeof(Affine<F2>);
+// ---- stage_finish: G16Stage -> G16Pk in seven steps, each called once, top to bottom ------------------------------------------------
+// 1. what the caller staged is complete and consistent (joins the helper threads that build the gather lists)
+static int stage_check(G16Stage* st) {
     for (int w = 0; w < GA_KEY_NB_VECTORS; w++)
         if (!st->v[w].reserved || st->v[w].seen != st->v[w].total) {
             set_error("proving key: vector %d incomplete (%llu of %llu points)", w, (unsigned long long)st->v[w].seen,
@@ -383,251 +386,273 @@ static int stage_finish(G16Stage* st, int precompute, G16Pk** out) {
                   st->win_index, st->win_count);
         return GA_ERR_INVALID;
     }
-    PinTrace tr;
     for (int k = 0; k < 2; k++) {
         if (!st->lists[k].job.joinable()) st->start_list(k);   // (a caller that set the mask through a path without the early start)
         st->lists[k].job.join();
     }
-    const uint32_t *ia = st->lists[0].ids.get(), *ib = st->lists[1].ids.get();
     if (st->lists[0].size != len_a || st->lists[1].size != len_b || len_b2 != len_b) {
         set_error("proving key: InfinityA/B masks disagree with len(A)/len(B), or len(G2.B) != len(G1.B)");
         return GA_ERR_INVALID;
     }
+    return GA_OK;
+}
+
+// 2. a key that owns the device buffers of this shard's vectors and of the commitment keys
+static G16Pk* stage_move(G16Stage* st) {
     G16Pk* pk = new G16Pk();
-    pk->ctx = ctx;
-    pk->curve = C::ID;
+    pk->ctx = st->ctx;
+    pk->curve = st->curve;
     pk->n = st->n;
     pk->nb_wires = st->nb_wires;
     pk->shard_count = st->shard_count;
     pk->shard_index = st->shard_index;
     pk->win_count = st->win_count ? st->win_count : 1;
     pk->win_index = st->win_index;
-    auto take = [&](int which, void** slot, uint64_t* len) {   // the device buffer changes owner
-        *slot = st->v[which].d;
-        *len = st->v[which].cnt;
-        st->v[which].d = nullptr;
-    };
-    take(GA_KEY_G1_A, &pk->d_a, &pk->len_a);
-    take(GA_KEY_G1_B, &pk->d_b, &pk->len_b);
-    take(GA_KEY_G1_Z, &pk->d_z, &pk->len_z);
-    take(GA_KEY_G1_K, &pk->d_k, &pk->len_k);
-    take(GA_KEY_G2_B, &pk->d_b2, &pk->len_b2);
-    const uint64_t lo_a = st->v[GA_KEY_G1_A].lo, lo_b = st->v[GA_KEY_G1_B].lo, lo_k = st->v[GA_KEY_G1_K].lo;
-    pk->off_k = lo_k;
-    pk->off_z = st->v[GA_KEY_G1_Z].lo;
-    pk->full_len_k = len_k;
-    {   // wire range of this shard: the sorted gather lists are sliced contiguously, so min/max are the slice ends
-        uint64_t lo = st->nb_wires, hi = 0;
-        auto span = [&](const uint32_t* v, uint64_t off, uint64_t cnt) {
-            if (cnt == 0) return;
-            lo = lo < v[off] ? lo : v[off];
-            hi = hi > (uint64_t)v[off + cnt - 1] + 1 ? hi : (uint64_t)v[off + cnt - 1] + 1;
-        };
-        span(ia, lo_a, pk->len_a);
-        span(ib, lo_b, pk->len_b);
-        pk->w_lo = st->shard_count == 1 ? 0 : lo;
-        pk->w_hi = st->shard_count == 1 ? st->nb_wires : hi;
+    for (int w = 0; w < GA_KEY_NB_VECTORS; w++) {
+        pk->vec[w].d = st->v[w].d;
+        pk->vec[w].len = st->v[w].cnt;
+        pk->vec[w].off = st->v[w].lo;
+        st->v[w].d = nullptr;
     }
-    tr.mark("finish: gather lists built on the host");
-    int rc = GA_OK;
-    pk->dom = ntt_domain_take_spare(ctx, C::ID, pk->n);   // the domain of the key this context freed last, when it has this size
-    if (!pk->dom) rc = ntt_domain_new<C>(ctx, pk->n, &pk->dom);
-    tr.mark("finish: ntt_domain_new returned");
-    if (rc == GA_OK) rc = upload(ctx, ia + lo_a, pk->len_a * 4, (void**)&pk->d_idx_a);
-    if (rc == GA_OK) rc = upload(ctx, ib + lo_b, pk->len_b * 4, (void**)&pk->d_idx_b);
-    // K filter with commitments: wireValues[nbPublic:] minus the private committed and commitment wires (prove.go:231-235)
-    std::vector<uint32_t> ik;
+    pk->full_len_k = st->v[GA_KEY_G1_K].total;
     pk->len_k_remove = st->k_remove.size();
-    if (rc == GA_OK && pk->len_k_remove) {
-        const uint64_t nrem = st->k_remove.size();
-        if (len_k + nrem > st->nb_wires) {
-            set_error("proving key: len(K)+len(k_remove) > nbWires");
-            rc = GA_ERR_INVALID;
-        } else {
-            const uint64_t nb_public = st->nb_wires - len_k - nrem;
-            ik.reserve(len_k);
-            uint64_t j = 0;
-            bool ok = true;
-            for (uint64_t i = 0; i < nrem; i++)
-                ok = ok && st->k_remove[i] >= nb_public && st->k_remove[i] < st->nb_wires && (i == 0 || st->k_remove[i] > st->k_remove[i - 1]);
-            for (uint64_t i = nb_public; ok && i < st->nb_wires; i++) {
-                if (j < nrem && st->k_remove[j] == i) j++;
-                else ik.push_back((uint32_t)i);
-            }
-            if (!ok || ik.size() != len_k) {
-                set_error("proving key: k_remove must be strictly increasing wire ids in [nbPublic, nbWires)");
-                rc = GA_ERR_INVALID;
-            }
-        }
-        if (rc == GA_OK) rc = upload(ctx, ik.data() + lo_k, pk->len_k * 4, (void**)&pk->d_idx_k);
-        if (rc == GA_OK && pk->len_k && st->shard_count > 1) {
-            pk->w_lo = pk->w_lo < ik[lo_k] ? pk->w_lo : ik[lo_k];
-            pk->w_hi = pk->w_hi > (uint64_t)ik[lo_k + pk->len_k - 1] + 1 ? pk->w_hi : (uint64_t)ik[lo_k + pk->len_k - 1] + 1;
-        }
-    }
     pk->d_ck_basis.swap(st->d_ck_basis);
     pk->d_ck_sigma.swap(st->d_ck_sigma);
     pk->ck_len = st->ck_len;
-    if (rc == GA_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) {   // no host pointer survives this call
+    return pk;
+}
+
+// 4. this shard's slices of the gather lists on the device -- A's and B's from the masks, K's when commitments leave wires out:
+//    wireValues[nbPublic:] minus the private committed and commitment wires (prove.go:231-235) -- and the wire range they touch
+static int stage_gather_lists(G16Stage* st, G16Pk* pk) {
+    Ctx* ctx = st->ctx;
+    G16Vec &a = pk->vec[GA_KEY_G1_A], &b = pk->vec[GA_KEY_G1_B], &k = pk->vec[GA_KEY_G1_K];
+    uint64_t lo = st->nb_wires, hi = 0;   // the sorted lists are sliced contiguously, so min / max are the slice ends
+    auto put = [&](G16Vec& v, const uint32_t* ids) {
+        if (v.len) {
+            lo = std::min<uint64_t>(lo, ids[v.off]);
+            hi = std::max<uint64_t>(hi, (uint64_t)ids[v.off + v.len - 1] + 1);
+        }
+        void* d = nullptr;
+        const int rc = upload(ctx, ids + v.off, v.len * 4, &d);
+        v.idx = static_cast<const uint32_t*>(d);
+        return rc;
+    };
+    GA_CHECK(put(a, st->lists[0].ids.get()));
+    GA_CHECK(put(b, st->lists[1].ids.get()));
+    pk->vec[GA_KEY_G2_B].idx = b.idx;
+    std::vector<uint32_t> ik;
+    if (const uint64_t nrem = st->k_remove.size()) {
+        const uint64_t nb_public = st->nb_wires - pk->full_len_k - nrem;   // (>= 0: stage_check)
+        ik.reserve(pk->full_len_k);
+        uint64_t j = 0;
+        bool ok = true;
+        for (uint64_t i = 0; i < nrem; i++)
+            ok = ok && st->k_remove[i] >= nb_public && st->k_remove[i] < st->nb_wires && (i == 0 || st->k_remove[i] > st->k_remove[i - 1]);
+        for (uint64_t i = nb_public; ok && i < st->nb_wires; i++) {
+            if (j < nrem && st->k_remove[j] == i) j++;
+            else ik.push_back((uint32_t)i);
+        }
+        if (!ok || ik.size() != pk->full_len_k) {
+            set_error("proving key: k_remove must be strictly increasing wire ids in [nbPublic, nbWires)");
+            return GA_ERR_INVALID;
+        }
+        GA_CHECK(put(k, ik.data()));
+    }
+    pk->w_lo = st->shard_count == 1 ? 0 : lo;
+    pk->w_hi = st->shard_count == 1 ? st->nb_wires : hi;
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) {   // no host pointer survives this call
         set_error("proving key upload: stream synchronize failed");
-        rc = GA_ERR_HIP;
+        return GA_ERR_HIP;
     }
+    return GA_OK;
+}
+
+// Device bytes the tables may take when the caller leaves the choice to the library (precompute = 0) = free HBM - what a single
+// caller's proof will allocate on this context (measured: 1.15 KB per constraint at 2^26 with three tables -- sort pairs, task lists,
+// hat-domain copies of the plain vectors, input slots, NTT tables --, 1.25 KB allowed, + 10 %) - 4 GiB.  At 2^26 BN254 on an empty
+// device: 244 - 88 - 4 = 152 GiB -> A, B, K (144).  Scratch this context already holds (an earlier proof of this size) is credited
+// against the allowance: it is not free any more, but it is exactly what the allowance was for.
+static double free_table_bytes(Ctx* ctx, uint64_t n) {
+    {   // a key that is here to stay: the buffers kept for one-shot keys (6-9 GiB) go back to the device before the tables are sized
+        std::lock_guard<std::mutex> g(ctx->spare_mu);
+        for (void*& q : ctx->spare_vectors.p) {
+            hipFree(q);
+            q = nullptr;
+        }
+        ctx->spare_vectors.have = false;
+    }
+    size_t free_b = 0, total_b = 0;
+    hipMemGetInfo(&free_b, &total_b);
+    uint64_t held = 0;
+    {
+        std::lock_guard<std::mutex> g(ctx->scratch_mu);
+        for (const auto& kv : ctx->scratch) held += kv.second.second;
+    }
+    const double per_proof = (double)n * 1280.0;
+    const double allowance = per_proof > (double)held ? per_proof - (double)held : 0.0;
+    return (double)free_b - 1.1 * allowance - 4.0 * 1073741824.0;
+}
+
+// 5. layout and window width of every vector: arithmetic over the lengths, the table entry sizes, `precompute`, the free bytes and the
+//    two tunables.  precompute > 0: all five get a table (the caller insists; a table that does not fit fails the call).  precompute
+//    == 0: as many as fit the budget, in the order of what a table buys per byte.
+struct G16Plan {
+    G16Vec::Layout layout[GA_KEY_NB_VECTORS] = {};   // (PLAIN)
+    int c[GA_KEY_NB_VECTORS] = {};
+    int c_w = 0;
+};
+// A, B1, K (48 GiB each at 2^26 BN254; with all three the witness is sorted once instead of three times), Z, and last G2.B (twice the
+// bytes for the smallest relative gain; it follows G1.B's layout and never gets a table when G1.B, earlier and half as large, did not)
+static const int g16_table_preference[GA_KEY_NB_VECTORS] = {GA_KEY_G1_A, GA_KEY_G1_B, GA_KEY_G1_K, GA_KEY_G1_Z, GA_KEY_G2_B};
+
+template <class C>
+static int plan_layouts(const G16Pk* pk, int precompute, double free_bytes, int share_pct, uint64_t budget_pct, G16Plan* plan) {
+    int nw = 0, own_c[GA_KEY_NB_VECTORS] = {};
+    bool ok = msm_plan_table<C>(pk->nb_wires, &plan->c_w, &nw) == GA_OK;
+    const uint64_t wide = (uint64_t)nw * pk->nb_wires;   // entries of a wire-indexed table
+    for (int w : {GA_KEY_G1_A, GA_KEY_G1_B, GA_KEY_G1_Z, GA_KEY_G1_K}) ok = msm_plan_table<C>(pk->vec[w].len, &own_c[w], &nw) == GA_OK && ok;
+    own_c[GA_KEY_G2_B] = own_c[GA_KEY_G1_B];   // (G2.B's compact table is walked with the digits of G1.B's: witness_msms)
+    // vectors beyond the table index space (the 2^31 pair space, or a forced GA_TABLE_C too narrow): an error when the caller asked
+    // for tables explicitly, otherwise no tables
+    if (!ok) return precompute > 0 ? GA_ERR_INVALID : GA_OK;
+    // the witness sort is shared between the vectors that cover at least GA_G16_SHARE_MIN_PCT % of the wires (default 90: a sparse
+    // vector would make the lanes of the bucket kernel idle on its missing wires, and waste table memory)
+    auto dense = [&](uint64_t len) {
+        return pk->shard_count == 1 && pk->nb_wires < (1ull << 27) && len > 0 && (double)len * 100.0 >= (double)pk->nb_wires * share_pct;
+    };
+    const size_t t1 = msm_table_point_bytes<C, GA_G1>(), t2 = msm_table_point_bytes<C, GA_G2>();
+    G16Vec::Layout cand[GA_KEY_NB_VECTORS];
+    uint64_t bytes[GA_KEY_NB_VECTORS], all_bytes = 0;
+    for (int w = 0; w < GA_KEY_NB_VECTORS; w++) {
+        const uint64_t len = pk->vec[w].len;   // (len(G2.B) == len(G1.B): stage_check)
+        const bool wire = w != GA_KEY_G1_Z && dense(len);
+        cand[w] = wire ? G16Vec::WIRE_TABLE : G16Vec::COMPACT_TABLE;
+        plan->c[w] = wire ? plan->c_w : own_c[w];
+        bytes[w] = (wire ? wide : (own_c[w] > 0 ? (uint64_t)(C::FrP::BITS / own_c[w] + 1) : 0) * len) * (w == GA_KEY_G2_B ? t2 : t1);
+        all_bytes += bytes[w];
+    }
+    double budget = free_bytes;
+    if (budget_pct) budget = (double)budget_pct / 100.0 * (double)all_bytes;   // GA_G16_TABLE_BUDGET_PCT (tests: partial tables on small keys)
+    for (int w : g16_table_preference) {
+        // (the plain array a table replaces is freed once the table stands; while it is built both are resident)
+        if (precompute > 0 || (double)bytes[w] <= budget) {
+            plan->layout[w] = cand[w];
+            budget -= (double)bytes[w];
+        } else {
+            plan->c[w] = 0;
+        }
+    }
+    return GA_OK;
+}
+
+// compact base array -> wire-indexed array with (0,0) at the missing wires; d_idx = the wire id of every entry
+static int widen_vector(G16Pk* pk, int which, const uint32_t* d_idx) {
+    Ctx* ctx = pk->ctx;
+    G16Vec& v = pk->vec[which];
+    const size_t psz = stage_point_bytes(pk->curve, which);
+    void* wide_arr = nullptr;
+    if (device_malloc(&wide_arr, pk->nb_wires * psz) != hipSuccess) {
+        set_error("proving key: hipMalloc of a wire-indexed base array failed");
+        return GA_ERR_NOMEM;
+    }
+    hipError_t we = hipMemsetAsync(wide_arr, 0, pk->nb_wires * psz, ctx->stream);
+    const uint32_t chunks = (uint32_t)(psz / 16);
+    const uint64_t threads = v.len * chunks;
+    if (we == hipSuccess) {
+        hipLaunchKernelGGL(g16_scatter_points_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream,
+                           (u32x4*)wide_arr, (const u32x4*)v.d, d_idx, v.len, chunks);
+        we = hipGetLastError();
+    }
+    if (we == hipSuccess) we = hipStreamSynchronize(ctx->stream);
+    if (we != hipSuccess) {
+        set_error("proving key: building a wire-indexed base array failed: %s", hipGetErrorString(we));
+        hipFree(wide_arr);
+        return GA_ERR_HIP;
+    }
+    hipFree(v.d);
+    v.d = wide_arr;
+    return GA_OK;
+}
+
+// the (compact or widened) base array of a vector -> its table [2^(c*w)]P for every window w (one shared bucket set per MSM afterwards)
+template <class C, int G>
+static int table_from_vector(G16Pk* pk, int which) {
+    Ctx* ctx = pk->ctx;
+    G16Vec& v = pk->vec[which];
+    const uint64_t rows = v.wire_indexed() ? pk->nb_wires : v.len;
+    if (rows == 0) return GA_OK;
+    const uint64_t bytes = (uint64_t)(C::FrP::BITS / v.c + 1) * rows * msm_table_point_bytes<C, G>();
+    void* t = nullptr;
+    if (device_malloc(&t, bytes) != hipSuccess) {
+        set_error("proving key: hipMalloc of a %llu-byte window table failed", (unsigned long long)bytes);
+        return GA_ERR_NOMEM;
+    }
+    int r = msm_table_build<C, G>(ctx, v.d, rows, v.c, t);
+    if (r == GA_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) r = GA_ERR_HIP;
+    hipFree(v.d);
+    v.d = t;
+    return r;
+}
+
+// 6. the plan carried out: the wire-indexed vectors widened (A, B, G2.B, K), then the tables built (A, B, Z, K, G2.B).  A failure
+//    leaves a key without tables for pk_free.
+template <class C>
+static int build_tables(G16Pk* pk, const G16Plan& plan) {
+    Ctx* ctx = pk->ctx;
+    pk->c_w = plan.c_w;
+    for (int w = 0; w < GA_KEY_NB_VECTORS; w++) {
+        pk->vec[w].layout = plan.layout[w];
+        pk->vec[w].c = plan.c[w];
+    }
+    if (!pk->any_table()) return GA_OK;
+    int rc = GA_OK;
+    const G16Vec& k = pk->vec[GA_KEY_G1_K];
+    void* d_ik = nullptr;   // wire ids of K's entries when it has no remove-list gather: nbPublic + i
+    if (k.wire_indexed() && !k.idx) {
+        const uint64_t nbp = pk->nb_wires - k.len;
+        std::vector<uint32_t> ikk(k.len);
+        for (uint64_t i = 0; i < k.len; i++) ikk[i] = (uint32_t)(nbp + i);
+        rc = upload(ctx, ikk.data(), k.len * 4, &d_ik);
+        if (rc == GA_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = GA_ERR_HIP;
+    }
+    for (int w : {GA_KEY_G1_A, GA_KEY_G1_B, GA_KEY_G2_B, GA_KEY_G1_K})
+        if (rc == GA_OK && pk->vec[w].wire_indexed()) rc = widen_vector(pk, w, pk->vec[w].idx ? pk->vec[w].idx : static_cast<const uint32_t*>(d_ik));
+    hipFree(d_ik);
+    for (int w : {GA_KEY_G1_A, GA_KEY_G1_B, GA_KEY_G1_Z, GA_KEY_G1_K, GA_KEY_G2_B})
+        if (rc == GA_OK && pk->vec[w].has_table()) rc = w == GA_KEY_G2_B ? table_from_vector<C, GA_G2>(pk, w) : table_from_vector<C, GA_G1>(pk, w);
+    if (rc != GA_OK)
+        for (G16Vec& v : pk->vec) v.layout = G16Vec::PLAIN;
+    return rc;
+}
+
+template <class C>
+static int stage_finish(G16Stage* st, int precompute, G16Pk** out) {
+    Ctx* ctx = st->ctx;
+    PinTrace tr;
+    GA_CHECK(stage_check(st));                                                      // 1
+    tr.mark("finish: gather lists built on the host");
+    G16Pk* pk = stage_move(st);                                                     // 2
+    pk->dom = ntt_domain_take_spare(ctx, C::ID, pk->n);                             // 3: the domain of the key this context freed last, when it has this size
+    int rc = pk->dom ? GA_OK : ntt_domain_new<C>(ctx, pk->n, &pk->dom);
+    tr.mark("finish: ntt_domain_new returned");
+    if (rc == GA_OK) rc = stage_gather_lists(st, pk);                               // 4
     tr.mark("finish: gather lists uploaded, stream drained");
-    // ---- optional precomputation: [2^(c*w)]P for every window (one shared bucket set per MSM afterwards) ----------
     if (rc == GA_OK && precompute >= 0) {
-        {   // a key that is here to stay: the buffers kept for one-shot keys (6-9 GiB) go back to the device before the tables are sized
-            std::lock_guard<std::mutex> g(ctx->spare_mu);
-            for (void*& q : ctx->spare_vectors.p) {
-                hipFree(q);
-                q = nullptr;
-            }
-            ctx->spare_vectors.have = false;
-        }
-        int nw = 0;
-        const size_t t1 = msm_table_point_bytes<C, GA_G1>(), t2 = msm_table_point_bytes<C, GA_G2>();
-        // share the witness sort between the vectors that cover at least GA_G16_SHARE_MIN_PCT % of the wires (default 90: a
-        // sparse vector would make the lanes of the bucket kernel idle on its missing wires, and waste table memory)
-        const int share_pct = ctx->tun.g16_share_min_pct;
-        auto dense = [&](uint64_t len) {
-            return pk->shard_count == 1 && pk->nb_wires < (1ull << 27) && len > 0 && (double)len * 100.0 >= (double)pk->nb_wires * share_pct;
-        };
-        pk->share_a = dense(pk->len_a);
-        pk->share_b = dense(pk->len_b);
-        pk->share_k = dense(pk->len_k);
-        bool plan_ok = msm_plan_table<C>(pk->nb_wires, &pk->c_w, &nw) == GA_OK;
-        const uint64_t wide = (uint64_t)nw * pk->nb_wires;
-        plan_ok = msm_plan_table<C>(pk->len_a, &pk->c_a, &nw) == GA_OK && plan_ok;
-        plan_ok = msm_plan_table<C>(pk->len_b, &pk->c_b, &nw) == GA_OK && plan_ok;
-        plan_ok = msm_plan_table<C>(pk->len_z, &pk->c_z, &nw) == GA_OK && plan_ok;
-        plan_ok = msm_plan_table<C>(pk->len_k, &pk->c_k, &nw) == GA_OK && plan_ok;
-        if (!plan_ok && precompute > 0) rc = GA_ERR_INVALID;   // vectors beyond the table index space: the caller asked for tables explicitly
-        size_t free_b = 0, total_b = 0;
-        hipMemGetInfo(&free_b, &total_b);
-        // Which vectors get a table.  precompute > 0: all five (the caller insists; a table that does not fit fails the call).
-        // precompute == 0: as many as fit the free HBM next to the per-proof scratch, in the order of what a table buys per byte:
-        // A, B1, K (48 GiB each at 2^26 BN254; with all three the witness is sorted once instead of three times), Z, and last G2.B
-        // (twice the bytes for the smallest relative gain).
-        // (a vector the planner refused -- beyond the 2^31 pair space, or a forced GA_TABLE_C too narrow -- has c_* = 0: no table, no size)
-        auto nwin_of = [](int cbits) -> uint64_t { return cbits > 0 ? (uint64_t)(C::FrP::BITS / cbits + 1) : 0; };
-        const uint64_t bytes_a = !plan_ok ? 0 : pk->share_a ? wide * t1 : nwin_of(pk->c_a) * pk->len_a * t1;
-        const uint64_t bytes_b = !plan_ok ? 0 : pk->share_b ? wide * t1 : nwin_of(pk->c_b) * pk->len_b * t1;
-        const uint64_t bytes_b2 = !plan_ok ? 0 : pk->share_b ? wide * t2 : nwin_of(pk->c_b) * pk->len_b * t2;
-        const uint64_t bytes_z = !plan_ok ? 0 : nwin_of(pk->c_z) * pk->len_z * t1;
-        const uint64_t bytes_k = !plan_ok ? 0 : pk->share_k ? wide * t1 : nwin_of(pk->c_k) * pk->len_k * t1;
-        if (rc == GA_OK && plan_ok) {
-            if (precompute > 0) {
-                pk->tab_a = pk->tab_b = pk->tab_k = pk->tab_z = pk->tab_b2 = true;
-            } else {
-                // What the tables may take = free HBM - what a single caller's proof will allocate on this context (measured: 1.15 KB per
-                // constraint at 2^26 with three tables -- sort pairs, task lists, hat-domain copies of the plain vectors, input slots, NTT
-                // tables --, 1.25 KB allowed, + 10 %) - 4 GiB.  At 2^26 BN254 on an empty device: 244 - 88 - 4 = 152 GiB -> A, B, K (144).
-                // Scratch this context already holds (an earlier proof of this size) is credited against the allowance: it is not free
-                // any more, but it is exactly what the allowance was for.
-                uint64_t held = 0;
-                {
-                    std::lock_guard<std::mutex> g(ctx->scratch_mu);
-                    for (const auto& kv : ctx->scratch) held += kv.second.second;
-                }
-                const double per_proof = (double)pk->n * 1280.0;
-                const double allowance = per_proof > (double)held ? per_proof - (double)held : 0.0;
-                double budget = (double)free_b - 1.1 * allowance - 4.0 * 1073741824.0;
-                if (const uint64_t pct = ctx->tun.g16_table_budget_pct)   // GA_G16_TABLE_BUDGET_PCT (tests: partial tables on small keys)
-                    budget = (double)pct / 100.0 * (double)(bytes_a + bytes_b + bytes_k + bytes_z + bytes_b2);
-                struct Cand { bool* flag; uint64_t bytes; } order[5] = {{&pk->tab_a, bytes_a}, {&pk->tab_b, bytes_b}, {&pk->tab_k, bytes_k},
-                                                                       {&pk->tab_z, bytes_z}, {&pk->tab_b2, bytes_b2}};
-                for (auto& cnd : order) {
-                    // (the plain array it replaces is freed once the table stands; while it is built both are resident)
-                    if ((double)cnd.bytes <= budget) {
-                        *cnd.flag = true;
-                        budget -= (double)cnd.bytes;
-                    }
-                }
-            }
-        }
-        pk->share_a = pk->share_a && pk->tab_a;
-        pk->share_b = pk->share_b && pk->tab_b;
-        pk->share_k = pk->share_k && pk->tab_k;
-        pk->share_b2 = pk->share_b && pk->tab_b2;
-        pk->tables = pk->tab_a || pk->tab_b || pk->tab_k || pk->tab_z || pk->tab_b2;
-        if (rc == GA_OK && pk->tables) {
-            auto make = [&](void** slot, uint64_t len, int c, size_t psz, auto build) -> int {
-                if (len == 0) return GA_OK;
-                const int nwin = C::FrP::BITS / c + 1;
-                void* t = nullptr;
-                if (device_malloc(&t, (uint64_t)nwin * len * psz) != hipSuccess) {
-                    set_error("proving key: hipMalloc of a %llu-byte window table failed", (unsigned long long)((uint64_t)nwin * len * psz));
-                    return GA_ERR_NOMEM;
-                }
-                int r = build(*slot, len, c, t);
-                if (r == GA_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) r = GA_ERR_HIP;
-                hipFree(*slot);
-                *slot = t;
-                return r;
-            };
-            auto b1 = [&](const void* src, uint64_t len, int c, void* t) { return msm_table_build<C, GA_G1>(ctx, src, len, c, t); };
-            auto b2 = [&](const void* src, uint64_t len, int c, void* t) { return msm_table_build<C, GA_G2>(ctx, src, len, c, t); };
-            // compact base array -> wire-indexed array with (0,0) at the missing wires
-            auto widen = [&](void** slot, uint64_t len, const uint32_t* d_idx, size_t psz) -> int {
-                void* wide_arr = nullptr;
-                if (device_malloc(&wide_arr, pk->nb_wires * psz) != hipSuccess) {
-                    set_error("proving key: hipMalloc of a wire-indexed base array failed");
-                    return GA_ERR_NOMEM;
-                }
-                hipError_t we = hipMemsetAsync(wide_arr, 0, pk->nb_wires * psz, ctx->stream);
-                const uint32_t chunks = (uint32_t)(psz / 16);
-                const uint64_t threads = len * chunks;
-                if (we == hipSuccess) {
-                    hipLaunchKernelGGL(g16_scatter_points_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream,
-                                       (u32x4*)wide_arr, (const u32x4*)*slot, d_idx, len, chunks);
-                    we = hipGetLastError();
-                }
-                if (we == hipSuccess) we = hipStreamSynchronize(ctx->stream);
-                if (we != hipSuccess) {
-                    set_error("proving key: building a wire-indexed base array failed: %s", hipGetErrorString(we));
-                    hipFree(wide_arr);
-                    return GA_ERR_HIP;
-                }
-                hipFree(*slot);
-                *slot = wide_arr;
-                return GA_OK;
-            };
-            uint32_t* d_ik = pk->d_idx_k;   // wire ids of K's entries: the remove-list gather, or nbPublic + i
-            if (pk->share_k && !d_ik) {
-                const uint64_t nbp = pk->nb_wires - pk->len_k;
-                std::vector<uint32_t> ikk(pk->len_k);
-                for (uint64_t i = 0; i < pk->len_k; i++) ikk[i] = (uint32_t)(nbp + i);
-                rc = upload(ctx, ikk.data(), pk->len_k * 4, (void**)&d_ik);
-                if (rc == GA_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = GA_ERR_HIP;
-            }
-            if (rc == GA_OK && pk->share_a) rc = widen(&pk->d_a, pk->len_a, pk->d_idx_a, s1);
-            if (rc == GA_OK && pk->share_b) rc = widen(&pk->d_b, pk->len_b, pk->d_idx_b, s1);
-            if (rc == GA_OK && pk->share_b2) rc = widen(&pk->d_b2, pk->len_b2, pk->d_idx_b, s2);
-            if (rc == GA_OK && pk->share_k) rc = widen(&pk->d_k, pk->len_k, d_ik, s1);
-            if (d_ik && d_ik != pk->d_idx_k) hipFree(d_ik);
-            const uint64_t nwr = pk->nb_wires;
-            if (rc == GA_OK && pk->tab_a) rc = pk->share_a ? make(&pk->d_a, nwr, pk->c_w, t1, b1) : make(&pk->d_a, pk->len_a, pk->c_a, t1, b1);
-            if (rc == GA_OK && pk->tab_b) rc = pk->share_b ? make(&pk->d_b, nwr, pk->c_w, t1, b1) : make(&pk->d_b, pk->len_b, pk->c_b, t1, b1);
-            if (rc == GA_OK && pk->tab_z) rc = make(&pk->d_z, pk->len_z, pk->c_z, t1, b1);
-            if (rc == GA_OK && pk->tab_k) rc = pk->share_k ? make(&pk->d_k, nwr, pk->c_w, t1, b1) : make(&pk->d_k, pk->len_k, pk->c_k, t1, b1);
-            if (rc == GA_OK && pk->tab_b2) rc = pk->share_b2 ? make(&pk->d_b2, nwr, pk->c_w, t2, b2) : make(&pk->d_b2, pk->len_b2, pk->c_b, t2, b2);
-            if (rc != GA_OK) pk->tables = false;
-        }
-    }
-    if (!pk->tables) {
-        pk->share_a = pk->share_b = pk->share_k = pk->share_b2 = false;
-        pk->tab_a = pk->tab_b = pk->tab_k = pk->tab_z = pk->tab_b2 = false;
+        G16Plan plan;
+        rc = plan_layouts<C>(pk, precompute, free_table_bytes(ctx, pk->n), ctx->tun.g16_share_min_pct, ctx->tun.g16_table_budget_pct, &plan);   // 5
+        if (rc == GA_OK) rc = build_tables<C>(pk, plan);                            // 6
     }
     if (rc != GA_OK) {
         if (st->early_uploader && st->early_uploader->joinable()) st->early_uploader->join();   // (it writes into the buffers pk_free frees)
         pk_free(pk);
         return rc;
     }
-    pk->alpha1 = st->pts[GA_KEY_G1_ALPHA];
+    pk->alpha1 = st->pts[GA_KEY_G1_ALPHA];                                          // 7
     pk->beta1 = st->pts[GA_KEY_G1_BETA];
     pk->delta1 = st->pts[GA_KEY_G1_DELTA];
     pk->beta2 = st->pts[GA_KEY_G2_BETA];
     pk->delta2 = st->pts[GA_KEY_G2_DELTA];
-    (void)s2;
     *out = pk;
     return GA_OK;
 }
@@ -758,14 +783,19 @@ static int start_uploader(Ctx* ctx, G16Stage* st, const ga_g16_key* key, G16Pk::
     return GA_OK;
 }
 
+// the five points, the two masks and every non-empty base vector of a host key description are there
+static bool key_points_present(const ga_g16_key* key) {
+    return key->g1_alpha && key->g1_beta && key->g1_delta && key->g2_beta && key->g2_delta && key->infinity_a && key->infinity_b &&
+           (!key->len_a || key->g1_a) && (!key->len_b || key->g1_b) && (!key->len_z || key->g1_z) && (!key->len_k || key->g1_k) &&
+           (!key->len_b2 || key->g2_b);
+}
+
 // ga_g16_pk_create: the struct-of-pointers form of the staged builder (C and ctypes callers; from Go only with runtime.Pinner)
 // defer_uploads (ga_g16_prove_oneshot): the five base vectors get their device buffers here but are copied by an uploader thread
 // that this function starts before it returns -- plain vectors only (no tables), the whole key on one device; the caller must keep
 // the host vectors alive until the thread has been joined (pk_free does).
 static int pk_create_from_struct(Ctx* ctx, const ga_g16_key* key, G16Pk** out, bool defer_uploads = false) {
-    if (!key->g1_alpha || !key->g1_beta || !key->g1_delta || !key->g2_beta || !key->g2_delta || !key->infinity_a || !key->infinity_b ||
-        (key->len_a && !key->g1_a) || (key->len_b && !key->g1_b) || (key->len_z && !key->g1_z) || (key->len_k && !key->g1_k) ||
-        (key->len_b2 && !key->g2_b)) {
+    if (!key_points_present(key)) {
         set_error("ga_g16_pk_create: null pointer inside ga_g16_key");
         return GA_ERR_INVALID;
     }

@@ -1,5 +1,6 @@
 // Groth16 prover: one-call proof from the solver's output on a device-resident proving key, and the Groth16 entry points of the C
-// ABI.  The key builder is g16_key.hip.h, key files and proof bytes are g16_io.hip.h: one translation unit.
+// ABI.  The key (one record per base vector) and its builder are g16_key.hip.h, key files and proof bytes are g16_io.hip.h: one
+// translation unit.
 //
 // Mirrors backend/groth16/bn254/prove.go:130-315 (CPU) and backend/accelerated/icicle/groth16/bn254/icicle.go:784-1360
 // (GPU):  computeH -> filter wire values -> 4 G1 MSMs + 1 G2 MSM -> host epilogue with the caller-supplied randomness
@@ -21,27 +22,46 @@
 namespace ga {
 
 // ---- the device part of a proof, in pieces (a multi-GPU proof runs them on different devices) ----------------------------------
-// witness_msms : upload W (only the wire range this shard's bases cover), filter, MSM A, B (G1 + G2), K      prove.go:147-237,283
-// h_chain      : v <- FFT_coset(iFFT(v)) for one of the solver's A, B, C                                       prove.go:362-368
-// h_combine    : h <- iFFT_coset((a*b - c) * den), bit-reversed like pk.G1.Z                                  prove.go:377-386
-// z_msm        : MSM over this shard's slice of pk.G1.Z and h                                                  prove.go:225-227
-// W -> device, only the wire range this shard reads.  Returns when the copy has been handed to the DMA engine from pageable
-// memory, i.e. when the host buffer has been consumed -- callers start the (PCIe-competing) upload of A, B, C only after it.
-static int witness_upload(G16Pk* pk, const SlotLease& slot, const void* w, uint64_t nb_public, hipStream_t up_stream = nullptr) {
-    Ctx* ctx = pk->ctx;
+// witness_upload : W -> device, only the wire range this shard's bases cover
+// witness_msms   : the schedule of the MSMs over W -- filter, A, B (G1 + G2), K                               prove.go:147-237,283
+// vector_msm     : ONE MSM over a base vector of the key, on the path its layout names (wire-indexed table over the shared witness
+//                  sort, compact table with its own digits + sort, plain array); k_msm and z_msm feed it K's and Z's scalars
+// h_chain        : v <- FFT_coset(iFFT(v)) for one of the solver's A, B, C                                     prove.go:362-368
+// h_combine      : h <- iFFT_coset((a*b - c) * den), bit-reversed like pk.G1.Z                                prove.go:377-386
+// z_msm          : MSM over this shard's slice of pk.G1.Z and h                                                prove.go:225-227
+// prove_partial runs them on one device (two lanes), prove_multi on several; finish is the host epilogue.
+
+// nbPublic of a proof agrees with the key: nbWires - nbPublic wires feed K, some of them through the commitments' remove list
+static int check_nb_public(const G16Pk* pk, uint64_t nb_public) {
     if (nb_public > pk->nb_wires || pk->nb_wires - nb_public != pk->full_len_k + pk->len_k_remove) {
         set_error("prove: inconsistent sizes (nbWires %llu - nbPublic %llu != len(K) %llu + len(k_remove) %llu)", (unsigned long long)pk->nb_wires,
                   (unsigned long long)nb_public, (unsigned long long)pk->full_len_k, (unsigned long long)pk->len_k_remove);
         return GA_ERR_INVALID;
     }
+    return GA_OK;
+}
+static int check_nb_constraints(const G16Pk* pk, uint64_t n_constraints) {
+    if (n_constraints > pk->n) {
+        set_error("prove: %llu constraints exceed the domain cardinality %llu", (unsigned long long)n_constraints, (unsigned long long)pk->n);
+        return GA_ERR_INVALID;
+    }
+    return GA_OK;
+}
+
+// W -> device, only the wire range this shard reads.  Returns when the copy has been handed to the DMA engine from pageable
+// memory, i.e. when the host buffer has been consumed -- callers start the (PCIe-competing) upload of A, B, C only after it.
+static int witness_upload(G16Pk* pk, const SlotLease& slot, const void* w, uint64_t nb_public, hipStream_t up_stream = nullptr) {
+    Ctx* ctx = pk->ctx;
+    GA_CHECK(check_nb_public(pk, nb_public));
     void* d_w;
     GA_CHECK(ctx->scratch_get(slot.name("g16_w").c_str(), pk->nb_wires * 32, &d_w));
     if (!up_stream) up_stream = ctx->work_stream();
     // the wire range this shard reads: everything for an unsharded key, ~1/N of W for shard k of N (the gather lists of a
     // shard are contiguous pieces of the sorted wire lists); K's range depends on nbPublic
     uint64_t lo = pk->w_lo, hi = pk->w_hi;
-    if (pk->len_k && !pk->d_idx_k) {
-        const uint64_t klo = nb_public + pk->off_k, khi = klo + pk->len_k;
+    const G16Vec& k = pk->vec[GA_KEY_G1_K];
+    if (k.len && !k.idx) {
+        const uint64_t klo = nb_public + k.off, khi = klo + k.len;
         lo = lo < klo ? lo : klo;
         hi = hi > khi ? hi : khi;
     }
@@ -110,67 +130,71 @@ struct WitnessShared {
     }
 };
 
-// this device's share of the windows of a table with window width c (everything unless the key is window-sharded)
-template <class C>
-static void g16_window_share(const G16Pk* pk, int c, int* lo, int* hi) {
-    window_share(C::FrP::BITS / c + 1, pk->win_index, pk->win_count, lo, hi);
-}
+// digits + sort a compact-table MSM has left in scratch slot 0: the next MSM over the SAME scalars, window width and window share
+// (G2.B after G1.B) walks its table with them instead of preparing its own
+struct PrepSlot {
+    MsmPrepared prep;
+    bool live = false;
+};
 
-// one G1 MSM over a compact (not wire-indexed) table with its own digits + sort; `prep` is left holding them
-template <class C>
-static int g16_table_msm_g1(G16Pk* pk, const void* table, const void* scal, uint64_t len, int c, MsmPrepared* prep, bool* prep_live,
-                            XYZZ<Fe<typename C::FpP>>* out) {
-    typedef Fe<typename C::FpP> F1;
-    int lo, hi;
-    g16_window_share<C>(pk, c, &lo, &hi);
-    *prep_live = false;
-    if (len == 0 || hi <= lo) {
-        *out = xyzz_inf<F1>();
-        return GA_OK;
+// One MSM over base vector `which` of the key on the calling thread's lane, on the path the vector's layout names:
+//   WIRE_TABLE    over `shared_sort`, the digits + sort of the whole witness (null: this device's window share is empty -> infinity)
+//   COMPACT_TABLE over the vector's own digits + sort of `scalars` (one per point), made here unless `reuse` holds live ones; they are
+//                 left in `reuse`.  An empty vector or an empty window share gives infinity.
+//   PLAIN         an un-pinned MSM over `scalars` with the key's window share, once the vector is on the device (await_vector)
+template <class C, int G>
+static int vector_msm(G16Pk* pk, int which, const void* scalars, const MsmPrepared* shared_sort, PrepSlot* reuse,
+                      XYZZ<typename GroupField<C, G>::F>* out) {
+    Ctx* ctx = pk->ctx;
+    const G16Vec& v = pk->vec[which];
+    *out = xyzz_inf<typename GroupField<C, G>::F>();
+    switch (v.layout) {
+    case G16Vec::WIRE_TABLE:
+        return shared_sort ? msm_table_device_reuse<C, G>(ctx, v.d, *shared_sort, out) : GA_OK;
+    case G16Vec::COMPACT_TABLE: {
+        int lo, hi;
+        window_share(C::FrP::BITS / v.c + 1, pk->win_index, pk->win_count, &lo, &hi);
+        if (v.len == 0 || hi <= lo) return GA_OK;
+        PrepSlot own;
+        PrepSlot& p = reuse ? *reuse : own;
+        if (!p.live) GA_CHECK(msm_prepare_table_scalars<C>(ctx, scalars, v.len, true, v.c, &p.prep, 0, lo, hi));
+        p.live = true;
+        return msm_table_device_reuse<C, G>(ctx, v.d, p.prep, out);
     }
-    GA_CHECK(msm_prepare_table_scalars<C>(pk->ctx, scal, len, true, c, prep, 0, lo, hi));
-    *prep_live = true;
-    return msm_table_device_reuse<C, GA_G1>(pk->ctx, table, *prep, out);
+    default:
+        GA_CHECK(await_vector(pk, which));
+        return host_msm<C, G>(ctx, v.d, scalars, v.len, true, out, pk->win_index, pk->win_count);
+    }
 }
 
-// the K MSM (prove.go:231-237) on the CALLING thread's lane: over the shared witness sort when K's table is wire-indexed,
-// otherwise over its own gather + sort (scratch of the calling lane).  `sh` must have been posted.
+// the K MSM (prove.go:231-237) on the CALLING thread's lane: its scalars are W[nbPublic:], gathered through the remove list when
+// commitments leave wires out (scratch of the calling lane); a wire-indexed K needs neither.  `sh` must have been posted.
 template <class C>
 static int k_msm(G16Pk* pk, uint64_t nb_public, WitnessShared& sh, XYZZ<Fe<typename C::FpP>>* out) {
-    typedef Fe<typename C::FpP> F1;
     Ctx* ctx = pk->ctx;
-    if (pk->share_k) {
-        if (!sh.w_live) {
-            *out = xyzz_inf<F1>();
-            return GA_OK;
+    const G16Vec& k = pk->vec[GA_KEY_G1_K];
+    const void* d_wk = nullptr;
+    if (!k.wire_indexed()) {
+        void* const d_w = sh.d_w;   // (not scratch_get: the calling thread may be on the partner lane, whose namespace differs)
+        d_wk = (const char*)d_w + (nb_public + k.off) * 32;
+        if (k.idx) {
+            void* g;
+            GA_CHECK(ctx->scratch_get("g16_wk", k.len * 32 + 32, &g));
+            GA_CHECK(util_gather_fr<C>(ctx, g, d_w, k.idx, k.len));
+            d_wk = g;
         }
-        return msm_table_device_reuse<C, GA_G1>(ctx, pk->d_k, sh.prep_w, out);
     }
-    void* const d_w = sh.d_w;   // (not scratch_get: the calling thread may be on the partner lane, whose namespace differs)
-    const void* d_wk = (const char*)d_w + (nb_public + pk->off_k) * 32;
-    if (pk->d_idx_k) {
-        void* g;
-        GA_CHECK(ctx->scratch_get("g16_wk", pk->len_k * 32 + 32, &g));
-        GA_CHECK(util_gather_fr<C>(ctx, g, d_w, pk->d_idx_k, pk->len_k));
-        d_wk = g;
-    }
-    if (pk->tab_k) {
-        MsmPrepared prep;
-        bool live;
-        return g16_table_msm_g1<C>(pk, pk->d_k, d_wk, pk->len_k, pk->c_k, &prep, &live, out);
-    }
-    GA_CHECK(await_vector(pk, GA_KEY_G1_K));
-    return host_msm<C, GA_G1>(ctx, pk->d_k, d_wk, pk->len_k, true, out, pk->win_index, pk->win_count);
+    return vector_msm<C, GA_G1>(pk, GA_KEY_G1_K, d_wk, sh.w_live ? &sh.prep_w : nullptr, nullptr, out);
 }
 
 // The witness MSMs A, B (G1 and G2) and -- unless the partner lane claims it first -- K, on the calling thread's lane, into
 // out->ar, bs1, bs2 and (the K sum alone) krs.  `sh` is posted as soon as the shared witness sort has been launched; out->krs is
-// written only when *did_k comes back true.
+// written only when *did_k comes back true.  This function is the SCHEDULE; every MSM is a vector_msm.
 template <class C>
 static int witness_msms(G16Pk* pk, const SlotLease& slot, uint64_t nb_public, WitnessShared& sh, G16Partials<C>* out, bool* did_k) {
     typedef Fe<typename C::FpP> F1;
-    typedef Fe2<typename C::FpP> F2;
     Ctx* ctx = pk->ctx;
+    const G16Vec &a = pk->vec[GA_KEY_G1_A], &b = pk->vec[GA_KEY_G1_B], &k = pk->vec[GA_KEY_G1_K], &b2 = pk->vec[GA_KEY_G2_B];
     struct PostGuard {   // a failure before the post must still release the partner lane
         WitnessShared& sh;
         bool done = false;
@@ -179,117 +203,76 @@ static int witness_msms(G16Pk* pk, const SlotLease& slot, uint64_t nb_public, Wi
         }
     } pg{sh};
     *did_k = false;
-    if (nb_public > pk->nb_wires || pk->nb_wires - nb_public != pk->full_len_k + pk->len_k_remove) {
-        set_error("prove: inconsistent sizes (nbWires %llu - nbPublic %llu != len(K) %llu + len(k_remove) %llu)", (unsigned long long)pk->nb_wires,
-                  (unsigned long long)nb_public, (unsigned long long)pk->full_len_k, (unsigned long long)pk->len_k_remove);
-        return GA_ERR_INVALID;
-    }
+    GA_CHECK(check_nb_public(pk, nb_public));
+    // 1. scratch
     hipStream_t st = ctx->work_stream();
     void *d_w, *d_wa, *d_wb;
     GA_CHECK(ctx->scratch_get(slot.name("g16_w").c_str(), pk->nb_wires * 32, &d_w));
-    GA_CHECK(ctx->scratch_get("g16_wa", pk->len_a * 32 + 32, &d_wa));
-    GA_CHECK(ctx->scratch_get("g16_wb", pk->len_b * 32 + 32, &d_wb));
-    // digits + sort of the WHOLE witness once (scratch slot 1), reused by every wire-indexed table
-    if (pk->share_a || pk->share_b || pk->share_k) {
+    GA_CHECK(ctx->scratch_get("g16_wa", a.len * 32 + 32, &d_wa));
+    GA_CHECK(ctx->scratch_get("g16_wb", b.len * 32 + 32, &d_wb));
+    // 2. digits + sort of the WHOLE witness once (scratch slot 1), reused by every wire-indexed table
+    if (pk->any_wire_indexed()) {
         int lo, hi;
-        g16_window_share<C>(pk, pk->c_w, &lo, &hi);
+        window_share(C::FrP::BITS / pk->c_w + 1, pk->win_index, pk->win_count, &lo, &hi);
         if (hi > lo) {
             GA_CHECK(msm_prepare_table_scalars<C>(ctx, d_w, pk->nb_wires, true, pk->c_w, &sh.prep_w, 1, lo, hi));
             sh.w_live = true;
         }
     }
+    const MsmPrepared* const shared = sh.w_live ? &sh.prep_w : nullptr;
+    // 3. the partner lane may go ahead
     sh.d_w = d_w;
     GA_HIP_CHECK(hipEventRecord(sh.w_ev, st));
     pg.done = true;
     sh.post(true);
-    // ---- wire filtering (prove.go:147-168) ------------------------------------------------------------
-    if (!pk->share_a) GA_CHECK(util_gather_fr<C>(ctx, d_wa, d_w, pk->d_idx_a, pk->len_a));
-    if (!pk->share_b || !pk->share_b2) GA_CHECK(util_gather_fr<C>(ctx, d_wb, d_w, pk->d_idx_b, pk->len_b));   // (G2.B may be plain beside a wire-indexed G1.B)
-    // ---- the witness MSMs (prove.go:194,207,237,283) ---------------------------------------------------
-    XYZZ<F1>& ar = out->ar;
-    XYZZ<F1>& bs1 = out->bs1;
-    XYZZ<F2>& bs2 = out->bs2;
-    {   // every vector on its own kind of path: wire-indexed table over the shared sort, compact table with its own digits + sort, or
-        // plain bases (no table: un-pinned MSM, one bucket set per window + Horner)
-        MsmPrepared prep;
-        bool prep_live = false;   // `prep` holds the digits of wB for G2.B
-        auto shared_g1 = [&](const void* table, XYZZ<F1>* out) -> int {
-            if (!sh.w_live) {
-                *out = xyzz_inf<F1>();
-                return GA_OK;
-            }
-            return msm_table_device_reuse<C, GA_G1>(ctx, table, sh.prep_w, out);
+    // 4. wire filtering (prove.go:147-168) for the vectors that are not walked by wire id
+    if (!a.wire_indexed()) GA_CHECK(util_gather_fr<C>(ctx, d_wa, d_w, a.idx, a.len));
+    if (!b.wire_indexed() || !b2.wire_indexed()) GA_CHECK(util_gather_fr<C>(ctx, d_wb, d_w, b.idx, b.len));   // (G2.B may be plain beside a wire-indexed G1.B)
+    // 5. The wire-indexed G1 tables (A, B1 and -- when this lane gets it -- K) in ONE pass of the bucket kernel, the merge and the window
+    // reduction over the shared witness sort (msm_table_device_reuse_multi): one kernel tail, one reduction with k x the waves and
+    // one host synchronisation instead of k of each (prove.go:194,207,237: three MultiExp over the same wireValues).  A table the
+    // bucket kernel has found degenerate (a DummySetup key) keeps its own pass with the complete loop; GA_G16_BATCH_TABLES=0: round 5.
+    bool in_pass[GA_KEY_NB_VECTORS] = {};
+    if (shared && ctx->tun.g16_batch_tables.load(std::memory_order_relaxed)) {
+        int who[3], nt = 0;
+        const void* tabs[3];
+        XYZZ<F1>* dst[3];
+        auto fits = [&](const G16Vec& v) { return v.wire_indexed() && !ctx->is_degenerate(v.d); };
+        auto join = [&](int which, XYZZ<F1>* sum) {
+            who[nt] = which;
+            tabs[nt] = pk->vec[which].d;
+            dst[nt++] = sum;
         };
-        // The wire-indexed G1 tables (A, B1 and -- when this lane gets it -- K) in ONE pass of the bucket kernel, the merge and the window
-        // reduction over the shared witness sort (msm_table_device_reuse_multi): one kernel tail, one reduction with k x the waves and
-        // one host synchronisation instead of k of each (prove.go:194,207,237: three MultiExp over the same wireValues).  A table the
-        // bucket kernel has found degenerate (a DummySetup key) keeps its own pass with the complete loop; GA_G16_BATCH_TABLES=0: round 5.
-        bool multi_a = false, multi_b = false;
-        if (sh.w_live && ctx->tun.g16_batch_tables.load(std::memory_order_relaxed)) {
-            const void* tabs[3];
-            XYZZ<F1>* dst[3];
-            int nt = 0;
-            auto want = [&](bool shared, const void* table, XYZZ<F1>* out) {
-                if (!shared || ctx->is_degenerate(table)) return false;
-                tabs[nt] = table;
-                dst[nt++] = out;
-                return true;
-            };
-            multi_a = want(pk->share_a, pk->d_a, &ar);
-            multi_b = want(pk->share_b, pk->d_b, &bs1);
-            const bool k_fits = pk->share_k && !ctx->is_degenerate(pk->d_k);
-            if (nt + (k_fits ? 1 : 0) >= 2) {
-                if (k_fits && sh.claim_k(current_lane())) {
-                    want(true, pk->d_k, &out->krs);
-                    *did_k = true;
-                }
-                if (nt >= 2) {
-                    XYZZ<F1> sums[3];
-                    GA_CHECK((msm_table_device_reuse_multi<C, GA_G1>(ctx, tabs, nt, sh.prep_w, sums)));
-                    for (int i = 0; i < nt; i++) *dst[i] = sums[i];
-                } else {   // (K went to the partner lane after all: one table left)
-                    GA_CHECK(shared_g1(tabs[0], dst[0]));
-                }
-            } else {
-                multi_a = multi_b = false;
+        if (fits(a)) join(GA_KEY_G1_A, &out->ar);
+        if (fits(b)) join(GA_KEY_G1_B, &out->bs1);
+        const bool k_fits = fits(k);
+        if (nt + (k_fits ? 1 : 0) >= 2) {
+            if (k_fits && sh.claim_k(current_lane())) {
+                join(GA_KEY_G1_K, &out->krs);
+                *did_k = true;
             }
-        }
-        if (multi_a) {
-        } else if (pk->share_a) GA_CHECK(shared_g1(pk->d_a, &ar));
-        else if (pk->tab_a) GA_CHECK(g16_table_msm_g1<C>(pk, pk->d_a, d_wa, pk->len_a, pk->c_a, &prep, &prep_live, &ar));
-        else {
-            GA_CHECK(await_vector(pk, GA_KEY_G1_A));
-            GA_CHECK((host_msm<C, GA_G1>(ctx, pk->d_a, d_wa, pk->len_a, true, &ar, pk->win_index, pk->win_count)));
-        }
-        prep_live = false;   // (whatever A left in `prep` is not wB's)
-        if (multi_b) {
-        } else if (pk->share_b) GA_CHECK(shared_g1(pk->d_b, &bs1));
-        else if (pk->tab_b) GA_CHECK(g16_table_msm_g1<C>(pk, pk->d_b, d_wb, pk->len_b, pk->c_b, &prep, &prep_live, &bs1));
-        else {
-            GA_CHECK(await_vector(pk, GA_KEY_G1_B));
-            GA_CHECK((host_msm<C, GA_G1>(ctx, pk->d_b, d_wb, pk->len_b, true, &bs1, pk->win_index, pk->win_count)));
-        }
-        if (pk->pending && !*did_k && sh.claim_k(current_lane())) {   // a key still on its way: K's MSM before G2.B's (upload order)
-            GA_CHECK(k_msm<C>(pk, nb_public, sh, &out->krs));
-            *did_k = true;
-        }
-        if (pk->share_b2) {   // G2.B wire-indexed: the shared witness sort again
-            if (sh.w_live) GA_CHECK((msm_table_device_reuse<C, GA_G2>(ctx, pk->d_b2, sh.prep_w, &bs2)));
-            else bs2 = xyzz_inf<F2>();
-        } else if (pk->tab_b2) {   // compact G2.B table (window width c_b): the digits / sort of wB that G1.B's compact table has just made, or its own
-            int lo, hi;
-            g16_window_share<C>(pk, pk->c_b, &lo, &hi);
-            if (pk->len_b2 == 0 || hi <= lo) {
-                bs2 = xyzz_inf<F2>();
-            } else {
-                if (!prep_live) GA_CHECK(msm_prepare_table_scalars<C>(ctx, d_wb, pk->len_b2, true, pk->c_b, &prep, 0, lo, hi));
-                GA_CHECK((msm_table_device_reuse<C, GA_G2>(ctx, pk->d_b2, prep, &bs2)));
+            if (nt >= 2) {
+                XYZZ<F1> sums[3];
+                GA_CHECK((msm_table_device_reuse_multi<C, GA_G1>(ctx, tabs, nt, *shared, sums)));
+                for (int i = 0; i < nt; i++) *dst[i] = sums[i];
+            } else {   // (K went to the partner lane after all: one table left)
+                GA_CHECK((vector_msm<C, GA_G1>(pk, who[0], nullptr, shared, nullptr, dst[0])));
             }
-        } else {
-            GA_CHECK(await_vector(pk, GA_KEY_G2_B));
-            GA_CHECK((host_msm<C, GA_G2>(ctx, pk->d_b2, d_wb, pk->len_b2, true, &bs2, pk->win_index, pk->win_count)));
+            for (int i = 0; i < nt; i++) in_pass[who[i]] = true;
         }
     }
+    // 6. A   7. G1.B, which leaves the digits of wB behind when its table is compact
+    PrepSlot wb;
+    if (!in_pass[GA_KEY_G1_A]) GA_CHECK((vector_msm<C, GA_G1>(pk, GA_KEY_G1_A, d_wa, shared, nullptr, &out->ar)));
+    if (!in_pass[GA_KEY_G1_B]) GA_CHECK((vector_msm<C, GA_G1>(pk, GA_KEY_G1_B, d_wb, shared, &wb, &out->bs1)));
+    // 8. a key still on its way: K's MSM before G2.B's (upload order)
+    if (pk->pending && !*did_k && sh.claim_k(current_lane())) {
+        GA_CHECK(k_msm<C>(pk, nb_public, sh, &out->krs));
+        *did_k = true;
+    }
+    // 9. G2.B: the shared witness sort again, or a compact table (window width of G1.B's) walked with the digits G1.B has just made
+    GA_CHECK((vector_msm<C, GA_G2>(pk, GA_KEY_G2_B, d_wb, shared, &wb, &out->bs2)));
+    // 10. K, unless some lane has it already
     if (!*did_k && sh.claim_k(current_lane())) {
         GA_CHECK(k_msm<C>(pk, nb_public, sh, &out->krs));
         *did_k = true;
@@ -300,10 +283,7 @@ static int witness_msms(G16Pk* pk, const SlotLease& slot, uint64_t nb_public, Wi
 // v (host, n_constraints elements) -> device buffer d_v (n elements, zero-padded) on `up_stream`; the main stream waits for it
 static int h_upload(G16Pk* pk, const void* v, uint64_t n_constraints, void* d_v, hipStream_t up_stream) {
     const uint64_t n = pk->n;
-    if (n_constraints > n) {
-        set_error("prove: %llu constraints exceed the domain cardinality %llu", (unsigned long long)n_constraints, (unsigned long long)n);
-        return GA_ERR_INVALID;
-    }
+    GA_CHECK(check_nb_constraints(pk, n_constraints));
     GA_HIP_CHECK(pk->ctx->h2d_pageable(d_v, v, n_constraints * 32, up_stream));
     if (n > n_constraints)   // computeH pads to the domain size (prove.go:356-359)
         GA_HIP_CHECK(hipMemsetAsync((char*)d_v + n_constraints * 32, 0, (n - n_constraints) * 32, up_stream));
@@ -312,25 +292,11 @@ static int h_upload(G16Pk* pk, const void* v, uint64_t n_constraints, void* d_v,
 
 template <class C>
 static int z_msm(G16Pk* pk, const void* d_h_slice, XYZZ<Fe<typename C::FpP>>* out) {
-    typedef Fe<typename C::FpP> F1;
-    Ctx* ctx = pk->ctx;
-    if (pk->len_z == 0) {
-        *out = xyzz_inf<F1>();
+    if (pk->vec[GA_KEY_G1_Z].len == 0) {   // (a shard without a slice of Z does not wait for the vector either)
+        *out = xyzz_inf<Fe<typename C::FpP>>();
         return GA_OK;
     }
-    if (pk->tab_z) {
-        int lo, hi;
-        window_share(C::FrP::BITS / pk->c_z + 1, pk->win_index, pk->win_count, &lo, &hi);
-        if (hi <= lo) {
-            *out = xyzz_inf<F1>();
-            return GA_OK;
-        }
-        MsmPrepared prep;
-        GA_CHECK(msm_prepare_table_scalars<C>(ctx, d_h_slice, pk->len_z, true, pk->c_z, &prep, 0, lo, hi));
-        return msm_table_device_reuse<C, GA_G1>(ctx, pk->d_z, prep, out);
-    }
-    GA_CHECK(await_vector(pk, GA_KEY_G1_Z));
-    return host_msm<C, GA_G1>(ctx, pk->d_z, d_h_slice, pk->len_z, true, out, pk->win_index, pk->win_count);
+    return vector_msm<C, GA_G1>(pk, GA_KEY_G1_Z, d_h_slice, nullptr, nullptr, out);
 }
 
 // RAII for the pieces that must not outlive an early return
@@ -383,10 +349,7 @@ static int prove_partial(G16Pk* pk, const SlotLease& slot, bool preloaded, const
     typedef Fe<typename C::FpP> F1;
     Ctx* ctx = pk->ctx;
     const uint64_t n = pk->n;
-    if (n_constraints > n) {
-        set_error("prove: %llu constraints exceed the domain cardinality %llu", (unsigned long long)n_constraints, (unsigned long long)n);
-        return GA_ERR_INVALID;
-    }
+    GA_CHECK(check_nb_constraints(pk, n_constraints));
     void* d_h[3];
     static const char* const names[3] = {"h_a", "h_b", "h_c"};
     for (int k = 0; k < 3; k++) GA_CHECK(ctx->scratch_get(slot.name(names[k]).c_str(), n * 32, &d_h[k]));
@@ -451,7 +414,7 @@ static int prove_partial(G16Pk* pk, const SlotLease& slot, bool preloaded, const
                 rc = ntt_domain_h_chain<C>(pk->dom, d_h[k]);
             }
             if (rc == GA_OK) rc = ntt_domain_h_combine<C>(pk->dom, d_h[0], d_h[1], d_h[2]);   // h in d_h[0], bit-reversed like pk.G1.Z
-            if (rc == GA_OK) rc = z_msm<C>(pk, (const char*)d_h[0] + pk->off_z * 32, &z_part);
+            if (rc == GA_OK) rc = z_msm<C>(pk, (const char*)d_h[0] + pk->vec[GA_KEY_G1_Z].off * 32, &z_part);
             if (rc != GA_OK) {
                 hipStreamSynchronize(st);
                 drain_uploads();
@@ -493,7 +456,7 @@ static int prove_partial(G16Pk* pk, const SlotLease& slot, bool preloaded, const
         // ---- H (prove.go:134,346-389), then the MSM over pk.G1.Z (prove.go:225-227), on this lane ------------
         if (!preloaded) GA_HIP_CHECK(hipStreamWaitEvent(ctx->work_stream(), ev[2].ev, 0));
         GA_CHECK(ntt_domain_compute_h<C>(pk->dom, d_h[0], d_h[1], d_h[2]));   // h in d_h[0], bit-reversed like pk.G1.Z
-        GA_CHECK(z_msm<C>(pk, (const char*)d_h[0] + pk->off_z * 32, &z_part));
+        GA_CHECK(z_msm<C>(pk, (const char*)d_h[0] + pk->vec[GA_KEY_G1_Z].off * 32, &z_part));
     }
     if (!did_k && !h_did_k) {
         set_error("prove: the K MSM was claimed by no lane");
@@ -665,7 +628,7 @@ static int prove_multi(G16Pk* const* pks, uint32_t n, const void* w, const void*
             if (t == 0 && ok) ok = ctx->scratch_get(slot.name(names[k]).c_str(), N * 32, &dev0_buf[k]) == GA_OK;
         }
         // a base-range shard receives its slice of h, a window shard all of it
-        if (ok && pk->len_z) ok = t == 0 || ctx->scratch_get("h_slice", pk->len_z * 32, &h_slice[t]) == GA_OK;
+        if (ok && pk->vec[GA_KEY_G1_Z].len) ok = t == 0 || ctx->scratch_get("h_slice", pk->vec[GA_KEY_G1_Z].len * 32, &h_slice[t]) == GA_OK;
         if (!ok) bail("multi-device prove: buffers");
         if (!sh.barrier(0)) return;
         if (witness_upload(pk, slot, w, nb_public) != GA_OK) {
@@ -754,15 +717,15 @@ static int prove_multi(G16Pk* const* pks, uint32_t n, const void* w, const void*
         if (t == 0) {
             ok = ntt_domain_h_combine<C>(pk->dom, dev0_buf[0], dev0_buf[1], dev0_buf[2]) == GA_OK;
             for (uint32_t q = 1; ok && q < n; q++)   // every device gets its slice of h[:n-1]
-                if (pks[q]->len_z)
-                    ok = hipMemcpyPeerAsync(h_slice[q], pks[q]->ctx->device, (const char*)dev0_buf[0] + pks[q]->off_z * 32, ctx->device,
-                                            pks[q]->len_z * 32, ctx->stream) == hipSuccess;
+                if (pks[q]->vec[GA_KEY_G1_Z].len)
+                    ok = hipMemcpyPeerAsync(h_slice[q], pks[q]->ctx->device, (const char*)dev0_buf[0] + pks[q]->vec[GA_KEY_G1_Z].off * 32, ctx->device,
+                                            pks[q]->vec[GA_KEY_G1_Z].len * 32, ctx->stream) == hipSuccess;
             if (ok) ok = hipStreamSynchronize(ctx->stream) == hipSuccess;
             if (!ok) {
                 if (!get_error()[0]) set_error("HIP error while finishing / scattering h");
                 bail("multi-device prove: h");
             }
-            h_slice[0] = (char*)dev0_buf[0] + pk->off_z * 32;
+            h_slice[0] = (char*)dev0_buf[0] + pk->vec[GA_KEY_G1_Z].off * 32;
         }
         if (!sh.barrier(2)) return;
         XYZZ<F1> z;
@@ -961,27 +924,26 @@ void ga_g16_pk_destroy(ga_g16_pk* p) try {
 } GA_ABI_CATCH_VOID
 
 // what a key holds, for callers that orchestrate a sharded proof themselves (gnark_amd/multigpu.py)
-int ga_g16_shard_layout(ga_g16_pk* p, uint64_t* out6) try {
+int ga_g16_shard_layout(ga_g16_pk* p, uint64_t* out8) try {
     GA_ABI_ENTRY();
     G16Pk* pk = reinterpret_cast<G16Pk*>(p);
-    uint64_t* out8 = out6;
-    if (!pk || !out6) {
+    if (!pk || !out8) {
         set_error("ga_g16_shard_layout: null argument");
         return GA_ERR_INVALID;
     }
-    out6[0] = pk->off_z;
-    out6[1] = pk->len_z;
-    out6[2] = pk->w_lo;
-    out6[3] = pk->w_hi;
-    out6[4] = pk->n;
-    out6[5] = pk->nb_wires;
+    out8[0] = pk->vec[GA_KEY_G1_Z].off;
+    out8[1] = pk->vec[GA_KEY_G1_Z].len;
+    out8[2] = pk->w_lo;
+    out8[3] = pk->w_hi;
+    out8[4] = pk->n;
+    out8[5] = pk->nb_wires;
     out8[6] = pk->win_index;
     out8[7] = pk->win_count;   // (the plain count: which vectors carry tables is ga_g16_table_layout's answer)
     return GA_OK;
 } GA_ABI_CATCH
 
-// out2[0]: which vectors carry a window table (bit 0 G1.A, 1 G1.B, 2 G1.Z, 3 G1.K, 4 G2.B); out2[1]: which of those are laid out by
-// wire id over the shared witness sort (bit 0 A, 1 B, 3 K, 4 G2.B)
+// out2[0]: which vectors carry a window table (bit GA_KEY_*: 0 G1.A, 1 G1.B, 2 G1.Z, 3 G1.K, 4 G2.B); out2[1]: which of those are laid
+// out by wire id over the shared witness sort
 int ga_g16_table_layout(ga_g16_pk* p, uint64_t* out2) try {
     GA_ABI_ENTRY();
     G16Pk* pk = reinterpret_cast<G16Pk*>(p);
@@ -989,8 +951,11 @@ int ga_g16_table_layout(ga_g16_pk* p, uint64_t* out2) try {
         set_error("ga_g16_table_layout: null argument");
         return GA_ERR_INVALID;
     }
-    out2[0] = (uint64_t)pk->tab_a | (uint64_t)pk->tab_b << 1 | (uint64_t)pk->tab_z << 2 | (uint64_t)pk->tab_k << 3 | (uint64_t)pk->tab_b2 << 4;
-    out2[1] = (uint64_t)pk->share_a | (uint64_t)pk->share_b << 1 | (uint64_t)pk->share_k << 3 | (uint64_t)pk->share_b2 << 4;
+    out2[0] = out2[1] = 0;
+    for (int w = 0; w < GA_KEY_NB_VECTORS; w++) {
+        out2[0] |= (uint64_t)pk->vec[w].has_table() << w;
+        out2[1] |= (uint64_t)pk->vec[w].wire_indexed() << w;
+    }
     return GA_OK;
 } GA_ABI_CATCH
 
@@ -1027,9 +992,7 @@ int ga_g16_key_write_fd(ga_ctx* h, const ga_g16_key* key, int format, int fd, ui
         set_error("ga_g16_key_write_fd: bad argument");
         return GA_ERR_INVALID;
     }
-    if (!key->g1_alpha || !key->g1_beta || !key->g1_delta || !key->g2_beta || !key->g2_delta || !key->infinity_a || !key->infinity_b ||
-        (key->len_a && !key->g1_a) || (key->len_b && !key->g1_b) || (key->len_z && !key->g1_z) || (key->len_k && !key->g1_k) ||
-        (key->len_b2 && !key->g2_b) || (key->nb_commitments && (!key->ck_basis || !key->ck_basis_exp_sigma || !key->ck_len))) {
+    if (!key_points_present(key) || (key->nb_commitments && (!key->ck_basis || !key->ck_basis_exp_sigma || !key->ck_len))) {
         set_error("ga_g16_key_write_fd: null pointer inside ga_g16_key");
         return GA_ERR_INVALID;
     }
@@ -1325,7 +1288,7 @@ int ga_g16_h_combine(ga_g16_pk* p, void* a_dev, const void* b_dev, const void* c
 int ga_g16_z_partial(ga_g16_pk* p, const void* h_slice_dev, void* partial_out) try {
     GA_ABI_ENTRY();
     G16Pk* pk = reinterpret_cast<G16Pk*>(p);
-    if (!pk || (!h_slice_dev && pk->len_z) || !partial_out) {
+    if (!pk || (!h_slice_dev && pk->vec[GA_KEY_G1_Z].len) || !partial_out) {
         set_error("ga_g16_z_partial: null argument");
         return GA_ERR_INVALID;
     }

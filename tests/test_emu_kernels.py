@@ -637,6 +637,74 @@ def test_emu_groth16_synthetic_vs_c_oracle(emu_ctx, c, monkeypatch, logn=7):
     assert len(proof.WriteTo()) == (164 if c.cid == 0 else 244)
 
 
+@pytest.mark.parametrize("c", CURVES, ids=lambda c: c.name)
+def test_emu_groth16_mixed_vector_layouts(emu_ctx, c, monkeypatch, logn=7):
+    """A key whose vectors take DIFFERENT paths by their own density in one proof (2^7 under the emulation, 2^10 on the GPU): the
+    synthetic key of the test above, except that InfinityB masks every second wire -- B covers 50 % of the wires (below
+    GA_G16_SHARE_MIN_PCT's default of 90), A and K about 97 %.  With all tables: A and K wire-indexed over the shared witness sort,
+    G1.B a compact table whose digits G2.B's compact table reuses, Z a compact table.  Then the partial table sets of precompute = 0."""
+    ctx = emu_ctx
+    lib = ctx.lib
+    n = 1 << logn
+    nw = n
+    nb_public = 3
+    monkeypatch.delenv("GA_G16_SHARE_MIN_PCT", raising=False)
+    monkeypatch.delenv("GA_G16_TABLE_BUDGET_PCT", raising=False)
+
+    def gen(group, count, seed):
+        buf = ctx.malloc(count * affine_words(c.cid, group) * 8)
+        lib.check(lib.ga_gen_bases(ctx.handle, c.cid, group, seed, count, buf.ptr, None))
+        h = buf.to_host((count, affine_words(c.cid, group)))
+        buf.free()
+        return h
+
+    def scal(count, seed):
+        buf = ctx.malloc(count * 32)
+        lib.check(lib.ga_gen_scalars(ctx.handle, c.cid, seed, count, buf.ptr))
+        h = buf.to_host((count, 4))
+        buf.free()
+        return h
+    infA = np.zeros(nw, np.uint8)
+    infB = np.zeros(nw, np.uint8)
+    infA[[1, 5, nw - 1]] = 1
+    infB[1::2] = 1
+    nb = nw // 2
+    m1, m2 = gen(0, 3, 1), gen(1, 2, 2)
+    key = dict(alpha1=m1[0:1], beta1=m1[1:2], delta1=m1[2:3], A=gen(0, nw - 3, 3), B=gen(0, nb, 4), Z=gen(0, n - 1, 5),
+               K=gen(0, nw - nb_public, 6), beta2=m2[0:1], delta2=m2[1:2], B2=gen(1, nb, 7), infinityA=infA, infinityB=infB)
+    m = n - 9
+    W, A, B = scal(nw, 10), scal(m, 11), scal(m, 12)
+    Cc = oracle.fr_mul(c.cid, A, B)
+    rs = scal(2, 13)
+    want = oracle.groth16_prove(c.cid, dict(key, n=n), W, A, B, Cc, nb_public, rs[0], rs[1], nthreads=8)
+
+    def prove(precompute):
+        pk = groth16.ProvingKey(ctx, c.name, domain_cardinality=n, precompute=precompute, **key)
+        try:
+            lay = groth16.ShardLayout(pk)
+            proof = groth16.Prove(pk, groth16.Solution(W, A, B, Cc), nb_public, rs[0], rs[1])
+        finally:
+            pk.FreeGPUResources()
+        assert np.array_equal(proof.Ar, want[0]) and np.array_equal(proof.Bs, want[1]) and np.array_equal(proof.Krs, want[2]), (precompute, lay)
+        return lay
+    lay = prove(1)
+    assert lay["tables"] == dict(A=True, B=True, Z=True, K=True, B2=True), lay
+    assert lay["wire_indexed"] == dict(A=True, B=False, K=True, B2=False), lay   # (Z has no wire-indexed form: a compact table)
+    order = ("A", "B", "K", "Z", "B2")
+    sizes = []
+    for pct in (5, 30, 55, 80):
+        monkeypatch.setenv("GA_G16_TABLE_BUDGET_PCT", str(pct))
+        lay = prove(0)
+        have = [k for k in order if lay["tables"][k]]
+        assert have == list(order[:len(have)]), lay["tables"]                      # a prefix of the preference order
+        assert all(lay["tables"][k] for k, v in lay["wire_indexed"].items() if v)  # wire-indexed implies a table
+        sizes.append(len(have))
+    monkeypatch.delenv("GA_G16_TABLE_BUDGET_PCT", raising=False)
+    # literals recorded from this test's run on the commit before G16Pk held one record per vector (the same for both curves, at 2^7 and
+    # at 2^10): none / A / A, B / A, B, K, Z -- the half-size B fits where K no longer does.  A refactor must plan the same table sets.
+    assert sizes == [0, 1, 2, 4], sizes
+
+
 def _device_inputs(ctx, c, group, n, seed):
     lib = ctx.lib
     wa = affine_words(c.cid, group)

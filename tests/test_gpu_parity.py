@@ -356,6 +356,13 @@ def test_groth16_synthetic_2_10_vs_oracle(gpu_ctx, c, monkeypatch):
     cases.test_emu_groth16_synthetic_vs_c_oracle(gpu_ctx, c, monkeypatch, logn=10)
 
 
+@pytest.mark.parametrize("c", CURVES, ids=lambda c: c.name)
+def test_groth16_mixed_vector_layouts(gpu_ctx, c, monkeypatch):
+    """2^10 (the table kernels run more than one workgroup): A and K wire-indexed, B and G2.B compact tables sharing one set of digits,
+    Z a compact table in ONE proof, then the partial table sets of precompute = 0 -- proof points equal to the C oracle's"""
+    cases.test_emu_groth16_mixed_vector_layouts(gpu_ctx, c, monkeypatch, logn=10)
+
+
 @pytest.mark.parametrize("precompute", [1, -1, "shared-sort"], ids=["tables", "no-tables", "tables-shared-sort"])
 @pytest.mark.parametrize("c", CURVES, ids=lambda c: c.name)
 def test_groth16_bsb22_commitments_bytes(gpu_ctx, c, precompute):
