@@ -114,12 +114,12 @@ int Ctx::scratch_get(const char* base_key, size_t bytes, void** out) {
     const char* key = lane_key.c_str();
     std::lock_guard<std::mutex> g(scratch_mu);
     auto it = scratch.find(key);
-    if (it != scratch.end() && it->second.second >= bytes) {
-        *out = it->second.first;
+    if (it != scratch.end() && it->second.bytes >= bytes) {
+        *out = it->second.p;
         return GA_OK;
     }
     if (it != scratch.end()) {
-        hipFree(it->second.first);
+        hipFree(it->second.p);
         scratch.erase(it);
     }
     void* p = nullptr;
@@ -132,24 +132,22 @@ int Ctx::scratch_get(const char* base_key, size_t bytes, void** out) {
         set_error("device scratch '%s': device_malloc(%zu) failed: %s", key, want, device_malloc_error(e));
         return GA_ERR_NOMEM;
     }
-    scratch[key] = std::make_pair(p, want);
+    scratch[key] = ScratchBuf{p, want, lane};
     *out = p;
     return GA_OK;
 }
 
 void Ctx::scratch_free_all() {
     std::lock_guard<std::mutex> g(scratch_mu);
-    for (auto& kv : scratch) hipFree(kv.second.first);
+    for (auto& kv : scratch) hipFree(kv.second.p);
     scratch.clear();
 }
 
 void Ctx::scratch_free_lanes(int first_lane) {
     std::lock_guard<std::mutex> g(scratch_mu);
     for (auto it = scratch.begin(); it != scratch.end();) {
-        const size_t at = it->first.rfind('@');
-        const int lane = at == std::string::npos ? 0 : atoi(it->first.c_str() + at + 1);
-        if (lane >= first_lane) {
-            hipFree(it->second.first);
+        if (it->second.lane >= first_lane) {
+            hipFree(it->second.p);
             it = scratch.erase(it);
         } else
             ++it;

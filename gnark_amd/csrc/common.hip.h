@@ -58,7 +58,7 @@ const char* get_error();
 // process; the reference turns device errors into Go errors, icicle.go:122-208).  EVERY entry point is a function-try-block
 //     int ga_x(...) try { GA_ABI_ENTRY(); ... } GA_ABI_CATCH
 // whose handler maps the exception to an error code + ga_last_error text (abi_exception_code); the RAII guards inside (locks, lanes,
-// slot leases, staged buffers, thread joiners) release on the way out, so the context stays usable.
+// slot leases, staged buffers, helper threads) release on the way out, so the context stays usable.
 // GA_ABI_ENTRY also names the entry point for the fault knob GA_FAULT_THROW=<entry point> (tests only): Ctx::scratch_get then throws
 // std::bad_alloc when called under that entry point on the calling thread.
 int abi_exception_code(const char* entry) noexcept;   // call inside a catch (...) handler
@@ -189,7 +189,8 @@ struct Tunables {
 // Lane 0 is the context's main stream, guarded by Ctx::mu (every entry point); lanes 1..3 are guarded by Ctx::lane_mu[lane].
 //   * a proof runs on a PAIR of lanes: the witness MSMs on the caller's lane (0, or 2 for a second concurrent caller) and its H
 //     side -- uploads of A, B, C, computeH, the Z MSM -- on the partner lane (1, or 3) from a helper thread, so that the sorts,
-//     reduction tails and host round trips of one half run under the bucket kernels of the other (groth16.hip prove_partial);
+//     reduction tails and host round trips of one half run under the bucket kernels of the other (groth16.hip: prove_partial
+//     takes the partner lane and starts a HelperThread on it, whose body runs h_side);
 //   * a second ga_g16_prove caller computes its proof CONCURRENTLY on lanes 2/3 instead of queueing behind the first: its
 //     uploads hide behind the other proof's kernels;
 //   * the table MSM entry points and the pieces of a sharded proof take lane 1 when lane 0 is busy (LaneLock).
@@ -297,8 +298,13 @@ struct Ctx {
     } spare_vectors;
     std::atomic<bool> profiling{false};
     std::vector<StageRec> stages;
-    // reusable device scratch, grown on demand (keyed by purpose)
-    std::map<std::string, std::pair<void*, size_t>> scratch;
+    // reusable device scratch, grown on demand (keyed by purpose; scratch_get appends "@lane" for lanes 1..3)
+    struct ScratchBuf {
+        void* p;
+        size_t bytes;
+        int lane;   // the lane whose namespace the entry belongs to
+    };
+    std::map<std::string, ScratchBuf> scratch;
 
     // base tables on which the fast bucket loop flagged most of its tasks (all bases equal: a DummySetup key); msm_bucket.hip.h
     std::mutex degenerate_mu;
@@ -409,10 +415,6 @@ struct StageTimer {
     ~StageTimer() {
         if (idx >= 0) hipEventRecord(ctx->stages[idx].b, st);
     }
-};
-
-struct DeviceGuard {
-    explicit DeviceGuard(int dev) { hipSetDevice(dev); }
 };
 
 static inline int ilog2_u64(uint64_t x) {

@@ -487,7 +487,7 @@ static double free_table_bytes(Ctx* ctx, uint64_t n) {
     uint64_t held = 0;
     {
         std::lock_guard<std::mutex> g(ctx->scratch_mu);
-        for (const auto& kv : ctx->scratch) held += kv.second.second;
+        for (const auto& kv : ctx->scratch) held += kv.second.bytes;
     }
     const double per_proof = (double)n * 1280.0;
     const double allowance = per_proof > (double)held ? per_proof - (double)held : 0.0;

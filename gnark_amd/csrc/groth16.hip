@@ -26,10 +26,14 @@ namespace ga {
 // witness_msms   : the schedule of the MSMs over W -- filter, A, B (G1 + G2), K                               prove.go:147-237,283
 // vector_msm     : ONE MSM over a base vector of the key, on the path its layout names (wire-indexed table over the shared witness
 //                  sort, compact table with its own digits + sort, plain array); k_msm and z_msm feed it K's and Z's scalars
-// h_chain        : v <- FFT_coset(iFFT(v)) for one of the solver's A, B, C                                     prove.go:362-368
-// h_combine      : h <- iFFT_coset((a*b - c) * den), bit-reversed like pk.G1.Z                                prove.go:377-386
+// h_upload       : one of the solver's A, B, C -> device, zero-padded to the domain (h_pad)                      prove.go:356-359
+// h_chain        : v <- FFT_coset(iFFT(v)) for one of them (ntt_domain_h_chain)                                prove.go:362-368
+// h_combine      : h <- iFFT_coset((a*b - c) * den), bit-reversed like pk.G1.Z (ntt_domain_h_combine)          prove.go:377-386
 // z_msm          : MSM over this shard's slice of pk.G1.Z and h                                                prove.go:225-227
-// prove_partial runs them on one device (two lanes), prove_multi on several; finish is the host epilogue.
+// h_side         : the three chains, each once its vector has landed, h_combine and z_msm on ONE lane
+// HelperThread   : a thread that runs such pieces beside the caller; its result code, error text and exceptions come back in join()
+// prove_partial runs them on one device (witness_msms on the caller's lane, h_helper beside it), prove_multi / MultiProof on several;
+// finish is the host epilogue.
 
 // nbPublic of a proof agrees with the key: nbWires - nbPublic wires feed K, some of them through the commitments' remove list
 static int check_nb_public(const G16Pk* pk, uint64_t nb_public) {
@@ -280,13 +284,26 @@ static int witness_msms(G16Pk* pk, const SlotLease& slot, uint64_t nb_public, Wi
     return GA_OK;
 }
 
-// v (host, n_constraints elements) -> device buffer d_v (n elements, zero-padded) on `up_stream`; the main stream waits for it
-static int h_upload(G16Pk* pk, const void* v, uint64_t n_constraints, void* d_v, hipStream_t up_stream) {
-    const uint64_t n = pk->n;
+// ---- the H side -----------------------------------------------------------------------------------------------------------------
+// the slot's staging buffer for the solver's A, B or C (k = 0, 1, 2): n elements
+static int h_buffer(G16Pk* pk, const SlotLease& slot, int k, void** out) {
+    static const char* const names[3] = {"h_a", "h_b", "h_c"};
+    return pk->ctx->scratch_get(slot.name(names[k]).c_str(), pk->n * 32, out);
+}
+
+// computeH pads to the domain size (prove.go:356-359): rows [n_constraints, n) of d_v <- 0 on `st`
+static int h_pad(G16Pk* pk, void* d_v, uint64_t n_constraints, hipStream_t st) {
+    if (pk->n > n_constraints) GA_HIP_CHECK(hipMemsetAsync((char*)d_v + n_constraints * 32, 0, (pk->n - n_constraints) * 32, st));
+    return GA_OK;
+}
+
+// v (host, n_constraints elements) -> device buffer d_v (n elements, zero-padded) on `up_stream`; `landed` (optional) is recorded
+// behind it for the stream that consumes d_v
+static int h_upload(G16Pk* pk, const void* v, uint64_t n_constraints, void* d_v, hipStream_t up_stream, hipEvent_t landed = nullptr) {
     GA_CHECK(check_nb_constraints(pk, n_constraints));
     GA_HIP_CHECK(pk->ctx->h2d_pageable(d_v, v, n_constraints * 32, up_stream));
-    if (n > n_constraints)   // computeH pads to the domain size (prove.go:356-359)
-        GA_HIP_CHECK(hipMemsetAsync((char*)d_v + n_constraints * 32, 0, (n - n_constraints) * 32, up_stream));
+    GA_CHECK(h_pad(pk, d_v, n_constraints, up_stream));
+    if (landed) GA_HIP_CHECK(hipEventRecord(landed, up_stream));
     return GA_OK;
 }
 
@@ -299,17 +316,71 @@ static int z_msm(G16Pk* pk, const void* d_h_slice, XYZZ<Fe<typename C::FpP>>* ou
     return vector_msm<C, GA_G1>(pk, GA_KEY_G1_Z, d_h_slice, nullptr, nullptr, out);
 }
 
-// RAII for the pieces that must not outlive an early return
-struct EventGuard {
-    hipEvent_t ev = nullptr;
-    ~EventGuard() {
-        if (ev) hipEventDestroy(ev);
+// The H side of a proof on the calling thread's lane (prove.go:134,346-389, then 225-227): each chain FFT_coset(iFFT(.)) as soon as
+// its vector is complete -- landed[k], when given, is waited for on the lane's stream --, the point-wise step and the last transform
+// (h in d_h[0], bit-reversed like pk.G1.Z), then the MSM over this key's slice of Z.
+template <class C>
+static int h_side(G16Pk* pk, void* const d_h[3], const hipEvent_t* landed, XYZZ<Fe<typename C::FpP>>* z_part) {
+    hipStream_t st = pk->ctx->work_stream();
+    for (int k = 0; k < 3; k++) {
+        if (landed) GA_HIP_CHECK(hipStreamWaitEvent(st, landed[k], 0));
+        GA_CHECK(ntt_domain_h_chain<C>(pk->dom, d_h[k]));
     }
-};
-struct ThreadJoiner {
-    std::thread& t;
-    ~ThreadJoiner() {
-        if (t.joinable()) t.join();
+    GA_CHECK(ntt_domain_h_combine<C>(pk->dom, d_h[0], d_h[1], d_h[2]));
+    return z_msm<C>(pk, (const char*)d_h[0] + pk->vec[GA_KEY_G1_Z].off * 32, z_part);
+}
+
+// the K MSM on the PARTNER lane, if the witness lane has not got to it yet (its W and its witness sort are on the device: w_ev)
+template <class C>
+static int k_msm_late(G16Pk* pk, uint64_t nb_public, WitnessShared& sh, XYZZ<Fe<typename C::FpP>>* out, bool* did_k) {
+    if (!sh.wait_posted() || !sh.claim_k(current_lane())) return GA_OK;
+    GA_HIP_CHECK(hipStreamWaitEvent(pk->ctx->work_stream(), sh.w_ev, 0));
+    GA_CHECK(k_msm<C>(pk, nb_public, sh, out));
+    *did_k = true;
+    return GA_OK;
+}
+
+// A helper thread of an entry point.  It runs `body` -- an ordinary function that returns a GA_* code -- on the context's device, on
+// `lane`, under the entry-point name of the thread that started it.  No exception leaves the thread function, which would terminate
+// the process: it becomes the code abi_exception_code gives it.  join() returns body's code unchanged and republishes its error text
+// on the joining thread; the destructor joins, so neither an early return nor an exception on the starting thread leaves a joinable
+// std::thread behind.  run_here() takes a body that shares the calling thread through the same wrapper.
+class HelperThread {
+    std::thread th;
+    int rc = GA_OK;
+    char err[1024] = "";   // (a fixed buffer: keeping the text of a std::bad_alloc must not allocate)
+    template <class F>
+    void run(Ctx* ctx, int lane, const char* entry, F& body) noexcept {
+        EntryScope under(entry);
+        LaneScope on_lane(lane);
+        try {
+            rc = [&]() -> int {
+                GA_HIP_CHECK(hipSetDevice(ctx->device));
+                return body();
+            }();
+        } catch (...) {
+            rc = abi_exception_code(entry);
+        }
+        if (rc != GA_OK) snprintf(err, sizeof(err), "%s", get_error());
+    }
+
+public:
+    template <class F>
+    void start(Ctx* ctx, int lane, F body) {
+        const char* entry = current_entry();
+        th = std::thread([this, ctx, lane, entry, body]() mutable { run(ctx, lane, entry, body); });
+    }
+    template <class F>
+    void run_here(Ctx* ctx, int lane, F body) {
+        run(ctx, lane, current_entry(), body);
+    }
+    int join() {
+        if (th.joinable()) th.join();
+        if (rc != GA_OK) set_error("%s", err);
+        return rc;
+    }
+    ~HelperThread() {
+        if (th.joinable()) th.join();
     }
 };
 
@@ -317,18 +388,61 @@ struct ThreadJoiner {
 // with another proof does this while it waits); returns when the copies have completed, so the host buffers are free again
 static int preload_solution(G16Pk* pk, const SlotLease& slot, const void* w, const void* a, const void* b, const void* c,
                             uint64_t n_constraints, uint64_t nb_public) {
-    Ctx* ctx = pk->ctx;
-    const uint64_t n = pk->n;
-    hipStream_t st = ctx->slot_stream[slot.slot];
+    hipStream_t st = pk->ctx->slot_stream[slot.slot];
     GA_CHECK(witness_upload(pk, slot, w, nb_public, st));
     const void* src[3] = {a, b, c};
-    static const char* const names[3] = {"h_a", "h_b", "h_c"};
     for (int k = 0; k < 3; k++) {
         void* d;
-        GA_CHECK(ctx->scratch_get(slot.name(names[k]).c_str(), n * 32, &d));
+        GA_CHECK(h_buffer(pk, slot, k, &d));
         GA_CHECK(h_upload(pk, src[k], n_constraints, d, st));
     }
     GA_HIP_CHECK(hipStreamSynchronize(st));
+    return GA_OK;
+}
+
+// What the two threads of prove_partial share about the H side: the slot's buffers for A, B, C with the events recorded behind
+// their uploads, and what the helper thread computed when the proof was split.
+template <class C>
+struct HShared {
+    void* d_h[3];
+    hipEvent_t landed[3] = {nullptr, nullptr, nullptr};
+    XYZZ<Fe<typename C::FpP>> z_part = xyzz_inf<Fe<typename C::FpP>>(), k_part = z_part;
+    bool did_k = false;
+    int init(G16Pk* pk, const SlotLease& slot) {
+        for (int k = 0; k < 3; k++) {
+            GA_CHECK(h_buffer(pk, slot, k, &d_h[k]));
+            GA_HIP_CHECK(hipEventCreateWithFlags(&landed[k], hipEventDisableTiming));
+        }
+        return GA_OK;
+    }
+    ~HShared() {
+        for (hipEvent_t e : landed)
+            if (e) hipEventDestroy(e);
+    }
+};
+
+// The body of prove_partial's helper thread.  src: the solver's A, B, C on the host (null: preloaded), uploaded on the slot's own
+// copy stream (two proofs in flight do not queue their uploads).  split: the thread is on the partner lane and runs the H side there,
+// then K's MSM.  It returns with the copy stream drained -- no host pointer outlives the call -- and the partner lane idle.
+template <class C>
+static int h_helper_steps(G16Pk* pk, hipStream_t up, const void* const* src, uint64_t n_constraints, uint64_t nb_public, bool split,
+                          WitnessShared& sh, HShared<C>& h) {
+    for (int k = 0; src && k < 3; k++) GA_CHECK(h_upload(pk, src[k], n_constraints, h.d_h[k], up, h.landed[k]));
+    if (!split) return GA_OK;
+    pk->ctx->stat_split++;
+    GA_CHECK(h_side<C>(pk, h.d_h, src ? h.landed : nullptr, &h.z_part));
+    return k_msm_late<C>(pk, nb_public, sh, &h.k_part, &h.did_k);
+}
+template <class C>
+static int h_helper(G16Pk* pk, const SlotLease& slot, const void* const* src, uint64_t n_constraints, uint64_t nb_public, bool split,
+                    WitnessShared& sh, HShared<C>& h) {
+    hipStream_t up = pk->ctx->slot_stream[slot.slot];
+    const int rc = h_helper_steps<C>(pk, up, src, n_constraints, nb_public, split, sh, h);
+    const hipError_t lane_idle = split ? hipStreamSynchronize(pk->ctx->work_stream()) : hipSuccess;   // (z_msm returns synchronised unless this shard's Z slice is empty)
+    const hipError_t uploads_done = src ? hipStreamSynchronize(up) : hipSuccess;
+    GA_CHECK(rc);
+    GA_HIP_CHECK(lane_idle);
+    GA_HIP_CHECK(uploads_done);
     return GA_OK;
 }
 
@@ -336,133 +450,46 @@ static int preload_solution(G16Pk* pk, const SlotLease& slot, const void* w, con
 // Outputs (before randomisation): A-sum, B1-sum, K-sum + Z-sum (G1), B2-sum (G2) -- to be added across shards.
 // preloaded: W, A, B, C already sit in the slot's buffers (preload_solution).
 //
-// Schedule.  The calling thread uploads W and runs the witness MSMs (A, B1, B2) on its own lane.  A helper thread uploads A, B, C
-// on the slot's copy stream (pageable H2D copies block the thread that issues them) and -- when the partner lane is free -- also
-// runs the H side there: each chain FFT_coset(iFFT(.)) as soon as its vector has landed, the point-wise step, the last
-// transform, then the Z MSM over h.  The K MSM goes to whichever lane reaches it first.  The two halves share the device: the
-// sorts, reduction tails, host round trips and launch gaps of one run under the bucket kernels of the other.  Without a partner
-// lane (profiling on, GA_G16_SPLIT=0, or the lane is taken) the helper only uploads and the H side follows on the caller's lane,
-// as in round 2.  Everything is joined before this function returns, so no host pointer outlives the call.
+// Schedule.  The calling thread uploads W and runs the witness MSMs (A, B1, B2) on its own lane.  A helper thread (h_helper) uploads
+// A, B, C on the slot's copy stream and -- when the partner lane is free -- also runs the H side there (h_side): each chain as soon
+// as its vector has landed, the point-wise step, the last transform, then the Z MSM over h.  The K MSM goes to whichever lane
+// reaches it first.  The two halves share the device: the sorts, reduction tails, host round trips and launch gaps of one run under
+// the bucket kernels of the other.  Without a partner lane (profiling on, GA_G16_SPLIT=0, or the lane is taken) the helper only
+// uploads and the same h_side follows on the caller's lane after the join, as in round 2.  Either half's result code is returned
+// verbatim: ga_g16_prove's lane-2 fallback keys on GA_ERR_NOMEM.  Everything is joined before this function returns.
 template <class C>
 static int prove_partial(G16Pk* pk, const SlotLease& slot, bool preloaded, const void* w, const void* a, const void* b, const void* c,
                          uint64_t n_constraints, uint64_t nb_public, G16Partials<C>* out) {
-    typedef Fe<typename C::FpP> F1;
     Ctx* ctx = pk->ctx;
-    const uint64_t n = pk->n;
     GA_CHECK(check_nb_constraints(pk, n_constraints));
-    void* d_h[3];
-    static const char* const names[3] = {"h_a", "h_b", "h_c"};
-    for (int k = 0; k < 3; k++) GA_CHECK(ctx->scratch_get(slot.name(names[k]).c_str(), n * 32, &d_h[k]));
-    const int lane = current_lane();
-    const int partner = lane + 1;   // lanes pair up: (0, 1) and (2, 3)
-    const bool may_split = !ctx->profiling && ctx->tun.g16_split && (lane == 0 || lane == 2);
+    HShared<C> h;
+    GA_CHECK(h.init(pk, slot));
     WitnessShared sh;
     GA_HIP_CHECK(hipEventCreateWithFlags(&sh.w_ev, hipEventDisableTiming));
-    EventGuard ev[3];
-    for (int k = 0; k < 3; k++) GA_HIP_CHECK(hipEventCreateWithFlags(&ev[k].ev, hipEventDisableTiming));
+    // lanes pair up, (0, 1) and (2, 3): the H side goes to the partner of the caller's lane when that lane is free
+    const int lane = current_lane();
+    std::unique_lock<std::mutex> partner;
+    if (!ctx->profiling && ctx->tun.g16_split && (lane == 0 || lane == 2)) partner = std::unique_lock<std::mutex>(ctx->lane_mu[lane + 1], std::try_to_lock);
+    const bool split = partner.owns_lock();
     // W first: the witness MSMs only need W, and the (PCIe-competing) upload of A, B, C starts when this one has been handed over
     if (!preloaded) GA_CHECK(witness_upload(pk, slot, w, nb_public));
-    XYZZ<F1> k_part_h = xyzz_inf<F1>(), z_part = xyzz_inf<F1>();
-    bool split = false, h_did_k = false;
-    int h_rc = GA_OK;
-    std::string h_err;
-    hipStream_t up = ctx->slot_stream[slot.slot];   // the slot's own copy stream: two proofs in flight do not queue their uploads
-    std::thread helper;
-    if (!preloaded || may_split)
-        helper = std::thread([&]() {
-          try {   // (an exception leaving a thread function terminates the process: host allocations below can throw)
-            auto fail = [&](int rc, const char* what) {
-                h_rc = rc;
-                h_err = std::string(what) + ": " + get_error();
-            };
-            if (hipSetDevice(ctx->device) != hipSuccess) {
-                set_error("hipSetDevice(%d) failed", ctx->device);
-                return fail(GA_ERR_HIP, "selecting the device");
-            }
-            std::unique_lock<std::mutex> pl(ctx->lane_mu[partner < GA_NUM_LANES ? partner : 1], std::defer_lock);
-            if (may_split && pl.try_lock()) split = true;
-            LaneScope on_lane(split ? partner : lane);
-            if (!preloaded) {
-                const void* src[3] = {a, b, c};
-                for (int k = 0; k < 3; k++) {
-                    if (h_upload(pk, src[k], n_constraints, d_h[k], up) != GA_OK) return fail(GA_ERR_HIP, "uploading A, B, C");
-                    if (hipEventRecord(ev[k].ev, up) != hipSuccess) {
-                        set_error("hipEventRecord failed");
-                        return fail(GA_ERR_HIP, "uploading A, B, C");
-                    }
-                }
-            }
-            auto drain_uploads = [&]() -> bool {
-                if (preloaded || hipStreamSynchronize(up) == hipSuccess) return true;
-                set_error("hipStreamSynchronize failed on the copy stream");
-                fail(GA_ERR_HIP, "uploading A, B, C");
-                return false;
-            };
-            if (!split) {
-                drain_uploads();
-                return;
-            }
-            ctx->stat_split++;
-            hipStream_t st = ctx->work_stream();
-            int rc = GA_OK;
-            for (int k = 0; k < 3 && rc == GA_OK; k++) {
-                if (!preloaded && hipStreamWaitEvent(st, ev[k].ev, 0) != hipSuccess) {
-                    set_error("hipStreamWaitEvent failed");
-                    rc = GA_ERR_HIP;
-                    break;
-                }
-                rc = ntt_domain_h_chain<C>(pk->dom, d_h[k]);
-            }
-            if (rc == GA_OK) rc = ntt_domain_h_combine<C>(pk->dom, d_h[0], d_h[1], d_h[2]);   // h in d_h[0], bit-reversed like pk.G1.Z
-            if (rc == GA_OK) rc = z_msm<C>(pk, (const char*)d_h[0] + pk->vec[GA_KEY_G1_Z].off * 32, &z_part);
-            if (rc != GA_OK) {
-                hipStreamSynchronize(st);
-                drain_uploads();
-                return fail(rc, "computeH / Z MSM");
-            }
-            if (hipStreamSynchronize(st) != hipSuccess) {   // (z_msm returns synchronised unless this shard's Z slice is empty)
-                set_error("hipStreamSynchronize failed on the H lane");
-                return fail(GA_ERR_HIP, "computeH / Z MSM");
-            }
-            if (!drain_uploads()) return;
-            // the K MSM, if the witness lane has not got to it yet (its W and its witness sort are on the device: w_ev)
-            if (sh.wait_posted() && sh.claim_k(partner)) {
-                if (hipStreamWaitEvent(st, sh.w_ev, 0) != hipSuccess) {
-                    set_error("hipStreamWaitEvent failed");
-                    return fail(GA_ERR_HIP, "K MSM");
-                }
-                rc = k_msm<C>(pk, nb_public, sh, &k_part_h);
-                if (rc != GA_OK) return fail(rc, "K MSM");
-                h_did_k = true;
-            }
-          } catch (...) {
-              h_rc = GA_ERR_STATE;
-              h_err = "exception on the helper thread (out of host memory?)";
-          }
-        });
-    ThreadJoiner joiner{helper};
+    const void* const abc[3] = {a, b, c};
+    const void* const* src = preloaded ? nullptr : abc;
+    HelperThread helper;
+    if (src || split) helper.start(ctx, split ? lane + 1 : lane, [&] { return h_helper<C>(pk, slot, src, n_constraints, nb_public, split, sh, h); });
     bool did_k = false;
     const int w_rc = witness_msms<C>(pk, slot, nb_public, sh, out, &did_k);
-    if (helper.joinable()) helper.join();
-    if (w_rc != GA_OK) {
+    if (w_rc != GA_OK) {   // (the witness side's error is the one reported; the helper is joined on the way out)
         hipStreamSynchronize(ctx->work_stream());
         return w_rc;
     }
-    if (h_rc != GA_OK) {
-        set_error("prove (H side): %s", h_err.c_str());
-        return h_rc;
-    }
-    if (!split) {
-        // ---- H (prove.go:134,346-389), then the MSM over pk.G1.Z (prove.go:225-227), on this lane ------------
-        if (!preloaded) GA_HIP_CHECK(hipStreamWaitEvent(ctx->work_stream(), ev[2].ev, 0));
-        GA_CHECK(ntt_domain_compute_h<C>(pk->dom, d_h[0], d_h[1], d_h[2]));   // h in d_h[0], bit-reversed like pk.G1.Z
-        GA_CHECK(z_msm<C>(pk, (const char*)d_h[0] + pk->vec[GA_KEY_G1_Z].off * 32, &z_part));
-    }
-    if (!did_k && !h_did_k) {
+    GA_CHECK(helper.join());
+    if (!split) GA_CHECK(h_side<C>(pk, h.d_h, src ? h.landed : nullptr, &h.z_part));
+    if (!did_k && !h.did_k) {
         set_error("prove: the K MSM was claimed by no lane");
         return GA_ERR_STATE;
     }
-    out->krs = add(did_k ? out->krs : k_part_h, z_part);
+    out->krs = add(did_k ? out->krs : h.k_part, h.z_part);
     return GA_OK;
 }
 
@@ -567,21 +594,17 @@ static int fold_pok(const void* poks, uint64_t n, const void* challenge_mont, vo
 // forwards the rows to the chain owners over xGMI), b and c travel to device 0 (hipMemcpyPeerAsync), device 0 finishes h and sends
 // every device its slice; partial sums are added on the host.  With n = 1 this is ga_g16_prove.
 struct MultiShared {
+    const uint32_t n;   // threads that meet at each barrier
     std::mutex mu;
     std::condition_variable cv;
     int arrived[4] = {0, 0, 0, 0};
     bool failed = false;
-    std::string err;
-    uint32_t n = 0;
-    void fail(const char* msg) {
+    void fail() {
         std::lock_guard<std::mutex> g(mu);
-        if (!failed) {
-            failed = true;
-            err = msg;
-        }
+        failed = true;
         cv.notify_all();
     }
-    // all n threads meet here; returns false when some thread failed (everyone then unwinds)
+    // all n threads meet here; returns false when some thread failed (everyone then unwinds, the failed thread reports)
     bool barrier(int k) {
         std::unique_lock<std::mutex> g(mu);
         arrived[k]++;
@@ -591,158 +614,140 @@ struct MultiShared {
     }
 };
 
+// The state of one multi-device proof and the bodies of its threads, all HelperThreads: worker(t) for device t (worker 0 on the
+// calling thread) and h_helper(t) beside it.  A thread that leaves early -- an error code or an exception -- releases both sets of
+// barriers (Release): the others unwind with GA_OK and are joined, the one that failed returns its own code.
 template <class C>
-static int prove_multi(G16Pk* const* pks, uint32_t n, const void* w, const void* a, const void* b, const void* c, uint64_t n_constraints,
-                       uint64_t nb_public, const void* r, const void* s, void* proof_out) {
+struct MultiProof {
     typedef Fe<typename C::FpP> F1;
-    std::vector<G16Partials<C>> parts(n);   // per device; the Z sum is added into krs
-    const uint64_t N = pks[0]->n;
-    // which device runs which chain: a on 0, b on 1 (or 0), c on 2 (or 0)
-    const uint32_t owner[3] = {0, n >= 2 ? 1u : 0u, n >= 3 ? 2u : 0u};
-    const void* src[3] = {a, b, c};
-    static const char* const names[3] = {"h_a", "h_b", "h_c"};
-    void* chain_buf[3] = {nullptr, nullptr, nullptr};   // on the owner's device
-    void* dev0_buf[3] = {nullptr, nullptr, nullptr};     // on device 0
-    std::vector<void*> h_slice(n, nullptr);
-    MultiShared sh, hs;   // sh: the device workers; hs: their H-side helper threads
-    sh.n = n;
-    hs.n = n;
-    const bool sliced = n >= 3;
-    const uint64_t cshare = (n_constraints + n - 1) / n;
-    auto worker = [&](uint32_t t) {
+    G16Pk* const* pks;
+    const uint32_t n;
+    const void* w;
+    const void* src[3];   // the solver's A, B, C
+    const uint64_t n_constraints, nb_public;
+    const uint32_t owner[3] = {0, n >= 2 ? 1u : 0u, n >= 3 ? 2u : 0u};   // which device runs which chain: a on 0, b on 1 (or 0), c on 2 (or 0)
+    const bool sliced = n >= 3;                                          // three or more devices: no PCIe link carries a whole vector
+    const uint64_t cshare = (n_constraints + n - 1) / n;                 // rows of A, B, C per device then
+    void* chain_buf[3] = {nullptr, nullptr, nullptr};                    // on the owner's device
+    void* dev0_buf[3] = {nullptr, nullptr, nullptr};                     // on device 0
+    std::vector<void*> h_slice = std::vector<void*>(n, nullptr);
+    std::vector<G16Partials<C>> parts = std::vector<G16Partials<C>>(n);   // per device; the Z sum is added into krs
+    MultiShared sh{n}, hs{n};                                            // sh: the device workers; hs: their H-side helper threads
+    struct Release {
+        MultiProof& p;
+        bool done = false;
+        ~Release() {
+            if (done) return;
+            p.sh.fail();
+            p.hs.fail();
+        }
+    };
+
+    // The H side of device t, on the context's second lane (own stream and scratch) BESIDE the witness MSMs: uploads, the chain(s)
+    // this device owns, the hop of b / c to device 0.  Sliced: every device uploads rows [t*cshare, ...) of A, B and C over its own
+    // link into a staging buffer and forwards them to the chain owners over xGMI; the owners start when all pieces have landed.
+    int h_helper(uint32_t t) {
+        G16Pk* pk = pks[t];
+        Ctx* ctx = pk->ctx;
+        Release rel{*this};
+        std::lock_guard<std::mutex> l1(ctx->lane_mu[1]);
+        hipStream_t st = ctx->work_stream();
+        if (sliced) {
+            const uint64_t lo = std::min<uint64_t>((uint64_t)t * cshare, n_constraints), hi = std::min<uint64_t>(lo + cshare, n_constraints);
+            void* stage = nullptr;
+            GA_CHECK(ctx->scratch_get("h_stage", 3 * cshare * 32 + 32, &stage));
+            for (int k = 0; k < 3; k++) {
+                char* mine = (char*)stage + (uint64_t)k * cshare * 32;
+                if (hi > lo) {
+                    GA_HIP_CHECK(hipMemcpyAsync(mine, (const char*)src[k] + lo * 32, (hi - lo) * 32, hipMemcpyHostToDevice, st));
+                    GA_HIP_CHECK(hipMemcpyPeerAsync((char*)chain_buf[k] + lo * 32, pks[owner[k]]->ctx->device, mine, ctx->device, (hi - lo) * 32, st));
+                }
+                if (owner[k] == t) GA_CHECK(h_pad(pk, chain_buf[k], n_constraints, st));
+            }
+            GA_HIP_CHECK(hipStreamSynchronize(st));
+            if (!hs.barrier(0)) return GA_OK;   // every device's rows have landed on the chain owners
+        } else {
+            for (int k = 0; k < 3; k++)
+                if (owner[k] == t) GA_CHECK(h_upload(pk, src[k], n_constraints, chain_buf[k], st));
+        }
+        for (int k = 0; k < 3; k++)
+            if (owner[k] == t) {
+                GA_CHECK(ntt_domain_h_chain<C>(pk->dom, chain_buf[k]));
+                if (t != 0) GA_HIP_CHECK(hipMemcpyPeerAsync(dev0_buf[k], pks[0]->ctx->device, chain_buf[k], ctx->device, pk->n * 32, st));
+            }
+        GA_HIP_CHECK(hipStreamSynchronize(st));
+        rel.done = true;
+        return GA_OK;
+    }
+
+    // device 0, once every chain has arrived: h, then every device gets its slice of h[:n-1]
+    int finish_h() {
+        G16Pk* pk = pks[0];
+        Ctx* ctx = pk->ctx;
+        GA_CHECK(ntt_domain_h_combine<C>(pk->dom, dev0_buf[0], dev0_buf[1], dev0_buf[2]));
+        for (uint32_t q = 1; q < n; q++) {
+            const G16Vec& z = pks[q]->vec[GA_KEY_G1_Z];
+            if (z.len) GA_HIP_CHECK(hipMemcpyPeerAsync(h_slice[q], pks[q]->ctx->device, (const char*)dev0_buf[0] + z.off * 32, ctx->device, z.len * 32, ctx->stream));
+        }
+        GA_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        h_slice[0] = (char*)dev0_buf[0] + pk->vec[GA_KEY_G1_Z].off * 32;
+        return GA_OK;
+    }
+
+    int worker(uint32_t t) {
         G16Pk* pk = pks[t];
         Ctx* ctx = pk->ctx;
         SlotLease slot(ctx);
         std::lock_guard<std::mutex> g(ctx->mu);   // one proof at a time per device (icicle.go:821-823)
+        HelperThread helper;                      // (declared before `rel`: the barriers are released before the helper is joined)
+        Release rel{*this};
         ctx->tun.read_env();
-        auto bail = [&](const char* what) {   // releases the workers AND the H-side helpers waiting on their barriers
-            const std::string m = std::string(what) + ": " + get_error();
-            sh.fail(m.c_str());
-            hs.fail(m.c_str());
-        };
-        bool ok = hipSetDevice(ctx->device) == hipSuccess;
-        if (!ok) set_error("hipSetDevice(%d) failed", ctx->device);
         // buffers first, so that peers can address them after barrier 0
-        for (int k = 0; ok && k < 3; k++) {
-            if (owner[k] == t) ok = ctx->scratch_get(slot.name(names[k]).c_str(), N * 32, &chain_buf[k]) == GA_OK;
-            if (t == 0 && ok) ok = ctx->scratch_get(slot.name(names[k]).c_str(), N * 32, &dev0_buf[k]) == GA_OK;
+        for (int k = 0; k < 3; k++) {
+            if (owner[k] == t) GA_CHECK(h_buffer(pk, slot, k, &chain_buf[k]));
+            if (t == 0) GA_CHECK(h_buffer(pk, slot, k, &dev0_buf[k]));
         }
         // a base-range shard receives its slice of h, a window shard all of it
-        if (ok && pk->vec[GA_KEY_G1_Z].len) ok = t == 0 || ctx->scratch_get("h_slice", pk->vec[GA_KEY_G1_Z].len * 32, &h_slice[t]) == GA_OK;
-        if (!ok) bail("multi-device prove: buffers");
-        if (!sh.barrier(0)) return;
-        if (witness_upload(pk, slot, w, nb_public) != GA_OK) {
-            bail("multi-device prove: uploading W");
-            ok = false;
-        }
-        // The H side of this device on a helper thread, on the context's second lane (own stream and scratch), BESIDE the witness
-        // MSMs: uploads, the chain(s) this device owns, the hop of b / c to device 0.  With three or more devices no PCIe link
-        // carries a whole vector: every device uploads rows [t*cshare, ...) of A, B and C over its own link into a staging buffer
-        // and forwards them to the chain owners over xGMI (hipMemcpyPeerAsync); the owners start when all pieces have landed.
-        bool owns = false;
-        for (int k = 0; k < 3; k++) owns = owns || owner[k] == t;
-        int h_rc = GA_OK;
-        std::string h_err;
-        std::thread helper;
-        if (ok && (owns || sliced)) {
-            helper = std::thread([&, t]() {
-                auto hfail = [&](const char* what) {
-                    h_rc = GA_ERR_HIP;
-                    h_err = std::string(what) + ": " + get_error();
-                    hs.fail(h_err.c_str());
-                };
-                if (hipSetDevice(ctx->device) != hipSuccess) {
-                    set_error("hipSetDevice(%d) failed", ctx->device);
-                    return hfail("multi-device prove (H side)");
-                }
-                std::lock_guard<std::mutex> l1(ctx->lane_mu[1]);
-                LaneScope lane(1);
-                hipStream_t st = ctx->work_stream();
-                bool hok = true;
-                if (sliced) {
-                    const uint64_t lo = std::min<uint64_t>((uint64_t)t * cshare, n_constraints), hi = std::min<uint64_t>(lo + cshare, n_constraints);
-                    void* stage = nullptr;
-                    hok = ctx->scratch_get("h_stage", 3 * cshare * 32 + 32, &stage) == GA_OK;
-                    for (int k = 0; hok && k < 3; k++) {
-                        char* mine = (char*)stage + (uint64_t)k * cshare * 32;
-                        if (hi > lo) {
-                            hok = hipMemcpyAsync(mine, (const char*)src[k] + lo * 32, (hi - lo) * 32, hipMemcpyHostToDevice, st) == hipSuccess;
-                            if (hok)
-                                hok = hipMemcpyPeerAsync((char*)chain_buf[k] + lo * 32, pks[owner[k]]->ctx->device, mine, ctx->device, (hi - lo) * 32,
-                                                         st) == hipSuccess;
-                        }
-                        if (hok && owner[k] == t && N > n_constraints)   // computeH pads to the domain size (prove.go:356-359)
-                            hok = hipMemsetAsync((char*)chain_buf[k] + n_constraints * 32, 0, (N - n_constraints) * 32, st) == hipSuccess;
-                    }
-                    if (hok) hok = hipStreamSynchronize(st) == hipSuccess;
-                    if (!hok) {
-                        if (!get_error()[0]) set_error("HIP error while uploading / forwarding the rows of A, B, C");
-                        return hfail("multi-device prove: uploading A, B, C");
-                    }
-                    if (!hs.barrier(0)) return;   // every device's rows have landed on the chain owners
-                } else {
-                    for (int k = 0; hok && k < 3; k++)
-                        if (owner[k] == t) hok = h_upload(pk, src[k], n_constraints, chain_buf[k], st) == GA_OK;
-                    if (!hok) return hfail("multi-device prove: uploading A, B, C");
-                }
-                for (int k = 0; hok && k < 3; k++)
-                    if (owner[k] == t) {
-                        hok = ntt_domain_h_chain<C>(pk->dom, chain_buf[k]) == GA_OK;
-                        if (hok && t != 0)
-                            hok = hipMemcpyPeerAsync(dev0_buf[k], pks[0]->ctx->device, chain_buf[k], ctx->device, N * 32, st) == hipSuccess;
-                    }
-                if (hok) hok = hipStreamSynchronize(st) == hipSuccess;
-                if (!hok) {
-                    if (!get_error()[0]) set_error("HIP error in the computeH chain");
-                    return hfail("multi-device prove: computeH chain");
-                }
-            });
-        }
-        ThreadJoiner joiner{helper};
-        if (ok) {
-            WitnessShared wsh;
-            bool did_k = false;
-            if (hipEventCreateWithFlags(&wsh.w_ev, hipEventDisableTiming) != hipSuccess ||
-                witness_msms<C>(pk, slot, nb_public, wsh, &parts[t], &did_k) != GA_OK) {
-                bail("multi-device prove: witness MSMs");
-                ok = false;
-            }
-        }
-        if (helper.joinable()) helper.join();
-        if (h_rc != GA_OK) {
-            sh.fail(h_err.c_str());
-            ok = false;
-        }
-        if (!sh.barrier(1)) return;
-        if (t == 0) {
-            ok = ntt_domain_h_combine<C>(pk->dom, dev0_buf[0], dev0_buf[1], dev0_buf[2]) == GA_OK;
-            for (uint32_t q = 1; ok && q < n; q++)   // every device gets its slice of h[:n-1]
-                if (pks[q]->vec[GA_KEY_G1_Z].len)
-                    ok = hipMemcpyPeerAsync(h_slice[q], pks[q]->ctx->device, (const char*)dev0_buf[0] + pks[q]->vec[GA_KEY_G1_Z].off * 32, ctx->device,
-                                            pks[q]->vec[GA_KEY_G1_Z].len * 32, ctx->stream) == hipSuccess;
-            if (ok) ok = hipStreamSynchronize(ctx->stream) == hipSuccess;
-            if (!ok) {
-                if (!get_error()[0]) set_error("HIP error while finishing / scattering h");
-                bail("multi-device prove: h");
-            }
-            h_slice[0] = (char*)dev0_buf[0] + pk->vec[GA_KEY_G1_Z].off * 32;
-        }
-        if (!sh.barrier(2)) return;
+        if (t != 0 && pk->vec[GA_KEY_G1_Z].len) GA_CHECK(ctx->scratch_get("h_slice", pk->vec[GA_KEY_G1_Z].len * 32, &h_slice[t]));
+        if (!sh.barrier(0)) return GA_OK;
+        GA_CHECK(witness_upload(pk, slot, w, nb_public));
+        helper.start(ctx, 1, [this, t] { return h_helper(t); });   // (every device has a part: it owns a chain, or the upload is sliced)
+        WitnessShared wsh;
+        bool did_k = false;
+        GA_HIP_CHECK(hipEventCreateWithFlags(&wsh.w_ev, hipEventDisableTiming));
+        GA_CHECK(witness_msms<C>(pk, slot, nb_public, wsh, &parts[t], &did_k));
+        GA_CHECK(helper.join());
+        if (!sh.barrier(1)) return GA_OK;
+        if (t == 0) GA_CHECK(finish_h());
+        if (!sh.barrier(2)) return GA_OK;
         XYZZ<F1> z;
-        if (z_msm<C>(pk, h_slice[t], &z) != GA_OK) bail("multi-device prove: Z MSM");
-        else parts[t].krs = add(parts[t].krs, z);
+        GA_CHECK(z_msm<C>(pk, h_slice[t], &z));
+        parts[t].krs = add(parts[t].krs, z);
         sh.barrier(3);
-    };
-    std::vector<std::thread> threads;
-    for (uint32_t t = 1; t < n; t++) threads.emplace_back(worker, t);
-    worker(0);
-    for (auto& th : threads) th.join();
-    if (sh.failed) {
-        set_error("%s", sh.err.c_str());
-        return GA_ERR_HIP;
+        rel.done = true;
+        return GA_OK;
+    }
+};
+
+template <class C>
+static int prove_multi(G16Pk* const* pks, uint32_t n, const void* w, const void* a, const void* b, const void* c, uint64_t n_constraints,
+                       uint64_t nb_public, const void* r, const void* s, void* proof_out) {
+    MultiProof<C> p{pks, n, w, {a, b, c}, n_constraints, nb_public};
+    {
+        std::vector<HelperThread> workers(n);
+        typename MultiProof<C>::Release rel{p};   // (a worker thread that cannot be started: the ones already waiting are released, then joined)
+        for (uint32_t t = 1; t < n; t++) workers[t].start(pks[t]->ctx, 0, [&p, t] { return p.worker(t); });
+        workers[0].run_here(pks[0]->ctx, 0, [&p] { return p.worker(0); });
+        rel.done = true;
+        int rc = GA_OK;
+        for (uint32_t t = n; t-- > 0;) {   // the failure reported, code and text, is the one of the first device that has one
+            const int rc_t = workers[t].join();
+            if (rc_t != GA_OK) rc = rc_t;
+        }
+        GA_CHECK(rc);
     }
     G16Partials<C> sum;
-    for (const G16Partials<C>& q : parts) {
+    for (const G16Partials<C>& q : p.parts) {
         sum.ar = add(sum.ar, q.ar);
         sum.bs1 = add(sum.bs1, q.bs1);
         sum.krs = add(sum.krs, q.krs);
@@ -1168,11 +1173,7 @@ int ga_g16_lane_stats(ga_ctx* h, uint64_t* out6) try {
     out6[3] = ctx->stat_split;
     out6[4] = out6[5] = 0;
     std::lock_guard<std::mutex> g(ctx->scratch_mu);
-    for (const auto& kv : ctx->scratch) {
-        const size_t at = kv.first.rfind('@');
-        const int lane = at == std::string::npos ? 0 : atoi(kv.first.c_str() + at + 1);
-        out6[lane < 2 ? 4 : 5] += kv.second.second;
-    }
+    for (const auto& kv : ctx->scratch) out6[kv.second.lane < 2 ? 4 : 5] += kv.second.bytes;
     return GA_OK;
 } GA_ABI_CATCH
 
@@ -1257,15 +1258,10 @@ int ga_g16_h_chain_dev(ga_g16_pk* p, void* buf_dev, uint64_t n_constraints) try 
         return GA_ERR_INVALID;
     }
     GA_PK_USE(pk, "ga_g16_h_chain_dev");
-    if (n_constraints > pk->n) {
-        set_error("ga_g16_h_chain_dev: %llu constraints exceed the domain cardinality %llu", (unsigned long long)n_constraints,
-                  (unsigned long long)pk->n);
-        return GA_ERR_INVALID;
-    }
+    GA_CHECK(check_nb_constraints(pk, n_constraints));
     LaneLock g(pk->ctx);
     hipStream_t st = pk->ctx->work_stream();
-    if (pk->n > n_constraints)   // computeH pads to the domain size (prove.go:356-359)
-        GA_HIP_CHECK(hipMemsetAsync((char*)buf_dev + n_constraints * 32, 0, (pk->n - n_constraints) * 32, st));
+    GA_CHECK(h_pad(pk, buf_dev, n_constraints, st));
     GA_DISPATCH_CURVE(pk->curve, GA_CHECK(ntt_domain_h_chain<C>(pk->dom, buf_dev)));
     GA_HIP_CHECK(hipStreamSynchronize(st));
     return GA_OK;
@@ -1334,6 +1330,9 @@ int ga_g16_prove_multi(ga_g16_pk* const* keys, uint32_t n, const void* w, const 
             return GA_ERR_STATE;
         }
     }
+    // the solution's sizes against the key, before any thread starts or anything is launched
+    GA_CHECK(check_nb_constraints(pks[0], n_constraints));
+    for (uint32_t t = 0; t < n; t++) GA_CHECK(check_nb_public(pks[t], nb_public));
     // One multi-device proof at a time per process: every worker thread holds its device's lock while it waits for the others at
     // the barriers, so two calls over the same devices could each hold one lock the other needs (A holds dev0 and waits for its
     // worker on dev1, B holds dev1 and waits for its worker on dev0).  A sharded proof occupies all its devices anyway.

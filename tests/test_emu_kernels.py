@@ -1662,6 +1662,74 @@ def test_emu_groth16_prove_multi(emu_ctx, c, nshards, precompute, logn=7):
     assert np.array_equal(got.Ar, pt(0, exp["Ar"])) and np.array_equal(got.Bs, pt(1, exp["Bs"])) and np.array_equal(got.Krs, pt(0, exp["Krs"]))
 
 
+def _sharded_keys(ctx, inst, nshards):
+    """shard i of nshards of inst's key (plain vectors), each in a context of its own on device 0"""
+    from gnark_amd.device import Context
+    ctxs = [Context(0, lib=ctx.lib) for _ in range(nshards)]
+    return ctxs, [inst.proving_key(cx, precompute=-1, shard=(i, nshards)) for i, cx in enumerate(ctxs)]
+
+
+def test_emu_abi_exception_barrier_groth16_multi(emu_ctx, monkeypatch, c=BN254, logn=6):
+    """the exception barrier covers the THREADS of ga_g16_prove_multi: with three shards (the sliced upload, every chain owner) a
+    std::bad_alloc thrown on the per-device workers -- worker 0 shares the calling thread -- and on their H-side helpers comes back
+    as GA_ERR_NOMEM instead of ending the process, every thread is joined, and afterwards the same keys give the same proof bytes
+    and every context still computes an MSM"""
+    from gnark_amd import synth
+    inst = synth.make_instance(emu_ctx, c.name, logn, 0xFA18, want_dlogs=False)
+    ctxs, pks = _sharded_keys(emu_ctx, inst, 3)
+    try:
+        args = (pks, inst.solution, inst.nb_public, inst.r, inst.s)
+        before = groth16.ProveMulti(*args).raw()
+        monkeypatch.setenv("GA_FAULT_THROW", "ga_g16_prove_multi")
+        with pytest.raises(Exception, match=r"error -3"):
+            groth16.ProveMulti(*args)
+        monkeypatch.delenv("GA_FAULT_THROW")
+        assert np.array_equal(groth16.ProveMulti(*args).raw(), before)
+        for i, cx in enumerate(ctxs):
+            bases, dlogs, scal = _device_inputs(cx, c, 0, 64, 0xE20 + i)
+            got = oracle.jac_to_affine(c.cid, 0, ecc.MultiExp(cx, c.name, 0, bases, scal, n=64))
+            assert np.array_equal(got, _expect_from_dlogs(c, 0, scal.to_host((64, 4)), dlogs.to_host((64, 4))))
+            for b in (bases, dlogs, scal):
+                b.free()
+    finally:
+        monkeypatch.delenv("GA_FAULT_THROW", raising=False)
+        for p in pks:
+            p.FreeGPUResources()
+        for cx in ctxs:
+            cx.close()
+
+
+@pytest.mark.parametrize("nshards", [2, 3])
+def test_emu_groth16_prove_multi_rejects_oversized_solution(emu_ctx, nshards, c=BN254, logn=6):
+    """ga_g16_prove_multi checks the solution's sizes against the key on the calling thread, before any thread starts or anything is
+    launched: n + 1 rows of A, B, C (more than the chain buffers hold) and an nbPublic that disagrees with the key are GA_ERR_INVALID
+    with two shards (whole-vector uploads) and with three (sliced uploads); a valid call right after gives the unsharded proof"""
+    from gnark_amd import synth
+    inst = synth.make_instance(emu_ctx, c.name, logn, 0x0B16 + nshards, want_dlogs=False)
+    sol = inst.solution
+    pk1 = inst.proving_key(emu_ctx, precompute=-1)
+    try:
+        want = groth16.Prove(pk1, sol, inst.nb_public, inst.r, inst.s).raw()
+    finally:
+        pk1.FreeGPUResources()
+    longer = lambda v: np.concatenate([v, v[:1]])
+    too_long = groth16.Solution(sol.W, longer(sol.A), longer(sol.B), longer(sol.C))
+    assert too_long.A.shape[0] == inst.n + 1
+    ctxs, pks = _sharded_keys(emu_ctx, inst, nshards)
+    try:
+        with pytest.raises(Exception, match=r"error -1: .*exceed the domain cardinality"):
+            groth16.ProveMulti(pks, too_long, inst.nb_public, inst.r, inst.s)
+        assert np.array_equal(groth16.ProveMulti(pks, sol, inst.nb_public, inst.r, inst.s).raw(), want)
+        with pytest.raises(Exception, match=r"error -1"):
+            groth16.ProveMulti(pks, sol, inst.nb_public + 1, inst.r, inst.s)
+        assert np.array_equal(groth16.ProveMulti(pks, sol, inst.nb_public, inst.r, inst.s).raw(), want)
+    finally:
+        for p in pks:
+            p.FreeGPUResources()
+        for cx in ctxs:
+            cx.close()
+
+
 @pytest.mark.parametrize("c", CURVES, ids=lambda c: c.name)
 @pytest.mark.parametrize("group", [0, 1], ids=["G1", "G2"])
 def test_emu_msm_table_window_ranges(emu_ctx, c, group):

@@ -204,6 +204,15 @@ def test_abi_exception_barrier_groth16(gpu_ctx, monkeypatch):
     cases.test_emu_abi_exception_barrier_groth16(gpu_ctx, monkeypatch)
 
 
+def test_abi_exception_barrier_groth16_multi(gpu_ctx, monkeypatch):
+    cases.test_emu_abi_exception_barrier_groth16_multi(gpu_ctx, monkeypatch, logn=8)
+
+
+@pytest.mark.parametrize("nshards", [2, 3])
+def test_groth16_prove_multi_rejects_oversized_solution(gpu_ctx, nshards):
+    cases.test_emu_groth16_prove_multi_rejects_oversized_solution(gpu_ctx, nshards, logn=8)
+
+
 def test_raw_msm_2_24_takes_the_fused_sort(gpu_ctx):
     """a raw-bases (no table) BN254 G1 MSM of 2^24 points -- 13 windows x 2^19 buckets, 23 key bits -- runs on the fused sort since
     round 4 (no library sort on any BASELINE path) and equals [sum s_i k_i]G"""
