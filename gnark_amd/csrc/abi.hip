@@ -218,6 +218,17 @@ static uint64_t fixed_base_forced_chunk() {
     return e ? strtoull(e, nullptr, 10) : 0;
 }
 
+// kzg.ToLagrangeG1 (ec_ntt.hip.h; instantiated in ec_ntt_<curve>.hip): powers / out host or device per flags.  One run-time knob,
+// read by the entry point itself like the two above:
+//   GA_EC_NTT_UNIFORM    0: the lanes of every stage are consecutive butterflies of one group (the A/B of tools/to_lagrange_bench.py);
+//                        default 1: from stage 6 on the lanes of a wave share their scalar
+template <class C>
+int ec_ntt_to_lagrange(Ctx* ctx, const void* powers, size_t n, unsigned flags, void* out, int uniform);
+static int ec_ntt_uniform() {
+    const char* e = getenv("GA_EC_NTT_UNIFORM");
+    return e ? atoi(e) != 0 : 1;
+}
+
 // Bring inputs to the device when they are host pointers.
 struct Staged {
     Ctx* ctx;
@@ -514,6 +525,25 @@ int ga_batch_scalar_mul_plan(int curve, size_t n, int* window_bits, int* num_win
     }
     const int forced_c = fixed_base_forced_c();
     GA_DISPATCH_CURVE(curve, return fixed_base_plan_abi<C>(n, forced_c, window_bits, num_windows));
+    return GA_OK;
+} GA_ABI_CATCH
+
+// ---- kzg.ToLagrangeG1 (ec_ntt.hip.h) -----------------------------------------------------------------------
+int ga_kzg_to_lagrange_g1(ga_ctx* h, int curve, const void* powers_affine, size_t n, unsigned flags, void* out_affine) try {
+    GA_ABI_ENTRY();
+    Ctx* c = reinterpret_cast<Ctx*>(h);
+    if (curve != GA_BN254 && curve != GA_BLS12_381) {
+        set_error("ga_kzg_to_lagrange_g1: unknown curve id %d", curve);
+        return GA_ERR_INVALID;
+    }
+    if (n == 0) return GA_OK;
+    if (!c || !powers_affine || !out_affine) {
+        set_error("ga_kzg_to_lagrange_g1: null argument");
+        return GA_ERR_INVALID;
+    }
+    Lock l(c);
+    const int uniform = ec_ntt_uniform();
+    GA_DISPATCH_CURVE(curve, return ec_ntt_to_lagrange<C>(c, powers_affine, n, flags, out_affine, uniform));
     return GA_OK;
 } GA_ABI_CATCH
 

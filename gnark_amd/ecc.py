@@ -92,6 +92,35 @@ def batch_scalar_mul_plan(curve, n: int, lib=None):
     return c.value, nw.value
 
 
+def ToLagrangeG1(ctx: Context, curve, powers, n: int | None = None, out_device: bool = False):
+    """kzg.ToLagrangeG1 (gnark-crypto ecc/<curve>/kzg): powers[i] = [tau^i]G1 -> [l_i(tau)]G1 over the size-n domain, natural order.
+
+    powers : (n, affine_words) uint64 array of G1Affine images or a DeviceBuffer of n points (then n is required); never modified
+    n must be a power of two (at most 2^28 for BN254, 2^32 for BLS12-381).  The points are not validated.
+    Returns an (n, affine_words) array, or with out_device=True a DeviceBuffer of n affine points (the caller frees it) that
+    MultiExp and PrecomputedBases take as they are.
+    """
+    cid = curve_id(curve)
+    wa = affine_words(cid, G1)
+    if not isinstance(powers, (DeviceBuffer, int)):
+        powers = as_u64(powers, wa)
+        n = powers.shape[0]
+    if n is None:
+        raise ValueError("n is required for device-resident points")
+    pp, f = _arg(powers, _lib.BASES_ON_DEVICE)
+    if out_device:
+        buf = ctx.malloc(max(n, 1) * wa * 8)
+        try:
+            ctx.lib.check(ctx.lib.ga_kzg_to_lagrange_g1(ctx.handle, cid, pp, n, f | _lib.RESULT_ON_DEVICE, C.c_void_p(buf.ptr)))
+        except Exception:
+            buf.free()
+            raise
+        return buf
+    out = np.zeros((n, wa), dtype=np.uint64)
+    ctx.lib.check(ctx.lib.ga_kzg_to_lagrange_g1(ctx.handle, cid, pp, n, f, _ptr(out)))
+    return out
+
+
 class PrecomputedBases:
     """Bases pinned on the device together with [2^(c*w)]P for every Pippenger window w (ga_msm_table_*): the GPU analogue of
     keeping `pk.G1.A` etc. resident ("PinToGPU", provingkey.go:37-42) with ICICLE's PrecomputeFactor."""

@@ -414,6 +414,16 @@ func BatchScalarMulPlan(curve Curve, n uint64) (windowBits, windows int, err err
 	return int(c), int(nw), err
 }
 
+// ToLagrangeG1 is kzg.ToLagrangeG1 on the device: powers[i] = [tau^i]G1 (n affine points, n a power of two) -> out[i] = [l_i(tau)]G1
+// over the size-n domain, natural order, in gnark's memory image.  flags: BasesOnDevice for a device input, ResultOnDevice for a
+// device output, which NewTable takes as it is (the pinned pk.KzgLagrange.G1 of the PLONK hooks).  The input is not modified and
+// must not overlap the output; the points are not validated.
+func (c *Context) ToLagrangeG1(curve Curve, powers unsafe.Pointer, n uint64, flags uint, outAffine unsafe.Pointer) error {
+	return call("ga_kzg_to_lagrange_g1", func() C.int {
+		return C.ga_kzg_to_lagrange_g1(c.h, C.int(curve), powers, C.size_t(n), C.uint(flags), outAffine)
+	})
+}
+
 // Table is a pinned base vector with its window multiples (ga_msm_table_*): the KZG SRS of a PLONK key.
 type Table struct {
 	h *C.ga_msm_table

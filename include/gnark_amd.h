@@ -55,7 +55,7 @@ extern "C" {
 #define GA_G2 1
 
 /* flags for ga_msm */
-#define GA_BASES_ON_DEVICE 0x1u        /* `bases` is a device pointer */
+#define GA_BASES_ON_DEVICE 0x1u        /* `bases` (ga_kzg_to_lagrange_g1: `powers_affine`) is a device pointer */
 #define GA_SCALARS_ON_DEVICE 0x2u      /* `scalars` is a device pointer */
 #define GA_TABLE_BATCHED 0x10u         /* ga_msm_table_create: the table will mostly serve ga_msm_table_run_batch (PLONK's grouped
                                          * commitments over the SRS): plan a narrower window -- k bucket sets make the sort keys
@@ -64,7 +64,7 @@ extern "C" {
 #define GA_SCALARS_MONTGOMERY 0x4u     /* scalars are fr.Element images (Montgomery); else canonical LE integers
                                           (ICICLE's AreScalarsMontgomeryForm, icicle.go:861-863,1232) */
 #define GA_RESULT_WINDOW_SUMS 0x8u     /* multi-GPU window sharding: see ga_msm_windows */
-#define GA_RESULT_ON_DEVICE 0x20u      /* ga_batch_scalar_mul: `out_affine` is a device pointer */
+#define GA_RESULT_ON_DEVICE 0x20u      /* ga_batch_scalar_mul, ga_kzg_to_lagrange_g1: `out_affine` is a device pointer */
 #define GA_RESULT_BITREVERSED 0x40u    /* ga_batch_scalar_mul: result i is written at index bitrev(i, log2 n) */
 
 /* NTT direction / ordering, mirroring gnark-crypto fft.Domain.FFT / FFTInverse (prove.go:362-386) */
@@ -141,6 +141,23 @@ int ga_batch_scalar_mul(ga_ctx* ctx, int curve, int group, const void* base_affi
 /* window width / number of windows ga_batch_scalar_mul will use for n scalars: deterministic in (curve, n), the same for both groups;
  * GA_FIXED_BASE_C, when set, is what it reports */
 int ga_batch_scalar_mul_plan(int curve, size_t n, int* window_bits, int* num_windows);
+
+/* ---- kzg.ToLagrangeG1: the SRS in Lagrange form ------------------------------------------------------------
+ * replaces: gnark-crypto's kzg.ToLagrangeG1 (ecc/<curve>/kzg), the step between a ceremony SRS and plonk.Setup(ccs, srs, srsLagrange).
+ * kzg.ToLagrangeG1: powers[i] = [tau^i]G1, i < n  ->  out[i] = [l_i(tau)]G1, natural order, l_i the Lagrange basis of the size-n
+ * domain fft.NewDomain(n) builds (generator = fr_root_of_unity(n)).
+ * out[i] = [1/n] * sum_j [w^(-i*j)] powers[j] -- a linear map, defined for ANY n points of the group, (0,0) = infinity in and out.
+ *   powers : n affine G1 points (gnark's memory image), host, or device with GA_BASES_ON_DEVICE; never modified
+ *   out    : n affine G1 points in gnark's memory image, host, or device with GA_RESULT_ON_DEVICE: usable as `bases` of ga_msm and of
+ *            ga_msm_table_create(..., GA_BASES_ON_DEVICE).  The bytes are bit-identical to gnark's.
+ * `powers` and `out` must not overlap.  The points are NOT validated (gnark does not validate them either): for points off the
+ * curve or outside the subgroup the result is whatever the group law's formulas give.
+ * GA_ERR_INVALID: unknown curve, a null pointer with n > 0, n not a power of two, n above 2^28 (BN254) / 2^32 (BLS12-381), the
+ * two-adicity of r.  n = 0 is GA_OK and touches nothing; n = 1 copies the point.
+ * Device scratch, kept by the context: n extended points (128 B each for BN254, 192 B for BLS12-381), n/2 twiddle scalars (32 B each),
+ * n/2 + 4 words of redo list, and n affine points (64 / 96 B) of staging when `powers` or `out` is on the host.  GA_ERR_NOMEM when
+ * that does not fit (always above n = 2^31); the context stays usable. */
+int ga_kzg_to_lagrange_g1(ga_ctx* ctx, int curve, const void* powers_affine, size_t n, unsigned flags, void* out_affine);
 
 /* ---- MSM over pinned bases with precomputed window multiples ---------------------------------------------
  * (ICICLE's MSMConfig.PrecomputeFactor / precompute-bases, icicle.go:507-525.)  ga_msm_table_create uploads (or takes
