@@ -109,7 +109,8 @@ GA_HD F29<P> f29_add_raw(const F29<P>& a, const F29<P>& b) {
     for (int i = 0; i < F29<P>::NL; i++) r.l[i] = a.l[i] + b.l[i];
     return r;
 }
-// a - b + K*p limb-wise without the carry sweep (b normalized, b < K*p)
+// a - b + K*p limb-wise without the carry sweep (b normalized, and b's top limb below K*p's: before the sweep the top limb cannot
+// wait for what its lower neighbours repay -- the margin of one top-limb unit that tools/lazy_bounds.py asserts); limbs < 3*2^L
 template <int K, class P>
 GA_HD F29<P> f29_sub_raw(const F29<P>& a, const F29<P>& b) {
     F29<P> r;
@@ -241,7 +242,7 @@ GA_HD F29<P> f29_unpack(const Fe<P>& t) {
 template <class P>
 GA_HD F29<P> f29_from_mem(const Fe<P>& x) { return f29_unpack(f29_hat_packed(x)); }
 
-// hat(x) with any value < 2^(32N) -> canonical memory image x * 2^(32N) mod p
+// hat(x) as any normalized value < 2^(NL*L) -> canonical memory image x * 2^(32N) mod p
 template <class P>
 GA_HD_BIG Fe<P> f29_to_mem(const F29<P>& a) {
     typedef Radix<P> R;
@@ -267,7 +268,9 @@ GA_HD_BIG Fe<P> f29_to_mem(const F29<P>& a) {
     return r;
 }
 
-// one step towards [0, p): v - floor(v / 2^BITS) * p   (>= 0; result < 2^BITS + q*(2^BITS - p), i.e. < 4p for v < 2^(BITS+3))
+// one step towards [0, p): v - q*p with q = floor(v / 2^BITS), for any normalized v < 2^(NL*L).  The result is >= 0 and below
+// 2^BITS + q*(2^BITS - p).  It is below 4p only for inputs v < 2^(BITS+3) (q <= 7; all four moduli exceed 8/11 * 2^BITS), which is
+// what every caller passes; a larger v is still reduced correctly but may leave more (tests/field_cases.py case_lazy_reductions).
 template <class P>
 GA_HD F29<P> f29_partial_reduce(const F29<P>& a) {
     typedef Radix<P> R;
@@ -292,8 +295,10 @@ GA_HD F29<P> f29_partial_reduce(const F29<P>& a) {
     return r;
 }
 
-// Barrett step: v - q*p with q = ((v >> (BITS-4)) * MU12) >> 12, q <= floor(v/p) <= q+2  =>  result in [0, 3p)
-// (valid for any normalized v < 2^(NL*L)); used where sums keep doubling (NTT butterflies)
+// Barrett step: v - q*p with q = ((v >> (BITS-4)) * MU12) >> 12, valid for any normalized v < 2^(NL*L).  q is never too large and
+// at most 1 too small: the result is in [0, 1.35 p) for all four fields (below 1.3496 p BN254 Fp/Fr, 1.2607 p BLS12-381 Fp,
+// 1.2152 p BLS12-381 Fr; every top-limb estimate enumerated in tests/field_cases.py reduce_3p_bound).  Its consumers need only [0, 3p) and a
+// result that fits 32N bits -- 3p itself would not for BLS12-381 Fr.  Used where sums keep doubling (NTT butterflies).
 template <class P>
 GA_HD F29<P> f29_reduce_3p(const F29<P>& a) {
     typedef Radix<P> R;
@@ -318,7 +323,7 @@ GA_HD F29<P> f29_reduce_3p(const F29<P>& a) {
     return r;
 }
 
-// exact test v == 0 (mod p) of a lazy value (normalized limbs, any v < 2^(NL*L)): one Barrett step to [0, 3p), then the three
+// exact test v == 0 (mod p) of a lazy value (normalized limbs, any v < 2^(NL*L)): one Barrett step (to below 1.35 p), then the three
 // candidates 0, p, 2p.  Used only where the addition law needs it (the complete variant of the bucket loop, msm_bucket.hip.h).
 template <class P>
 GA_HD bool f29_is_zero_mod_p(const F29<P>& a) {
@@ -334,7 +339,7 @@ GA_HD bool f29_is_zero_mod_p(const F29<P>& a) {
     return (z0 == 0) | (z1 == 0) | (z2 == 0);
 }
 
-// limbs (value < 3p) -> canonical packed words
+// limbs (normalized, value < 3p and < 2^(32N)) -> canonical packed words
 template <class P>
 GA_HD Fe<P> f29_pack_canonical(const F29<P>& v) {
     typedef Radix<P> R;

@@ -18,8 +18,9 @@ G1 = dict(Kx=8, Ky=8, K3=4, Kq=8, Ky3=2)
 G2 = dict(Kx=4, Ky=4, K3=4, Kq=8, Ky3=8, KQ=8, partial_reduce=("X",))
 
 
-def check(curve: str, fp2: bool, verbose=False, init=None):
-    """init: optional upper bounds (X, Y, ZZ, ZZZ) the accumulator may START from besides an affine point (the output of mdbl29)"""
+def check(curve: str, fp2: bool, verbose=False, init=None, exact=False):
+    """exact: return the fixed-point bounds of X, Y, ZZ, ZZZ as integers instead of log2 (tests/field_cases.py lifts operands to them).
+    init: optional upper bounds (X, Y, ZZ, ZZZ) the accumulator may START from besides an affine point (the output of mdbl29)"""
     p, L, NL, bits = CURVES[curve]
     R = 1 << (L * NL)
     unit = 1 << (L * (NL - 1))
@@ -107,6 +108,8 @@ def check(curve: str, fp2: bool, verbose=False, init=None):
         bx, by, bzz, bzzz = nb
     else:
         raise AssertionError("accumulator bounds do not converge")
+    if exact:
+        return {"X": bx, "Y": by, "ZZ": bzz, "ZZZ": bzzz}
     out = {"X": log2(bx), "Y": log2(by), "ZZ": log2(bzz), "ZZZ": log2(bzzz), "P": log2(Pp), "R": log2(Rr), "limit": L * NL}
     if verbose:
         print(curve, "G2" if fp2 else "G1", {a: round(b, 2) for a, b in out.items()})
@@ -118,7 +121,7 @@ ADD_G1 = dict(KP=4, KR=4, K3=4, Kq=8, Kms=8, partial_reduce=())
 ADD_G2 = dict(KP=4, KR=4, K3=4, Kq=8, Kms=16, partial_reduce=("X",))
 
 
-def check_add(curve: str, fp2: bool, verbose=False):
+def check_add(curve: str, fp2: bool, verbose=False, exact=False):
     """Fixed point of the coordinate bounds under a = add29(a, b) when both operands are earlier results (running sums added
     into running sums); every subtraction constant and every Fp2 operand bound of msm_lazy.hip.h::add29 is asserted."""
     p, L, NL, bits = CURVES[curve]
@@ -193,6 +196,8 @@ def check_add(curve: str, fp2: bool, verbose=False):
         bx, by, bzz, bzzz = nb
     else:
         raise AssertionError("bounds of the general addition do not converge")
+    if exact:
+        return {"X": bx, "Y": by, "ZZ": bzz, "ZZZ": bzzz}
     out = {"X": log2(bx), "Y": log2(by), "ZZ": log2(bzz), "ZZZ": log2(bzzz), "P": log2(Pp), "R": log2(Rr), "limit": L * NL}
     if verbose:
         print(curve, "add G2" if fp2 else "add G1", {a: round(b, 2) for a, b in out.items()})
@@ -200,7 +205,7 @@ def check_add(curve: str, fp2: bool, verbose=False):
 
 
 # ---- affine doubling into the lazy accumulator (msm_bucket.hip.h::mdbl29, the complete variant of the bucket loop) ---------------------
-def check_mdbl(curve: str, fp2: bool, verbose=False):
+def check_mdbl(curve: str, fp2: bool, verbose=False, exact=False):
     """acc = 2*(qx, qy) for a table point (qx canonical, qy canonical or negated = 2p - y): every subtraction constant and Fp2
     operand bound of mdbl29, and the outputs must not exceed the accumulator bounds madd29 was analysed with (check())."""
     p, L, NL, bits = CURVES[curve]
@@ -265,6 +270,8 @@ def check_mdbl(curve: str, fp2: bool, verbose=False):
     need(8, X3, "t: X3 below 8p")
     t = S + 8 * p
     Y3 = mulsub(Kms, M, t, W, qy)
+    if exact:
+        return {"X": X3, "Y": Y3, "ZZ": V, "ZZZ": W}
     out = {"X": log2(X3), "Y": log2(Y3), "ZZ": log2(V), "ZZZ": log2(W)}
     # the mixed additions that follow start from these values: every assertion of check() must hold from there too
     acc = check(curve, fp2, init=(X3, Y3, V, W))
@@ -275,7 +282,7 @@ def check_mdbl(curve: str, fp2: bool, verbose=False):
 
 
 # ---- repeated doubling of a general XYZZ point (msm_lazy.hip.h::dbl29, the window-table build) ----------------------------------------
-def check_dbl(curve: str, fp2: bool, verbose=False):
+def check_dbl(curve: str, fp2: bool, verbose=False, exact=False):
     """fixed point of the coordinate bounds under a = dbl29(a), starting from an affine point with canonical coordinates"""
     p, L, NL, bits = CURVES[curve]
     R = 1 << (L * NL)
@@ -349,6 +356,8 @@ def check_dbl(curve: str, fp2: bool, verbose=False):
         bx, by, bzz, bzzz = nb
     else:
         raise AssertionError("bounds of the repeated doubling do not converge")
+    if exact:
+        return {"X": bx, "Y": by, "ZZ": bzz, "ZZZ": bzzz}
     out = {"X": log2(bx), "Y": log2(by), "ZZ": log2(bzz), "ZZZ": log2(bzzz), "limit": L * NL}
     if verbose:
         print(curve, "dbl G2" if fp2 else "dbl G1", {a: round(b, 2) for a, b in out.items()})
