@@ -48,7 +48,8 @@ struct NttPass {
     int s_lo, K, lc;
 };
 
-// global element index of local slot l of tile `tile`
+// global element index of local slot l of tile `tile`; requires lc <= s_lo (a row of 2^lc elements lies below the pass's first
+// stage: the shifts by s_lo - lc are undefined otherwise) and lc + K <= lg_tile -- ntt_plan's passes satisfy both
 __device__ __forceinline__ uint64_t ntt_gidx(uint32_t l, uint64_t tile, int lg_tile, int s_lo, int K, int lc) {
     uint32_t col = l & ((1u << lc) - 1);
     uint32_t mid = (l >> lc) & ((1u << K) - 1);
@@ -439,10 +440,15 @@ struct Domain {
 };
 
 // Passes of a size-2^logn transform, ascending stage order.  The first pass owns the contiguous low stages (up to a whole tile),
-// every further pass K strided stages over rows of 2^lc contiguous elements, lc = min(3, NTT_LG_TILE - K) (256-byte rows, 128-byte
-// ones for K = 8).  Among the splits with the fewest passes the one with the fewest ODD stage counts wins (an odd count ends
-// with a radix-2 round: a whole LDS round trip and barrier for one stage), then the most balanced one, then the larger first pass.
-// GA_NTT_PLAN="8,8,8" (read when a domain is created) forces a split -- experiments only.
+// every further pass K strided stages over rows of 2^lc contiguous elements, lc = min(3, NTT_LG_TILE - K, s_lo) (256-byte rows,
+// 128-byte ones for K = 8; a row lies below the pass's first stage, ntt_gidx splits the element index at s_lo - lc >= 0, so a pass
+// that starts at stage 1 or 2 gets narrower rows -- no default plan has one).  Among the splits with the fewest passes the one with
+// the fewest ODD stage counts wins (an odd count ends with a radix-2 round: a whole LDS round trip and barrier for one stage), then
+// the most balanced one, then the larger first pass.
+// GA_NTT_PLAN="8,8,8" (read when a domain is created) forces a split -- experiments only.  It is taken when every stage count is at
+// least 1, the first at most NTT_LG_TILE, the others at most NTT_LG_TILE - 2, and they add up to logn; anything else is ignored
+// and the domain gets the default plan.  Every plan returned, forced or not, satisfies for each pass: s_lo = the stages below it,
+// 1 <= K, lc + K <= NTT_LG_TILE, and lc = 0 for the first pass, 0 <= lc <= min(3, s_lo) for the others.
 inline std::vector<NttPass> ntt_plan(int logn) {
     std::vector<NttPass> v;
     if (logn == 0) return v;
@@ -453,6 +459,7 @@ inline std::vector<NttPass> ntt_plan(int logn) {
         for (size_t p = 0; p < ks.size(); p++) {
             int lc = 0;
             if (p > 0) lc = NTT_LG_TILE - ks[p] < LCMAX ? NTT_LG_TILE - ks[p] : LCMAX;
+            if (lc > s) lc = s;   // (forced plans only: the default ones have s >= 6)
             out.push_back({s, ks[p], lc});
             s += ks[p];
         }

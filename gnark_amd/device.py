@@ -49,6 +49,7 @@ class Context:
         self.lib.check(self.lib.ga_ctx_create(device, C.byref(h)))
         self.handle = h
         self.device = device
+        self.profiling = False
 
     def close(self):
         if self.handle:
@@ -92,6 +93,7 @@ class Context:
     # profiling (ICICLE_STEP_PROFILE analogue)
     def profile(self, on: bool):
         self.lib.check(self.lib.ga_profile_enable(self.handle, 1 if on else 0))
+        self.profiling = bool(on)
 
     def profile_reset(self):
         self.lib.check(self.lib.ga_profile_reset(self.handle))

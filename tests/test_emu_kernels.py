@@ -1,5 +1,6 @@
 """Kernel-logic checks of the product sources under the functional HIP emulation (tests/emu), against the
 big-integer oracle.  These run on CPU (`-m "not gpu"`); the same cases run on the real GPU in test_gpu_*.py."""
+import itertools
 import os
 
 import numpy as np
@@ -51,25 +52,197 @@ def test_emu_fft_multi_pass(emu_ctx, c):
         d.close()
 
 
-@pytest.mark.parametrize("c", CURVES, ids=lambda c: c.name)
-@pytest.mark.parametrize("logn", [2, 4, 6, 7, 9, 11, 13, 14])
-def test_emu_fft_pass_shapes_vs_c_oracle(emu_ctx, c, logn):
-    """every pass shape of the radix-4 kernel -- even / odd stage counts (the radix-2 tail), one, two and three passes, the
-    natural -> bit-reversed transform on Cooley-Tukey butterflies with block-indexed twiddles (ntt.hip.h) -- element for element
-    against the C oracle's radix-2 transform, all eight mode combinations"""
-    n = 1 << logn
-    rng = np.random.default_rng(900 + logn)
-    a = fr_to_arr(c, [int.from_bytes(rng.bytes(40), "little") % c.r for _ in range(n)])
-    d = fft.Domain(emu_ctx, c.name, n)
+# ---- NTT pass shapes: which plan ran, default plans, forced plans (GA_NTT_PLAN) --------------------------------------------------
+# (inverse, decimation, on_coset): the eight modes of ga_fft
+FFT_MODES = [(inv, dec, coset) for dec in (pyref.DIF, pyref.DIT) for coset in (False, True) for inv in (0, 1)]
+# the three transforms computeH is made of: the forward DIT coset transform runs over the coset twiddle table and scales nothing,
+# the inverse DIF ones scale in their last pass (the coset one by a power table read at bit-reversed indices)
+FFT_H_MODES = [(0, pyref.DIT, True), (1, pyref.DIF, False), (1, pyref.DIF, True)]
+FFT_SHAPE_LOGN = [2, 4, 6, 7, 8, 9, 11, 13, 14, 15]
+
+
+def _count_ntt_passes(ctx, run):
+    """run() under the stage profile; returns (its result, the number of NTT pass launches it made).  ntt_run records one
+    "ntt_pass_dit" / "ntt_pass_dif" stage per launch of the pass kernel, so the count is the length of the plan the domain got: a
+    GA_NTT_PLAN the planner refused (wrong sum, a stage count out of range) shows up as the default plan's count."""
+    was_on = ctx.profiling
+    ctx.profile(True)
     try:
-        for dec in (pyref.DIF, pyref.DIT):
-            for coset in (False, True):
-                for inv in (False, True):
-                    want = oracle.fft(c.cid, a, 1 if inv else 0, dec, coset, nthreads=2)
-                    got = (d.FFTInverse if inv else d.FFT)(a, dec, coset)
-                    assert np.array_equal(got, want), (logn, dec, coset, inv)
+        ctx.profile_reset()
+        out = run()
+        names = [name for name, _ in ctx.profile_read()]
+    finally:
+        ctx.profile_reset()
+        ctx.profile(was_on)
+    return out, sum(name in ("ntt_pass_dit", "ntt_pass_dif") for name in names)
+
+
+def _default_ntt_plan(logn):
+    """ntt_plan's default split, restated: one pass up to 2^10; above it the fewest passes with a first pass of at most 10 stages and
+    upper passes of at most 7, and among those the fewest odd stage counts, then the largest smallest pass, then the larger first
+    pass (the first one found in ascending enumeration wins a full tie).  The device reports only the number of launches, so the
+    plans the docstrings below name are checked against this copy."""
+    if logn <= 10:
+        return [logn] if logn else []
+    npass = 1 + (logn - 10 + 6) // 7
+    best, best_key = None, None
+    for ks in itertools.product(range(1, 11), *([range(1, 8)] * (npass - 1))):
+        if sum(ks) != logn:
+            continue
+        key = (-sum(k & 1 for k in ks), min(ks), ks[0])
+        if best is None or key > best_key:
+            best, best_key = list(ks), key
+    return best
+
+
+def _default_ntt_passes(logn):
+    return len(_default_ntt_plan(logn))
+
+
+def test_default_ntt_plans_named_in_this_file():
+    """the plans the docstrings of the pass-shape cases name are the ones the planner's rule gives"""
+    want = {4: [4], 7: [7], 8: [8], 9: [9], 10: [10], 11: [6, 5], 12: [6, 6], 13: [7, 6], 14: [8, 6], 15: [8, 7], 17: [10, 7],
+            18: [6, 6, 6], 19: [7, 6, 6], 21: [9, 6, 6], 23: [10, 6, 7]}
+    assert {logn: _default_ntt_plan(logn) for logn in want} == want
+
+
+def _forced_ntt_passes(plan, logn):
+    """passes of a GA_NTT_PLAN string, after checking it against what ntt_plan accepts (the count alone cannot tell a refused
+    two-pass plan from the default two-pass one)"""
+    ks = [int(k) for k in plan.split(",")]
+    assert sum(ks) == logn and 1 <= ks[0] <= 10 and all(1 <= k <= 8 for k in ks[1:]), plan
+    return len(ks)
+
+
+def _uniform_fr(c, n, rng):
+    """n uniform residues mod r (320 random bits reduced), as Montgomery images"""
+    return fr_to_arr(c, [int.from_bytes(rng.bytes(40), "little") % c.r for _ in range(n)])
+
+
+def _uniform_fr_np(c, n, rng):
+    """the same distribution for sizes at which a Python loop over the elements costs more than the transform: integers of r's bit
+    length, redrawn until below r (a uniform Montgomery image is a uniform residue)"""
+    rl = [np.uint64(w) for w in pyref.to_limbs(c.r, 4)]
+    top = np.uint64((1 << (c.r.bit_length() - 192)) - 1)
+    a = np.empty((n, 4), dtype=np.uint64)
+    todo = np.arange(n)
+    while todo.size:
+        x = rng.integers(0, 1 << 64, size=(todo.size, 4), dtype=np.uint64)
+        x[:, 3] &= top
+        lt, eq = np.zeros(todo.size, dtype=bool), np.ones(todo.size, dtype=bool)
+        for k in (3, 2, 1, 0):
+            lt |= eq & (x[:, k] < rl[k])
+            eq &= x[:, k] == rl[k]
+        a[todo] = x
+        todo = todo[~lt]
+    top_first = a[np.lexsort((a[:, 0], a[:, 1], a[:, 2], a[:, 3]))[-1]]   # the largest row, as an integer: every row is below r
+    assert sum(int(w) << (64 * k) for k, w in enumerate(top_first)) < c.r
+    return a
+
+
+_fft_reference_cache = {}
+
+
+def _fft_reference(c, logn):
+    """inputs and C-oracle results shared by the pass-shape cases of one (curve, size), computed once and never written to: a vector
+    with its eight transforms, and computeH of m = n - 3 constraints for C = A o B and for a random C (the quotient map is a
+    formula: any C is a valid input)"""
+    key = (c.name, logn)
+    if key not in _fft_reference_cache:
+        n = 1 << logn
+        rng = np.random.default_rng(900 + logn)
+        a = _uniform_fr(c, n, rng)
+        want = {m: oracle.fft(c.cid, a, m[0], m[1], m[2], nthreads=2) for m in FFT_MODES}
+        A, B, Cr = (_uniform_fr(c, n - 3, rng) for _ in range(3))
+        h = [(A, B, Cc, oracle.compute_h(c.cid, A, B, Cc, n, nthreads=2)) for Cc in (oracle.fr_mul(c.cid, A, B), Cr)]
+        for x in [a, A, B] + list(want.values()) + [y for t in h for y in t[2:]]:
+            x.setflags(write=False)
+        _fft_reference_cache[key] = (a, want, h)
+    return _fft_reference_cache[key]
+
+
+def _check_pass_shapes(ctx, c, logn, npass):
+    """a fresh domain of 2^logn (it takes whatever plan the environment gives it now): all eight transforms and computeH twice,
+    element for element against the C oracle, each call with the expected number of pass launches"""
+    a, want, h = _fft_reference(c, logn)
+    d = fft.Domain(ctx, c.name, 1 << logn)
+    try:
+        for m in FFT_MODES:
+            inv, dec, coset = m
+            got, k = _count_ntt_passes(ctx, lambda: (d.FFTInverse if inv else d.FFT)(a, dec, coset))
+            assert k == npass, (logn, m, k)
+            assert np.array_equal(got, want[m]), (logn, m)
+        for i, (A, B, Cc, want_h) in enumerate(h):
+            # three chains of an unscaled inverse DIF and a coset-table DIT transform each, then the scaling inverse coset DIF
+            got, k = _count_ntt_passes(ctx, lambda: d.compute_h(A, B, Cc))
+            assert k == 7 * npass, (logn, "compute_h", i, k)
+            assert np.array_equal(got, want_h), (logn, "compute_h", i)
     finally:
         d.close()
+
+
+@pytest.mark.parametrize("c", CURVES, ids=lambda c: c.name)
+@pytest.mark.parametrize("logn", FFT_SHAPE_LOGN)
+def test_emu_fft_pass_shapes_vs_c_oracle(emu_ctx, c, logn):
+    """every pass shape of the radix-4 kernel that a default plan below 2^16 has -- even / odd stage counts (the radix-2 round),
+    sub-tile sizes, a first pass of 6, 7, 8 stages under an upper pass of 5, 6, 7 (2^11: 6,5 -- every round wave-local; 2^13: 7,6;
+    2^14: 8,6; 2^15: 8,7), the natural -> bit-reversed transform on Cooley-Tukey butterflies with block-indexed twiddles (ntt.hip.h)
+    -- element for element against the C oracle's radix-2 transform, all eight mode combinations, then computeH (the unscaled
+    chain passes and the coset-table pass) for C = A o B and for a random C; every call with the plan's number of launches"""
+    _check_pass_shapes(emu_ctx, c, logn, _default_ntt_passes(logn))
+
+
+@pytest.mark.parametrize("logn,modes", [(19, FFT_MODES), (21, FFT_H_MODES)], ids=["2^19", "2^21"])
+def test_emu_fft_large_default_plans(emu_ctx, logn, modes, c=BN254):
+    """the default three-pass plans with an odd stage count (2^19: 7,6,6 -- a first pass of 7 stages; 2^21: 9,6,6 -- one of 9;
+    2^23: 10,6,7 -- upper passes of 6 and of 7 stages in one transform, on the device only) on uniform residues against the C oracle
+    on 16 threads: all eight modes at 2^19, above it the three transforms computeH uses.  (Three 7-stage passes, or 9 stages under
+    7-stage upper passes, are no default plan of any size below 2^25: the planner avoids odd counts.)"""
+    assert len(_default_ntt_plan(logn)) == 3
+    n = 1 << logn
+    a = _uniform_fr_np(c, n, np.random.default_rng(900 + logn))
+    d = fft.Domain(emu_ctx, c.name, n)
+    try:
+        for m in modes:
+            inv, dec, coset = m
+            want = oracle.fft(c.cid, a, inv, dec, coset, nthreads=16)
+            got, k = _count_ntt_passes(emu_ctx, lambda: (d.FFTInverse if inv else d.FFT)(a, dec, coset))
+            assert k == 3, (logn, m, k)
+            assert np.array_equal(got, want), (logn, m)
+    finally:
+        d.close()
+
+
+# GA_NTT_PLAN at 2^11: a first pass of 1 .. 10 stages on a full tile, an upper pass of 1 .. 8 stages, once each; the first two put
+# an upper pass on stages below its row width (ntt_plan narrows the rows: lc <= s_lo); then three passes, 128-byte rows (K = 8) high
+# up, and eleven launches of a lone radix-2 round
+FORCED_PLANS = ["1,8,2", "2,8,1", "3,8", "4,7", "5,6", "6,5", "7,4", "8,3", "9,2", "10,1", "5,4,4", "3,2,8", "1,1,1,1,1,1,1,1,1,1,1"]
+FORCED_PLAN_CASES = [(BN254, p) for p in FORCED_PLANS] + [(BLS12_381, p) for p in ("6,5", "4,7", "3,8", "9,2")]
+# the plans whose wave-local / direct classification differs most from the default ones', under the other knob sets of
+# device test of the wave-local rounds as well (the default set is FORCED_PLAN_CASES')
+NTT_KNOBS = {"default": {}, "no-direct": {"GA_NTT_DIRECT": "0"}, "round3": {"GA_NTT_WAVE_LOCAL": "0", "GA_NTT_DIRECT": "0"}}
+FORCED_PLAN_KNOB_CASES = [(p, k) for p in ("6,5", "7,4", "3,8") for k in ("no-direct", "round3")]
+
+
+@pytest.mark.parametrize("c,plan", FORCED_PLAN_CASES, ids=lambda v: getattr(v, "name", v))
+def test_emu_fft_forced_plans(emu_ctx, monkeypatch, c, plan, knobs="default"):
+    """every pass shape (first / upper, K, lc, s_lo) the planner's knob can produce, at the smallest sizes that have an upper pass
+    under a full tile (2^11, 2^13): the kernel derives the round list, which rounds stay inside a wave and which go straight to HBM
+    from the shape at run time.  All eight modes and computeH against the C oracle, with the forced plan's launch count."""
+    logn = sum(int(k) for k in plan.split(","))
+    npass = _forced_ntt_passes(plan, logn)
+    for k, v in NTT_KNOBS[knobs].items():
+        monkeypatch.setenv(k, v)
+    monkeypatch.setenv("GA_NTT_PLAN", plan)   # read by ntt_plan when the domain is created
+    try:
+        _check_pass_shapes(emu_ctx, c, logn, npass)
+    finally:
+        monkeypatch.delenv("GA_NTT_PLAN")     # a later domain of this process plans normally
+
+
+@pytest.mark.parametrize("plan,knobs", FORCED_PLAN_KNOB_CASES)
+def test_emu_fft_forced_plans_knobs(emu_ctx, monkeypatch, plan, knobs):
+    test_emu_fft_forced_plans(emu_ctx, monkeypatch, BN254, plan, knobs)
 
 
 @pytest.mark.parametrize("knobs", [{}, {"GA_NTT_DIRECT": "0"}, {"GA_NTT_WAVE_LOCAL": "0"}, {"GA_NTT_WAVE_LOCAL": "0", "GA_NTT_DIRECT": "0"}],
@@ -78,8 +251,10 @@ def test_emu_fft_pass_shapes_vs_c_oracle(emu_ctx, c, logn):
 def test_emu_fft_wave_local_rounds(emu_ctx, monkeypatch, logn, knobs):
     """round 4's pass structure on full 1024-slot tiles: rounds below slot bit 8 exchange inside a wave (no workgroup barrier),
     bits 8/9 form one radix-4 round behind the only __syncthreads, first / last rounds move quads straight between registers and
-    HBM -- every plan shape the 2^24 transforms use (10 stages alone, 10+2, 10+7, 10+8 / 9+9 with a single-stage round at slot
-    bit 7 or 8), each of the two A/B knobs off as well, against the C oracle's radix-2 transform in all eight modes."""
+    HBM.  The plans these sizes take: 10 stages alone (2^10), 6,6 (2^12), 10,7 (2^17: a single-stage round at slot bit 7 of the
+    upper pass) and 6,6,6 (2^18) -- so upper passes of 6 and 7 stages on 256-byte rows; the other shapes are
+    test_emu_fft_forced_plans'.  Each of the two A/B knobs off as well, against the C oracle's radix-2 transform in all eight
+    modes, each with the plan's number of launches."""
     for k, v in knobs.items():
         monkeypatch.setenv(k, v)
     c = BN254
@@ -93,7 +268,8 @@ def test_emu_fft_wave_local_rounds(emu_ctx, monkeypatch, logn, knobs):
             for coset in (False, True):
                 for inv in (False, True):
                     want = oracle.fft(c.cid, a, 1 if inv else 0, dec, coset, nthreads=4)
-                    got = (d.FFTInverse if inv else d.FFT)(a, dec, coset)
+                    got, npass = _count_ntt_passes(emu_ctx, lambda: (d.FFTInverse if inv else d.FFT)(a, dec, coset))
+                    assert npass == {10: 1, 12: 2, 17: 2, 18: 3}[logn], (logn, dec, coset, inv, npass)
                     assert np.array_equal(got, want), (logn, dec, coset, inv)
     finally:
         d.close()
@@ -492,6 +668,26 @@ def test_emu_plonk_quotient(emu_ctx, c, n, nb_bsb, seed=11):
     finally:
         d0.close()
         d1.close()
+
+
+@pytest.mark.parametrize("c", CURVES, ids=lambda c: c.name)
+def test_emu_plonk_quotient_forced_upper_pass(emu_ctx, monkeypatch, c):
+    """the quotient of 1024 gates (one BSB22 commitment) with the 2^12 domain split 7,5 by GA_NTT_PLAN: its coset evaluations read
+    the canonical polynomials out of place in their first pass and run over one twiddle table per coset, here through an upper pass
+    whose rounds are all wave-local (5 stages on slot bits 3..7).  The variable is process-wide, but 7 + 5 is not 10: the small
+    domain keeps its default single pass."""
+    monkeypatch.setenv("GA_NTT_PLAN", "7,5")
+    try:
+        for logn, npass in ((10, 1), (12, _forced_ntt_passes("7,5", 12))):
+            d = fft.Domain(emu_ctx, c.name, 1 << logn)
+            try:
+                z = np.zeros((1 << logn, 4), dtype=np.uint64)
+                assert _count_ntt_passes(emu_ctx, lambda: d.FFT(z, pyref.DIT))[1] == npass, logn
+            finally:
+                d.close()
+        test_emu_plonk_quotient(emu_ctx, c, 1024, 1)
+    finally:
+        monkeypatch.delenv("GA_NTT_PLAN")
 
 
 def test_emu_plonk_null_arguments(emu_ctx):

@@ -34,6 +34,32 @@ def test_fft_wave_local_rounds(gpu_ctx, monkeypatch, logn, knobs):
 
 
 @pytest.mark.parametrize("c", CURVES, ids=lambda c: c.name)
+@pytest.mark.parametrize("logn", [4, 7, 8, 9, 11, 13, 14, 15])
+def test_fft_pass_shapes_vs_c_oracle(gpu_ctx, c, logn):
+    """the default plans no other device test takes: sub-tile passes of 4, 7, 8, 9 stages, 6,5 (2^11: an upper pass with no workgroup
+    barrier between its load and its store), 7,6 (2^13), 8,6 (2^14), 8,7 (2^15) -- all eight modes and computeH, both curves"""
+    cases.test_emu_fft_pass_shapes_vs_c_oracle(gpu_ctx, c, logn)
+
+
+@pytest.mark.parametrize("logn,modes", [(19, cases.FFT_MODES), (21, cases.FFT_H_MODES), (23, cases.FFT_H_MODES)], ids=["2^19", "2^21", "2^23"])
+def test_fft_large_default_plans(gpu_ctx, logn, modes):
+    """7,6,6 / 9,6,6 / 10,6,7: a first pass of 7 and of 9 stages under 6-stage upper passes, a 6,7 upper pair under a whole tile"""
+    cases.test_emu_fft_large_default_plans(gpu_ctx, logn, modes)
+
+
+@pytest.mark.parametrize("c,plan", cases.FORCED_PLAN_CASES, ids=lambda v: getattr(v, "name", v))
+def test_fft_forced_plans(gpu_ctx, monkeypatch, c, plan):
+    """what the emulation cannot show: that hipcc's code for the wave-local exchanges (a compiler fence and a wave barrier, no
+    s_barrier) and the slot ownership of a 64-lane wave hold for every (K, lc, s_lo) the kernel can be launched with"""
+    cases.test_emu_fft_forced_plans(gpu_ctx, monkeypatch, c, plan)
+
+
+@pytest.mark.parametrize("plan,knobs", cases.FORCED_PLAN_KNOB_CASES)
+def test_fft_forced_plans_knobs(gpu_ctx, monkeypatch, plan, knobs):
+    cases.test_emu_fft_forced_plans_knobs(gpu_ctx, monkeypatch, plan, knobs)
+
+
+@pytest.mark.parametrize("c", CURVES, ids=lambda c: c.name)
 def test_compute_h_small(gpu_ctx, c):
     cases.test_emu_compute_h(gpu_ctx, c)
 
@@ -450,6 +476,11 @@ def test_groth16_bsb22_synthetic_2_14_vs_oracle(gpu_ctx, c):
 @pytest.mark.parametrize("n,nb_bsb", [(4, 0), (8, 1), (64, 2), (1024, 1)])
 def test_plonk_quotient_vs_oracle(gpu_ctx, c, n, nb_bsb):
     cases.test_emu_plonk_quotient(gpu_ctx, c, n, nb_bsb, seed=77 + n)
+
+
+@pytest.mark.parametrize("c", CURVES, ids=lambda c: c.name)
+def test_plonk_quotient_forced_upper_pass(gpu_ctx, monkeypatch, c):
+    cases.test_emu_plonk_quotient_forced_upper_pass(gpu_ctx, monkeypatch, c)
 
 
 def test_plonk_null_arguments(gpu_ctx):
