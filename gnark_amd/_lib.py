@@ -16,6 +16,7 @@ BN254, BLS12_381 = 0, 1
 G1, G2 = 0, 1
 BASES_ON_DEVICE, SCALARS_ON_DEVICE, SCALARS_MONTGOMERY, TABLE_BATCHED = 0x1, 0x2, 0x4, 0x10
 RESULT_ON_DEVICE, RESULT_BITREVERSED = 0x20, 0x40
+SCALE_EACH, SCALE_ONE, SCALE_POWERS = 0, 1, 2
 FFT_FORWARD, FFT_INVERSE = 0, 1
 DIF, DIT = 0, 1
 
@@ -79,6 +80,7 @@ _PROTOS = {
     "ga_batch_scalar_mul": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_size_t, C.c_uint, _P]),
     "ga_batch_scalar_mul_plan": (C.c_int, [C.c_int, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ga_kzg_to_lagrange_g1": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.c_uint, _P]),
+    "ga_scale_points": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_size_t, C.c_int, _P, C.c_uint64, C.c_uint, _P, C.POINTER(C.c_uint64)]),
     "ga_msm_table_create": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_size_t, C.c_uint, C.POINTER(_P)]),
     "ga_msm_table_destroy": (None, [_P]),
     "ga_msm_table_run": (C.c_int, [_P, _P, C.c_uint, _P]),

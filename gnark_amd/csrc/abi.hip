@@ -229,6 +229,22 @@ static int ec_ntt_uniform() {
     return e ? atoi(e) != 0 : 1;
 }
 
+// per-point scalar multiplication (scale_points.hip.h; instantiated in scale_points_<curve>_g<k>.hip).  Two run-time knobs, read by the
+// entry point itself like the ones above:
+//   GA_SCALE_WINDOW      0: the plain double-and-add ladder (the A/B of tools/scale_points_bench.py); default 1: signed 4-bit windows
+//   GA_SCALE_CHUNK       points per pass (0 = 2^20, at most 2^30; tests force a small chunk)
+template <class C, int G>
+int scale_points_run(Ctx* ctx, const void* points, size_t n, int mode, const void* scalars, uint64_t first, unsigned flags, void* out,
+                     uint64_t* redone, int windowed, uint64_t forced_chunk);
+static int scale_windowed() {
+    const char* e = getenv("GA_SCALE_WINDOW");
+    return e ? atoi(e) != 0 : 1;
+}
+static uint64_t scale_forced_chunk() {
+    const char* e = getenv("GA_SCALE_CHUNK");
+    return e ? strtoull(e, nullptr, 10) : 0;
+}
+
 // Bring inputs to the device when they are host pointers.
 struct Staged {
     Ctx* ctx;
@@ -544,6 +560,47 @@ int ga_kzg_to_lagrange_g1(ga_ctx* h, int curve, const void* powers_affine, size_
     Lock l(c);
     const int uniform = ec_ntt_uniform();
     GA_DISPATCH_CURVE(curve, return ec_ntt_to_lagrange<C>(c, powers_affine, n, flags, out_affine, uniform));
+    return GA_OK;
+} GA_ABI_CATCH
+
+// ---- per-point scalar multiplication (scale_points.hip.h) ---------------------------------------------------
+int ga_scale_points(ga_ctx* h, int curve, int group, const void* points_affine, size_t n, int mode, const void* scalars, uint64_t first,
+                    unsigned flags, void* out_affine, uint64_t* redone) try {
+    GA_ABI_ENTRY();
+    Ctx* c = reinterpret_cast<Ctx*>(h);
+    if ((curve != GA_BN254 && curve != GA_BLS12_381) || (group != GA_G1 && group != GA_G2)) {
+        set_error("ga_scale_points: unknown curve id %d or group id %d", curve, group);
+        return GA_ERR_INVALID;
+    }
+    if (mode != GA_SCALE_EACH && mode != GA_SCALE_ONE && mode != GA_SCALE_POWERS) {
+        set_error("ga_scale_points: unknown mode %d", mode);
+        return GA_ERR_INVALID;
+    }
+    if (first != 0 && mode != GA_SCALE_POWERS) {
+        set_error("ga_scale_points: first = %llu outside GA_SCALE_POWERS", (unsigned long long)first);
+        return GA_ERR_INVALID;
+    }
+    if ((flags & GA_SCALARS_ON_DEVICE) && mode != GA_SCALE_EACH) {
+        set_error("ga_scale_points: GA_SCALARS_ON_DEVICE outside GA_SCALE_EACH (one or two scalars are read on the host)");
+        return GA_ERR_INVALID;
+    }
+    if ((uint64_t)n > (1ull << 32) || (n > 0 && first > UINT64_MAX - (uint64_t)n + 1)) {
+        set_error("ga_scale_points: n = %zu above 2^32, or first + n above 2^64", n);
+        return GA_ERR_INVALID;
+    }
+    if (n == 0) {
+        if (redone) *redone = 0;
+        return GA_OK;
+    }
+    if (!c || !points_affine || !scalars || !out_affine) {
+        set_error("ga_scale_points: null argument");
+        return GA_ERR_INVALID;
+    }
+    Lock l(c);
+    const int windowed = scale_windowed();
+    const uint64_t forced_chunk = scale_forced_chunk();
+    GA_DISPATCH_CURVE(curve, GA_DISPATCH_GROUP(group, return (scale_points_run<C, G>(c, points_affine, n, mode, scalars, first, flags, out_affine, redone,
+                                                                                    windowed, forced_chunk))));
     return GA_OK;
 } GA_ABI_CATCH
 

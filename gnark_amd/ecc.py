@@ -121,6 +121,75 @@ def ToLagrangeG1(ctx: Context, curve, powers, n: int | None = None, out_device: 
     return out
 
 
+def ScalePoints(ctx: Context, curve, group: int, points, scalars=None, *, scalar=None, powers=None, first: int = 0, n: int | None = None,
+                montgomery: bool = False, out_device: bool = False, in_place: bool = False):
+    """out[i] = [s_i] points[i] -- the ScalarMultiplication loops of the Groth16 MPC ceremony (backend/groth16/<curve>/mpcsetup:
+    SrsCommons.update, Phase2.update) as one call (ga_scale_points).  Exactly one of
+      scalars      : (n, 4) uint64 array or a DeviceBuffer of n elements   s_i = scalars[i]
+      scalar       : one element (int, or 4 uint64 words)                  s_i = scalar
+      powers=(c, t): two elements                                          s_i = c * t^(first + i)
+    Elements are canonical integers, fr.Element images with montgomery=True (ints are always canonical: pass words for images).
+
+    points : (n, affine_words) uint64 array of G1Affine / G2Affine images, or a DeviceBuffer of n points (then n is required).
+    in_place: the result overwrites `points` (a DeviceBuffer: the same buffer is returned; an array: the array is written and
+    returned); otherwise `points` is never written.  The points are not validated.
+    Returns (array | DeviceBuffer, redone): redone counts the points that took the complete formulas (0 for an honest SRS).
+    """
+    cid = curve_id(curve)
+    wa = affine_words(cid, group)
+    if sum(x is not None for x in (scalars, scalar, powers)) != 1:
+        raise ValueError("exactly one of scalars, scalar and powers=(c, t) must be given")
+    on_dev = isinstance(points, (DeviceBuffer, int))
+    if not on_dev:
+        points = as_u64(points, wa)
+        n = points.shape[0]
+    if n is None:
+        raise ValueError("n is required for device-resident points")
+
+    def words(k):
+        if isinstance(k, (int, np.integer)):
+            return [(int(k) >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)]
+        return list(np.asarray(k, dtype=np.uint64).reshape(4))
+
+    sflag = 0
+    if scalars is not None:
+        mode = _lib.SCALE_EACH
+        if not isinstance(scalars, (DeviceBuffer, int)):
+            scalars = as_u64(scalars, 4)
+            if scalars.shape[0] != n:
+                raise ValueError("len(points) != len(scalars)")
+        sp, sflag = _arg(scalars, _lib.SCALARS_ON_DEVICE)
+    else:
+        mode = _lib.SCALE_ONE if scalar is not None else _lib.SCALE_POWERS
+        keep = np.array([words(k) for k in ([scalar] if scalar is not None else list(powers))], dtype=np.uint64)
+        if keep.shape != ((1, 4) if scalar is not None else (2, 4)):
+            raise ValueError("powers takes two elements (c, t)")
+        sp = _ptr(keep)
+    pp, pflag = _arg(points, _lib.BASES_ON_DEVICE)
+    flags = pflag | sflag | (_lib.SCALARS_MONTGOMERY if montgomery else 0)
+    redone = C.c_uint64(0)
+
+    def run(out_ptr, oflag):
+        ctx.lib.check(ctx.lib.ga_scale_points(ctx.handle, cid, group, pp, n, mode, sp, int(first), flags | oflag, out_ptr, C.byref(redone)))
+
+    if in_place:
+        if out_device != on_dev and out_device:
+            raise ValueError("in_place with out_device needs device-resident points")
+        run(pp, _lib.RESULT_ON_DEVICE if on_dev else 0)
+        return points, redone.value
+    if out_device:
+        buf = ctx.malloc(max(n, 1) * wa * 8)
+        try:
+            run(C.c_void_p(buf.ptr), _lib.RESULT_ON_DEVICE)
+        except Exception:
+            buf.free()
+            raise
+        return buf, redone.value
+    out = np.zeros((n, wa), dtype=np.uint64)
+    run(_ptr(out), 0)
+    return out, redone.value
+
+
 class PrecomputedBases:
     """Bases pinned on the device together with [2^(c*w)]P for every Pippenger window w (ga_msm_table_*): the GPU analogue of
     keeping `pk.G1.A` etc. resident ("PinToGPU", provingkey.go:37-42) with ICICLE's PrecomputeFactor."""

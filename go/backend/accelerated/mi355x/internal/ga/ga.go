@@ -424,6 +424,28 @@ func (c *Context) ToLagrangeG1(curve Curve, powers unsafe.Pointer, n uint64, fla
 	})
 }
 
+// The modes of ScalePoints: what `scalars` holds.
+const (
+	ScaleEach   = C.GA_SCALE_EACH   // n fr elements: out[i] = [scalars[i]] points[i]
+	ScaleOne    = C.GA_SCALE_ONE    // one fr element s: out[i] = [s] points[i]
+	ScalePowers = C.GA_SCALE_POWERS // two fr elements (c, t): out[i] = [c * t^(first+i)] points[i]
+)
+
+// ScalePoints is the ScalarMultiplication loop of the Groth16 MPC ceremony (mpcsetup: SrsCommons.update, Phase2.update) on the
+// device: out[i] = [s_i] points[i] over n affine points in gnark's memory image.  flags: BasesOnDevice / ResultOnDevice for the
+// points and the output, ScalarsOnDevice (ScaleEach only) and ScalarsMontgomery for the scalars; outAffine == points with the same
+// placement scales in place.  first is the exponent of point 0 in ScalePowers and 0 otherwise.  The points are not validated.
+// redone is the number of points that took the complete formulas: 0 for an honest SRS.
+func (c *Context) ScalePoints(curve Curve, group int, points unsafe.Pointer, n uint64, mode int, scalars unsafe.Pointer, first uint64,
+	flags uint, outAffine unsafe.Pointer) (redone uint64, err error) {
+	var r C.uint64_t
+	err = call("ga_scale_points", func() C.int {
+		return C.ga_scale_points(c.h, C.int(curve), C.int(group), points, C.size_t(n), C.int(mode), scalars, C.uint64_t(first),
+			C.uint(flags), outAffine, &r)
+	})
+	return uint64(r), err
+}
+
 // Table is a pinned base vector with its window multiples (ga_msm_table_*): the KZG SRS of a PLONK key.
 type Table struct {
 	h *C.ga_msm_table

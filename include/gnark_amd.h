@@ -55,7 +55,7 @@ extern "C" {
 #define GA_G2 1
 
 /* flags for ga_msm */
-#define GA_BASES_ON_DEVICE 0x1u        /* `bases` (ga_kzg_to_lagrange_g1: `powers_affine`) is a device pointer */
+#define GA_BASES_ON_DEVICE 0x1u        /* `bases` (ga_kzg_to_lagrange_g1: `powers_affine`; ga_scale_points: `points_affine`) is a device pointer */
 #define GA_SCALARS_ON_DEVICE 0x2u      /* `scalars` is a device pointer */
 #define GA_TABLE_BATCHED 0x10u         /* ga_msm_table_create: the table will mostly serve ga_msm_table_run_batch (PLONK's grouped
                                          * commitments over the SRS): plan a narrower window -- k bucket sets make the sort keys
@@ -64,7 +64,7 @@ extern "C" {
 #define GA_SCALARS_MONTGOMERY 0x4u     /* scalars are fr.Element images (Montgomery); else canonical LE integers
                                           (ICICLE's AreScalarsMontgomeryForm, icicle.go:861-863,1232) */
 #define GA_RESULT_WINDOW_SUMS 0x8u     /* multi-GPU window sharding: see ga_msm_windows */
-#define GA_RESULT_ON_DEVICE 0x20u      /* ga_batch_scalar_mul, ga_kzg_to_lagrange_g1: `out_affine` is a device pointer */
+#define GA_RESULT_ON_DEVICE 0x20u      /* ga_batch_scalar_mul, ga_kzg_to_lagrange_g1, ga_scale_points: `out_affine` is a device pointer */
 #define GA_RESULT_BITREVERSED 0x40u    /* ga_batch_scalar_mul: result i is written at index bitrev(i, log2 n) */
 
 /* NTT direction / ordering, mirroring gnark-crypto fft.Domain.FFT / FFTInverse (prove.go:362-386) */
@@ -158,6 +158,36 @@ int ga_batch_scalar_mul_plan(int curve, size_t n, int* window_bits, int* num_win
  * n/2 + 4 words of redo list, and n affine points (64 / 96 B) of staging when `powers` or `out` is on the host.  GA_ERR_NOMEM when
  * that does not fit (always above n = 2^31); the context stays usable. */
 int ga_kzg_to_lagrange_g1(ga_ctx* ctx, int curve, const void* powers_affine, size_t n, unsigned flags, void* out_affine);
+
+/* ---- per-point scalar multiplication: the curve work of the Groth16 MPC ceremony ---------------------------
+ * replaces: the ScalarMultiplication loops of backend/groth16/<curve>/mpcsetup -- SrsCommons.update (phase1.go:104-147: the i-th
+ * point of G1.Tau, G2.Tau, G1.AlphaTau, G1.BetaTau times c * tau^i) and Phase2.update (phase2.go:110-135: Z and PKK times 1/delta,
+ * SigmaCKK[i] times sigma_i).  out[i] = [s_i] points[i]: n full-width variable-base multiplications, a map and not a sum.
+ *   points  : n affine points (gnark's memory image, (0,0) = infinity), host, or device with GA_BASES_ON_DEVICE
+ *   out     : n affine points in gnark's memory image, host, or device with GA_RESULT_ON_DEVICE.  out == points (the same pointer
+ *             AND the same placement) scales in place, as the reference does; otherwise `points` is never written.  Any other
+ *             overlap of the two is the caller's error and is not detected.
+ *   scalars : fr elements, canonical LE 4x64 integers, or Montgomery with GA_SCALARS_MONTGOMERY.  A canonical value that is not
+ *             below r (any 256-bit integer, r itself included) is reduced mod r.
+ *             GA_SCALE_EACH: n of them, host, or device with GA_SCALARS_ON_DEVICE; GA_SCALE_ONE / GA_SCALE_POWERS: 1 / 2, host.
+ *   first   : GA_SCALE_POWERS only (0 otherwise): the exponent of point 0 -- the tail G1.Tau[N .. 2N-1) of phase1.go:141-146, or a
+ *             caller's own chunking, needs no powers from the host.  first + n must not exceed 2^64.
+ *   redone  : may be NULL; receives the number of points that left the fast loop for the complete formulas (points of order <= 8,
+ *             a prefix of the scalar hitting +-d P; never points at infinity or zero scalars).  0 for an honest SRS.
+ * The bytes are gnark's G1Affine / G2Affine images of the exact group elements, whatever the schedule; a zero scalar or a point at
+ * infinity gives (0,0).  The points are NOT validated (ScalarMultiplication does not validate them either): for a point of small
+ * order or outside the subgroup the result is still the group law's.
+ * GA_ERR_INVALID: unknown curve, group or mode; a null pointer with n > 0; first != 0 outside GA_SCALE_POWERS; GA_SCALARS_ON_DEVICE
+ * outside GA_SCALE_EACH; n above 2^32.  n = 0 is GA_OK and touches nothing.
+ * Device scratch, kept by the context, per pass of at most GA_SCALE_CHUNK points (default 2^20, at most 2^30): 8 + 1 extended points
+ * (128 B each for BN254 G1 .. 384 B for BLS12-381 G2), 32 B of scalar, 4 B of redo list per point, and the staging of whatever is on
+ * the host.  GA_ERR_NOMEM when that does not fit: nothing is in flight and the context stays usable.  GA_SCALE_WINDOW=0 runs the
+ * plain double-and-add ladder instead of the signed 4-bit windows (same bytes; tools/scale_points_bench.py measures both). */
+#define GA_SCALE_EACH   0   /* scalars: n fr elements;              out[i] = [scalars[i]] points[i]          */
+#define GA_SCALE_ONE    1   /* scalars: 1 fr element s;             out[i] = [s] points[i]                   */
+#define GA_SCALE_POWERS 2   /* scalars: 2 fr elements (c, t);       out[i] = [c * t^(first + i)] points[i]   */
+int ga_scale_points(ga_ctx* ctx, int curve, int group, const void* points_affine, size_t n, int mode,
+                    const void* scalars, uint64_t first, unsigned flags, void* out_affine, uint64_t* redone);
 
 /* ---- MSM over pinned bases with precomputed window multiples ---------------------------------------------
  * (ICICLE's MSMConfig.PrecomputeFactor / precompute-bases, icicle.go:507-525.)  ga_msm_table_create uploads (or takes

@@ -364,17 +364,20 @@ def check_dbl(curve: str, fp2: bool, verbose=False, exact=False):
     return out
 
 
-# ---- double-and-add on general XYZZ points (ec_ntt.hip.h::ec_ntt_scalar_mul29, the butterflies of kzg.ToLagrangeG1) --------------------
-def check_ladder(curve: str, verbose=False):
-    """G1 only.  A butterfly of the point FFT feeds add29 with canonical points (one of them with a negated y, 2p - y) and then
+# ---- double-and-add on general XYZZ points (ec_ntt.hip.h::ec_ntt_scalar_mul29: the butterflies of kzg.ToLagrangeG1; scale_points.hip.h) ----
+def check_ladder(curve: str, fp2: bool = False, verbose=False):
+    """A butterfly of the point FFT feeds add29 with canonical points (one of them with a negated y, 2p - y) and then
     alternates dbl29 and add29 on the results without ever normalising: acc = dbl29(acc); acc = add29(acc, D) where D is an earlier
     add29 output.  One set of bounds covers every point either function may see there -- a canonical point, a negated one, any
     output of add29 or dbl29 on points within the bounds -- and is iterated to its fixed point; every subtraction constant of
-    msm_lazy.hip.h::add29 and ::dbl29 is asserted on the way, with the values below R'/4 as in check_add / check_dbl."""
+    msm_lazy.hip.h::add29 and ::dbl29 is asserted on the way, with the values below R'/4 as in check_add / check_dbl.
+    fp2: the same alternation over Fp2 (scale_points.hip.h on G2: the table [1..8]P and the windowed ladder are made of the same two
+    functions), with the Fp2 operand limit FP2Z_K*p, the squaring constant KQ, the partial reduction of X3 and the negation constant
+    of f29_mul_sub asserted as check_add / check_dbl do for fp2=True."""
     p, L, NL, bits = CURVES[curve]
     R = 1 << (L * NL)
     unit = 1 << (L * (NL - 1))
-    k = ADD_G1
+    k = ADD_G2 if fp2 else ADD_G1
 
     def lim(v):
         assert v < R // 4, ("value exceeds R'/4", log2(v))
@@ -383,37 +386,67 @@ def check_ladder(curve: str, verbose=False):
     def need(K, b, what):
         assert K * p - b > unit, (what, K, log2(b), log2(K * p))
 
-    def mul(a, b):
+    def mul1(a, b):
         lim(a), lim(b)
         return a * b // R + p
 
-    def mulsub(K, a, b, c, d):
-        assert c + unit < K * p
-        lim(a), lim(b), lim(d)
-        return (a * b + K * p * d) // R + p
+    def pr(v):   # f29_partial_reduce
+        q = v >> bits
+        return (1 << bits) + q * ((1 << bits) - p)
+
+    if fp2:
+        import os
+        import sys
+        sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+        from gen_constants import FP2_LAZY_K as FK
+
+        def mul(a, b):   # f29_mul(F29x2): real a0*b0 + (FK*p - a1)*b1, imaginary a0*b1 + a1*b0
+            assert a + unit < FK * p and b < FK * p, ("Fp2 operand above FP2Z_K*p", log2(a), log2(b))
+            lim(a), lim(b)
+            return max((a * b + (FK * p + unit) * b) // R + p, 2 * a * b // R + p)
+
+        def sqr(a):
+            need(G2["KQ"], a, "KQ")
+            return max(mul1(lim(2 * a), a + G2["KQ"] * p), 2 * mul1(a, a))
+
+        def mulsub(K, a, b, c, d):
+            assert max(a, c) + unit < K * p and max(a, b, c, d) < FK * p
+            return max(a * b + K * p * b + K * p * d + c * d, 2 * a * b + 2 * K * p * d) // R + p
+        red = lambda v: pr(v)
+    else:
+        mul = mul1
+
+        def sqr(a):
+            return mul1(a, a)
+
+        def mulsub(K, a, b, c, d):
+            assert c + unit < K * p
+            lim(a), lim(b), lim(d)
+            return (a * b + K * p * d) // R + p
+        red = lambda v: v
 
     def add_out(bx, by, bzz, bzzz):
         U, S = mul(bx, bzz), mul(by, bzzz)
         need(k["KP"], U, "KP")
         need(k["KR"], S, "KR")
         Pp, Rr = U + k["KP"] * p, S + k["KR"] * p
-        PP = mul(Pp, Pp)
+        PP = sqr(Pp)
         PPP, Q = mul(Pp, PP), mul(U, PP)
         need(k["K3"], PPP + 2 * Q, "K3")
-        X3 = mul(Rr, Rr) + k["K3"] * p
+        X3 = red(sqr(Rr) + k["K3"] * p)
         need(k["Kq"], X3, "Kq")
         Y3 = mulsub(k["Kms"], Rr, Q + k["Kq"] * p, S, PPP)
         return tuple(lim(v) for v in (X3, Y3, mul(mul(bzz, bzz), PP), mul(mul(bzzz, bzzz), PPP)))
 
     def dbl_out(bx, by, bzz, bzzz):
         U = lim(2 * by)
-        V = mul(U, U)
+        V = sqr(U)
         W, S = mul(U, V), mul(bx, V)
-        M = lim(3 * mul(bx, bx))
+        M = lim(3 * sqr(bx))
         need(4, 2 * S, "X3: 2S below 4p")
-        X3 = mul(M, M) + 4 * p
+        X3 = red(sqr(M) + 4 * p)
         need(8, X3, "t: X3 below 8p")
-        Y3 = mulsub(8, M, S + 8 * p, W, by)
+        Y3 = mulsub(k["Kms"], M, S + 8 * p, W, by)
         return tuple(lim(v) for v in (X3, Y3, mul(V, bzz), mul(W, bzzz)))
 
     b = (p, 2 * p + unit, p, p)              # canonical coordinates; f29_sub<2>(0, y) = 2p - y before its carry sweep settles
@@ -426,13 +459,14 @@ def check_ladder(curve: str, verbose=False):
         raise AssertionError("bounds of the double-and-add ladder do not converge")
     out = {"X": log2(b[0]), "Y": log2(b[1]), "ZZ": log2(b[2]), "ZZZ": log2(b[3]), "limit": L * NL}
     if verbose:
-        print(curve, "ladder G1", {a: round(v, 2) for a, v in out.items()})
+        print(curve, "ladder G2" if fp2 else "ladder G1", {a: round(v, 2) for a, v in out.items()})
     return out
 
 
 if __name__ == "__main__":
     for c in CURVES:
-        check_ladder(c, verbose=True)
+        for fp2 in (False, True):
+            check_ladder(c, fp2, verbose=True)
     for c in CURVES:
         for fp2 in (False, True):
             check_dbl(c, fp2, verbose=True)
