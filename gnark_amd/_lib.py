@@ -80,6 +80,8 @@ _PROTOS = {
     "ga_batch_scalar_mul": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_size_t, C.c_uint, _P]),
     "ga_batch_scalar_mul_plan": (C.c_int, [C.c_int, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ga_kzg_to_lagrange_g1": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.c_uint, _P]),
+    "ga_lagrange_coeffs": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_size_t, C.c_uint, _P]),
+    "ga_sparse_point_sums": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_size_t, _P, C.c_size_t, _P, _P, C.c_size_t, C.c_uint, _P, C.POINTER(C.c_uint64)]),
     "ga_scale_points": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_size_t, C.c_int, _P, C.c_uint64, C.c_uint, _P, C.POINTER(C.c_uint64)]),
     "ga_msm_table_create": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_size_t, C.c_uint, C.POINTER(_P)]),
     "ga_msm_table_destroy": (None, [_P]),

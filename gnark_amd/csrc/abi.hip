@@ -218,11 +218,11 @@ static uint64_t fixed_base_forced_chunk() {
     return e ? strtoull(e, nullptr, 10) : 0;
 }
 
-// kzg.ToLagrangeG1 (ec_ntt.hip.h; instantiated in ec_ntt_<curve>.hip): powers / out host or device per flags.  One run-time knob,
-// read by the entry point itself like the two above:
+// kzg.ToLagrangeG1 and mpcsetup's lagrangeCoeffsG1 / G2 (ec_ntt.hip.h; instantiated in ec_ntt_<curve>.hip and ec_ntt_<curve>_g2.hip):
+// powers / out host or device per flags.  One run-time knob, read by the entry points themselves like the two above:
 //   GA_EC_NTT_UNIFORM    0: the lanes of every stage are consecutive butterflies of one group (the A/B of tools/to_lagrange_bench.py);
 //                        default 1: from stage 6 on the lanes of a wave share their scalar
-template <class C>
+template <class C, int G>
 int ec_ntt_to_lagrange(Ctx* ctx, const void* powers, size_t n, unsigned flags, void* out, int uniform);
 static int ec_ntt_uniform() {
     const char* e = getenv("GA_EC_NTT_UNIFORM");
@@ -242,6 +242,19 @@ static int scale_windowed() {
 }
 static uint64_t scale_forced_chunk() {
     const char* e = getenv("GA_SCALE_CHUNK");
+    return e ? strtoull(e, nullptr, 10) : 0;
+}
+
+// sparse point sums (sparse_sums.hip.h; instantiated in sparse_sums_<curve>_g<k>.hip).  Three run-time knobs, read by the entry point
+// itself like the ones above:
+//   GA_SPARSE_CHUNK      general terms (products) per pass (0 = 2^20, at most 2^30; tests force a small chunk)
+//   GA_SPARSE_SEGMENT    terms, or partial sums, per lane of the row sums (0 or 1 = 16; tests force 4)
+//   GA_SPARSE_ORDER      0: the products in row order (default); 1: sorted by coefficient id (the A/B of tools/phase2_init_bench.py)
+template <class C, int G>
+int sparse_sums_run(Ctx* ctx, const void* points, size_t n_points, const uint64_t* row_start, size_t n_rows, const uint32_t* terms, const void* coeffs,
+                    size_t n_coeffs, unsigned flags, void* out, uint64_t* redone, uint64_t forced_chunk, uint32_t segment, int cid_order);
+static uint64_t sparse_knob(const char* name) {
+    const char* e = getenv(name);
     return e ? strtoull(e, nullptr, 10) : 0;
 }
 
@@ -559,7 +572,25 @@ int ga_kzg_to_lagrange_g1(ga_ctx* h, int curve, const void* powers_affine, size_
     }
     Lock l(c);
     const int uniform = ec_ntt_uniform();
-    GA_DISPATCH_CURVE(curve, return ec_ntt_to_lagrange<C>(c, powers_affine, n, flags, out_affine, uniform));
+    GA_DISPATCH_CURVE(curve, return (ec_ntt_to_lagrange<C, GA_G1>(c, powers_affine, n, flags, out_affine, uniform)));
+    return GA_OK;
+} GA_ABI_CATCH
+
+int ga_lagrange_coeffs(ga_ctx* h, int curve, int group, const void* powers_affine, size_t n, unsigned flags, void* out_affine) try {
+    GA_ABI_ENTRY();
+    Ctx* c = reinterpret_cast<Ctx*>(h);
+    if ((curve != GA_BN254 && curve != GA_BLS12_381) || (group != GA_G1 && group != GA_G2)) {
+        set_error("ga_lagrange_coeffs: unknown curve id %d or group id %d", curve, group);
+        return GA_ERR_INVALID;
+    }
+    if (n == 0) return GA_OK;
+    if (!c || !powers_affine || !out_affine) {
+        set_error("ga_lagrange_coeffs: null argument");
+        return GA_ERR_INVALID;
+    }
+    Lock l(c);
+    const int uniform = ec_ntt_uniform();
+    GA_DISPATCH_CURVE(curve, GA_DISPATCH_GROUP(group, return (ec_ntt_to_lagrange<C, G>(c, powers_affine, n, flags, out_affine, uniform))));
     return GA_OK;
 } GA_ABI_CATCH
 
@@ -601,6 +632,41 @@ int ga_scale_points(ga_ctx* h, int curve, int group, const void* points_affine, 
     const uint64_t forced_chunk = scale_forced_chunk();
     GA_DISPATCH_CURVE(curve, GA_DISPATCH_GROUP(group, return (scale_points_run<C, G>(c, points_affine, n, mode, scalars, first, flags, out_affine, redone,
                                                                                     windowed, forced_chunk))));
+    return GA_OK;
+} GA_ABI_CATCH
+
+// ---- sparse point sums (sparse_sums.hip.h) ----------------------------------------------------------------
+int ga_sparse_point_sums(ga_ctx* h, int curve, int group, const void* points_affine, size_t n_points, const uint64_t* row_start, size_t n_rows,
+                         const uint32_t* terms, const void* coeffs, size_t n_coeffs, unsigned flags, void* out_affine, uint64_t* redone) try {
+    GA_ABI_ENTRY();
+    Ctx* c = reinterpret_cast<Ctx*>(h);
+    if ((curve != GA_BN254 && curve != GA_BLS12_381) || (group != GA_G1 && group != GA_G2)) {
+        set_error("ga_sparse_point_sums: unknown curve id %d or group id %d", curve, group);
+        return GA_ERR_INVALID;
+    }
+    if (n_rows == 0) {
+        if (redone) *redone = 0;
+        return GA_OK;
+    }
+    if ((uint64_t)n_rows >= (1ull << 31) || (uint64_t)n_points > (1ull << 32) || (uint64_t)n_coeffs > (1ull << 32)) {
+        set_error("ga_sparse_point_sums: n_rows = %zu (at most 2^31 - 1), n_points = %zu or n_coeffs = %zu (at most 2^32) out of range", n_rows, n_points,
+                  n_coeffs);
+        return GA_ERR_INVALID;
+    }
+    if ((flags & GA_RESULT_BITREVERSED) && (n_rows & (n_rows - 1)) != 0) {
+        set_error("ga_sparse_point_sums: GA_RESULT_BITREVERSED needs a power-of-two n_rows (got %zu)", n_rows);
+        return GA_ERR_INVALID;
+    }
+    if (!c || !row_start || !out_affine || (row_start[n_rows] != 0 && (!points_affine || !terms || !coeffs))) {
+        set_error("ga_sparse_point_sums: null argument");
+        return GA_ERR_INVALID;
+    }
+    Lock l(c);
+    const uint64_t forced_chunk = sparse_knob("GA_SPARSE_CHUNK"), segment = sparse_knob("GA_SPARSE_SEGMENT");
+    const int cid_order = sparse_knob("GA_SPARSE_ORDER") != 0;
+    GA_DISPATCH_CURVE(curve, GA_DISPATCH_GROUP(group, return (sparse_sums_run<C, G>(c, points_affine, n_points, row_start, n_rows, terms, coeffs, n_coeffs, flags,
+                                                                                   out_affine, redone, forced_chunk,
+                                                                                   (uint32_t)(segment < (1u << 20) ? segment : (1u << 20)), cid_order))));
     return GA_OK;
 } GA_ABI_CATCH
 

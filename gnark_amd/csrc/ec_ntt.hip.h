@@ -1,4 +1,5 @@
-// kzg.ToLagrangeG1 (gnark-crypto ecc/<curve>/kzg): the inverse FFT whose elements are G1 points.
+// kzg.ToLagrangeG1 (gnark-crypto ecc/<curve>/kzg) and mpcsetup's lagrangeCoeffsG1 / lagrangeCoeffsG2 (backend/groth16/<curve>/mpcsetup/
+// lagrange.go:21-64): the inverse FFT whose elements are points of G1 or G2 (ec_ntt_to_lagrange<C, G>; F = GroupField<C, G>::F).
 //     out[i] = [1/n] sum_j [w^(-i j)] powers[j],   w = the generator of the size-n domain (fft.NewDomain(n)), natural order in and out
 // -- n/2 log2 n full-width variable-base scalar multiplications, the whole cost of turning a ceremony SRS into its Lagrange form.
 //
@@ -32,6 +33,13 @@ namespace ga {
 // (one wave per SIMD) and 256 with 15 spilled registers under it -- two workgroups of 68 KiB of LDS then fit a CU
 constexpr int EC_NTT_MIN_WAVES = 2;
 constexpr unsigned EC_NTT_EXACT_MAX_BLOCKS = 1024;   // one-wave workgroups of the exact redo (its private segment is per resident wave)
+// over Fp2 one extended point is 72 (BN254) or 112 (BLS12-381) registers and the butterfly holds two around the ladder: under the
+// two-wave bound the BN254 G2 kernel spilled 250 registers (688 B of scratch per lane), with the whole register file of a SIMD lane
+// it spills 11 and the transform runs 10 % faster at 2^12 and 2^16, 3 % at 2^18 (same box, G1 unchanged beside it).
+// BLS12-381 G2 runs 128-lane workgroups, for which both bounds mean one wave per SIMD.  G1 keeps EC_NTT_MIN_WAVES
+template <class F> struct EcNttStage {
+    static constexpr int MIN_WAVES = Lazy<F>::FP2 ? 1 : EC_NTT_MIN_WAVES;
+};
 
 template <class FrP>
 __global__ void __launch_bounds__(256)
@@ -131,7 +139,7 @@ __device__ __forceinline__ XYZZ<F> ec_ntt_from_exact(const XYZZ<F>& p) {
 }
 
 template <class F, class FrP>
-__global__ void __launch_bounds__(Table29<F>::THREADS, EC_NTT_MIN_WAVES)
+__global__ void __launch_bounds__(Table29<F>::THREADS, EcNttStage<F>::MIN_WAVES)
 ec_ntt_stage_kernel(XYZZ<F>* __restrict__ work, const uint32_t* __restrict__ tw, uint64_t half, int s, int logn, int uniform, const Fe<FrP> ninv_mont,
                     uint32_t* __restrict__ redo, uint32_t* __restrict__ redo_count) {
     constexpr int NW = Lazy<F>::NW;
@@ -205,16 +213,16 @@ ec_ntt_scale_kernel(XYZZ<F>* __restrict__ work, uint32_t count, const Fe<FrP> k_
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
 // uniform: the lane order of stages >= 6 (1: one scalar per wave, the default; 0: consecutive j, the A/B of tools/to_lagrange_bench.py)
-template <class C>
+template <class C, int G>
 int ec_ntt_to_lagrange(Ctx* ctx, const void* powers, size_t n, unsigned flags, void* out, int uniform) {
-    typedef typename GroupField<C, GA_G1>::F F;
+    typedef typename GroupField<C, G>::F F;
     typedef typename C::FrP FrP;
     if ((n & (n - 1)) != 0 || ilog2_u64(n) > FrP::ADICITY) {
-        set_error("ga_kzg_to_lagrange_g1: n = %zu is not a power of two up to 2^%d", n, (int)FrP::ADICITY);
+        set_error("%s: n = %zu is not a power of two up to 2^%d", current_entry(), n, (int)FrP::ADICITY);
         return GA_ERR_INVALID;
     }
     if ((uint64_t)n > (1ull << 31)) {   // (BLS12-381 admits 2^32: 768 GiB of work array; the kernels index butterflies with 32 bits)
-        set_error("ga_kzg_to_lagrange_g1: n = %zu needs more device memory than there is", n);
+        set_error("%s: n = %zu needs more device memory than there is", current_entry(), n);
         return GA_ERR_NOMEM;
     }
     const bool i_dev = (flags & GA_BASES_ON_DEVICE) != 0, o_dev = (flags & GA_RESULT_ON_DEVICE) != 0;

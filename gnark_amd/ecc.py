@@ -190,6 +190,84 @@ def ScalePoints(ctx: Context, curve, group: int, points, scalars=None, *, scalar
     return out, redone.value
 
 
+def LagrangeCoeffs(ctx: Context, curve, group: int, powers, n: int | None = None, out_device: bool = False):
+    """lagrangeCoeffsG1 / lagrangeCoeffsG2 of the Groth16 MPC ceremony (backend/groth16/<curve>/mpcsetup/lagrange.go): the inverse
+    FFT over n points of G1 or G2, natural order in and out (ga_lagrange_coeffs).  group = G1 gives the bytes of ToLagrangeG1.
+
+    powers : (n, affine_words) uint64 array of G1Affine / G2Affine images or a DeviceBuffer of n points (then n is required); never
+    modified.  n must be a power of two (at most 2^28 for BN254, 2^32 for BLS12-381).  The points are not validated.
+    Returns an (n, affine_words) array, or with out_device=True a DeviceBuffer of n affine points (the caller frees it).
+    """
+    cid = curve_id(curve)
+    wa = affine_words(cid, group)
+    if not isinstance(powers, (DeviceBuffer, int)):
+        powers = as_u64(powers, wa)
+        n = powers.shape[0]
+    if n is None:
+        raise ValueError("n is required for device-resident points")
+    pp, f = _arg(powers, _lib.BASES_ON_DEVICE)
+    if out_device:
+        buf = ctx.malloc(max(n, 1) * wa * 8)
+        try:
+            ctx.lib.check(ctx.lib.ga_lagrange_coeffs(ctx.handle, cid, group, pp, n, f | _lib.RESULT_ON_DEVICE, C.c_void_p(buf.ptr)))
+        except Exception:
+            buf.free()
+            raise
+        return buf
+    out = np.zeros((n, wa), dtype=np.uint64)
+    ctx.lib.check(ctx.lib.ga_lagrange_coeffs(ctx.handle, cid, group, pp, n, f, _ptr(out)))
+    return out
+
+
+def SparsePointSums(ctx: Context, curve, group: int, points, row_start, terms, coeffs, *, montgomery: bool = False, bitreversed: bool = False,
+                    n_points: int | None = None, out_device: bool = False):
+    """out[r] = sum_k [coeffs[cid_k]] points[col_k] over the terms k of row r -- a sparse Fr matrix in CSR form applied to a vector of
+    points: the constraint loop of the Groth16 MPC ceremony's Phase2.Initialize (ga_sparse_point_sums).
+
+    points    : (n_points, affine_words) uint64 array of G1Affine / G2Affine images, or a DeviceBuffer (then n_points is required)
+    row_start : n_rows + 1 offsets into terms, row_start[0] = 0, row_start[-1] = len(terms)
+    terms     : (nnz, 2) uint32 {cid, col} pairs, row after row (constraint.Term's memory image with the column in VID)
+    coeffs    : (n_coeffs, 4) uint64 elements, canonical integers (any 256-bit value: reduced), fr.Element images with montgomery=True
+    bitreversed: row r lands at index bitrev(r, log2 n_rows); n_rows must be a power of two
+    Returns (array | DeviceBuffer of n_rows affine points, redone): redone counts the products and row segments that took the complete
+    formulas (repeated or cancelling operands); the result is exact either way.  An empty row and a cancelled sum are (0,0).
+    """
+    cid = curve_id(curve)
+    wa = affine_words(cid, group)
+    if not isinstance(points, (DeviceBuffer, int)):
+        points = as_u64(points, wa)
+        n_points = points.shape[0]
+    if n_points is None:
+        raise ValueError("n_points is required for device-resident points")
+    row_start = np.ascontiguousarray(row_start, dtype=np.uint64).reshape(-1)
+    if row_start.size == 0:
+        raise ValueError("row_start holds n_rows + 1 offsets")
+    n_rows = row_start.size - 1
+    terms = np.ascontiguousarray(terms, dtype=np.uint32).reshape(-1, 2)
+    if terms.shape[0] != int(row_start[-1]):
+        raise ValueError("len(terms) != row_start[-1]")
+    coeffs = as_u64(coeffs, 4)
+    pp, pflag = _arg(points, _lib.BASES_ON_DEVICE)
+    flags = pflag | (_lib.SCALARS_MONTGOMERY if montgomery else 0) | (_lib.RESULT_BITREVERSED if bitreversed else 0)
+    redone = C.c_uint64(0)
+
+    def run(out_ptr, oflag):
+        ctx.lib.check(ctx.lib.ga_sparse_point_sums(ctx.handle, cid, group, pp, n_points, _ptr(row_start), n_rows, _ptr(terms), _ptr(coeffs),
+                                                   coeffs.shape[0], flags | oflag, out_ptr, C.byref(redone)))
+
+    if out_device:
+        buf = ctx.malloc(max(n_rows, 1) * wa * 8)
+        try:
+            run(C.c_void_p(buf.ptr), _lib.RESULT_ON_DEVICE)
+        except Exception:
+            buf.free()
+            raise
+        return buf, redone.value
+    out = np.zeros((n_rows, wa), dtype=np.uint64)
+    run(_ptr(out), 0)
+    return out, redone.value
+
+
 class PrecomputedBases:
     """Bases pinned on the device together with [2^(c*w)]P for every Pippenger window w (ga_msm_table_*): the GPU analogue of
     keeping `pk.G1.A` etc. resident ("PinToGPU", provingkey.go:37-42) with ICICLE's PrecomputeFactor."""

@@ -446,6 +446,32 @@ func (c *Context) ScalePoints(curve Curve, group int, points unsafe.Pointer, n u
 	return uint64(r), err
 }
 
+// LagrangeCoeffs is mpcsetup's lagrangeCoeffsG1 / lagrangeCoeffsG2 on the device (the four transforms of Phase2.Initialize): the
+// inverse FFT over n affine points of G1 or G2 (n a power of two), natural order in and out, in gnark's memory image.  group == G1
+// gives the bytes of ToLagrangeG1; flags and rules as there.
+func (c *Context) LagrangeCoeffs(curve Curve, group int, powers unsafe.Pointer, n uint64, flags uint, outAffine unsafe.Pointer) error {
+	return call("ga_lagrange_coeffs", func() C.int {
+		return C.ga_lagrange_coeffs(c.h, C.int(curve), C.int(group), powers, C.size_t(n), C.uint(flags), outAffine)
+	})
+}
+
+// SparsePointSums applies a sparse Fr matrix in CSR form to a vector of points (the constraint loop of mpcsetup's
+// Phase2.Initialize): out[r] = sum over the terms k of row r of [coeffs[terms[k].CID]] points[terms[k].VID].  rowStart holds
+// nRows+1 offsets into terms (rowStart[0] = 0, rowStart[nRows] = len(terms)); terms is the memory of a []constraint.Term whose VID
+// is the column; coeffs is the memory of nCoeffs fr.Element (ScalarsMontgomery) or canonical 4-word integers.  rowStart, terms
+// and coeffs are host memory; flags: BasesOnDevice for the points, ResultOnDevice for the output, ResultBitReversed (nRows a
+// power of two).  The points are not validated and must not overlap the output.  redone is the number of products and row
+// segments that took the complete formulas (repeated or cancelling operands): the result is exact either way.
+func (c *Context) SparsePointSums(curve Curve, group int, points unsafe.Pointer, nPoints uint64, rowStart *uint64, nRows uint64,
+	terms unsafe.Pointer, coeffs unsafe.Pointer, nCoeffs uint64, flags uint, outAffine unsafe.Pointer) (redone uint64, err error) {
+	var r C.uint64_t
+	err = call("ga_sparse_point_sums", func() C.int {
+		return C.ga_sparse_point_sums(c.h, C.int(curve), C.int(group), points, C.size_t(nPoints), (*C.uint64_t)(unsafe.Pointer(rowStart)),
+			C.size_t(nRows), (*C.uint32_t)(terms), coeffs, C.size_t(nCoeffs), C.uint(flags), outAffine, &r)
+	})
+	return uint64(r), err
+}
+
 // Table is a pinned base vector with its window multiples (ga_msm_table_*): the KZG SRS of a PLONK key.
 type Table struct {
 	h *C.ga_msm_table

@@ -55,7 +55,8 @@ extern "C" {
 #define GA_G2 1
 
 /* flags for ga_msm */
-#define GA_BASES_ON_DEVICE 0x1u        /* `bases` (ga_kzg_to_lagrange_g1: `powers_affine`; ga_scale_points: `points_affine`) is a device pointer */
+#define GA_BASES_ON_DEVICE 0x1u        /* `bases` (ga_kzg_to_lagrange_g1, ga_lagrange_coeffs: `powers_affine`; ga_scale_points,
+                                         * ga_sparse_point_sums: `points_affine`) is a device pointer */
 #define GA_SCALARS_ON_DEVICE 0x2u      /* `scalars` is a device pointer */
 #define GA_TABLE_BATCHED 0x10u         /* ga_msm_table_create: the table will mostly serve ga_msm_table_run_batch (PLONK's grouped
                                          * commitments over the SRS): plan a narrower window -- k bucket sets make the sort keys
@@ -64,8 +65,9 @@ extern "C" {
 #define GA_SCALARS_MONTGOMERY 0x4u     /* scalars are fr.Element images (Montgomery); else canonical LE integers
                                           (ICICLE's AreScalarsMontgomeryForm, icicle.go:861-863,1232) */
 #define GA_RESULT_WINDOW_SUMS 0x8u     /* multi-GPU window sharding: see ga_msm_windows */
-#define GA_RESULT_ON_DEVICE 0x20u      /* ga_batch_scalar_mul, ga_kzg_to_lagrange_g1, ga_scale_points: `out_affine` is a device pointer */
-#define GA_RESULT_BITREVERSED 0x40u    /* ga_batch_scalar_mul: result i is written at index bitrev(i, log2 n) */
+#define GA_RESULT_ON_DEVICE 0x20u      /* ga_batch_scalar_mul, ga_kzg_to_lagrange_g1, ga_lagrange_coeffs, ga_scale_points,
+                                         * ga_sparse_point_sums: `out_affine` is a device pointer */
+#define GA_RESULT_BITREVERSED 0x40u    /* ga_batch_scalar_mul, ga_sparse_point_sums: result i is written at index bitrev(i, log2 n) */
 
 /* NTT direction / ordering, mirroring gnark-crypto fft.Domain.FFT / FFTInverse (prove.go:362-386) */
 #define GA_FFT_FORWARD 0
@@ -159,6 +161,15 @@ int ga_batch_scalar_mul_plan(int curve, size_t n, int* window_bits, int* num_win
  * that does not fit (always above n = 2^31); the context stays usable. */
 int ga_kzg_to_lagrange_g1(ga_ctx* ctx, int curve, const void* powers_affine, size_t n, unsigned flags, void* out_affine);
 
+/* ---- the point iFFT for G1 and G2: the Lagrange transforms of the Groth16 MPC ceremony --------------------
+ * replaces: lagrangeCoeffsG1 / lagrangeCoeffsG2 of backend/groth16/<curve>/mpcsetup (lagrange.go:21-64), which Phase2.Initialize
+ * (phase2.go:207-210) runs over G1.Tau, G1.AlphaTau, G1.BetaTau and G2.Tau, and VerifyPhase2 runs again for every verifier.
+ * mpcsetup lagrangeCoeffsG1 / lagrangeCoeffsG2 (lagrange.go:21-64): out[i] = [1/n] sum_j [w^(-ij)] powers[j], natural order in and out.
+ * group == GA_G1 gives the bytes of ga_kzg_to_lagrange_g1.  Flags, limits on n, aliasing and validation rules as there; the device
+ * scratch likewise, with G2 points twice the size of G1 points (256 B extended for BN254, 384 B for BLS12-381).
+ * GA_ERR_INVALID additionally for an unknown group. */
+int ga_lagrange_coeffs(ga_ctx* ctx, int curve, int group, const void* powers_affine, size_t n, unsigned flags, void* out_affine);
+
 /* ---- per-point scalar multiplication: the curve work of the Groth16 MPC ceremony ---------------------------
  * replaces: the ScalarMultiplication loops of backend/groth16/<curve>/mpcsetup -- SrsCommons.update (phase1.go:104-147: the i-th
  * point of G1.Tau, G2.Tau, G1.AlphaTau, G1.BetaTau times c * tau^i) and Phase2.update (phase2.go:110-135: Z and PKK times 1/delta,
@@ -188,6 +199,31 @@ int ga_kzg_to_lagrange_g1(ga_ctx* ctx, int curve, const void* powers_affine, siz
 #define GA_SCALE_POWERS 2   /* scalars: 2 fr elements (c, t);       out[i] = [c * t^(first + i)] points[i]   */
 int ga_scale_points(ga_ctx* ctx, int curve, int group, const void* points_affine, size_t n, int mode,
                     const void* scalars, uint64_t first, unsigned flags, void* out_affine, uint64_t* redone);
+
+/* ---- a sparse Fr matrix applied to a vector of points: the constraint loop of Phase2.Initialize ------------
+ * replaces: the loops of Phase2.Initialize in backend/groth16/<curve>/mpcsetup (phase2.go:224-247: every term (coeff, wire) of
+ * constraint i adds [coeff] coeffX[i] into out[wire], for A, beta A, B, B2, alpha B and C; :283-300: PKK / VKK / CKK = beta A + alpha B + C;
+ * :256-261: Z[i] = Tau[i + n] - Tau[i]), each as the rows of one matrix in CSR form (INTEGRATION.md has the table).
+ * out[r] = sum_{k = row_start[r]}^{row_start[r+1]-1} [coeffs[terms[k].cid]] points[terms[k].col],  r < n_rows;  an empty row is (0,0).
+ *   terms: nnz pairs of uint32 {cid, col} (the memory image of constraint.Term{CID, VID} with VID holding the column), row-major;
+ *   row_start: n_rows + 1 offsets, row_start[0] = 0, row_start[n_rows] = nnz;  coeffs: n_coeffs Fr values (gnark's r1cs.Coefficients).
+ *   row_start, terms and coeffs are host memory.  Flags: GA_BASES_ON_DEVICE (points), GA_RESULT_ON_DEVICE, GA_SCALARS_MONTGOMERY
+ *   (coeffs are fr.Element images; otherwise any 256-bit integers, reduced), GA_RESULT_BITREVERSED (n_rows a power of two: out[bitrev(r)]).
+ *   Points are not validated; input and output must not overlap.  *redone (may be NULL): work items that left the fast formulas.
+ * A coefficient is treated by its VALUE: 0 drops the term, +-1 and +-2 cost one addition (and one doubling), anything else one
+ * scalar multiplication by min(c, r - c).  A (0,0) point contributes nothing.  The bytes are gnark's affine images of the exact
+ * group elements whatever the schedule; `redone` counts products and row segments that met an exceptional addition (a repeated or
+ * cancelling operand) and were recomputed with the complete formulas -- 0 for generic inputs, never an error.
+ * GA_ERR_INVALID, before anything is launched: unknown curve or group; a null pointer (terms, coeffs and points may be null when
+ * nnz = 0); row_start[0] != 0 or row_start decreasing; nnz above 2^32 - 1, n_rows above 2^31 - 1; a cid >= n_coeffs or a
+ * col >= n_points; GA_RESULT_BITREVERSED with n_rows not a power of two.  n_rows = 0 is GA_OK and touches nothing.
+ * Device scratch, kept by the context: 8 B per term, 12 B per row segment, one extended point per row, per general term and per
+ * partial sum of a row longer than GA_SPARSE_SEGMENT (default 16) terms; per pass of at most GA_SPARSE_CHUNK general terms (default
+ * 2^20) the ladder's scratch of ga_scale_points; the staging of what is on the host.  GA_ERR_NOMEM when that does not fit: nothing
+ * is in flight and the context stays usable.  GA_SPARSE_ORDER=1 sorts the products by coefficient id (same bytes). */
+int ga_sparse_point_sums(ga_ctx* ctx, int curve, int group, const void* points_affine, size_t n_points,
+                         const uint64_t* row_start, size_t n_rows, const uint32_t* terms,
+                         const void* coeffs, size_t n_coeffs, unsigned flags, void* out_affine, uint64_t* redone);
 
 /* ---- MSM over pinned bases with precomputed window multiples ---------------------------------------------
  * (ICICLE's MSMConfig.PrecomputeFactor / precompute-bases, icicle.go:507-525.)  ga_msm_table_create uploads (or takes
