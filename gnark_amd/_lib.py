@@ -16,6 +16,7 @@ BN254, BLS12_381 = 0, 1
 G1, G2 = 0, 1
 BASES_ON_DEVICE, SCALARS_ON_DEVICE, SCALARS_MONTGOMERY, TABLE_BATCHED = 0x1, 0x2, 0x4, 0x10
 RESULT_ON_DEVICE, RESULT_BITREVERSED = 0x20, 0x40
+VECTOR_ON_DEVICE = BASES_ON_DEVICE
 SCALE_EACH, SCALE_ONE, SCALE_POWERS = 0, 1, 2
 FFT_FORWARD, FFT_INVERSE = 0, 1
 DIF, DIT = 0, 1
@@ -83,6 +84,10 @@ _PROTOS = {
     "ga_lagrange_coeffs": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_size_t, C.c_uint, _P]),
     "ga_sparse_point_sums": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_size_t, _P, C.c_size_t, _P, _P, C.c_size_t, C.c_uint, _P, C.POINTER(C.c_uint64)]),
     "ga_scale_points": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_size_t, C.c_int, _P, C.c_uint64, C.c_uint, _P, C.POINTER(C.c_uint64)]),
+    "ga_fr_lagrange_at": (C.c_int, [_P, C.c_int, C.c_uint64, _P, C.c_size_t, C.c_uint, _P]),
+    "ga_fr_sparse_matvec": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, C.c_size_t, _P, _P, C.c_size_t, _P, _P, C.c_size_t, C.c_uint, _P]),
+    "ga_fr_compact_nonzero": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.c_uint, _P, _P, C.POINTER(C.c_uint64)]),
+    "ga_fr_powers": (C.c_int, [_P, C.c_int, _P, C.c_uint64, C.c_size_t, C.c_uint, _P]),
     "ga_msm_table_create": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_size_t, C.c_uint, C.POINTER(_P)]),
     "ga_msm_table_destroy": (None, [_P]),
     "ga_msm_table_run": (C.c_int, [_P, _P, C.c_uint, _P]),

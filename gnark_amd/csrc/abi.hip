@@ -258,6 +258,20 @@ static uint64_t sparse_knob(const char* name) {
     return e ? strtoull(e, nullptr, 10) : 0;
 }
 
+// the Fr vector calls of groth16.Setup's scalar side (fr_sparse.hip.h, fr_setup.hip.h; instantiated in fr_setup_<curve>.hip).  One
+// run-time knob, read by the entry point itself like the ones above:
+//   GA_FR_SPARSE_SEGMENT terms, or partial sums, per lane of ga_fr_sparse_matvec: 2 .. 2^20; unset, 0 or 1 = the default
+//                        (FR_SPARSE_DEFAULT_SEGMENT); a larger value is taken as 2^20; tests force 2
+template <class C>
+int fr_sparse_run(Ctx* ctx, const void* x, size_t n_cols, const uint64_t* row_start, size_t n_rows, const uint32_t* terms, const void* coeffs,
+                  size_t n_coeffs, const uint8_t* row_class, const void* row_scales, size_t n_classes, unsigned flags, void* out, uint32_t segment);
+template <class C>
+int fr_lagrange_run(Ctx* ctx, int logn, const void* tau, size_t m, unsigned flags, void* out);
+template <class C>
+int fr_compact_run(Ctx* ctx, const void* v, size_t n, unsigned flags, void* out, uint8_t* mask, uint64_t* count);
+template <class C>
+int fr_powers_run(Ctx* ctx, const void* scalars, uint64_t first, size_t n, unsigned flags, void* out);
+
 // Bring inputs to the device when they are host pointers.
 struct Staged {
     Ctx* ctx;
@@ -667,6 +681,112 @@ int ga_sparse_point_sums(ga_ctx* h, int curve, int group, const void* points_aff
     GA_DISPATCH_CURVE(curve, GA_DISPATCH_GROUP(group, return (sparse_sums_run<C, G>(c, points_affine, n_points, row_start, n_rows, terms, coeffs, n_coeffs, flags,
                                                                                    out_affine, redone, forced_chunk,
                                                                                    (uint32_t)(segment < (1u << 20) ? segment : (1u << 20)), cid_order))));
+    return GA_OK;
+} GA_ABI_CATCH
+
+// ---- the scalar side of groth16.Setup (fr_sparse.hip.h, fr_setup.hip.h) -----------------------------------
+int ga_fr_lagrange_at(ga_ctx* h, int curve, uint64_t n, const void* tau, size_t m, unsigned flags, void* out) try {
+    GA_ABI_ENTRY();
+    Ctx* c = reinterpret_cast<Ctx*>(h);
+    if (curve != GA_BN254 && curve != GA_BLS12_381) {
+        set_error("ga_fr_lagrange_at: unknown curve id %d", curve);
+        return GA_ERR_INVALID;
+    }
+    int adicity = 0;
+    GA_DISPATCH_CURVE(curve, adicity = C::FrP::ADICITY);
+    if (n == 0 || (n & (n - 1)) != 0 || n > (1ull << adicity)) {
+        set_error("ga_fr_lagrange_at: n = %llu is not a power of two of at most 2^%d", (unsigned long long)n, adicity);
+        return GA_ERR_INVALID;
+    }
+    if ((uint64_t)m > n) {
+        set_error("ga_fr_lagrange_at: m = %zu above n = %llu", m, (unsigned long long)n);
+        return GA_ERR_INVALID;
+    }
+    if (m == 0) return GA_OK;
+    if (!c || !tau || !out) {
+        set_error("ga_fr_lagrange_at: null argument");
+        return GA_ERR_INVALID;
+    }
+    Lock l(c);
+    GA_DISPATCH_CURVE(curve, return fr_lagrange_run<C>(c, ilog2_u64(n), tau, m, flags, out));
+    return GA_OK;
+} GA_ABI_CATCH
+
+int ga_fr_sparse_matvec(ga_ctx* h, int curve, const void* x, size_t n_cols, const uint64_t* row_start, size_t n_rows, const uint32_t* terms,
+                        const void* coeffs, size_t n_coeffs, const uint8_t* row_class, const void* row_scales, size_t n_classes, unsigned flags,
+                        void* out) try {
+    GA_ABI_ENTRY();
+    Ctx* c = reinterpret_cast<Ctx*>(h);
+    if (curve != GA_BN254 && curve != GA_BLS12_381) {
+        set_error("ga_fr_sparse_matvec: unknown curve id %d", curve);
+        return GA_ERR_INVALID;
+    }
+    if (n_rows == 0) return GA_OK;
+    if ((uint64_t)n_rows >= (1ull << 31) || (uint64_t)n_cols > (1ull << 32) || (uint64_t)n_coeffs > (1ull << 32)) {
+        set_error("ga_fr_sparse_matvec: n_rows = %zu (at most 2^31 - 1), n_cols = %zu or n_coeffs = %zu (at most 2^32) out of range", n_rows, n_cols, n_coeffs);
+        return GA_ERR_INVALID;
+    }
+    if ((row_class == nullptr) != (row_scales == nullptr) || (row_class && (n_classes == 0 || n_classes > 256))) {
+        set_error("ga_fr_sparse_matvec: row_class and row_scales come together (both null, or 1 .. 256 classes)");
+        return GA_ERR_INVALID;
+    }
+    if (!c || !row_start || !out || (row_start[n_rows] != 0 && (!x || !terms || !coeffs))) {
+        set_error("ga_fr_sparse_matvec: null argument");
+        return GA_ERR_INVALID;
+    }
+    Lock l(c);
+    const uint64_t segment = sparse_knob("GA_FR_SPARSE_SEGMENT");
+    GA_DISPATCH_CURVE(curve, return fr_sparse_run<C>(c, x, n_cols, row_start, n_rows, terms, coeffs, n_coeffs, row_class, row_scales, n_classes, flags, out,
+                                                    (uint32_t)(segment < (1u << 20) ? segment : (1u << 20))));
+    return GA_OK;
+} GA_ABI_CATCH
+
+int ga_fr_compact_nonzero(ga_ctx* h, int curve, const void* v, size_t n, unsigned flags, void* out, uint8_t* mask, uint64_t* count) try {
+    GA_ABI_ENTRY();
+    Ctx* c = reinterpret_cast<Ctx*>(h);
+    if (curve != GA_BN254 && curve != GA_BLS12_381) {
+        set_error("ga_fr_compact_nonzero: unknown curve id %d", curve);
+        return GA_ERR_INVALID;
+    }
+    if (!count) {
+        set_error("ga_fr_compact_nonzero: null count");
+        return GA_ERR_INVALID;
+    }
+    if ((uint64_t)n >= (1ull << 31)) {
+        set_error("ga_fr_compact_nonzero: n = %zu, at most 2^31 - 1", n);
+        return GA_ERR_INVALID;
+    }
+    if (n == 0) {
+        *count = 0;
+        return GA_OK;
+    }
+    if (!c || !v || !out) {
+        set_error("ga_fr_compact_nonzero: null argument");
+        return GA_ERR_INVALID;
+    }
+    Lock l(c);
+    GA_DISPATCH_CURVE(curve, return fr_compact_run<C>(c, v, n, flags, out, mask, count));
+    return GA_OK;
+} GA_ABI_CATCH
+
+int ga_fr_powers(ga_ctx* h, int curve, const void* scalars, uint64_t first, size_t n, unsigned flags, void* out) try {
+    GA_ABI_ENTRY();
+    Ctx* c = reinterpret_cast<Ctx*>(h);
+    if (curve != GA_BN254 && curve != GA_BLS12_381) {
+        set_error("ga_fr_powers: unknown curve id %d", curve);
+        return GA_ERR_INVALID;
+    }
+    if ((uint64_t)n > (1ull << 32) || (n > 0 && first > UINT64_MAX - (uint64_t)n + 1)) {
+        set_error("ga_fr_powers: n = %zu above 2^32, or first + n above 2^64", n);
+        return GA_ERR_INVALID;
+    }
+    if (n == 0) return GA_OK;
+    if (!c || !scalars || !out) {
+        set_error("ga_fr_powers: null argument");
+        return GA_ERR_INVALID;
+    }
+    Lock l(c);
+    GA_DISPATCH_CURVE(curve, return fr_powers_run<C>(c, scalars, first, n, flags, out));
     return GA_OK;
 } GA_ABI_CATCH
 

@@ -28,6 +28,7 @@
 // Bounds of the unreduced sequence, G1 and G2: tools/lazy_bounds.py check_ladder(curve, fp2).
 #pragma once
 #include "ec_ntt.hip.h"   // ec_ntt_scalar_mul29, ec_ntt_pack / _unpack / _to_exact / _from_exact; fixed_base_affine_kernel
+#include "fr_powers.hip.h"   // fr_canonical, fr_power_term
 
 namespace ga {
 
@@ -50,16 +51,10 @@ scale_points_scalars_kernel(const uint32_t* __restrict__ in, uint32_t n, int mod
                             uint32_t* __restrict__ out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    auto canonical = [&](Fe<FrP> s) {
-        if (mont) return from_mont(s);
-#pragma unroll 1
-        for (int k = 0; k < 6; k++) reduce_once<FrP>(s.l);   // any 256-bit integer: below r after at most 2^256 / r < 6 steps
-        return s;
-    };
     Fe<FrP> s;
-    if (mode == GA_SCALE_EACH) s = canonical(load_fe<FrP>(in + (uint64_t)i * 8));
-    else if (mode == GA_SCALE_ONE) s = canonical(a);
-    else s = from_mont(mul(to_mont(canonical(a)), pow_u64(to_mont(canonical(b)), first + i)));
+    if (mode == GA_SCALE_EACH) s = fr_canonical(load_fe<FrP>(in + (uint64_t)i * 8), mont);
+    else if (mode == GA_SCALE_ONE) s = fr_canonical(a, mont);
+    else s = fr_power_term(a, b, mont, first + i);   // fr_powers.hip.h: shared with ga_fr_powers
     store_pod(out + (uint64_t)i * 8, s);
 }
 

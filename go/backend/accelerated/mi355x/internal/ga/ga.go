@@ -472,6 +472,48 @@ func (c *Context) SparsePointSums(curve Curve, group int, points unsafe.Pointer,
 	return uint64(r), err
 }
 
+// The four calls below are the scalar side of groth16.Setup (setupABC, the K and Z loops, the zero filter of setup.go) on the
+// device.  Every Fr vector is the memory of a []fr.Element with ScalarsMontgomery, of canonical 4-word integers without; the output
+// has the form of the input.  flags: BasesOnDevice for the input vector (x, v), ResultOnDevice for out.
+
+// LagrangeAt writes out[i] = L_i(tau), i < m <= n: the Lagrange basis of the size-n domain of fft.NewDomain(n) at one point, with
+// inv(0) = 0 as fr.BatchInvert leaves it (tau inside the domain gives zeros).  tau is one host element.
+func (c *Context) LagrangeAt(curve Curve, n uint64, tau unsafe.Pointer, m uint64, flags uint, out unsafe.Pointer) error {
+	return call("ga_fr_lagrange_at", func() C.int {
+		return C.ga_fr_lagrange_at(c.h, C.int(curve), C.uint64_t(n), tau, C.size_t(m), C.uint(flags), out)
+	})
+}
+
+// SparseMatVec applies a sparse Fr matrix in CSR form to an Fr vector: out[r] = s_r * sum over the terms k of row r of
+// coeffs[terms[k].CID] * x[terms[k].VID], with s_r = rowScales[rowClass[r]] (both nil: s_r = 1).  rowStart, terms and coeffs as in
+// SparsePointSums; rowClass holds nRows bytes and rowScales nClasses elements, host memory.  x and out must not overlap.
+func (c *Context) SparseMatVec(curve Curve, x unsafe.Pointer, nCols uint64, rowStart *uint64, nRows uint64, terms unsafe.Pointer,
+	coeffs unsafe.Pointer, nCoeffs uint64, rowClass *uint8, rowScales unsafe.Pointer, nClasses uint64, flags uint, out unsafe.Pointer) error {
+	return call("ga_fr_sparse_matvec", func() C.int {
+		return C.ga_fr_sparse_matvec(c.h, C.int(curve), x, C.size_t(nCols), (*C.uint64_t)(unsafe.Pointer(rowStart)), C.size_t(nRows),
+			(*C.uint32_t)(terms), coeffs, C.size_t(nCoeffs), (*C.uint8_t)(unsafe.Pointer(rowClass)), rowScales, C.size_t(nClasses),
+			C.uint(flags), out)
+	})
+}
+
+// CompactNonZero is the zero filter of setup.go:195-219: out receives the non-zero elements of v in order (out == v with the same
+// placement compacts in place), mask (nil, or n bytes of host memory: a []bool) is set where v[i] == 0, and the number kept is returned.
+func (c *Context) CompactNonZero(curve Curve, v unsafe.Pointer, n uint64, flags uint, out unsafe.Pointer, mask *bool) (kept uint64, err error) {
+	var k C.uint64_t
+	err = call("ga_fr_compact_nonzero", func() C.int {
+		return C.ga_fr_compact_nonzero(c.h, C.int(curve), v, C.size_t(n), C.uint(flags), out, (*C.uint8_t)(unsafe.Pointer(mask)), &k)
+	})
+	return uint64(k), err
+}
+
+// Powers writes out[i] = c * t^(first+i), i < n; scalars holds the two host elements (c, t): the Z scalars of setup.go:181-192
+// and the powers of tau of kzg.NewSRS.
+func (c *Context) Powers(curve Curve, scalars unsafe.Pointer, first uint64, n uint64, flags uint, out unsafe.Pointer) error {
+	return call("ga_fr_powers", func() C.int {
+		return C.ga_fr_powers(c.h, C.int(curve), scalars, C.uint64_t(first), C.size_t(n), C.uint(flags), out)
+	})
+}
+
 // Table is a pinned base vector with its window multiples (ga_msm_table_*): the KZG SRS of a PLONK key.
 type Table struct {
 	h *C.ga_msm_table

@@ -225,6 +225,62 @@ int ga_sparse_point_sums(ga_ctx* ctx, int curve, int group, const void* points_a
                          const uint64_t* row_start, size_t n_rows, const uint32_t* terms,
                          const void* coeffs, size_t n_coeffs, unsigned flags, void* out_affine, uint64_t* redone);
 
+/* ---- the scalar side of groth16.Setup: Fr vectors that never leave the device ------------------------------
+ * With these four calls groth16.Setup runs from (toxic waste, R1CS matrices) to a pinned proving key without a scalar or a point
+ * crossing PCIe: their outputs feed ga_batch_scalar_mul(..., GA_SCALARS_ON_DEVICE | GA_RESULT_ON_DEVICE), whose outputs feed
+ * ga_g16_builder_* / ga_msm_table_create(..., GA_BASES_ON_DEVICE).  INTEGRATION.md ("Setup on the device") has the table.
+ * Every Fr vector is 4x64-bit little-endian words per element.  Without GA_SCALARS_MONTGOMERY every input element (vectors,
+ * coefficients, scales, tau, (c, t)) is a canonical integer -- any 256-bit value, reduced mod r -- and every output element is canonical
+ * and below r: what ga_batch_scalar_mul takes without a flag and what setup.go feeds it.  With GA_SCALARS_MONTGOMERY inputs and outputs
+ * are fr.Element images.  All results are exact field elements.  Placement: GA_VECTOR_ON_DEVICE for the input vector (`x`, `v`),
+ * GA_RESULT_ON_DEVICE for `out`; everything else is host memory.  GA_ERR_NOMEM (device scratch) leaves nothing in flight and the
+ * context usable. */
+#define GA_VECTOR_ON_DEVICE GA_BASES_ON_DEVICE   /* ga_fr_sparse_matvec: `x`, ga_fr_compact_nonzero: `v` is a device pointer */
+
+/* replaces: the Lagrange values of setupABC (backend/groth16/bn254/setup.go:356-421: a running product over the domain, then one
+ * fr.BatchInvert).  out[i] = L_i(tau), i < m <= n, over the domain fft.NewDomain(n) builds (generator = fr_root_of_unity(n)):
+ * L_i = (tau^n - 1) * n^-1 * w^i * inv(tau - w^i) with inv(0) = 0 as fr.BatchInvert leaves zeros -- for tau inside the domain
+ * tau^n - 1 = 0 and every output is 0, which is what the reference produces.  tau: one host element.
+ * GA_ERR_INVALID: unknown curve; a null pointer with m > 0; n not a power of two or above 2^28 (BN254) / 2^32 (BLS12-381), the
+ * two-adicity of r; m > n.  m = 0 is GA_OK and touches nothing.
+ * Device scratch, kept by the context: 3 x 32 B per element (differences and the batch inversion's two buffers), and 32 B per element
+ * of staging when `out` is on the host. */
+int ga_fr_lagrange_at(ga_ctx* ctx, int curve, uint64_t n, const void* tau, size_t m, unsigned flags, void* out);
+
+/* replaces: the term loops of setupABC (setup.go:346-428: every term (coeff, wire) of constraint i adds coeff * L_i(tau) into A[wire],
+ * B[wire], C[wire]) and the K loop (:142-178: (beta A + alpha B + C) / delta, or / gamma for public, commitment and private-committed
+ * wires), each as the rows of one matrix in CSR form -- the Fr twin of ga_sparse_point_sums, with the same memory image.
+ * out[r] = s_r * sum_{k = row_start[r]}^{row_start[r+1]-1} coeffs[terms[k].cid] * x[terms[k].col],  r < n_rows;  an empty row gives 0.
+ *   x: n_cols elements, host, or device with GA_VECTOR_ON_DEVICE; terms, row_start, coeffs (n_coeffs elements): as in
+ *   ga_sparse_point_sums, host memory;  s_r = row_scales[row_class[r]]: row_class n_rows bytes, row_scales n_classes (1 .. 256)
+ *   elements, host; both NULL means s_r = 1.  `x` and `out` must not overlap.  Coefficients are not classified by value: a zero one
+ *   contributes zero by arithmetic.
+ * GA_ERR_INVALID, before anything is written: unknown curve; a null pointer (x, terms and coeffs may be null when nnz = 0); only one
+ * of row_class / row_scales null, or n_classes outside 1 .. 256; row_start[0] != 0 or row_start decreasing; nnz above 2^32 - 1,
+ * n_rows above 2^31 - 1; a cid >= n_coeffs, a col >= n_cols or a row_class[r] >= n_classes.  n_rows = 0 is GA_OK and touches nothing.
+ * Device scratch, kept by the context: 8 B per term, 12 B per row segment, 32 B per coefficient and per partial sum of a row longer
+ * than GA_FR_SPARSE_SEGMENT (environment, default 32) terms, 1 B per row of classes; the staging of what is on the host. */
+int ga_fr_sparse_matvec(ga_ctx* ctx, int curve, const void* x, size_t n_cols, const uint64_t* row_start, size_t n_rows,
+                        const uint32_t* terms, const void* coeffs, size_t n_coeffs, const uint8_t* row_class,
+                        const void* row_scales, size_t n_classes, unsigned flags, void* out);
+
+/* replaces: the zero filter of setup.go:195-219 (A and B lose their zero entries before the point stage; InfinityA / InfinityB
+ * remember where they were).  out receives the non-zero elements of v in order -- moved, not converted: zero is zero in both forms --,
+ * mask[i] = 1 where v[i] == 0 (host, n bytes, may be NULL), *count = the number kept.  Elements of out past *count are not written.
+ * out == v (the same pointer AND the same placement) compacts in place, as the reference does; any other overlap is the caller's error.
+ * GA_ERR_INVALID: unknown curve; a null pointer (count always; v, out with n > 0); n above 2^31 - 1.  n = 0 sets *count = 0.
+ * Device scratch, kept by the context: 8 B per element and the scan's temporary storage; n bytes of mask; 32 B per element for each
+ * of: `v` on the host, `out` on the host or in place. */
+int ga_fr_compact_nonzero(ga_ctx* ctx, int curve, const void* v, size_t n, unsigned flags, void* out, uint8_t* mask,
+                          uint64_t* count);
+
+/* replaces: the Z scalars of setup.go:181-192 (tau^i * (tau^n - 1) / delta) and the powers of tau of kzg.NewSRS.
+ * out[i] = c * t^(first + i), i < n;  scalars: the two elements (c, t), host.  The progression ga_scale_points generates for
+ * GA_SCALE_POWERS, written out as a vector.  first + n must not exceed 2^64.
+ * GA_ERR_INVALID: unknown curve; a null pointer with n > 0; n above 2^32 or first + n above 2^64.  n = 0 is GA_OK and touches nothing.
+ * Device scratch: 32 B per element of staging when `out` is on the host. */
+int ga_fr_powers(ga_ctx* ctx, int curve, const void* scalars, uint64_t first, size_t n, unsigned flags, void* out);
+
 /* ---- MSM over pinned bases with precomputed window multiples ---------------------------------------------
  * (ICICLE's MSMConfig.PrecomputeFactor / precompute-bases, icicle.go:507-525.)  ga_msm_table_create uploads (or takes
  * from the device) n affine bases and stores [2^(c*w)]P_i for every window w: windows x n points, sized for the
