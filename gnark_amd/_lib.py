@@ -15,7 +15,8 @@ GA_OK = 0
 BN254, BLS12_381 = 0, 1
 G1, G2 = 0, 1
 BASES_ON_DEVICE, SCALARS_ON_DEVICE, SCALARS_MONTGOMERY, TABLE_BATCHED = 0x1, 0x2, 0x4, 0x10
-RESULT_ON_DEVICE, RESULT_BITREVERSED = 0x20, 0x40
+RESULT_ON_DEVICE, RESULT_BITREVERSED, CHECK_CURVE_ONLY = 0x20, 0x40, 0x80
+POINT_OK, POINT_OFF_CURVE, POINT_NOT_IN_SUBGROUP = 0, 1, 2
 VECTOR_ON_DEVICE = BASES_ON_DEVICE
 SCALE_EACH, SCALE_ONE, SCALE_POWERS = 0, 1, 2
 FFT_FORWARD, FFT_INVERSE = 0, 1
@@ -83,6 +84,7 @@ _PROTOS = {
     "ga_kzg_to_lagrange_g1": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.c_uint, _P]),
     "ga_lagrange_coeffs": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_size_t, C.c_uint, _P]),
     "ga_sparse_point_sums": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_size_t, _P, C.c_size_t, _P, _P, C.c_size_t, C.c_uint, _P, C.POINTER(C.c_uint64)]),
+    "ga_check_points": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_size_t, C.c_uint, _P, C.POINTER(C.c_uint64)]),
     "ga_scale_points": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_size_t, C.c_int, _P, C.c_uint64, C.c_uint, _P, C.POINTER(C.c_uint64)]),
     "ga_fr_lagrange_at": (C.c_int, [_P, C.c_int, C.c_uint64, _P, C.c_size_t, C.c_uint, _P]),
     "ga_fr_sparse_matvec": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, C.c_size_t, _P, _P, C.c_size_t, _P, _P, C.c_size_t, C.c_uint, _P]),
@@ -138,6 +140,8 @@ _PROTOS = {
     "ga_g16_prove_multi": (C.c_int, [C.POINTER(_P), C.c_uint32, _P, _P, _P, _P, C.c_uint64, C.c_uint64, _P, _P, _P]),
     "ga_g16_pk_read_mem": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.c_int32, C.c_uint32, C.c_uint32, _P, C.c_uint64, C.POINTER(_P), C.POINTER(C.c_uint64)]),
     "ga_g16_pk_read_fd": (C.c_int, [_P, C.c_int, C.c_int, C.c_int32, C.c_uint32, C.c_uint32, _P, C.c_uint64, C.POINTER(_P), C.POINTER(C.c_uint64)]),
+    "ga_g16_pk_read_mem_checked": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.c_int32, C.c_uint32, C.c_uint32, _P, C.c_uint64, C.POINTER(_P), C.POINTER(C.c_uint64)]),
+    "ga_g16_pk_read_fd_checked": (C.c_int, [_P, C.c_int, C.c_int, C.c_int32, C.c_uint32, C.c_uint32, _P, C.c_uint64, C.POINTER(_P), C.POINTER(C.c_uint64)]),
     "ga_g16_key_write_fd": (C.c_int, [_P, C.POINTER(G16Key), C.c_int, C.c_int, C.POINTER(C.c_uint64)]),
     "ga_g16_proof_unmarshal": (C.c_int, [C.c_int, _P, C.c_size_t, _P, _P, C.c_uint32, C.POINTER(C.c_uint32), _P, C.POINTER(C.c_size_t)]),
     "ga_point_unmarshal": (C.c_int, [C.c_int, C.c_int, _P, C.c_size_t, _P, C.POINTER(C.c_size_t)]),

@@ -245,6 +245,21 @@ static uint64_t scale_forced_chunk() {
     return e ? strtoull(e, nullptr, 10) : 0;
 }
 
+// batch curve and subgroup checks (check_points.hip.h; instantiated in check_points_<curve>_g<k>.hip).  Two run-time knobs, read by the
+// entry point itself like the ones above:
+//   GA_CHECK_NAIVE       1: the definitional test [r - 1]P = -P on the plain ladder (the A/B of tools/check_points_bench.py); default 0
+//   GA_CHECK_CHUNK       points per pass (0 = 2^20, at most 2^30; tests force a small chunk)
+template <class C, int G>
+int check_points_run(Ctx* ctx, const void* points, size_t n, unsigned flags, uint8_t* status, uint64_t* out4, int naive, uint64_t forced_chunk);
+static int check_naive() {
+    const char* e = getenv("GA_CHECK_NAIVE");
+    return e ? atoi(e) != 0 : 0;
+}
+static uint64_t check_forced_chunk() {
+    const char* e = getenv("GA_CHECK_CHUNK");
+    return e ? strtoull(e, nullptr, 10) : 0;
+}
+
 // sparse point sums (sparse_sums.hip.h; instantiated in sparse_sums_<curve>_g<k>.hip).  Three run-time knobs, read by the entry point
 // itself like the ones above:
 //   GA_SPARSE_CHUNK      general terms (products) per pass (0 = 2^20, at most 2^30; tests force a small chunk)
@@ -646,6 +661,34 @@ int ga_scale_points(ga_ctx* h, int curve, int group, const void* points_affine, 
     const uint64_t forced_chunk = scale_forced_chunk();
     GA_DISPATCH_CURVE(curve, GA_DISPATCH_GROUP(group, return (scale_points_run<C, G>(c, points_affine, n, mode, scalars, first, flags, out_affine, redone,
                                                                                     windowed, forced_chunk))));
+    return GA_OK;
+} GA_ABI_CATCH
+
+// ---- batch curve and subgroup checks (check_points.hip.h) ---------------------------------------------------
+int ga_check_points(ga_ctx* h, int curve, int group, const void* points_affine, size_t n, unsigned flags, uint8_t* status, uint64_t* out4) try {
+    GA_ABI_ENTRY();
+    Ctx* c = reinterpret_cast<Ctx*>(h);
+    if ((curve != GA_BN254 && curve != GA_BLS12_381) || (group != GA_G1 && group != GA_G2)) {
+        set_error("ga_check_points: unknown curve id %d or group id %d", curve, group);
+        return GA_ERR_INVALID;
+    }
+    if ((uint64_t)n > (1ull << 32)) {
+        set_error("ga_check_points: n = %zu above 2^32", n);
+        return GA_ERR_INVALID;
+    }
+    if (!out4 || (n > 0 && (!c || !points_affine))) {
+        set_error("ga_check_points: null argument");
+        return GA_ERR_INVALID;
+    }
+    if (n == 0) {
+        out4[0] = out4[1] = out4[3] = 0;
+        out4[2] = UINT64_MAX;
+        return GA_OK;
+    }
+    Lock l(c);
+    const int naive = check_naive();
+    const uint64_t forced_chunk = check_forced_chunk();
+    GA_DISPATCH_CURVE(curve, GA_DISPATCH_GROUP(group, return (check_points_run<C, G>(c, points_affine, n, flags, status, out4, naive, forced_chunk))));
     return GA_OK;
 } GA_ABI_CATCH
 

@@ -12,16 +12,61 @@
 
 namespace ga {
 
+// ---- checked reads: ProvingKey.ReadFrom semantics (ga_g16_pk_read_*_checked) ------------------------------------------------------------
+// Every point the read keeps is tested for curve and subgroup membership where it first sits on the device (check_points.hip.h,
+// instantiated in check_points_<curve>_g<k>.hip): an encoded vector chunk by chunk in the staging buffer, right behind the decode
+// kernel and beside the file read of the next chunk; a dumped slice once it is uploaded; a header point from its host image.
+// The first bad point of a vector ends the read: GA_ERR_INVALID naming the vector, the index within the FILE's vector and the failure.
+template <class C, int G>
+int check_points_run(Ctx* ctx, const void* points, size_t n, unsigned flags, uint8_t* status, uint64_t* out4, int naive, uint64_t forced_chunk);
+template <class C, int G>
+int check_points_resident(Ctx* ctx, hipStream_t st, const void* d_points, uint64_t n, uint64_t base, int reset, int naive);
+template <class C, int G>
+int check_points_tally(Ctx* ctx, hipStream_t st, uint64_t* out4, int* first_status);
+
+static const char* key_vector_name(int which, int commitment_half) {
+    static const char* const names[GA_KEY_NB_VECTORS] = {"G1.A", "G1.B", "G1.Z", "G1.K", "G2.B"};
+    if (which >= 0 && which < GA_KEY_NB_VECTORS) return names[which];
+    return commitment_half ? "a commitment key's BasisExpSigma" : "a commitment key's Basis";
+}
+static int key_check_naive() {
+    const char* e = getenv("GA_CHECK_NAIVE");
+    return e ? atoi(e) != 0 : 0;
+}
+static int key_check_verdict(const char* name, const uint64_t* out4, int first_status) {
+    if (first_status == GA_POINT_OK) return GA_OK;
+    set_error("key file: point %llu of %s is %s (%llu of the points kept are off the curve, %llu outside the subgroup)", (unsigned long long)out4[2], name,
+              first_status == GA_POINT_OFF_CURVE ? "not on the curve" : "not in the prime-order subgroup", (unsigned long long)out4[0],
+              (unsigned long long)out4[1]);
+    return GA_ERR_INVALID;
+}
+// cnt points on the device whose first is point `base` of the file's vector; drains the stream
+template <class C, int G>
+static int key_check_resident(Ctx* ctx, const void* d_points, uint64_t cnt, uint64_t base, const char* name) {
+    uint64_t out4[4];
+    int first = GA_POINT_OK;
+    GA_CHECK((check_points_resident<C, G>(ctx, ctx->stream, d_points, cnt, base, 1, key_check_naive())));
+    GA_CHECK((check_points_tally<C, G>(ctx, ctx->stream, out4, &first)));
+    return key_check_verdict(name, out4, first);
+}
+template <class C, int G>
+static int key_check_header_point(Ctx* ctx, const std::vector<uint8_t>& image, const char* name) {
+    uint64_t out4[4];
+    GA_CHECK((check_points_run<C, G>(ctx, image.data(), 1, 0, nullptr, out4, key_check_naive(), 0)));
+    return key_check_verdict(name, out4, out4[0] ? GA_POINT_OFF_CURVE : out4[1] ? GA_POINT_NOT_IN_SUBGROUP : GA_POINT_OK);
+}
+
 // ---- key files -> staged key (keyio.hip.h has the formats) --------------------------------------------------------------------------
 // `count` encoded points of group G from `src`: decoded on the device, the part inside [keep_lo, keep_lo + keep_cnt) lands at d_dst
 template <class C, int G>
 static int decode_stream(Ctx* ctx, Staging& sg, ByteSource& src, uint64_t count, bool compressed, void* d_dst, uint64_t keep_lo,
-                         uint64_t keep_cnt) {
+                         uint64_t keep_cnt, const char* check_name = nullptr) {   // check_name: a checked read, and what to call the vector
     typedef typename GroupField<C, G>::F F;
     const size_t enc = compressed ? sizeof(F) : 2 * sizeof(F), psz = sizeof(Affine<F>);
     const uint64_t per_chunk = Staging::BYTES / enc;
     GA_HIP_CHECK(hipMemsetAsync(sg.d_bad, 0, 4, ctx->stream));
-    int k = 0;
+    const int naive = check_name ? key_check_naive() : 0;
+    int k = 0, tally = 0;
     for (uint64_t done = 0; done < count; k ^= 1) {
         const uint64_t cn = count - done < per_chunk ? count - done : per_chunk;
         GA_HIP_CHECK(hipEventSynchronize(sg.ev[k]));   // the previous copy out of this staging buffer has finished
@@ -33,9 +78,14 @@ static int decode_stream(Ctx* ctx, Staging& sg, ByteSource& src, uint64_t count,
         GA_KERNEL_CHECK();
         const uint64_t b0 = done > keep_lo ? done : keep_lo;
         const uint64_t e0 = done + cn < keep_lo + keep_cnt ? done + cn : keep_lo + keep_cnt;
-        if (e0 > b0)
+        if (e0 > b0) {
             GA_HIP_CHECK(hipMemcpyAsync((char*)d_dst + (b0 - keep_lo) * psz, (const char*)sg.d_points + (b0 - done) * psz, (e0 - b0) * psz,
                                         hipMemcpyDeviceToDevice, ctx->stream));
+            if (check_name) {   // the kept part of the staged chunk (a point that does not decode is (0,0) here and counted in d_bad)
+                GA_CHECK((check_points_resident<C, G>(ctx, ctx->stream, (const char*)sg.d_points + (b0 - done) * psz, e0 - b0, b0, tally == 0, naive)));
+                tally = 1;
+            }
+        }
         done += cn;
     }
     uint32_t bad = 0;
@@ -46,6 +96,12 @@ static int decode_stream(Ctx* ctx, Staging& sg, ByteSource& src, uint64_t count,
                   (unsigned long long)count);
         return GA_ERR_INVALID;
     }
+    if (tally) {
+        uint64_t out4[4];
+        int first = GA_POINT_OK;
+        GA_CHECK((check_points_tally<C, G>(ctx, ctx->stream, out4, &first)));
+        GA_CHECK(key_check_verdict(check_name, out4, first));
+    }
     return GA_OK;
 }
 
@@ -54,7 +110,8 @@ static int decode_stream(Ctx* ctx, Staging& sg, ByteSource& src, uint64_t count,
 // unknown, guess from the first byte of the vector (a vector that starts with a point at infinity is then ambiguous on BN254,
 // whose infinity flag is the same in both encodings)
 template <class C, int G>
-static int read_encoded_vector(G16Stage* st, Staging& sg, ByteSource& src, int which, void** d_plain, uint64_t* len_out, int mode = -1) {
+static int read_encoded_vector(G16Stage* st, Staging& sg, ByteSource& src, int which, void** d_plain, uint64_t* len_out, int mode = -1,
+                               int commitment_half = 0) {
     typedef typename GroupField<C, G>::F F;
     uint32_t len = 0;
     GA_CHECK(src.u32be(&len));
@@ -74,7 +131,7 @@ static int read_encoded_vector(G16Stage* st, Staging& sg, ByteSource& src, int w
     if (which >= 0) {
         GA_CHECK(stage_reserve(st, which, len));
         G16Stage::Vec& x = st->v[which];
-        GA_CHECK((decode_stream<C, G>(st->ctx, sg, src, len, compressed, x.d, x.lo, x.cnt)));
+        GA_CHECK((decode_stream<C, G>(st->ctx, sg, src, len, compressed, x.d, x.lo, x.cnt, st->checked ? key_vector_name(which, 0) : nullptr)));
         x.seen = len;
         return GA_OK;
     }
@@ -84,12 +141,12 @@ static int read_encoded_vector(G16Stage* st, Staging& sg, ByteSource& src, int w
         set_error("key file: hipMalloc of a commitment basis failed: %s", hipGetErrorString(e));
         return GA_ERR_NOMEM;
     }
-    return decode_stream<C, G>(st->ctx, sg, src, len, compressed, *d_plain, 0, len);
+    return decode_stream<C, G>(st->ctx, sg, src, len, compressed, *d_plain, 0, len, st->checked ? key_vector_name(which, commitment_half) : nullptr);
 }
 
 // a slice of unsafe.WriteSlice: u64 LE length + gnark's own memory image; no arithmetic, file -> pinned buffer -> HBM
 template <class C, int G>
-static int read_dumped_vector(G16Stage* st, Staging& sg, ByteSource& src, int which, void** d_plain, uint64_t* len_out) {
+static int read_dumped_vector(G16Stage* st, Staging& sg, ByteSource& src, int which, void** d_plain, uint64_t* len_out, int commitment_half = 0) {
     typedef typename GroupField<C, G>::F F;
     const size_t psz = sizeof(Affine<F>);
     uint64_t len = 0;
@@ -122,6 +179,14 @@ static int read_dumped_vector(G16Stage* st, Staging& sg, ByteSource& src, int wh
         done += cn;
     }
     GA_HIP_CHECK(hipStreamSynchronize(st->ctx->stream));
+    if (st->checked) {   // a dump is raw memory: nothing has looked at these bytes yet
+        if (len > (1ull << 32)) {
+            set_error("key dump: a checked read takes slices of at most 2^32 points, this one has %llu", (unsigned long long)len);
+            return GA_ERR_INVALID;
+        }
+        if (which >= 0) GA_CHECK((key_check_resident<C, G>(st->ctx, st->v[which].d, st->v[which].cnt, st->v[which].lo, key_vector_name(which, 0))));
+        else GA_CHECK((key_check_resident<C, G>(st->ctx, plain, len, 0, key_vector_name(which, commitment_half))));
+    }
     return GA_OK;
 }
 
@@ -189,9 +254,10 @@ static bool source_is_dump(ByteSource& src) {
 
 template <class C>
 static int pk_read(Ctx* ctx, ByteSource& src, int32_t precompute, uint32_t shard_index, uint32_t shard_count, const uint64_t* k_remove,
-                   uint64_t len_k_remove, G16Pk** out) {
+                   uint64_t len_k_remove, G16Pk** out, bool checked) {
     G16Stage st;
     st.ctx = ctx;
+    st.checked = checked;
     st.curve = C::ID;
     st.shard_index = shard_index;
     st.shard_count = shard_count ? shard_count : 1;
@@ -271,11 +337,18 @@ static int pk_read(Ctx* ctx, ByteSource& src, int32_t precompute, uint32_t shard
         set_error("key file: implausible number of commitment keys %u", nb_commitments);
         return GA_ERR_INVALID;
     }
+    if (checked) {   // the header points: decoded on the host (the curve equation) in either format
+        GA_CHECK((key_check_header_point<C, GA_G1>(ctx, st.pts[GA_KEY_G1_ALPHA], "[alpha]1")));
+        GA_CHECK((key_check_header_point<C, GA_G1>(ctx, st.pts[GA_KEY_G1_BETA], "[beta]1")));
+        GA_CHECK((key_check_header_point<C, GA_G1>(ctx, st.pts[GA_KEY_G1_DELTA], "[delta]1")));
+        GA_CHECK((key_check_header_point<C, GA_G2>(ctx, st.pts[GA_KEY_G2_BETA], "[beta]2")));
+        GA_CHECK((key_check_header_point<C, GA_G2>(ctx, st.pts[GA_KEY_G2_DELTA], "[delta]2")));
+    }
     for (uint32_t i = 0; i < nb_commitments; i++) {   // pedersen.ProvingKey: Basis, BasisExpSigma
         void *db = nullptr, *ds = nullptr;
         uint64_t lb = 0, ls = 0;
         int rc = dump ? read_dumped_vector<C, GA_G1>(&st, sg, src, -1, &db, &lb) : read_encoded_vector<C, GA_G1>(&st, sg, src, -1, &db, &lb, mode);
-        if (rc == GA_OK) rc = dump ? read_dumped_vector<C, GA_G1>(&st, sg, src, -1, &ds, &ls) : read_encoded_vector<C, GA_G1>(&st, sg, src, -1, &ds, &ls, mode);
+        if (rc == GA_OK) rc = dump ? read_dumped_vector<C, GA_G1>(&st, sg, src, -1, &ds, &ls, 1) : read_encoded_vector<C, GA_G1>(&st, sg, src, -1, &ds, &ls, mode, 1);
         if (rc == GA_OK && lb != ls) {
             set_error("key file: commitment key %u has %llu basis points and %llu sigma points", i, (unsigned long long)lb, (unsigned long long)ls);
             rc = GA_ERR_INVALID;
@@ -476,9 +549,9 @@ static int marshal(const void* proof, const void* commitments, uint32_t ncom, co
     return GA_OK;
 }
 
-// ga_g16_pk_read_mem / _fd: a key file from either source
+// ga_g16_pk_read_mem / _fd and their _checked forms: a key file from either source
 static int pk_read_any(ga_ctx* h, int curve, ByteSource& src, int32_t precompute, uint32_t shard_index, uint32_t shard_count,
-                       const uint64_t* k_remove, uint64_t len_k_remove, ga_g16_pk** out, uint64_t* bytes_read) {
+                       const uint64_t* k_remove, uint64_t len_k_remove, ga_g16_pk** out, uint64_t* bytes_read, bool checked = false) {
     Ctx* ctx = reinterpret_cast<Ctx*>(h);
     if (!ctx || !out || (len_k_remove && !k_remove)) {
         set_error("ga_g16_pk_read: null argument");
@@ -486,7 +559,7 @@ static int pk_read_any(ga_ctx* h, int curve, ByteSource& src, int32_t precompute
     }
     CtxLock g(ctx);
     G16Pk* pk = nullptr;
-    GA_DISPATCH_CURVE(curve, GA_CHECK(pk_read<C>(ctx, src, precompute, shard_index, shard_count, k_remove, len_k_remove, &pk)));
+    GA_DISPATCH_CURVE(curve, GA_CHECK(pk_read<C>(ctx, src, precompute, shard_index, shard_count, k_remove, len_k_remove, &pk, checked)));
     *out = reinterpret_cast<ga_g16_pk*>(pk);
     if (bytes_read) *bytes_read = src.consumed;
     return GA_OK;

@@ -140,6 +140,7 @@ struct G16Stage {
     uint64_t n = 0, nb_wires = 0;
     uint32_t shard_index = 0, shard_count = 1;
     uint32_t win_index = 0, win_count = 1;
+    bool checked = false;                        // ga_g16_pk_read_*_checked: every kept point goes through check_points.hip.h (g16_io.hip.h)
     struct Vec {
         void* d = nullptr;
         uint64_t total = 0, lo = 0, cnt = 0, seen = 0;

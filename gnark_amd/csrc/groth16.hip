@@ -990,6 +990,32 @@ int ga_g16_pk_read_fd(ga_ctx* h, int curve, int fd, int32_t precompute, uint32_t
     return pk_read_any(h, curve, src, precompute, shard_index, shard_count, k_remove, len_k_remove, out, bytes_read);
 } GA_ABI_CATCH
 
+// ProvingKey.ReadFrom semantics: every point kept is tested for curve and subgroup membership (g16_io.hip.h, check_points.hip.h)
+int ga_g16_pk_read_mem_checked(ga_ctx* h, int curve, const uint8_t* data, size_t len, int32_t precompute, uint32_t shard_index, uint32_t shard_count,
+                               const uint64_t* k_remove, uint64_t len_k_remove, ga_g16_pk** out, uint64_t* bytes_read) try {
+    GA_ABI_ENTRY();
+    if (!data) {
+        set_error("ga_g16_pk_read_mem_checked: null data");
+        return GA_ERR_INVALID;
+    }
+    ByteSource src;
+    src.mem = data;
+    src.mem_len = len;
+    return pk_read_any(h, curve, src, precompute, shard_index, shard_count, k_remove, len_k_remove, out, bytes_read, true);
+} GA_ABI_CATCH
+
+int ga_g16_pk_read_fd_checked(ga_ctx* h, int curve, int fd, int32_t precompute, uint32_t shard_index, uint32_t shard_count, const uint64_t* k_remove,
+                              uint64_t len_k_remove, ga_g16_pk** out, uint64_t* bytes_read) try {
+    GA_ABI_ENTRY();
+    if (fd < 0) {
+        set_error("ga_g16_pk_read_fd_checked: bad file descriptor");
+        return GA_ERR_INVALID;
+    }
+    ByteSource src;
+    src.fd = fd;
+    return pk_read_any(h, curve, src, precompute, shard_index, shard_count, k_remove, len_k_remove, out, bytes_read, true);
+} GA_ABI_CATCH
+
 int ga_g16_key_write_fd(ga_ctx* h, const ga_g16_key* key, int format, int fd, uint64_t* bytes_written) try {
     GA_ABI_ENTRY();
     Ctx* ctx = reinterpret_cast<Ctx*>(h);

@@ -195,7 +195,7 @@ GA_HD bool point_decode(const uint8_t* b, bool compressed, Affine<typename Group
         if (fe_lex_largest(y) != f.largest) y = neg(y);
     } else {
         if (!coord_from_bytes(b + CB, 0xFF, &y)) return false;
-        if (!eq(sqr(y), rhs)) return false;              // on-curve check (subgroup membership is NOT checked: UnsafeReadFrom semantics)
+        if (!eq(sqr(y), rhs)) return false;              // on-curve check (subgroup membership is not checked HERE: the _checked readers of g16_io.hip.h do it)
     }
     out->x = x;
     out->y = y;

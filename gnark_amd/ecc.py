@@ -121,6 +121,50 @@ def ToLagrangeG1(ctx: Context, curve, powers, n: int | None = None, out_device: 
     return out
 
 
+POINT_OK, POINT_OFF_CURVE, POINT_NOT_IN_SUBGROUP = _lib.POINT_OK, _lib.POINT_OFF_CURVE, _lib.POINT_NOT_IN_SUBGROUP
+NONE_BAD = 0xFFFFFFFFFFFFFFFF   # `first` when every point is OK
+
+
+def CheckPoints(ctx: Context, curve, group: int, points, n: int | None = None, curve_only: bool = False, status_device: bool = False,
+                status: bool = True):
+    """G1Affine / G2Affine.IsOnCurve and IsInSubGroup for a whole vector (ga_check_points) -- what gnark-crypto's default decoder
+    does for every point of a ProvingKey.ReadFrom, of the ReadFrom of an mpcsetup phase and of kzg.SRS.ReadFrom.
+
+    points : (n, affine_words) uint64 array of G1Affine / G2Affine images, or a DeviceBuffer of n points (then n is required);
+             never written.  Any bytes are accepted: a coordinate that is not below p makes its point POINT_OFF_CURVE.
+    curve_only: the curve equation alone (IsOnCurve).
+    Returns (status, off_curve, outside, first, redone): status is an (n,) uint8 array of POINT_OK / POINT_OFF_CURVE /
+    POINT_NOT_IN_SUBGROUP, a DeviceBuffer of n bytes with status_device=True (the caller frees it), None with status=False;
+    off_curve and outside count the two failures, first is the index of the first point that is not OK (NONE_BAD if all are),
+    redone counts the points decided by [r]P with the complete formulas (0 on honest input).  Bad points are not an error.
+    """
+    cid = curve_id(curve)
+    wa = affine_words(cid, group)
+    if not isinstance(points, (DeviceBuffer, int)):
+        points = as_u64(points, wa)
+        n = points.shape[0]
+    if n is None:
+        raise ValueError("n is required for device-resident points")
+    pp, flags = _arg(points, _lib.BASES_ON_DEVICE)
+    if curve_only:
+        flags |= _lib.CHECK_CURVE_ONLY
+    out4 = (C.c_uint64 * 4)()
+    res, sp = None, C.c_void_p(None)
+    if status and status_device:
+        res = ctx.malloc(max(n, 1))
+        sp, flags = C.c_void_p(res.ptr), flags | _lib.RESULT_ON_DEVICE
+    elif status:
+        res = np.zeros(n, dtype=np.uint8)
+        sp = _ptr(res)
+    try:
+        ctx.lib.check(ctx.lib.ga_check_points(ctx.handle, cid, group, pp, n, flags, sp, out4))
+    except Exception:
+        if isinstance(res, DeviceBuffer):
+            res.free()
+        raise
+    return res, int(out4[0]), int(out4[1]), int(out4[2]), int(out4[3])
+
+
 def ScalePoints(ctx: Context, curve, group: int, points, scalars=None, *, scalar=None, powers=None, first: int = 0, n: int | None = None,
                 montgomery: bool = False, out_device: bool = False, in_place: bool = False):
     """out[i] = [s_i] points[i] -- the ScalarMultiplication loops of the Groth16 MPC ceremony (backend/groth16/<curve>/mpcsetup:

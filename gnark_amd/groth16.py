@@ -144,22 +144,26 @@ class ProvingKey:
         return self
 
     @classmethod
-    def ReadFrom(cls, ctx: Context, curve, source, *, precompute: int = 0, shard=(0, 1), k_remove=()):
+    def ReadFrom(cls, ctx: Context, curve, source, *, precompute: int = 0, shard=(0, 1), k_remove=(), subgroup_check: bool = False):
         """ProvingKey.ReadFrom / UnsafeReadFrom / ReadDump (marshal.go:305-373,449-539) straight into HBM: source is bytes or an
-        open binary file; the format (compressed / raw points / dump) is recognised from the stream.  k_remove: see __init__."""
+        open binary file; the format (compressed / raw points / dump) is recognised from the stream.  k_remove: see __init__.
+        subgroup_check=False is UnsafeReadFrom (the curve equation of encoded points only, a dump taken as it is); True is
+        ProvingKey.ReadFrom: every point this shard keeps is tested for curve and subgroup membership on the device, in all three
+        formats, and the first bad one raises GnarkAmdError naming its vector and index."""
         cid = curve_id(curve)
         self = cls.__new__(cls)
         self.ctx, self.curve, self.shard = ctx, cid, (int(shard[0]), int(shard[1]))
         rem = np.ascontiguousarray(k_remove, dtype=np.uint64)
         h, used = C.c_void_p(), C.c_uint64()
         lib = ctx.lib
+        read_mem, read_fd = (lib.ga_g16_pk_read_mem_checked, lib.ga_g16_pk_read_fd_checked) if subgroup_check else (lib.ga_g16_pk_read_mem, lib.ga_g16_pk_read_fd)
         if isinstance(source, (bytes, bytearray, memoryview)):
             buf = np.frombuffer(bytes(source), dtype=np.uint8)
-            lib.check(lib.ga_g16_pk_read_mem(ctx.handle, cid, _ptr(buf), buf.shape[0], int(precompute), int(shard[0]), int(shard[1]),
-                                             _ptr(rem) if rem.size else None, rem.size, C.byref(h), C.byref(used)))
+            lib.check(read_mem(ctx.handle, cid, _ptr(buf), buf.shape[0], int(precompute), int(shard[0]), int(shard[1]),
+                               _ptr(rem) if rem.size else None, rem.size, C.byref(h), C.byref(used)))
         else:
-            lib.check(lib.ga_g16_pk_read_fd(ctx.handle, cid, source.fileno(), int(precompute), int(shard[0]), int(shard[1]),
-                                            _ptr(rem) if rem.size else None, rem.size, C.byref(h), C.byref(used)))
+            lib.check(read_fd(ctx.handle, cid, source.fileno(), int(precompute), int(shard[0]), int(shard[1]),
+                              _ptr(rem) if rem.size else None, rem.size, C.byref(h), C.byref(used)))
         self.handle, self.bytes_read = h, int(used.value)
         lay = ShardLayout(self)
         self.nb_wires, self.domain_cardinality, self.nb_commitments = lay["nb_wires"], lay["n"], None

@@ -51,6 +51,7 @@ const (
 	ScalarsMontgomery = uint(C.GA_SCALARS_MONTGOMERY)
 	ResultOnDevice    = uint(C.GA_RESULT_ON_DEVICE)
 	ResultBitReversed = uint(C.GA_RESULT_BITREVERSED)
+	CheckCurveOnly    = uint(C.GA_CHECK_CURVE_ONLY) // CheckPoints: IsOnCurve alone
 )
 
 // Vector / point selectors of the staged key builder.
@@ -274,6 +275,28 @@ func (c *Context) ReadKeyFd(curve Curve, fd uintptr, precompute int32, shardInde
 	return pk, uint64(used), nil
 }
 
+// ReadKeyFdChecked is ReadKeyFd with ProvingKey.ReadFrom semantics (ga_g16_pk_read_fd_checked): every point the read keeps -- this
+// shard's slice of the five vectors, the five header points, the commitment bases -- is tested for curve and prime-order subgroup
+// membership on the device, in all three layouts (a dump's raw images included).  The first bad point ends the read; the error
+// names the vector, the index within the file's vector and the failure.  A shard checks what it keeps: the union of all shards'
+// checks covers the file.
+func (c *Context) ReadKeyFdChecked(curve Curve, fd uintptr, precompute int32, shardIndex, shardCount int, kRemove []uint64) (*ProvingKey, uint64, error) {
+	pk := &ProvingKey{}
+	var used C.uint64_t
+	var rem *C.uint64_t
+	if len(kRemove) > 0 {
+		rem = (*C.uint64_t)(unsafe.Pointer(unsafe.SliceData(kRemove)))
+	}
+	err := call("ga_g16_pk_read_fd_checked", func() C.int {
+		return C.ga_g16_pk_read_fd_checked(c.h, C.int(curve), C.int(fd), C.int32_t(precompute), C.uint32_t(shardIndex), C.uint32_t(shardCount),
+			rem, C.uint64_t(len(kRemove)), &pk.h, &used)
+	})
+	if err != nil {
+		return nil, 0, err
+	}
+	return pk, uint64(used), nil
+}
+
 // ParseProof is Proof.ReadFrom on WriteTo / WriteRawTo bytes (ga_g16_proof_unmarshal); proofOut: Ar | Bs | Krs affine.
 func ParseProof(curve Curve, data []byte, proofOut, commitmentsOut unsafe.Pointer, maxCommitments int, pokOut unsafe.Pointer) (nbCommitments int, consumed int, err error) {
 	var n C.uint32_t
@@ -444,6 +467,32 @@ func (c *Context) ScalePoints(curve Curve, group int, points unsafe.Pointer, n u
 			C.uint(flags), outAffine, &r)
 	})
 	return uint64(r), err
+}
+
+// The status of a point after CheckPoints.
+const (
+	PointOK            = C.GA_POINT_OK              // on the curve and in the prime-order subgroup (or infinity)
+	PointOffCurve      = C.GA_POINT_OFF_CURVE       // a coordinate not below p, or y^2 != x^3 + b
+	PointNotInSubgroup = C.GA_POINT_NOT_IN_SUBGROUP // on the curve, outside the subgroup
+)
+
+// CheckResult is what CheckPoints counted: points off the curve, points outside the subgroup, the index of the first point that is
+// not OK (math.MaxUint64 if all are) and the points decided by [r]P with the complete formulas (0 on honest input).
+type CheckResult struct {
+	OffCurve, NotInSubgroup, First, Redone uint64
+}
+
+// CheckPoints is G1Affine / G2Affine.IsOnCurve and IsInSubGroup for n affine points in gnark's memory image (ga_check_points): what
+// the default decoder does for every point of the ReadFrom of an mpcsetup phase or of kzg.SRS.ReadFrom, on a vector that may
+// already sit on the device.  flags: BasesOnDevice for the points, ResultOnDevice for status, CheckCurveOnly.  status receives one
+// byte per point (PointOK, PointOffCurve, PointNotInSubgroup) and may be nil.  The error says whether the check ran, not whether the
+// points are good.
+func (c *Context) CheckPoints(curve Curve, group int, points unsafe.Pointer, n uint64, flags uint, status unsafe.Pointer) (res CheckResult, err error) {
+	var out [4]C.uint64_t
+	err = call("ga_check_points", func() C.int {
+		return C.ga_check_points(c.h, C.int(curve), C.int(group), points, C.size_t(n), C.uint(flags), (*C.uint8_t)(status), &out[0])
+	})
+	return CheckResult{uint64(out[0]), uint64(out[1]), uint64(out[2]), uint64(out[3])}, err
 }
 
 // LagrangeCoeffs is mpcsetup's lagrangeCoeffsG1 / lagrangeCoeffsG2 on the device (the four transforms of Phase2.Initialize): the

@@ -56,7 +56,7 @@ extern "C" {
 
 /* flags for ga_msm */
 #define GA_BASES_ON_DEVICE 0x1u        /* `bases` (ga_kzg_to_lagrange_g1, ga_lagrange_coeffs: `powers_affine`; ga_scale_points,
-                                         * ga_sparse_point_sums: `points_affine`) is a device pointer */
+                                         * ga_sparse_point_sums, ga_check_points: `points_affine`) is a device pointer */
 #define GA_SCALARS_ON_DEVICE 0x2u      /* `scalars` is a device pointer */
 #define GA_TABLE_BATCHED 0x10u         /* ga_msm_table_create: the table will mostly serve ga_msm_table_run_batch (PLONK's grouped
                                          * commitments over the SRS): plan a narrower window -- k bucket sets make the sort keys
@@ -66,7 +66,8 @@ extern "C" {
                                           (ICICLE's AreScalarsMontgomeryForm, icicle.go:861-863,1232) */
 #define GA_RESULT_WINDOW_SUMS 0x8u     /* multi-GPU window sharding: see ga_msm_windows */
 #define GA_RESULT_ON_DEVICE 0x20u      /* ga_batch_scalar_mul, ga_kzg_to_lagrange_g1, ga_lagrange_coeffs, ga_scale_points,
-                                         * ga_sparse_point_sums: `out_affine` is a device pointer */
+                                         * ga_sparse_point_sums: `out_affine` (ga_check_points: `status`) is a device pointer */
+#define GA_CHECK_CURVE_ONLY 0x80u      /* ga_check_points: the curve equation only (IsOnCurve), no subgroup test */
 #define GA_RESULT_BITREVERSED 0x40u    /* ga_batch_scalar_mul, ga_sparse_point_sums: result i is written at index bitrev(i, log2 n) */
 
 /* NTT direction / ordering, mirroring gnark-crypto fft.Domain.FFT / FFTInverse (prove.go:362-386) */
@@ -199,6 +200,33 @@ int ga_lagrange_coeffs(ga_ctx* ctx, int curve, int group, const void* powers_aff
 #define GA_SCALE_POWERS 2   /* scalars: 2 fr elements (c, t);       out[i] = [c * t^(first + i)] points[i]   */
 int ga_scale_points(ga_ctx* ctx, int curve, int group, const void* points_affine, size_t n, int mode,
                     const void* scalars, uint64_t first, unsigned flags, void* out_affine, uint64_t* redone);
+
+/* ---- batch curve and subgroup checks: accepting points from somebody else -----------------------------------
+ * replaces: G1Affine / G2Affine.IsOnCurve and IsInSubGroup, one call for n points -- what gnark-crypto's default decoder
+ * (curve.NewDecoder without NoSubgroupChecks) does for every point of a ProvingKey.ReadFrom (backend/groth16/<curve>/marshal.go:305-312),
+ * of every ReadFrom of an mpcsetup phase and of kzg.SRS.ReadFrom, here on a vector that may already sit on the device.
+ *   points_affine : n G1Affine / G2Affine memory images, host, or device with GA_BASES_ON_DEVICE; never written.
+ *   status        : n bytes, may be NULL; host, or device with GA_RESULT_ON_DEVICE.  status[i] is one of the three values below.
+ *   out4          : host, required: {points off the curve, points outside the subgroup, index of the first point that is not OK or
+ *                   UINT64_MAX, redone}.
+ *   flags         : GA_BASES_ON_DEVICE, GA_RESULT_ON_DEVICE, GA_CHECK_CURVE_ONLY (no subgroup test: IsOnCurve alone).
+ * The return value says whether the check RAN, not whether the points are good: GA_OK for any mixture of points.  (0,0) is infinity
+ * and OK, as in gnark-crypto.  A coordinate whose image is not below p is GA_POINT_OFF_CURVE, decided before any arithmetic (a dump
+ * is raw memory).  The truth is "on the curve and [r]P = O"; it is decided by an identity in the curve's seed x0 -- BN254 G1: the
+ * curve equation alone (cofactor 1); BLS12-381 G1: P + [x0^2] phi(P) = O; BLS12-381 G2: psi(P) = [x0]P; BN254 G2:
+ * [x0 + 1]P + psi([x0]P) + psi^2([x0]P) = psi^3([2 x0]P) -- one or two 64-bit ladders per point instead of a 255-bit one.
+ * `redone` counts points that met an exceptional step of the fast formulas (points of small order) and were decided by [r]P with
+ * the complete formulas: 0 on honest input, never an error.  GA_CHECK_NAIVE=1 runs the definition instead ([r - 1]P = -P, same bytes;
+ * tools/check_points_bench.py measures both).
+ * GA_ERR_INVALID: unknown curve or group; a null points_affine with n > 0; a null out4; n above 2^32.  n = 0 gives
+ * {0, 0, UINT64_MAX, 0} and touches nothing.  Device scratch, kept by the context, per pass of at most GA_CHECK_CHUNK points (default
+ * 2^20, at most 2^30): 5 bytes per point, and the staging of points on the host.  GA_ERR_NOMEM when that does not fit: nothing is in
+ * flight and the context stays usable. */
+#define GA_POINT_OK              0
+#define GA_POINT_OFF_CURVE       1   /* a coordinate image not below p, or y^2 != x^3 + b */
+#define GA_POINT_NOT_IN_SUBGROUP 2   /* on the curve, outside the prime-order subgroup */
+int ga_check_points(ga_ctx* ctx, int curve, int group, const void* points_affine, size_t n, unsigned flags,
+                    uint8_t* status, uint64_t* out4);
 
 /* ---- a sparse Fr matrix applied to a vector of points: the constraint loop of Phase2.Initialize ------------
  * replaces: the loops of Phase2.Initialize in backend/groth16/<curve>/mpcsetup (phase2.go:224-247: every term (coeff, wire) of
@@ -527,7 +555,13 @@ int ga_g16_prove_multi(ga_g16_pk* const* keys, uint32_t n, const void* w, const 
  * flag bits) and ReadDump (marshal.go:449-539: raw memory images), read straight into HBM: the file streams through pinned
  * staging buffers, points are decoded (big-endian -> Montgomery, on-curve check, square roots of compressed points) by a device
  * kernel, and the dump's slices are copied without any arithmetic.  The format is recognised from the stream (the 0xdeadbeef
- * marker of WriteDump).  Subgroup membership of G2 points is not checked (UnsafeReadFrom semantics).
+ * marker of WriteDump).  ga_g16_pk_read_mem / _fd do not check subgroup membership, and take a dump's points as they are
+ * (UnsafeReadFrom semantics).  The _checked forms are ProvingKey.ReadFrom (the default decoder, marshal.go:305-312): same
+ * parameters, and every point the read keeps -- this shard's slice of the five vectors, the five header points, the commitment
+ * bases -- goes through the tests of ga_check_points where it first sits on the device, a dump's raw images included.  The first
+ * bad point ends the read with GA_ERR_INVALID; ga_last_error names the vector, the index within the file's vector and which of
+ * the two failures it was; nothing stays pinned and the context stays usable.  A shard checks what it keeps: the union of all
+ * shards' checks covers the file.
  *   k_remove: the toRemove wire list of prove.go:231-235 -- it comes from the constraint system, not from the key file; NULL / 0
  *   for circuits without commitments.  precompute, shard_index, shard_count: as in ga_g16_key.
  * ga_g16_key_write_fd writes the host description of a key in the WriteTo (GA_KEY_FORMAT_COMPRESSED), WriteRawTo (RAW) or
@@ -539,6 +573,10 @@ int ga_g16_pk_read_mem(ga_ctx* ctx, int curve, const uint8_t* data, size_t len, 
                        uint32_t shard_count, const uint64_t* k_remove, uint64_t len_k_remove, ga_g16_pk** out, uint64_t* bytes_read);
 int ga_g16_pk_read_fd(ga_ctx* ctx, int curve, int fd, int32_t precompute, uint32_t shard_index, uint32_t shard_count,
                       const uint64_t* k_remove, uint64_t len_k_remove, ga_g16_pk** out, uint64_t* bytes_read);
+int ga_g16_pk_read_mem_checked(ga_ctx* ctx, int curve, const uint8_t* data, size_t len, int32_t precompute, uint32_t shard_index,
+                               uint32_t shard_count, const uint64_t* k_remove, uint64_t len_k_remove, ga_g16_pk** out, uint64_t* bytes_read);
+int ga_g16_pk_read_fd_checked(ga_ctx* ctx, int curve, int fd, int32_t precompute, uint32_t shard_index, uint32_t shard_count,
+                              const uint64_t* k_remove, uint64_t len_k_remove, ga_g16_pk** out, uint64_t* bytes_read);
 int ga_g16_key_write_fd(ga_ctx* ctx, const ga_g16_key* key, int format, int fd, uint64_t* bytes_written);
 /* Proof.ReadFrom (marshal.go:62-86): Ar | Bs | Krs | u32 n | n commitments | CommitmentPok, compressed (WriteTo) or uncompressed
  * (WriteRawTo) points.  proof_out: Ar | Bs | Krs affine (Montgomery), commitments_out: room for max_commitments G1Affine. */

@@ -13,7 +13,11 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
-from pyref import BN254, BLS12_381  # noqa: E402
+from pyref import BN254, BLS12_381, Fp2Ops, g1_group, g2_group  # noqa: E402
+
+# the curves' seeds (x0 of the BN / BLS12 families): p, r and the cofactors are polynomials in them
+BN254_SEED = 4965661367192848881
+BLS12_381_SEED = -0xd201000000010000
 
 
 def limbs(x, n, w):
@@ -101,6 +105,56 @@ def c_field_block(name, mod, n64, extra=None):
     return "\n".join(out)
 
 
+def fp2_pow(F, a, e):
+    r = F.one
+    while e:
+        if e & 1:
+            r = F.mul(r, a)
+        a = F.mul(a, a)
+        e >>= 1
+    return r
+
+
+def endo_constants(c):
+    """The constants of check_points.hip.h (product header only), every one chosen by the identity it serves on the generator:
+    BLS12-381: BETA, the cube root of unity with P + [x0^2] phi(P) = O for phi(x, y) = (BETA x, y), and PSI_X / PSI_Y, the
+    coefficients of the untwist-Frobenius-twist psi(x, y) = (conj(x) PSI_X, conj(y) PSI_Y) with psi(P) = [x0] P;
+    BN254: PSI_X / PSI_Y, and psi^2, psi^3 folded: psi^2(x, y) = (x PSI2_X, y PSI2_Y), psi^3(x, y) = (conj(x) PSI3_X, conj(y) PSI3_Y),
+    with [x0 + 1] P + psi([x0] P) + psi^2([x0] P) = psi^3([2 x0] P)."""
+    p = c.p
+    F2, G1, G2 = Fp2Ops(p), g1_group(c), g2_group(c)
+    conj = lambda a: (a[0], (-a[1]) % p)
+    out = {}
+    if c is BLS12_381:
+        x0, xi, sign = BLS12_381_SEED, (1, 1), -1
+        g = next(g for g in range(2, 100) if pow(g, (p - 1) // 3, p) != 1)
+        w = pow(g, (p - 1) // 3, p)
+        ok = [b for b in (w, w * w % p) if G1.add(c.g1, G1.mul((b * c.g1[0] % p, c.g1[1]), x0 * x0)) is None]
+        assert len(ok) == 1, "exactly one cube root of unity satisfies P + [x0^2] phi(P) = O on the generator"
+        out["BETA"] = ok[0]
+    else:
+        x0, xi, sign = BN254_SEED, (9, 1), 1
+    cx, cy = fp2_pow(F2, xi, (p - 1) // 3), fp2_pow(F2, xi, (p - 1) // 2)
+    if sign < 0:
+        cx, cy = F2.inv(cx), F2.inv(cy)
+    psi = lambda P: None if P is None else (F2.mul(conj(P[0]), cx), F2.mul(conj(P[1]), cy))
+    assert G2.on_curve(psi(c.g2))
+    out.update(PSI_X0=cx[0], PSI_X1=cx[1], PSI_Y0=cy[0], PSI_Y1=cy[1])
+    if c is BLS12_381:
+        assert psi(c.g2) == G2.mul(c.g2, x0)
+    else:
+        nx, ny = F2.mul(cx, conj(cx)), F2.mul(cy, conj(cy))
+        assert nx[1] == 0 and ny[1] == 0
+        c3x, c3y = F2.mul(nx, cx), F2.mul(ny, cy)
+        psi2 = lambda P: (F2.mul(P[0], nx), F2.mul(P[1], ny))
+        psi3 = lambda P: (F2.mul(conj(P[0]), c3x), F2.mul(conj(P[1]), c3y))
+        Q = G2.mul(c.g2, x0)
+        assert psi2(Q) == psi(psi(Q)) and psi3(Q) == psi(psi2(Q))
+        assert G2.add(G2.add(G2.add(Q, c.g2), psi(Q)), psi2(Q)) == psi3(G2.add(Q, Q))
+        out.update(PSI2_X=nx[0], PSI2_Y=ny[0], PSI3_X0=c3x[0], PSI3_X1=c3x[1], PSI3_Y0=c3y[0], PSI3_Y1=c3y[1])
+    return out
+
+
 def main():
     hdr = ["// GENERATED by tools/gen_constants.py -- do not edit.", "#pragma once", "#include <stdint.h>", ""]
     prod = list(hdr) + ["namespace ga {", ""]
@@ -111,7 +165,7 @@ def main():
                     "GEN_INV": pow(c.fr_gen, -1, c.r), "I_ADICITY": c.fr_adicity}
         fp_extra = {"G1X": c.g1[0], "G1Y": c.g1[1], "G2X0": c.g2[0][0], "G2X1": c.g2[0][1],
                     "G2Y0": c.g2[1][0], "G2Y1": c.g2[1][1], "B1": c.b, "B2_0": c.b2[0], "B2_1": c.b2[1]}
-        prod.append(field_block(f"{tag}_Fp", c.p, c.fp_limbs, 32, fp_extra))
+        prod.append(field_block(f"{tag}_Fp", c.p, c.fp_limbs, 32, {**fp_extra, **endo_constants(c)}))
         prod.append("")
         prod.append(field_block(f"{tag}_Fr", c.r, c.fr_limbs, 32, fr_extra))
         prod.append("")
