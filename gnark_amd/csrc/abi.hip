@@ -154,138 +154,103 @@ void Ctx::scratch_free_lanes(int first_lane) {
     }
 }
 
+// a 64-bit knob (strtoull), an int knob (atoi), a 0 / 1 knob (anything atoi reads as non-zero is 1); the default when the variable is not set
+static uint64_t env_u64(const char* name, uint64_t dflt) {
+    const char* e = getenv(name);
+    return e ? strtoull(e, nullptr, 10) : dflt;
+}
+static int env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+static int env_flag(const char* name, int dflt) { return env_int(name, dflt) != 0; }
+int check_naive_knob() { return env_flag("GA_CHECK_NAIVE", 0); }
+
 void Tunables::read_env() {
     // a prover on another lane may be reading the knobs while lane 0 refreshes them: every field is an atomic, parsed into a
     // local first and stored only when the environment changed it, so a reader never sees the defaults flicker
-    auto num = [](const char* name, uint64_t dflt) -> uint64_t {
-        const char* e = getenv(name);
-        return e ? strtoull(e, nullptr, 10) : dflt;
-    };
     auto put64 = [](std::atomic<uint64_t>& f, uint64_t v) {
         if (f.load(std::memory_order_relaxed) != v) f.store(v, std::memory_order_relaxed);
     };
     auto put = [](std::atomic<int>& f, int v) {
         if (f.load(std::memory_order_relaxed) != v) f.store(v, std::memory_order_relaxed);
     };
-    put64(msm_max_chunk, num("GA_MSM_MAX_CHUNK", 0));
-    put64(reduce_lazy_min, num("GA_REDUCE_LAZY_MIN", 1u << 14));
-    put(g16_share_min_pct, (int)num("GA_G16_SHARE_MIN_PCT", 90));
-    put(g16_lanes, (int)num("GA_G16_LANES", 2));
-    put64(g16_table_budget_pct, num("GA_G16_TABLE_BUDGET_PCT", 0));
-    put(g16_split, (int)num("GA_G16_SPLIT", 1));
-    put(g16_batch_tables, (int)num("GA_G16_BATCH_TABLES", 1));
-    put(ntt_wave_local, (int)num("GA_NTT_WAVE_LOCAL", 1));
-    put(ntt_direct, (int)num("GA_NTT_DIRECT", 1));
-    put(table_c, (int)num("GA_TABLE_C", 0));
-    put(msm_exact_redo, (int)num("GA_MSM_EXACT_REDO", 0));
-    put64(msm_fuse_min, num("GA_MSM_FUSE_MIN", 1ull << 21));
-    put64(msm_task_exact_min, num("GA_MSM_TASK_EXACT_MIN", 1ull << 25));
-    put(msm_xcd, (int)num("GA_MSM_XCD", 3));
+    put64(msm_max_chunk, env_u64("GA_MSM_MAX_CHUNK", 0));
+    put64(reduce_lazy_min, env_u64("GA_REDUCE_LAZY_MIN", 1u << 14));
+    put(g16_share_min_pct, (int)env_u64("GA_G16_SHARE_MIN_PCT", 90));
+    put(g16_lanes, (int)env_u64("GA_G16_LANES", 2));
+    put64(g16_table_budget_pct, env_u64("GA_G16_TABLE_BUDGET_PCT", 0));
+    put(g16_split, (int)env_u64("GA_G16_SPLIT", 1));
+    put(g16_batch_tables, (int)env_u64("GA_G16_BATCH_TABLES", 1));
+    put(ntt_wave_local, (int)env_u64("GA_NTT_WAVE_LOCAL", 1));
+    put(ntt_direct, (int)env_u64("GA_NTT_DIRECT", 1));
+    put(table_c, (int)env_u64("GA_TABLE_C", 0));
+    put(msm_exact_redo, (int)env_u64("GA_MSM_EXACT_REDO", 0));
+    put64(msm_fuse_min, env_u64("GA_MSM_FUSE_MIN", 1ull << 21));
+    put64(msm_task_exact_min, env_u64("GA_MSM_TASK_EXACT_MIN", 1ull << 25));
+    put(msm_xcd, (int)env_u64("GA_MSM_XCD", 3));
     {
-        const uint64_t g = num("GA_MSM_P1_GRID", 512);
+        const uint64_t g = env_u64("GA_MSM_P1_GRID", 512);
         put64(msm_p1_grid, g ? g : 1);
     }
     {
         const char* e = getenv("GA_FAULT_THROW");
         put64(fault_throw, (e && *e) ? fnv1a(e) : 0);
     }
-    put(fault_lane2_nomem, (int)num("GA_FAULT_LANE2_NOMEM", 0));
-    const int grp = (int)num("GA_MSM_GROUP", 0);
+    put(fault_lane2_nomem, (int)env_u64("GA_FAULT_LANE2_NOMEM", 0));
+    const int grp = (int)env_u64("GA_MSM_GROUP", 0);
     put(msm_group, (grp >= 2 && grp <= 256 && (grp & (grp - 1)) == 0) ? grp : 0);
-    const uint64_t seg = num("GA_MSM_MIN_SEG", 256);
+    const uint64_t seg = env_u64("GA_MSM_MIN_SEG", 256);
     if (seg >= 32) put64(msm_min_seg, seg);
     g_table_c = table_c.load();
 }
 
 typedef CtxLock Lock;
 
-// fixed-base batch scalar multiplication (fixed_base.hip.h; instantiated in fixed_base_<curve>_g<k>.hip): out[i] = [scalars[i]] base.
-// h_base: one affine point on the host; scalars / out: host or device per flags; forced_c / forced_chunk: the knobs below (0 = planned)
-template <class C, int G>
-int fixed_base_run(Ctx* ctx, const void* h_base, const void* scalars, size_t n, unsigned flags, void* out, int forced_c, uint64_t forced_chunk);
-template <class C>
-int fixed_base_plan_abi(size_t n, int forced_c, int* c, int* nwin);
-// The two run-time knobs of the fixed-base entry points.  They are NOT part of Tunables (no other code reads them): each of the two
-// entry points reads them from the environment itself, once per call, before any launch:
-//   GA_FIXED_BASE_C      force the window width (2 .. 20; 0 or anything else = planned, 4 .. 18; tests run several widths at small n)
-//   GA_FIXED_BASE_CHUNK  scalars per pass (0 = 2^22, at most 2^30; tests force a small chunk)
-static int fixed_base_forced_c() {
-    const char* e = getenv("GA_FIXED_BASE_C");
-    return e ? atoi(e) : 0;
-}
-static uint64_t fixed_base_forced_chunk() {
-    const char* e = getenv("GA_FIXED_BASE_CHUNK");
-    return e ? strtoull(e, nullptr, 10) : 0;
-}
-
-// kzg.ToLagrangeG1 and mpcsetup's lagrangeCoeffsG1 / G2 (ec_ntt.hip.h; instantiated in ec_ntt_<curve>.hip and ec_ntt_<curve>_g2.hip):
-// powers / out host or device per flags.  One run-time knob, read by the entry points themselves like the two above:
-//   GA_EC_NTT_UNIFORM    0: the lanes of every stage are consecutive butterflies of one group (the A/B of tools/to_lagrange_bench.py);
-//                        default 1: from stage 6 on the lanes of a wave share their scalar
-template <class C, int G>
-int ec_ntt_to_lagrange(Ctx* ctx, const void* powers, size_t n, unsigned flags, void* out, int uniform);
-static int ec_ntt_uniform() {
-    const char* e = getenv("GA_EC_NTT_UNIFORM");
-    return e ? atoi(e) != 0 : 1;
+// ---- the run-time knobs of the point and Fr vector calls (their drivers are declared in common.hip.h) --------------------------
+// They are NOT part of Tunables (no other code reads them): the entry point reads them from the environment itself with env_u64 /
+// env_int / env_flag, once per call, under the context's lock, before any launch, and hands them to its driver.
+//   ga_batch_scalar_mul (and _plan)
+//     GA_FIXED_BASE_C       force the window width (2 .. 20; 0 or anything else = planned, 4 .. 18; tests run several widths at small n)
+//     GA_FIXED_BASE_CHUNK   scalars per pass (0 = 2^22, at most 2^30; tests force a small chunk)
+//   ga_kzg_to_lagrange_g1, ga_lagrange_coeffs
+//     GA_EC_NTT_UNIFORM     0: the lanes of every stage are consecutive butterflies of one group (the A/B of tools/to_lagrange_bench.py);
+//                           default 1: from stage 6 on the lanes of a wave share their scalar
+//   ga_scale_points
+//     GA_SCALE_WINDOW       0: the plain double-and-add ladder (the A/B of tools/scale_points_bench.py); default 1: signed 4-bit windows
+//     GA_SCALE_CHUNK        points per pass (0 = 2^20, at most 2^30; tests force a small chunk)
+//   ga_check_points; the checked key reads take GA_CHECK_NAIVE as well (check_naive_knob)
+//     GA_CHECK_NAIVE        1: the definitional test [r - 1]P = -P on the plain ladder (the A/B of tools/check_points_bench.py); default 0
+//     GA_CHECK_CHUNK        points per pass (0 = 2^20, at most 2^30; tests force a small chunk)
+//   ga_sparse_point_sums
+//     GA_SPARSE_CHUNK       general terms (products) per pass (0 = 2^20, at most 2^30; tests force a small chunk)
+//     GA_SPARSE_SEGMENT     terms, or partial sums, per lane of the row sums (0 or 1 = 16; tests force 4)
+//     GA_SPARSE_ORDER       0: the products in row order (default); 1: sorted by coefficient id (the A/B of tools/phase2_init_bench.py)
+//   ga_fr_sparse_matvec
+//     GA_FR_SPARSE_SEGMENT  terms, or partial sums, per lane: 2 .. 2^20; unset, 0 or 1 = the default (FR_SPARSE_DEFAULT_SEGMENT); a
+//                           larger value is taken as 2^20; tests force 2
+static uint32_t env_segment(const char* name) {   // the two segment knobs, capped
+    const uint64_t v = env_u64(name, 0);
+    return (uint32_t)(v < (1u << 20) ? v : (1u << 20));
 }
 
-// per-point scalar multiplication (scale_points.hip.h; instantiated in scale_points_<curve>_g<k>.hip).  Two run-time knobs, read by the
-// entry point itself like the ones above:
-//   GA_SCALE_WINDOW      0: the plain double-and-add ladder (the A/B of tools/scale_points_bench.py); default 1: signed 4-bit windows
-//   GA_SCALE_CHUNK       points per pass (0 = 2^20, at most 2^30; tests force a small chunk)
-template <class C, int G>
-int scale_points_run(Ctx* ctx, const void* points, size_t n, int mode, const void* scalars, uint64_t first, unsigned flags, void* out,
-                     uint64_t* redone, int windowed, uint64_t forced_chunk);
-static int scale_windowed() {
-    const char* e = getenv("GA_SCALE_WINDOW");
-    return e ? atoi(e) != 0 : 1;
+// ---- argument checks the entry points share: each sets the error under the entry point's name and returns false -------------------
+static bool abi_curve_ok(int curve) {
+    if (curve == GA_BN254 || curve == GA_BLS12_381) return true;
+    set_error("%s: unknown curve id %d", current_entry(), curve);
+    return false;
 }
-static uint64_t scale_forced_chunk() {
-    const char* e = getenv("GA_SCALE_CHUNK");
-    return e ? strtoull(e, nullptr, 10) : 0;
+static bool abi_curve_group_ok(int curve, int group) {
+    if ((curve == GA_BN254 || curve == GA_BLS12_381) && (group == GA_G1 || group == GA_G2)) return true;
+    set_error("%s: unknown curve id %d or group id %d", current_entry(), curve, group);
+    return false;
 }
-
-// batch curve and subgroup checks (check_points.hip.h; instantiated in check_points_<curve>_g<k>.hip).  Two run-time knobs, read by the
-// entry point itself like the ones above:
-//   GA_CHECK_NAIVE       1: the definitional test [r - 1]P = -P on the plain ladder (the A/B of tools/check_points_bench.py); default 0
-//   GA_CHECK_CHUNK       points per pass (0 = 2^20, at most 2^30; tests force a small chunk)
-template <class C, int G>
-int check_points_run(Ctx* ctx, const void* points, size_t n, unsigned flags, uint8_t* status, uint64_t* out4, int naive, uint64_t forced_chunk);
-static int check_naive() {
-    const char* e = getenv("GA_CHECK_NAIVE");
-    return e ? atoi(e) != 0 : 0;
+// n elements whose first has index `first`: at most 2^32 of them, and no index above 2^64 - 1
+static bool abi_range_ok(size_t n, uint64_t first) {
+    if ((uint64_t)n <= (1ull << 32) && (n == 0 || first <= UINT64_MAX - (uint64_t)n + 1)) return true;
+    set_error("%s: n = %zu above 2^32, or first + n above 2^64", current_entry(), n);
+    return false;
 }
-static uint64_t check_forced_chunk() {
-    const char* e = getenv("GA_CHECK_CHUNK");
-    return e ? strtoull(e, nullptr, 10) : 0;
-}
-
-// sparse point sums (sparse_sums.hip.h; instantiated in sparse_sums_<curve>_g<k>.hip).  Three run-time knobs, read by the entry point
-// itself like the ones above:
-//   GA_SPARSE_CHUNK      general terms (products) per pass (0 = 2^20, at most 2^30; tests force a small chunk)
-//   GA_SPARSE_SEGMENT    terms, or partial sums, per lane of the row sums (0 or 1 = 16; tests force 4)
-//   GA_SPARSE_ORDER      0: the products in row order (default); 1: sorted by coefficient id (the A/B of tools/phase2_init_bench.py)
-template <class C, int G>
-int sparse_sums_run(Ctx* ctx, const void* points, size_t n_points, const uint64_t* row_start, size_t n_rows, const uint32_t* terms, const void* coeffs,
-                    size_t n_coeffs, unsigned flags, void* out, uint64_t* redone, uint64_t forced_chunk, uint32_t segment, int cid_order);
-static uint64_t sparse_knob(const char* name) {
-    const char* e = getenv(name);
-    return e ? strtoull(e, nullptr, 10) : 0;
-}
-
-// the Fr vector calls of groth16.Setup's scalar side (fr_sparse.hip.h, fr_setup.hip.h; instantiated in fr_setup_<curve>.hip).  One
-// run-time knob, read by the entry point itself like the ones above:
-//   GA_FR_SPARSE_SEGMENT terms, or partial sums, per lane of ga_fr_sparse_matvec: 2 .. 2^20; unset, 0 or 1 = the default
-//                        (FR_SPARSE_DEFAULT_SEGMENT); a larger value is taken as 2^20; tests force 2
-template <class C>
-int fr_sparse_run(Ctx* ctx, const void* x, size_t n_cols, const uint64_t* row_start, size_t n_rows, const uint32_t* terms, const void* coeffs,
-                  size_t n_coeffs, const uint8_t* row_class, const void* row_scales, size_t n_classes, unsigned flags, void* out, uint32_t segment);
-template <class C>
-int fr_lagrange_run(Ctx* ctx, int logn, const void* tau, size_t m, unsigned flags, void* out);
-template <class C>
-int fr_compact_run(Ctx* ctx, const void* v, size_t n, unsigned flags, void* out, uint8_t* mask, uint64_t* count);
-template <class C>
-int fr_powers_run(Ctx* ctx, const void* scalars, uint64_t first, size_t n, unsigned flags, void* out);
 
 // Bring inputs to the device when they are host pointers.
 struct Staged {
@@ -555,10 +520,7 @@ int ga_batch_scalar_mul(ga_ctx* h, int curve, int group, const void* base_affine
                         void* out_affine) try {
     GA_ABI_ENTRY();
     Ctx* c = reinterpret_cast<Ctx*>(h);
-    if ((curve != GA_BN254 && curve != GA_BLS12_381) || (group != GA_G1 && group != GA_G2)) {
-        set_error("ga_batch_scalar_mul: unknown curve id %d or group id %d", curve, group);
-        return GA_ERR_INVALID;
-    }
+    if (!abi_curve_group_ok(curve, group)) return GA_ERR_INVALID;
     if (n == 0) return GA_OK;
     if (!c || !base_affine || !scalars || !out_affine) {
         set_error("ga_batch_scalar_mul: null argument");
@@ -569,8 +531,8 @@ int ga_batch_scalar_mul(ga_ctx* h, int curve, int group, const void* base_affine
         return GA_ERR_INVALID;
     }
     Lock l(c);
-    const int forced_c = fixed_base_forced_c();
-    const uint64_t forced_chunk = fixed_base_forced_chunk();
+    const int forced_c = env_int("GA_FIXED_BASE_C", 0);
+    const uint64_t forced_chunk = env_u64("GA_FIXED_BASE_CHUNK", 0);
     GA_DISPATCH_CURVE(curve, GA_DISPATCH_GROUP(group, return (fixed_base_run<C, G>(c, base_affine, scalars, n, flags, out_affine, forced_c, forced_chunk))));
     return GA_OK;
 } GA_ABI_CATCH
@@ -581,7 +543,7 @@ int ga_batch_scalar_mul_plan(int curve, size_t n, int* window_bits, int* num_win
         set_error("ga_batch_scalar_mul_plan: null argument");
         return GA_ERR_INVALID;
     }
-    const int forced_c = fixed_base_forced_c();
+    const int forced_c = env_int("GA_FIXED_BASE_C", 0);
     GA_DISPATCH_CURVE(curve, return fixed_base_plan_abi<C>(n, forced_c, window_bits, num_windows));
     return GA_OK;
 } GA_ABI_CATCH
@@ -590,17 +552,14 @@ int ga_batch_scalar_mul_plan(int curve, size_t n, int* window_bits, int* num_win
 int ga_kzg_to_lagrange_g1(ga_ctx* h, int curve, const void* powers_affine, size_t n, unsigned flags, void* out_affine) try {
     GA_ABI_ENTRY();
     Ctx* c = reinterpret_cast<Ctx*>(h);
-    if (curve != GA_BN254 && curve != GA_BLS12_381) {
-        set_error("ga_kzg_to_lagrange_g1: unknown curve id %d", curve);
-        return GA_ERR_INVALID;
-    }
+    if (!abi_curve_ok(curve)) return GA_ERR_INVALID;
     if (n == 0) return GA_OK;
     if (!c || !powers_affine || !out_affine) {
         set_error("ga_kzg_to_lagrange_g1: null argument");
         return GA_ERR_INVALID;
     }
     Lock l(c);
-    const int uniform = ec_ntt_uniform();
+    const int uniform = env_flag("GA_EC_NTT_UNIFORM", 1);
     GA_DISPATCH_CURVE(curve, return (ec_ntt_to_lagrange<C, GA_G1>(c, powers_affine, n, flags, out_affine, uniform)));
     return GA_OK;
 } GA_ABI_CATCH
@@ -608,17 +567,14 @@ int ga_kzg_to_lagrange_g1(ga_ctx* h, int curve, const void* powers_affine, size_
 int ga_lagrange_coeffs(ga_ctx* h, int curve, int group, const void* powers_affine, size_t n, unsigned flags, void* out_affine) try {
     GA_ABI_ENTRY();
     Ctx* c = reinterpret_cast<Ctx*>(h);
-    if ((curve != GA_BN254 && curve != GA_BLS12_381) || (group != GA_G1 && group != GA_G2)) {
-        set_error("ga_lagrange_coeffs: unknown curve id %d or group id %d", curve, group);
-        return GA_ERR_INVALID;
-    }
+    if (!abi_curve_group_ok(curve, group)) return GA_ERR_INVALID;
     if (n == 0) return GA_OK;
     if (!c || !powers_affine || !out_affine) {
         set_error("ga_lagrange_coeffs: null argument");
         return GA_ERR_INVALID;
     }
     Lock l(c);
-    const int uniform = ec_ntt_uniform();
+    const int uniform = env_flag("GA_EC_NTT_UNIFORM", 1);
     GA_DISPATCH_CURVE(curve, GA_DISPATCH_GROUP(group, return (ec_ntt_to_lagrange<C, G>(c, powers_affine, n, flags, out_affine, uniform))));
     return GA_OK;
 } GA_ABI_CATCH
@@ -628,10 +584,7 @@ int ga_scale_points(ga_ctx* h, int curve, int group, const void* points_affine, 
                     unsigned flags, void* out_affine, uint64_t* redone) try {
     GA_ABI_ENTRY();
     Ctx* c = reinterpret_cast<Ctx*>(h);
-    if ((curve != GA_BN254 && curve != GA_BLS12_381) || (group != GA_G1 && group != GA_G2)) {
-        set_error("ga_scale_points: unknown curve id %d or group id %d", curve, group);
-        return GA_ERR_INVALID;
-    }
+    if (!abi_curve_group_ok(curve, group)) return GA_ERR_INVALID;
     if (mode != GA_SCALE_EACH && mode != GA_SCALE_ONE && mode != GA_SCALE_POWERS) {
         set_error("ga_scale_points: unknown mode %d", mode);
         return GA_ERR_INVALID;
@@ -644,10 +597,7 @@ int ga_scale_points(ga_ctx* h, int curve, int group, const void* points_affine, 
         set_error("ga_scale_points: GA_SCALARS_ON_DEVICE outside GA_SCALE_EACH (one or two scalars are read on the host)");
         return GA_ERR_INVALID;
     }
-    if ((uint64_t)n > (1ull << 32) || (n > 0 && first > UINT64_MAX - (uint64_t)n + 1)) {
-        set_error("ga_scale_points: n = %zu above 2^32, or first + n above 2^64", n);
-        return GA_ERR_INVALID;
-    }
+    if (!abi_range_ok(n, first)) return GA_ERR_INVALID;
     if (n == 0) {
         if (redone) *redone = 0;
         return GA_OK;
@@ -657,8 +607,8 @@ int ga_scale_points(ga_ctx* h, int curve, int group, const void* points_affine, 
         return GA_ERR_INVALID;
     }
     Lock l(c);
-    const int windowed = scale_windowed();
-    const uint64_t forced_chunk = scale_forced_chunk();
+    const int windowed = env_flag("GA_SCALE_WINDOW", 1);
+    const uint64_t forced_chunk = env_u64("GA_SCALE_CHUNK", 0);
     GA_DISPATCH_CURVE(curve, GA_DISPATCH_GROUP(group, return (scale_points_run<C, G>(c, points_affine, n, mode, scalars, first, flags, out_affine, redone,
                                                                                     windowed, forced_chunk))));
     return GA_OK;
@@ -668,10 +618,7 @@ int ga_scale_points(ga_ctx* h, int curve, int group, const void* points_affine, 
 int ga_check_points(ga_ctx* h, int curve, int group, const void* points_affine, size_t n, unsigned flags, uint8_t* status, uint64_t* out4) try {
     GA_ABI_ENTRY();
     Ctx* c = reinterpret_cast<Ctx*>(h);
-    if ((curve != GA_BN254 && curve != GA_BLS12_381) || (group != GA_G1 && group != GA_G2)) {
-        set_error("ga_check_points: unknown curve id %d or group id %d", curve, group);
-        return GA_ERR_INVALID;
-    }
+    if (!abi_curve_group_ok(curve, group)) return GA_ERR_INVALID;
     if ((uint64_t)n > (1ull << 32)) {
         set_error("ga_check_points: n = %zu above 2^32", n);
         return GA_ERR_INVALID;
@@ -686,8 +633,8 @@ int ga_check_points(ga_ctx* h, int curve, int group, const void* points_affine, 
         return GA_OK;
     }
     Lock l(c);
-    const int naive = check_naive();
-    const uint64_t forced_chunk = check_forced_chunk();
+    const int naive = check_naive_knob();
+    const uint64_t forced_chunk = env_u64("GA_CHECK_CHUNK", 0);
     GA_DISPATCH_CURVE(curve, GA_DISPATCH_GROUP(group, return (check_points_run<C, G>(c, points_affine, n, flags, status, out4, naive, forced_chunk))));
     return GA_OK;
 } GA_ABI_CATCH
@@ -697,10 +644,7 @@ int ga_sparse_point_sums(ga_ctx* h, int curve, int group, const void* points_aff
                          const uint32_t* terms, const void* coeffs, size_t n_coeffs, unsigned flags, void* out_affine, uint64_t* redone) try {
     GA_ABI_ENTRY();
     Ctx* c = reinterpret_cast<Ctx*>(h);
-    if ((curve != GA_BN254 && curve != GA_BLS12_381) || (group != GA_G1 && group != GA_G2)) {
-        set_error("ga_sparse_point_sums: unknown curve id %d or group id %d", curve, group);
-        return GA_ERR_INVALID;
-    }
+    if (!abi_curve_group_ok(curve, group)) return GA_ERR_INVALID;
     if (n_rows == 0) {
         if (redone) *redone = 0;
         return GA_OK;
@@ -719,11 +663,11 @@ int ga_sparse_point_sums(ga_ctx* h, int curve, int group, const void* points_aff
         return GA_ERR_INVALID;
     }
     Lock l(c);
-    const uint64_t forced_chunk = sparse_knob("GA_SPARSE_CHUNK"), segment = sparse_knob("GA_SPARSE_SEGMENT");
-    const int cid_order = sparse_knob("GA_SPARSE_ORDER") != 0;
+    const uint64_t forced_chunk = env_u64("GA_SPARSE_CHUNK", 0);
+    const uint32_t segment = env_segment("GA_SPARSE_SEGMENT");
+    const int cid_order = env_u64("GA_SPARSE_ORDER", 0) != 0;
     GA_DISPATCH_CURVE(curve, GA_DISPATCH_GROUP(group, return (sparse_sums_run<C, G>(c, points_affine, n_points, row_start, n_rows, terms, coeffs, n_coeffs, flags,
-                                                                                   out_affine, redone, forced_chunk,
-                                                                                   (uint32_t)(segment < (1u << 20) ? segment : (1u << 20)), cid_order))));
+                                                                                   out_affine, redone, forced_chunk, segment, cid_order))));
     return GA_OK;
 } GA_ABI_CATCH
 
@@ -731,10 +675,7 @@ int ga_sparse_point_sums(ga_ctx* h, int curve, int group, const void* points_aff
 int ga_fr_lagrange_at(ga_ctx* h, int curve, uint64_t n, const void* tau, size_t m, unsigned flags, void* out) try {
     GA_ABI_ENTRY();
     Ctx* c = reinterpret_cast<Ctx*>(h);
-    if (curve != GA_BN254 && curve != GA_BLS12_381) {
-        set_error("ga_fr_lagrange_at: unknown curve id %d", curve);
-        return GA_ERR_INVALID;
-    }
+    if (!abi_curve_ok(curve)) return GA_ERR_INVALID;
     int adicity = 0;
     GA_DISPATCH_CURVE(curve, adicity = C::FrP::ADICITY);
     if (n == 0 || (n & (n - 1)) != 0 || n > (1ull << adicity)) {
@@ -760,10 +701,7 @@ int ga_fr_sparse_matvec(ga_ctx* h, int curve, const void* x, size_t n_cols, cons
                         void* out) try {
     GA_ABI_ENTRY();
     Ctx* c = reinterpret_cast<Ctx*>(h);
-    if (curve != GA_BN254 && curve != GA_BLS12_381) {
-        set_error("ga_fr_sparse_matvec: unknown curve id %d", curve);
-        return GA_ERR_INVALID;
-    }
+    if (!abi_curve_ok(curve)) return GA_ERR_INVALID;
     if (n_rows == 0) return GA_OK;
     if ((uint64_t)n_rows >= (1ull << 31) || (uint64_t)n_cols > (1ull << 32) || (uint64_t)n_coeffs > (1ull << 32)) {
         set_error("ga_fr_sparse_matvec: n_rows = %zu (at most 2^31 - 1), n_cols = %zu or n_coeffs = %zu (at most 2^32) out of range", n_rows, n_cols, n_coeffs);
@@ -778,19 +716,15 @@ int ga_fr_sparse_matvec(ga_ctx* h, int curve, const void* x, size_t n_cols, cons
         return GA_ERR_INVALID;
     }
     Lock l(c);
-    const uint64_t segment = sparse_knob("GA_FR_SPARSE_SEGMENT");
-    GA_DISPATCH_CURVE(curve, return fr_sparse_run<C>(c, x, n_cols, row_start, n_rows, terms, coeffs, n_coeffs, row_class, row_scales, n_classes, flags, out,
-                                                    (uint32_t)(segment < (1u << 20) ? segment : (1u << 20))));
+    const uint32_t segment = env_segment("GA_FR_SPARSE_SEGMENT");
+    GA_DISPATCH_CURVE(curve, return fr_sparse_run<C>(c, x, n_cols, row_start, n_rows, terms, coeffs, n_coeffs, row_class, row_scales, n_classes, flags, out, segment));
     return GA_OK;
 } GA_ABI_CATCH
 
 int ga_fr_compact_nonzero(ga_ctx* h, int curve, const void* v, size_t n, unsigned flags, void* out, uint8_t* mask, uint64_t* count) try {
     GA_ABI_ENTRY();
     Ctx* c = reinterpret_cast<Ctx*>(h);
-    if (curve != GA_BN254 && curve != GA_BLS12_381) {
-        set_error("ga_fr_compact_nonzero: unknown curve id %d", curve);
-        return GA_ERR_INVALID;
-    }
+    if (!abi_curve_ok(curve)) return GA_ERR_INVALID;
     if (!count) {
         set_error("ga_fr_compact_nonzero: null count");
         return GA_ERR_INVALID;
@@ -815,14 +749,8 @@ int ga_fr_compact_nonzero(ga_ctx* h, int curve, const void* v, size_t n, unsigne
 int ga_fr_powers(ga_ctx* h, int curve, const void* scalars, uint64_t first, size_t n, unsigned flags, void* out) try {
     GA_ABI_ENTRY();
     Ctx* c = reinterpret_cast<Ctx*>(h);
-    if (curve != GA_BN254 && curve != GA_BLS12_381) {
-        set_error("ga_fr_powers: unknown curve id %d", curve);
-        return GA_ERR_INVALID;
-    }
-    if ((uint64_t)n > (1ull << 32) || (n > 0 && first > UINT64_MAX - (uint64_t)n + 1)) {
-        set_error("ga_fr_powers: n = %zu above 2^32, or first + n above 2^64", n);
-        return GA_ERR_INVALID;
-    }
+    if (!abi_curve_ok(curve)) return GA_ERR_INVALID;
+    if (!abi_range_ok(n, first)) return GA_ERR_INVALID;
     if (n == 0) return GA_OK;
     if (!c || !scalars || !out) {
         set_error("ga_fr_powers: null argument");

@@ -24,13 +24,12 @@
 // Bounds of the unreduced sequence: tools/lazy_bounds.py check_ladder(curve, fp2) -- the base of the second BLS12-381 G1 ladder is
 // an output of the first, which that fixed point covers.
 #pragma once
-#include "ec_ntt.hip.h"   // ec_ntt_scalar_mul29, ec_ntt_pack, ec_ntt_to_exact; Table29, LdsAcc29; add29, dbl29
+#include "ec_ntt.hip.h"   // ec_ntt_scalar_mul29, ec_ntt_pack, ec_ntt_to_exact, affine_to_lazy4; Table29, LdsAcc29; add29, dbl29; CurveB (keyio.hip.h)
 
 namespace ga {
 
 constexpr uint64_t CHECK_DEFAULT_CHUNK = 1ull << 20;   // points per pass: one status byte and one redo word each
-constexpr uint64_t CHECK_MAX_CHUNK = 1ull << 30;
-constexpr unsigned CHECK_MAX_BLOCKS = 1024;            // workgroups of a ladder launch (grid-stride beyond), as SCALE_MAX_BLOCKS
+constexpr unsigned CHECK_MAX_BLOCKS = 1024;            // workgroups of a ladder launch (grid-stride beyond), as SCALE_MAX_BLOCKS (scale_points.hip.h)
 
 enum { CHECK_RULE_CURVE = 0, CHECK_RULE_BLS_G1 = 1, CHECK_RULE_BLS_G2 = 2, CHECK_RULE_BN_G2 = 3 };
 
@@ -69,14 +68,6 @@ struct CheckCounters {
     uint32_t first_off_inv, first_outside_inv;
 };
 
-template <class F> struct CheckB;
-template <class P> struct CheckB<Fe<P>> {
-    GA_HD static Fe<P> get() { return fe_const<P>(P::B1); }
-};
-template <class P> struct CheckB<Fe2<P>> {
-    GA_HD static Fe2<P> get() { return {fe_const<P>(P::B2_0), fe_const<P>(P::B2_1)}; }
-};
-
 template <class P> GA_HD bool check_reduced(const Fe<P>& a) { return !geq_mod<P>(a.l); }
 template <class P> GA_HD bool check_reduced(const Fe2<P>& a) { return !geq_mod<P>(a.c0.l) & !geq_mod<P>(a.c1.l); }
 
@@ -84,7 +75,7 @@ template <class P> GA_HD bool check_reduced(const Fe2<P>& a) { return !geq_mod<P
 template <class F>
 __device__ __forceinline__ bool check_on_curve(const Affine<F>& p) {
     if (!(check_reduced(p.x) & check_reduced(p.y))) return false;
-    return eq(sqr(p.y), add(mul(sqr(p.x), p.x), CheckB<F>::get()));
+    return eq(sqr(p.y), add(mul(sqr(p.x), p.x), CurveB<F>::get()));   // (written out: through a function shared with keyio.hip.h the kernels come out with other registers)
 }
 
 template <class P> GA_HD Fe2<P> check_conj(const Fe2<P>& a) { return {a.c0, neg(a.c1)}; }
@@ -116,12 +107,6 @@ __device__ __forceinline__ void check_seed_mul29(Lazy4<F>& acc, const LdsAcc29<F
             add29<F>(acc, d);
         }
     }
-}
-
-template <class F>
-__device__ __forceinline__ Lazy4<F> check_affine_lazy(const Affine<F>& a) {
-    const typename Lazy<F>::T one = Lazy<F>::from_mem(FieldTraits<F>::one());
-    return {Lazy<F>::from_mem(a.x), Lazy<F>::from_mem(a.y), one, one};
 }
 
 // the closing of each identity on reduced values; q = [|x0|]P (BLS12-381 G1: [x0^2]P), not infinity
@@ -179,7 +164,7 @@ check_points_kernel(const Affine<F>* __restrict__ points, uint32_t n, uint64_t b
             continue;
         }
         if constexpr (RULE != CHECK_RULE_CURVE) {
-            Lazy4<F> acc = check_affine_lazy<F>(P);
+            Lazy4<F> acc = affine_to_lazy4<F>(P);
             const LdsAcc29<F> D(lds + threadIdx.x);
             check_seed_mul29<F, SEED>(acc, D);
             if constexpr (RULE == CHECK_RULE_BLS_G1) check_seed_mul29<F, SEED>(acc, D);
@@ -214,7 +199,7 @@ check_points_naive_kernel(const Affine<F>* __restrict__ points, uint32_t n, uint
         uint32_t k[8];
 #pragma unroll
         for (int w = 0; w < 8; w++) k[w] = rm1.l[w];
-        Lazy4<F> acc = check_affine_lazy<F>(P);
+        Lazy4<F> acc = affine_to_lazy4<F>(P);
         ec_ntt_scalar_mul29<F>(acc, LdsAcc29<F>(lds + threadIdx.x), k);
         if (f29_is_zero_mod_p(acc.zz)) {
             redo[atomicAdd(redo_count, 1u)] = i;
@@ -247,21 +232,17 @@ check_points_exact_kernel(const Affine<F>* __restrict__ points, uint64_t base, c
 // ---- host ------------------------------------------------------------------------------------------------------------------------
 struct CheckScratch {
     uint8_t* status = nullptr;      // chunk bytes: the status of a chunk when the caller's is on the host, or NULL
-    uint32_t* words = nullptr;      // [CheckCounters (8 words) | count, pad, pad, pad | list of chunk]
+    RedoList redo;                  // header: CheckCounters (8 words), the chunk's count, pad, pad, pad
     uint64_t chunk = 0;
-    CheckCounters* counters() const { return (CheckCounters*)words; }
-    uint32_t* count() const { return words + 8; }
-    uint32_t* list() const { return words + 12; }
+    CheckCounters* counters() const { return (CheckCounters*)redo.words; }
+    uint32_t* count() const { return redo.words + 8; }
+    uint32_t* list() const { return redo.list; }
 };
 inline int check_scratch_get(Ctx* ctx, uint64_t n, uint64_t forced_chunk, CheckScratch* s) {
-    uint64_t chunk = forced_chunk ? forced_chunk : CHECK_DEFAULT_CHUNK;
-    if (chunk > CHECK_MAX_CHUNK) chunk = CHECK_MAX_CHUNK;
-    if (chunk > n) chunk = n;
-    if (chunk == 0) chunk = 1;
-    s->chunk = chunk;
-    GA_CHECK(ctx->scratch_get("check_status", (chunk + 15) & ~15ull, (void**)&s->status));
-    GA_CHECK(ctx->scratch_get("check_redo", (chunk + 12) * 4, (void**)&s->words));
-    return GA_OK;
+    s->chunk = clamp_chunk(forced_chunk, CHECK_DEFAULT_CHUNK, n);
+    if (s->chunk == 0) s->chunk = 1;   // (n = 0: the scratch still exists)
+    GA_CHECK(ctx->scratch_get("check_status", (s->chunk + 15) & ~15ull, (void**)&s->status));
+    return s->redo.get(ctx, "check_redo", s->chunk, 12);
 }
 
 // the counters -> the four words of the ABI, after draining the stream
@@ -292,15 +273,15 @@ int check_points_launch(Ctx* ctx, hipStream_t st, const CheckScratch& s, const v
     rm1.l[0] -= 1;   // r is odd
     GA_HIP_CHECK(hipMemsetAsync(s.count(), 0, 16, st));
     StageTimer tm(ctx, "check_ladder");
-    const unsigned all_blocks = (cn + T - 1) / T, blocks = all_blocks < CHECK_MAX_BLOCKS ? all_blocks : CHECK_MAX_BLOCKS, exact_blocks = (cn + 63) / 64;
+    const unsigned blocks = capped_grid(cn, T, CHECK_MAX_BLOCKS), exact_blocks = capped_grid(cn, 64, EC_NTT_EXACT_MAX_BLOCKS);
     if (naive)
         hipLaunchKernelGGL((check_points_naive_kernel<F, FrP>), dim3(blocks), dim3(T), 0, st, (const Affine<F>*)src, cn, base, curve_only, rm1, st_out, s.counters(),
                            s.list(), s.count());
     else
         hipLaunchKernelGGL((check_points_kernel<F>), dim3(blocks), dim3(T), 0, st, (const Affine<F>*)src, cn, base, curve_only, st_out, s.counters(), s.list(),
                            s.count());
-    hipLaunchKernelGGL((check_points_exact_kernel<F, FrP>), dim3(exact_blocks < EC_NTT_EXACT_MAX_BLOCKS ? exact_blocks : EC_NTT_EXACT_MAX_BLOCKS), dim3(64), 0, st,
-                       (const Affine<F>*)src, base, r, st_out, s.counters(), (const uint32_t*)s.list(), (const uint32_t*)s.count());
+    hipLaunchKernelGGL((check_points_exact_kernel<F, FrP>), dim3(exact_blocks), dim3(64), 0, st, (const Affine<F>*)src, base, r, st_out, s.counters(),
+                       (const uint32_t*)s.list(), (const uint32_t*)s.count());
     GA_KERNEL_CHECK();
     return GA_OK;
 }
@@ -318,19 +299,16 @@ int check_points_run(Ctx* ctx, const void* points, size_t n, unsigned flags, uin
     Affine<F>* io = nullptr;
     GA_CHECK(check_scratch_get(ctx, n, forced_chunk, &s));
     if (!i_dev) GA_CHECK(ctx->scratch_get("check_io", s.chunk * sizeof(Affine<F>), (void**)&io));
-    struct Drain {   // every return, an error's included, leaves with the stream idle: the caller's buffers outlive the copies
-        hipStream_t st;
-        ~Drain() { hipStreamSynchronize(st); }
-    } drain{st};
+    StreamDrain drain{st};
 
     GA_HIP_CHECK(hipMemsetAsync(s.counters(), 0, sizeof(CheckCounters), st));
     for (uint64_t done = 0; done < n; done += s.chunk) {
         const uint32_t cn = (uint32_t)(n - done < s.chunk ? n - done : s.chunk);
-        const Affine<F>* src = i_dev ? (const Affine<F>*)points + done : io;
-        if (!i_dev) GA_HIP_CHECK(hipMemcpyAsync(io, (const Affine<F>*)points + done, (size_t)cn * sizeof(Affine<F>), hipMemcpyHostToDevice, st));
+        const Affine<F>* src;
+        GA_CHECK(chunk_in(st, i_dev, (const Affine<F>*)points, done, cn, io, &src));
         uint8_t* st_out = (status && o_dev) ? status + done : s.status;
         GA_CHECK((check_points_launch<C, G>(ctx, st, s, src, cn, done, curve_only, naive, st_out)));
-        if (status && !o_dev) GA_HIP_CHECK(hipMemcpyAsync(status + done, s.status, cn, hipMemcpyDeviceToHost, st));
+        if (status) GA_CHECK(chunk_out(st, o_dev, status, done, cn, s.status));
     }
     GA_CHECK(check_read_counters(s, st, out4, nullptr));   // the one synchronisation of a call with everything on the device
     return GA_OK;

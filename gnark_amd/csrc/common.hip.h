@@ -511,6 +511,37 @@ template <class C> int fr_vec_batch_inverse(Ctx* ctx, void* v, uint64_t n, bool 
 template <class C> int fr_vec_lincomb(Ctx* ctx, uint64_t n, int k, const void* const* vecs, const void* scalars, void* out, bool on_device);
 template <class C> int kzg_domain_divide(Ctx* ctx, const void* d_poly, uint64_t n, const void* z_mont, void* d_quot, void* value_out);
 
+// ---- the point and Fr vector calls; explicitly instantiated in <call>_<curve>[_g<k>].hip.  Operands are host or device pointers per
+// the GA_*_ON_DEVICE flags; the trailing arguments are the run-time knobs as the entry point read them (abi.hip has the table)
+// fixed_base.hip.h: out[i] = [scalars[i]] base, one affine base on the host; and the (c, nwin) it will use for n scalars
+template <class C, int G>
+int fixed_base_run(Ctx* ctx, const void* h_base, const void* scalars, size_t n, unsigned flags, void* out, int forced_c, uint64_t forced_chunk);
+template <class C> int fixed_base_plan_abi(size_t n, int forced_c, int* c, int* nwin);
+// ec_ntt.hip.h: kzg.ToLagrangeG1, mpcsetup's lagrangeCoeffsG1 / G2
+template <class C, int G> int ec_ntt_to_lagrange(Ctx* ctx, const void* powers, size_t n, unsigned flags, void* out, int uniform);
+// scale_points.hip.h: out[i] = [s_i] points[i]
+template <class C, int G>
+int scale_points_run(Ctx* ctx, const void* points, size_t n, int mode, const void* scalars, uint64_t first, unsigned flags, void* out,
+                     uint64_t* redone, int windowed, uint64_t forced_chunk);
+// check_points.hip.h: the whole call; launches only, for points already on the device (the checked key reads of g16_io.hip.h); their tally
+template <class C, int G>
+int check_points_run(Ctx* ctx, const void* points, size_t n, unsigned flags, uint8_t* status, uint64_t* out4, int naive, uint64_t forced_chunk);
+template <class C, int G> int check_points_resident(Ctx* ctx, hipStream_t st, const void* d_points, uint64_t n, uint64_t base, int reset, int naive);
+template <class C, int G> int check_points_tally(Ctx* ctx, hipStream_t st, uint64_t* out4, int* first_status);
+int check_naive_knob();   // GA_CHECK_NAIVE, for ga_check_points and the key reader alike (abi.hip)
+// sparse_sums.hip.h: a sparse Fr matrix applied to a vector of points
+template <class C, int G>
+int sparse_sums_run(Ctx* ctx, const void* points, size_t n_points, const uint64_t* row_start, size_t n_rows, const uint32_t* terms, const void* coeffs,
+                    size_t n_coeffs, unsigned flags, void* out, uint64_t* redone, uint64_t forced_chunk, uint32_t segment, int cid_order);
+// fr_sparse.hip.h: the same matrix applied to a vector of Fr elements, a scale per row class
+template <class C>
+int fr_sparse_run(Ctx* ctx, const void* x, size_t n_cols, const uint64_t* row_start, size_t n_rows, const uint32_t* terms, const void* coeffs,
+                  size_t n_coeffs, const uint8_t* row_class, const void* row_scales, size_t n_classes, unsigned flags, void* out, uint32_t segment);
+// fr_setup.hip.h: L_i(tau) for i < m; the zero filter; c t^(first + i)
+template <class C> int fr_lagrange_run(Ctx* ctx, int logn, const void* tau, size_t m, unsigned flags, void* out);
+template <class C> int fr_compact_run(Ctx* ctx, const void* v, size_t n, unsigned flags, void* out, uint8_t* mask, uint64_t* count);
+template <class C> int fr_powers_run(Ctx* ctx, const void* scalars, uint64_t first, size_t n, unsigned flags, void* out);
+
 // utility kernels (util_*.hip)
 template <class C, int G> int util_gen_bases(Ctx* ctx, uint64_t seed, size_t n, void* d_bases, void* d_dlogs, uint64_t first = 0);
 template <class C> int util_gen_scalars(Ctx* ctx, uint64_t seed, size_t n, void* d_scalars);

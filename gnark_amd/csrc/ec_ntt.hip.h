@@ -25,7 +25,7 @@
 //   4. fixed_base_affine_kernel (fixed_base.hip.h)  XYZZ -> affine with one inversion per lane batch, written at the bit-reversed
 //                              index: the DIF stages leave the result in bit-reversed order.
 #pragma once
-#include "fixed_base.hip.h"   // fixed_base_affine_kernel; Table29, LdsAcc29 (msm_bucket.hip.h); add29, dbl29 (msm_lazy.hip.h)
+#include "fixed_base.hip.h"   // fixed_base_affine_kernel; Table29, LdsAcc29 (msm_bucket.hip.h); add29, dbl29 (msm_lazy.hip.h); vec_call.hip.h
 
 namespace ga {
 
@@ -137,6 +137,12 @@ __device__ __forceinline__ XYZZ<F> ec_ntt_from_exact(const XYZZ<F>& p) {
     if (is_inf(p)) return {z, z, z, z};
     return {Lazy<F>::hat_packed(p.x), Lazy<F>::hat_packed(p.y), Lazy<F>::hat_packed(p.zz), Lazy<F>::hat_packed(p.zzz)};
 }
+// an affine point that is not (0,0) -> the lazy representation, ZZ = ZZZ = 1
+template <class F>
+__device__ __forceinline__ Lazy4<F> affine_to_lazy4(const Affine<F>& a) {
+    const typename Lazy<F>::T one = Lazy<F>::from_mem(FieldTraits<F>::one());
+    return {Lazy<F>::from_mem(a.x), Lazy<F>::from_mem(a.y), one, one};
+}
 
 template <class F, class FrP>
 __global__ void __launch_bounds__(Table29<F>::THREADS, EcNttStage<F>::MIN_WAVES)
@@ -239,17 +245,15 @@ int ec_ntt_to_lagrange(Ctx* ctx, const void* powers, size_t n, unsigned flags, v
 
     // the scratch of the whole call first: an allocation failure leaves nothing in flight
     XYZZ<F>* work;
-    uint32_t *tw, *redo;
+    uint32_t* tw;
+    RedoList redo;   // header: the stage's count, pad
     Affine<F>* io = nullptr;
     GA_CHECK(ctx->scratch_get("ec_ntt_work", n * sizeof(XYZZ<F>), (void**)&work));
     GA_CHECK(ctx->scratch_get("ec_ntt_twiddles", half * 32, (void**)&tw));
-    GA_CHECK(ctx->scratch_get("ec_ntt_redo", (half + 4) * 4, (void**)&redo));   // [count, pad | list]
+    GA_CHECK(redo.get(ctx, "ec_ntt_redo", half, 4));
     if (!i_dev || !o_dev) GA_CHECK(ctx->scratch_get("ec_ntt_io", bytes, (void**)&io));
-    uint32_t *count = redo, *list = redo + 4;
-    struct Drain {   // every return, an error's included, leaves with the stream idle: the caller's buffers outlive the copies
-        hipStream_t st;
-        ~Drain() { hipStreamSynchronize(st); }
-    } drain{st};
+    uint32_t *count = redo.words, *list = redo.list;
+    StreamDrain drain{st};
 
     Fe<FrP> winv = fe_const<FrP>(FrP::ROOT_INV);
     for (int k = 0; k < FrP::ADICITY - logn; k++) winv = sqr(winv);
@@ -258,25 +262,25 @@ int ec_ntt_to_lagrange(Ctx* ctx, const void* powers, size_t n, unsigned flags, v
     nn.l[1] = (uint32_t)((uint64_t)n >> 32);
     const Fe<FrP> ninv_mont = inv(to_mont(nn));
 
-    if (!i_dev) GA_HIP_CHECK(hipMemcpyAsync(io, powers, bytes, hipMemcpyHostToDevice, st));
+    const Affine<F>* src;
+    GA_CHECK(chunk_in(st, i_dev, (const Affine<F>*)powers, 0, n, io, &src));
     {
         StageTimer tm(ctx, "ec_ntt_setup");
         hipLaunchKernelGGL((ec_ntt_twiddle_kernel<FrP>), dim3((unsigned)((half + 255) / 256)), dim3(256), 0, st, tw, half, winv);
-        hipLaunchKernelGGL((ec_ntt_load_kernel<F>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, i_dev ? (const Affine<F>*)powers : (const Affine<F>*)io,
-                           (uint64_t)n, work);
+        hipLaunchKernelGGL((ec_ntt_load_kernel<F>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, (uint64_t)n, work);
         GA_KERNEL_CHECK();
     }
     constexpr unsigned T = Table29<F>::THREADS;
     const unsigned blocks = (unsigned)((half + T - 1) / T);
-    const uint64_t exact_blocks = (half + 63) / 64;
+    const unsigned exact_blocks = capped_grid(half, 64, EC_NTT_EXACT_MAX_BLOCKS);
     for (int s = 0; s < logn; s++) {
         char name[32];
         snprintf(name, sizeof(name), "ec_ntt_stage_%02d", s);
         GA_HIP_CHECK(hipMemsetAsync(count, 0, 16, st));
         StageTimer tm(ctx, name);
         hipLaunchKernelGGL((ec_ntt_stage_kernel<F, FrP>), dim3(blocks), dim3(T), 0, st, work, (const uint32_t*)tw, half, s, logn, uniform, ninv_mont, list, count);
-        hipLaunchKernelGGL((ec_ntt_exact_kernel<F, FrP>), dim3((unsigned)(exact_blocks < EC_NTT_EXACT_MAX_BLOCKS ? exact_blocks : EC_NTT_EXACT_MAX_BLOCKS)), dim3(64),
-                           0, st, work, (const uint32_t*)tw, s, logn, uniform, ninv_mont, (const uint32_t*)list, (const uint32_t*)count);
+        hipLaunchKernelGGL((ec_ntt_exact_kernel<F, FrP>), dim3(exact_blocks), dim3(64), 0, st, work, (const uint32_t*)tw, s, logn, uniform, ninv_mont,
+                           (const uint32_t*)list, (const uint32_t*)count);
         GA_KERNEL_CHECK();
     }
     {
@@ -284,15 +288,8 @@ int ec_ntt_to_lagrange(Ctx* ctx, const void* powers, size_t n, unsigned flags, v
         hipLaunchKernelGGL((ec_ntt_scale_kernel<F, FrP>), dim3(1), dim3(T), 0, st, work, 1u, from_mont(ninv_mont));
         GA_KERNEL_CHECK();
     }
-    {
-        StageTimer tm(ctx, "ec_ntt_affine");
-        constexpr unsigned AK = (unsigned)FixedBaseBatch<F>::AFFINE_K;
-        const unsigned lanes = (unsigned)((n + AK - 1) / AK);
-        hipLaunchKernelGGL((fixed_base_affine_kernel<F>), dim3((lanes + 63) / 64), dim3(64), 0, st, (const XYZZ<F>*)work, (uint32_t)n, (uint64_t)0, logn,
-                           o_dev ? (Affine<F>*)out : io);
-        GA_KERNEL_CHECK();
-    }
-    if (!o_dev) GA_HIP_CHECK(hipMemcpyAsync(out, io, bytes, hipMemcpyDeviceToHost, st));
+    GA_CHECK(launch_to_affine<F>(ctx, st, "ec_ntt_affine", work, (uint32_t)n, 0, logn, o_dev ? (Affine<F>*)out : io));
+    GA_CHECK(chunk_out(st, o_dev, (Affine<F>*)out, 0, n, io));
     GA_HIP_CHECK(hipStreamSynchronize(st));
     return GA_OK;
 }

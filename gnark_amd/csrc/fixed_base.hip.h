@@ -23,12 +23,12 @@
 #pragma once
 #include "keyio.hip.h"        // CurveB: the on-curve test of the base
 #include "msm_bucket.hip.h"   // Table29, LdsAcc29, load_point29, madd29 / madd29_complete; DigitWalk (msm_sort.hip.h)
+#include "vec_call.hip.h"     // the driver kit: StreamDrain, clamp_chunk, capped_grid, RedoList, chunk_in / chunk_out
 
 namespace ga {
 
 constexpr int FB_MAX_C = 18;                         // widest PLANNED window: 15 x 2^17 entries (120 MiB for BN254 G1)
 constexpr int FB_MAX_FORCED_C = 20;                  // widest window GA_FIXED_BASE_C may force (13 x 2^19 entries); narrowest: 2
-constexpr uint64_t FB_MAX_CHUNK = 1ull << 30;        // scalars per pass at the most: indices inside a pass are 32-bit
 constexpr unsigned FB_TABLE_MAX_BLOCKS = 2048;       // one-wave workgroups of the table build (two per SIMD: the kernel's occupancy)
 constexpr uint64_t FB_DEFAULT_CHUNK = 1ull << 22;    // scalars per pass: 0.9 GiB (BN254 G1) .. 2.4 GiB (BLS12-381 G2) of scratch
 
@@ -274,6 +274,16 @@ fixed_base_affine_kernel(const XYZZ<F>* __restrict__ sums, uint32_t n, uint64_t 
     }
 }
 
+// stage 3 as the point drivers launch it: out[first + i], or its bit reversal over logn >= 0 bits, i < n
+template <class F>
+int launch_to_affine(Ctx* ctx, hipStream_t st, const char* stage_name, const XYZZ<F>* sums, uint32_t n, uint64_t first, int logn, Affine<F>* out) {
+    StageTimer tm(ctx, stage_name, st);
+    constexpr unsigned K = (unsigned)FixedBaseBatch<F>::AFFINE_K;
+    hipLaunchKernelGGL((fixed_base_affine_kernel<F>), dim3(((n + K - 1) / K + 63) / 64), dim3(64), 0, st, sums, n, first, logn, out);
+    GA_KERNEL_CHECK();
+    return GA_OK;
+}
+
 // ---- host ------------------------------------------------------------------------------------------------------------------------
 template <class C, int G>
 int fixed_base_run(Ctx* ctx, const void* h_base, const void* scalars, size_t n, unsigned flags, void* out, int forced_c, uint64_t forced_chunk) {
@@ -281,7 +291,7 @@ int fixed_base_run(Ctx* ctx, const void* h_base, const void* scalars, size_t n, 
     typedef typename C::FrP FrP;
     Affine<F> base;
     memcpy(&base, h_base, sizeof(base));
-    if (!is_inf(base) && !eq(sqr(base.y), add(mul(sqr(base.x), base.x), CurveB<C, G>::get()))) {
+    if (!is_inf(base) && !eq(sqr(base.y), add(mul(sqr(base.x), base.x), CurveB<F>::get()))) {
         set_error("ga_batch_scalar_mul: the base is not a point of the curve");
         return GA_ERR_INVALID;
     }
@@ -292,29 +302,25 @@ int fixed_base_run(Ctx* ctx, const void* h_base, const void* scalars, size_t n, 
     fixed_base_plan<C>(n, forced_c, &c, &nwin);
     const uint32_t half = 1u << (c - 1);
     const uint64_t entries = (uint64_t)nwin * half;
-    uint64_t chunk = forced_chunk ? forced_chunk : FB_DEFAULT_CHUNK;
-    if (chunk > FB_MAX_CHUNK) chunk = FB_MAX_CHUNK;
-    if (chunk > n) chunk = n;
+    const uint64_t chunk = clamp_chunk(forced_chunk, FB_DEFAULT_CHUNK, n);
     hipStream_t st = ctx->work_stream();
 
     // the scratch of the whole call first: an allocation failure leaves nothing in flight
     Affine<F>* d_win;
-    uint32_t *table, *redo, *d_scalars = nullptr;
+    uint32_t *table, *d_scalars = nullptr;
+    RedoList redo;   // header: the counts of the two lists; list 1 (the fast loop's) | list 2 (the complete lazy loop's), chunk words each
     XYZZ<F>* sums;
     Affine<F>* d_out = nullptr;
     GA_CHECK(ctx->scratch_get("fb_win_bases", (size_t)nwin * sizeof(Affine<F>), (void**)&d_win));
     GA_CHECK(ctx->scratch_get("fb_table", entries * Table29<F>::WORDS * 4 + 256, (void**)&table));
     GA_CHECK(ctx->scratch_get("fb_sums", chunk * sizeof(XYZZ<F>), (void**)&sums));
-    GA_CHECK(ctx->scratch_get("fb_redo", (2 * chunk + 4) * 4, (void**)&redo));   // [2 counts, pad | list 1 | list 2]
+    GA_CHECK(redo.get(ctx, "fb_redo", 2 * chunk, 4));
     if (!s_dev) GA_CHECK(ctx->scratch_get("fb_scalars", chunk * 32, (void**)&d_scalars));
     if (!o_dev) GA_CHECK(ctx->scratch_get("fb_out", chunk * sizeof(Affine<F>), (void**)&d_out));
-    uint32_t *count = redo, *list1 = redo + 4, *list2 = redo + 4 + chunk;
+    uint32_t *count = redo.words, *list1 = redo.list, *list2 = redo.list + chunk;
     std::vector<Affine<F>> h_stage(!o_dev && bitrev ? chunk : 0);   // host output at bit-reversed indices: permuted here
     std::vector<Affine<F>> win((size_t)nwin);
-    struct Drain {   // every return, an error's included, leaves with the stream idle: the copies above and the caller's buffers outlive it
-        hipStream_t st;
-        ~Drain() { hipStreamSynchronize(st); }
-    } drain{st};
+    StreamDrain drain{st};
 
     // 1. window bases on the host (BITS sequential doublings), their multiples on the device
     {
@@ -329,24 +335,21 @@ int fixed_base_run(Ctx* ctx, const void* h_base, const void* scalars, size_t n, 
     {
         StageTimer tm(ctx, "fixed_base_table");
         const uint32_t kk = half < (uint32_t)FixedBaseBatch<F>::TABLE_K ? half : (uint32_t)FixedBaseBatch<F>::TABLE_K;
-        const uint64_t lanes = entries / kk;
-        const uint64_t blocks = (lanes + 63) / 64;
-        hipLaunchKernelGGL((fixed_base_table_kernel<F>), dim3((unsigned)(blocks < FB_TABLE_MAX_BLOCKS ? blocks : FB_TABLE_MAX_BLOCKS)), dim3(64), 0, st, (const Affine<F>*)d_win, c, nwin, table);
+        hipLaunchKernelGGL((fixed_base_table_kernel<F>), dim3(capped_grid(entries / kk, 64, FB_TABLE_MAX_BLOCKS)), dim3(64), 0, st, (const Affine<F>*)d_win, c, nwin, table);
         GA_KERNEL_CHECK();
     }
 
     constexpr unsigned AT = Table29<F>::THREADS;
-    constexpr unsigned AK = (unsigned)FixedBaseBatch<F>::AFFINE_K;
     for (uint64_t done = 0; done < n; done += chunk) {
         const uint32_t cn = (uint32_t)(n - done < chunk ? n - done : chunk);
-        const uint32_t* sc = s_dev ? (const uint32_t*)scalars + done * 8 : d_scalars;
-        if (!s_dev) GA_HIP_CHECK(hipMemcpyAsync(d_scalars, (const char*)scalars + done * 32, (size_t)cn * 32, hipMemcpyHostToDevice, st));
+        const uint32_t* sc;
+        GA_CHECK(chunk_in(st, s_dev, (const uint32_t*)scalars, done * 8, (uint64_t)cn * 8, d_scalars, &sc));
         GA_HIP_CHECK(hipMemsetAsync(count, 0, 16, st));
         {
             // 2. the fast loop; the lanes it flagged once more with the complete lazy loop (GA_MSM_EXACT_REDO=1, tests: straight to the
             // exact kernel); whatever is left with the exact kernel
             StageTimer tm(ctx, "fixed_base_accumulate");
-            const unsigned blocks = (cn + AT - 1) / AT, redo_blocks = blocks < 1024 ? blocks : 1024;
+            const unsigned blocks = (cn + AT - 1) / AT, redo_blocks = capped_grid(cn, AT, 1024);
             hipLaunchKernelGGL((fixed_base_accumulate_kernel<F, FrP, false>), dim3(blocks), dim3(AT), 0, st, (const uint32_t*)table, sc, cn, (int)mont, c,
                                nwin, sums, (const uint32_t*)nullptr, (const uint32_t*)nullptr, list1, count);
             if (!ctx->tun.msm_exact_redo)
@@ -359,18 +362,12 @@ int fixed_base_run(Ctx* ctx, const void* h_base, const void* scalars, size_t n, 
                                (const uint32_t*)list2, (const uint32_t*)(count + 1));
             GA_KERNEL_CHECK();
         }
-        {
-            // 3. to affine: straight to its place in a device-resident output, else dense into the chunk's staging buffer
-            StageTimer tm(ctx, "fixed_base_affine");
-            const unsigned lanes = (cn + AK - 1) / AK;
-            hipLaunchKernelGGL((fixed_base_affine_kernel<F>), dim3((lanes + 63) / 64), dim3(64), 0, st, (const XYZZ<F>*)sums, cn, o_dev ? done : 0,
-                               o_dev ? logn : -1, o_dev ? (Affine<F>*)out : d_out);
-            GA_KERNEL_CHECK();
-        }
+        // 3. to affine: straight to its place in a device-resident output, else dense into the chunk's staging buffer
+        GA_CHECK(launch_to_affine<F>(ctx, st, "fixed_base_affine", sums, cn, o_dev ? done : 0, o_dev ? logn : -1, o_dev ? (Affine<F>*)out : d_out));
         if (!o_dev) {
             Affine<F>* h_out = (Affine<F>*)out;
             if (!bitrev) {
-                GA_HIP_CHECK(hipMemcpyAsync(h_out + done, d_out, (size_t)cn * sizeof(Affine<F>), hipMemcpyDeviceToHost, st));
+                GA_CHECK(chunk_out(st, false, h_out, done, cn, d_out));
             } else {
                 GA_HIP_CHECK(hipMemcpyAsync(h_stage.data(), d_out, (size_t)cn * sizeof(Affine<F>), hipMemcpyDeviceToHost, st));
                 GA_HIP_CHECK(hipStreamSynchronize(st));

@@ -12,8 +12,8 @@
 
 #include <vector>
 
-#include "common.hip.h"
 #include "fr_powers.hip.h"
+#include "vec_call.hip.h"   // StreamDrain, chunk_in / chunk_out
 
 namespace ga {
 
@@ -73,10 +73,7 @@ int fr_lagrange_run(Ctx* ctx, int logn, const void* tau, size_t m, unsigned flag
     GA_CHECK(ctx->scratch_get("fr_lagrange_den", m * 32, (void**)&den));
     if (!o_dev) GA_CHECK(ctx->scratch_get("fr_lagrange_out", m * 32, (void**)&d_out));
     uint32_t* dst = o_dev ? (uint32_t*)out : d_out;
-    struct Drain {
-        hipStream_t st;
-        ~Drain() { hipStreamSynchronize(st); }
-    } drain{st};
+    StreamDrain drain{st};
     {
         StageTimer tm(ctx, "fr_lagrange_points");
         const uint64_t per = 256 * FR_LAGRANGE_RUN;
@@ -91,7 +88,7 @@ int fr_lagrange_run(Ctx* ctx, int logn, const void* tau, size_t m, unsigned flag
         hipLaunchKernelGGL((fr_lagrange_fuse_kernel<FrP>), dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, c, (const uint32_t*)den, (uint64_t)m, (int)mont, dst);
         GA_KERNEL_CHECK();
     }
-    if (!o_dev) GA_HIP_CHECK(hipMemcpyAsync(out, d_out, m * 32, hipMemcpyDeviceToHost, st));
+    GA_CHECK(chunk_out(st, o_dev, (uint32_t*)out, 0, m * 8, d_out));
     GA_HIP_CHECK(hipStreamSynchronize(st));
     return GA_OK;
 }
@@ -134,12 +131,9 @@ int fr_compact_run(Ctx* ctx, const void* v, size_t n, unsigned flags, void* out,
     if (mask) GA_CHECK(ctx->scratch_get("fr_compact_mask", n, (void**)&d_mask));
     if (!i_dev) GA_CHECK(ctx->scratch_get("fr_compact_in", n * 32, (void**)&d_v));
     if (!direct) GA_CHECK(ctx->scratch_get("fr_compact_out", n * 32, (void**)&d_dst));
-    struct Drain {
-        hipStream_t st;
-        ~Drain() { hipStreamSynchronize(st); }
-    } drain{st};
-    if (!i_dev) GA_HIP_CHECK(hipMemcpyAsync(d_v, v, n * 32, hipMemcpyHostToDevice, st));
-    const uint32_t* src = i_dev ? (const uint32_t*)v : d_v;
+    StreamDrain drain{st};
+    const uint32_t* src;
+    GA_CHECK(chunk_in(st, i_dev, (const uint32_t*)v, 0, n * 8, d_v, &src));
     uint32_t* dst = direct ? (uint32_t*)out : d_dst;
     const unsigned blocks = (unsigned)((n + 255) / 256);
     uint32_t tail[2] = {0, 0};   // the last offset and the last flag: their sum is the number kept
@@ -186,16 +180,13 @@ int fr_powers_run(Ctx* ctx, const void* scalars, uint64_t first, size_t n, unsig
     hipStream_t st = ctx->work_stream();
     uint32_t* d_out = nullptr;
     if (!o_dev) GA_CHECK(ctx->scratch_get("fr_powers_out", n * 32, (void**)&d_out));
-    struct Drain {
-        hipStream_t st;
-        ~Drain() { hipStreamSynchronize(st); }
-    } drain{st};
+    StreamDrain drain{st};
     {
         StageTimer tm(ctx, "fr_powers");
         hipLaunchKernelGGL((fr_powers_kernel<FrP>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, c, t, (int)mont, first, (uint64_t)n, o_dev ? (uint32_t*)out : d_out);
         GA_KERNEL_CHECK();
     }
-    if (!o_dev) GA_HIP_CHECK(hipMemcpyAsync(out, d_out, n * 32, hipMemcpyDeviceToHost, st));
+    GA_CHECK(chunk_out(st, o_dev, (uint32_t*)out, 0, n * 8, d_out));
     GA_HIP_CHECK(hipStreamSynchronize(st));
     return GA_OK;
 }

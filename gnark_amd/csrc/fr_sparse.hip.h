@@ -21,8 +21,9 @@
 #pragma once
 #include <vector>
 
-#include "fr_powers.hip.h"     // fr_canonical
-#include "sparse_sums.hip.h"   // SPARSE_FINAL: one segment shape for both sparse calls
+#include "csr_plan.hip.h"    // CsrLevels, csr_validate, csr_cut_levels; SPARSE_FINAL: one segment shape for both sparse calls
+#include "fr_powers.hip.h"   // fr_canonical
+#include "vec_call.hip.h"    // StreamDrain, capped_grid, chunk_in / chunk_out
 
 namespace ga {
 
@@ -64,74 +65,17 @@ fr_sparse_kernel(const uint32_t* __restrict__ segs, uint32_t nseg, const uint32_
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
-// what the walk over the matrix leaves for the device
-struct FrSparsePlan {
-    std::vector<uint32_t> segs;    // 3 words per segment, level after level
-    struct Level {
-        uint64_t first;            // its first segment in `segs`
-        uint32_t nseg, nparts;     // segments; partial sums it writes
-    };
-    std::vector<Level> levels;
-};
-
 // validation (nothing has been written when it fails), then the segments
 inline int fr_sparse_plan(size_t n_cols, const uint64_t* row_start, size_t n_rows, const uint32_t* terms, size_t n_coeffs, const uint8_t* row_class,
-                          size_t n_classes, uint32_t S, FrSparsePlan& plan) {
-    if (row_start[0] != 0) {
-        set_error("ga_fr_sparse_matvec: row_start[0] = %llu, not 0", (unsigned long long)row_start[0]);
-        return GA_ERR_INVALID;
-    }
-    for (size_t r = 0; r < n_rows; r++)
-        if (row_start[r + 1] < row_start[r]) {
-            set_error("ga_fr_sparse_matvec: row_start decreases at row %zu (%llu after %llu)", r, (unsigned long long)row_start[r + 1],
-                      (unsigned long long)row_start[r]);
-            return GA_ERR_INVALID;
-        }
-    const uint64_t nnz = row_start[n_rows];
-    if (nnz >= (1ull << 32)) {
-        set_error("ga_fr_sparse_matvec: row_start[n_rows] = %llu terms, at most 2^32 - 1 per call", (unsigned long long)nnz);
-        return GA_ERR_INVALID;
-    }
-    for (uint64_t k = 0; k < nnz; k++)
-        if (terms[2 * k] >= n_coeffs || terms[2 * k + 1] >= n_cols) {
-            set_error("ga_fr_sparse_matvec: term %llu = {cid %u, col %u} outside %zu coefficients, %zu columns", (unsigned long long)k, terms[2 * k],
-                      terms[2 * k + 1], n_coeffs, n_cols);
-            return GA_ERR_INVALID;
-        }
+                          size_t n_classes, uint32_t S, CsrLevels& plan) {
+    GA_CHECK(csr_validate("ga_fr_sparse_matvec", "columns", n_cols, row_start, n_rows, terms, n_coeffs));
     if (row_class)
         for (size_t r = 0; r < n_rows; r++)
             if (row_class[r] >= n_classes) {
                 set_error("ga_fr_sparse_matvec: row_class[%zu] = %u outside %zu classes", r, (unsigned)row_class[r], n_classes);
                 return GA_ERR_INVALID;
             }
-    // level 0: every row; the levels after it: the rows that are still more than one partial sum
-    struct Long {
-        uint32_t row;
-        uint64_t first, count;
-    };
-    std::vector<Long> rows, longer;
-    auto cut = [&](uint32_t row, uint64_t first, uint64_t count, uint32_t& nparts) {
-        if (count <= S) {
-            plan.segs.insert(plan.segs.end(), {(uint32_t)first, (uint32_t)count, SPARSE_FINAL | row});
-            return;
-        }
-        longer.push_back({row, nparts, (count + S - 1) / S});
-        for (uint64_t o = 0; o < count; o += S) plan.segs.insert(plan.segs.end(), {(uint32_t)(first + o), (uint32_t)(count - o < S ? count - o : S), nparts++});
-    };
-    {
-        FrSparsePlan::Level lv{0, 0, 0};
-        for (size_t r = 0; r < n_rows; r++) cut((uint32_t)r, row_start[r], row_start[r + 1] - row_start[r], lv.nparts);
-        lv.nseg = (uint32_t)(plan.segs.size() / 3);
-        plan.levels.push_back(lv);
-    }
-    while (!longer.empty()) {
-        rows.swap(longer);
-        longer.clear();
-        FrSparsePlan::Level lv{plan.segs.size() / 3, 0, 0};
-        for (const Long& w : rows) cut(w.row, w.first, w.count, lv.nparts);
-        lv.nseg = (uint32_t)(plan.segs.size() / 3 - lv.first);
-        plan.levels.push_back(lv);
-    }
+    csr_cut_levels(row_start, n_rows, S, plan);
     return GA_OK;
 }
 
@@ -155,14 +99,13 @@ int fr_sparse_run(Ctx* ctx, const void* x, size_t n_cols, const uint64_t* row_st
     typedef typename C::FrP FrP;
     const bool mont = (flags & GA_SCALARS_MONTGOMERY) != 0, i_dev = (flags & GA_BASES_ON_DEVICE) != 0, o_dev = (flags & GA_RESULT_ON_DEVICE) != 0;
     const uint32_t S = segment >= 2 ? segment : FR_SPARSE_DEFAULT_SEGMENT;
-    FrSparsePlan plan;
+    CsrLevels plan;
     GA_CHECK(fr_sparse_plan(n_cols, row_start, n_rows, terms, n_coeffs, row_class, n_classes, S, plan));
     const uint64_t nnz = row_start[n_rows];
     const std::vector<uint32_t> h_coeffs = fr_host_montgomery<FrP>(coeffs, nnz ? n_coeffs : 0, mont);
     const std::vector<uint32_t> h_scales = fr_host_montgomery<FrP>(row_scales, row_class ? n_classes : 0, mont);
-    uint64_t parts[2] = {0, 0};
-    for (size_t l = 0; l < plan.levels.size(); l++)
-        if (plan.levels[l].nparts > parts[l & 1]) parts[l & 1] = plan.levels[l].nparts;
+    uint64_t parts[2];
+    plan.part_sizes(parts);
     hipStream_t st = ctx->work_stream();
 
     // the scratch of the whole call first: an allocation failure leaves nothing in flight
@@ -179,10 +122,7 @@ int fr_sparse_run(Ctx* ctx, const void* x, size_t n_cols, const uint64_t* row_st
         if (parts[b]) GA_CHECK(ctx->scratch_get(b ? "fr_sparse_partial_b" : "fr_sparse_partial_a", parts[b] * 32, (void**)&part[b]));
     if (!i_dev && n_cols) GA_CHECK(ctx->scratch_get("fr_sparse_x", n_cols * 32, (void**)&d_x));
     if (!o_dev) GA_CHECK(ctx->scratch_get("fr_sparse_out", n_rows * 32, (void**)&d_out));
-    struct Drain {   // every return, an error's included, leaves with the stream idle: the caller's buffers and the plan outlive the copies
-        hipStream_t st;
-        ~Drain() { hipStreamSynchronize(st); }
-    } drain{st};
+    StreamDrain drain{st};
 
     if (nnz) {
         GA_HIP_CHECK(hipMemcpyAsync(d_terms, terms, nnz * 8, hipMemcpyHostToDevice, st));
@@ -193,18 +133,18 @@ int fr_sparse_run(Ctx* ctx, const void* x, size_t n_cols, const uint64_t* row_st
         GA_HIP_CHECK(hipMemcpyAsync(d_scales, h_scales.data(), h_scales.size() * 4, hipMemcpyHostToDevice, st));
         GA_HIP_CHECK(hipMemcpyAsync(d_class, row_class, n_rows, hipMemcpyHostToDevice, st));
     }
-    if (!i_dev && n_cols) GA_HIP_CHECK(hipMemcpyAsync(d_x, x, n_cols * 32, hipMemcpyHostToDevice, st));
-    const uint32_t* src = i_dev ? (const uint32_t*)x : d_x;
+    const uint32_t* src;
+    GA_CHECK(chunk_in(st, i_dev, (const uint32_t*)x, 0, n_cols * 8, d_x, &src));
     uint32_t* dst = o_dev ? (uint32_t*)out : d_out;
 
     for (size_t l = 0; l < plan.levels.size(); l++) {
-        const FrSparsePlan::Level& lv = plan.levels[l];
+        const CsrLevels::Level& lv = plan.levels[l];
         if (lv.nseg == 0) continue;
         char name[32];
         snprintf(name, sizeof(name), "fr_sparse_%02d", (int)l);
         StageTimer tm(ctx, name);
         const uint32_t* sg = d_segs + 3 * lv.first;
-        const unsigned all_blocks = (lv.nseg + FR_SPARSE_THREADS - 1) / FR_SPARSE_THREADS, blocks = all_blocks < FR_SPARSE_MAX_BLOCKS ? all_blocks : FR_SPARSE_MAX_BLOCKS;
+        const unsigned blocks = capped_grid(lv.nseg, FR_SPARSE_THREADS, FR_SPARSE_MAX_BLOCKS);
         if (l == 0)
             hipLaunchKernelGGL((fr_sparse_kernel<FrP, true>), dim3(blocks), dim3(FR_SPARSE_THREADS), 0, st, sg, lv.nseg, (const uint32_t*)d_terms, (const uint32_t*)d_coeffs, src,
                                (int)mont, part[0], dst, (const uint8_t*)d_class, (const uint32_t*)d_scales);
@@ -213,7 +153,7 @@ int fr_sparse_run(Ctx* ctx, const void* x, size_t n_cols, const uint64_t* row_st
                                (const uint32_t*)part[(l - 1) & 1], (int)mont, part[l & 1], dst, (const uint8_t*)d_class, (const uint32_t*)d_scales);
         GA_KERNEL_CHECK();
     }
-    if (!o_dev) GA_HIP_CHECK(hipMemcpyAsync(out, d_out, n_rows * 32, hipMemcpyDeviceToHost, st));
+    GA_CHECK(chunk_out(st, o_dev, (uint32_t*)out, 0, n_rows * 8, d_out));
     GA_HIP_CHECK(hipStreamSynchronize(st));   // the one synchronisation of a call with everything on the device
     return GA_OK;
 }

@@ -14,24 +14,13 @@ namespace ga {
 
 // ---- checked reads: ProvingKey.ReadFrom semantics (ga_g16_pk_read_*_checked) ------------------------------------------------------------
 // Every point the read keeps is tested for curve and subgroup membership where it first sits on the device (check_points.hip.h,
-// instantiated in check_points_<curve>_g<k>.hip): an encoded vector chunk by chunk in the staging buffer, right behind the decode
+// declared in common.hip.h): an encoded vector chunk by chunk in the staging buffer, right behind the decode
 // kernel and beside the file read of the next chunk; a dumped slice once it is uploaded; a header point from its host image.
 // The first bad point of a vector ends the read: GA_ERR_INVALID naming the vector, the index within the FILE's vector and the failure.
-template <class C, int G>
-int check_points_run(Ctx* ctx, const void* points, size_t n, unsigned flags, uint8_t* status, uint64_t* out4, int naive, uint64_t forced_chunk);
-template <class C, int G>
-int check_points_resident(Ctx* ctx, hipStream_t st, const void* d_points, uint64_t n, uint64_t base, int reset, int naive);
-template <class C, int G>
-int check_points_tally(Ctx* ctx, hipStream_t st, uint64_t* out4, int* first_status);
-
 static const char* key_vector_name(int which, int commitment_half) {
     static const char* const names[GA_KEY_NB_VECTORS] = {"G1.A", "G1.B", "G1.Z", "G1.K", "G2.B"};
     if (which >= 0 && which < GA_KEY_NB_VECTORS) return names[which];
     return commitment_half ? "a commitment key's BasisExpSigma" : "a commitment key's Basis";
-}
-static int key_check_naive() {
-    const char* e = getenv("GA_CHECK_NAIVE");
-    return e ? atoi(e) != 0 : 0;
 }
 static int key_check_verdict(const char* name, const uint64_t* out4, int first_status) {
     if (first_status == GA_POINT_OK) return GA_OK;
@@ -45,14 +34,14 @@ template <class C, int G>
 static int key_check_resident(Ctx* ctx, const void* d_points, uint64_t cnt, uint64_t base, const char* name) {
     uint64_t out4[4];
     int first = GA_POINT_OK;
-    GA_CHECK((check_points_resident<C, G>(ctx, ctx->stream, d_points, cnt, base, 1, key_check_naive())));
+    GA_CHECK((check_points_resident<C, G>(ctx, ctx->stream, d_points, cnt, base, 1, check_naive_knob())));
     GA_CHECK((check_points_tally<C, G>(ctx, ctx->stream, out4, &first)));
     return key_check_verdict(name, out4, first);
 }
 template <class C, int G>
 static int key_check_header_point(Ctx* ctx, const std::vector<uint8_t>& image, const char* name) {
     uint64_t out4[4];
-    GA_CHECK((check_points_run<C, G>(ctx, image.data(), 1, 0, nullptr, out4, key_check_naive(), 0)));
+    GA_CHECK((check_points_run<C, G>(ctx, image.data(), 1, 0, nullptr, out4, check_naive_knob(), 0)));
     return key_check_verdict(name, out4, out4[0] ? GA_POINT_OFF_CURVE : out4[1] ? GA_POINT_NOT_IN_SUBGROUP : GA_POINT_OK);
 }
 
@@ -65,7 +54,7 @@ static int decode_stream(Ctx* ctx, Staging& sg, ByteSource& src, uint64_t count,
     const size_t enc = compressed ? sizeof(F) : 2 * sizeof(F), psz = sizeof(Affine<F>);
     const uint64_t per_chunk = Staging::BYTES / enc;
     GA_HIP_CHECK(hipMemsetAsync(sg.d_bad, 0, 4, ctx->stream));
-    const int naive = check_name ? key_check_naive() : 0;
+    const int naive = check_name ? check_naive_knob() : 0;
     int k = 0, tally = 0;
     for (uint64_t done = 0; done < count; k ^= 1) {
         const uint64_t cn = count - done < per_chunk ? count - done : per_chunk;

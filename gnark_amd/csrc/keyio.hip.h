@@ -111,13 +111,12 @@ GA_HD_CALL bool fe_sqrt(const Fe2<P>& a, Fe2<P>* out) {
     return eq(sqr(r), a);
 }
 
-template <class C, int G> struct CurveB;
-template <class C> struct CurveB<C, GA_G1> {
-    typedef typename C::FpP P;
+// the curve's b by coordinate field (Fp: G1, Fp2: the twist of G2)
+template <class F> struct CurveB;
+template <class P> struct CurveB<Fe<P>> {
     GA_HD static Fe<P> get() { return fe_const<P>(P::B1); }
 };
-template <class C> struct CurveB<C, GA_G2> {
-    typedef typename C::FpP P;
+template <class P> struct CurveB<Fe2<P>> {
     GA_HD static Fe2<P> get() { return {fe_const<P>(P::B2_0), fe_const<P>(P::B2_1)}; }
 };
 
@@ -189,7 +188,7 @@ GA_HD bool point_decode(const uint8_t* b, bool compressed, Affine<typename Group
     }
     F x, y;
     if (!coord_from_bytes(b, f.mask, &x)) return false;
-    const F rhs = add(mul(sqr(x), x), CurveB<C, G>::get());
+    const F rhs = add(mul(sqr(x), x), CurveB<F>::get());
     if (compressed) {
         if (!fe_sqrt(rhs, &y)) return false;             // x is not the abscissa of a curve point
         if (fe_lex_largest(y) != f.largest) y = neg(y);

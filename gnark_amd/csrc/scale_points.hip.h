@@ -23,11 +23,11 @@
 //        baseline of tools/scale_points_bench.py.
 //   3. scale_points_exact_kernel
 //        the flagged lanes once more with the complete formulas of ec.hip.h (scalar_mul), grid-stride over the redo list in one-wave
-//        workgroups like ec_ntt_exact_kernel.
+//        workgroups like ec_ntt_exact_kernel (ec_ntt.hip.h: EC_NTT_EXACT_MAX_BLOCKS).
 //   4. fixed_base_affine_kernel (fixed_base.hip.h)  XYZZ -> affine, dense.
 // Bounds of the unreduced sequence, G1 and G2: tools/lazy_bounds.py check_ladder(curve, fp2).
 #pragma once
-#include "ec_ntt.hip.h"   // ec_ntt_scalar_mul29, ec_ntt_pack / _unpack / _to_exact / _from_exact; fixed_base_affine_kernel
+#include "ec_ntt.hip.h"   // ec_ntt_scalar_mul29, ec_ntt_pack / _unpack / _to_exact / _from_exact, affine_to_lazy4; vec_call.hip.h
 #include "fr_powers.hip.h"   // fr_canonical, fr_power_term
 
 namespace ga {
@@ -84,12 +84,6 @@ struct ScaleDigits {
     }
 };
 
-template <class F>
-__device__ __forceinline__ Lazy4<F> scale_affine_lazy(const Affine<F>& a) {
-    const typename Lazy<F>::T one = Lazy<F>::from_mem(FieldTraits<F>::one());
-    return {Lazy<F>::from_mem(a.x), Lazy<F>::from_mem(a.y), one, one};
-}
-
 // table[e * n + i] = [e + 1] P_i, packed; returns true when an entry is a point at infinity (an exceptional step on the way to it).
 // One point is live at a time: what a step needs beside it comes back from the table (packed entries unpack without arithmetic).
 template <class F>
@@ -101,7 +95,7 @@ __device__ __forceinline__ bool scale_build_table(const Affine<F>& P, XYZZ<F>* _
         store_pod(&table[(uint64_t)(m - 1) * n + i], q);
     };
     auto get = [&](int m) { return ec_ntt_unpack<F>(load_pod<XYZZ<F>>(&table[(uint64_t)(m - 1) * n + i])); };
-    Lazy4<F> t = scale_affine_lazy<F>(P);
+    Lazy4<F> t = affine_to_lazy4<F>(P);
     put(1, t);
     dbl29<F>(t);
     put(2, t);
@@ -182,7 +176,7 @@ scale_points_plain_kernel(const Affine<F>* __restrict__ points, const uint32_t* 
             scale_store_inf<F>(&sums[i]);
             continue;
         }
-        Lazy4<F> acc = scale_affine_lazy<F>(P);
+        Lazy4<F> acc = affine_to_lazy4<F>(P);
         ec_ntt_scalar_mul29<F>(acc, LdsAcc29<F>(lds + threadIdx.x), s);
         if (f29_is_zero_mod_p(acc.zz)) redo[atomicAdd(redo_count, 1u)] = i;
         else store_pod(&sums[i], ec_ntt_pack<F>(acc));
@@ -215,28 +209,23 @@ int scale_points_run(Ctx* ctx, const void* points, size_t n, int mode, const voi
     typedef typename C::FrP FrP;
     const bool mont = (flags & GA_SCALARS_MONTGOMERY) != 0, s_dev = (flags & GA_SCALARS_ON_DEVICE) != 0;
     const bool i_dev = (flags & GA_BASES_ON_DEVICE) != 0, o_dev = (flags & GA_RESULT_ON_DEVICE) != 0;
-    uint64_t chunk = forced_chunk ? forced_chunk : SCALE_DEFAULT_CHUNK;
-    if (chunk > FB_MAX_CHUNK) chunk = FB_MAX_CHUNK;
-    if (chunk > n) chunk = n;
+    const uint64_t chunk = clamp_chunk(forced_chunk, SCALE_DEFAULT_CHUNK, n);
     hipStream_t st = ctx->work_stream();
 
     // the scratch of the whole call first: an allocation failure leaves nothing in flight
     XYZZ<F>*table = nullptr, *sums;
-    uint32_t *canon, *redo, *d_scalars = nullptr;
-    uint64_t* total;
+    uint32_t *canon, *d_scalars = nullptr;
+    RedoList redo;   // header: the call's total (64 bits), the chunk's count, pad
     Affine<F>* io = nullptr;
     if (windowed) GA_CHECK(ctx->scratch_get("scale_table", SCALE_TABLE * chunk * sizeof(XYZZ<F>), (void**)&table));
     GA_CHECK(ctx->scratch_get("scale_sums", chunk * sizeof(XYZZ<F>), (void**)&sums));
     GA_CHECK(ctx->scratch_get("scale_canonical", chunk * 32, (void**)&canon));
-    GA_CHECK(ctx->scratch_get("scale_redo", (chunk + 8) * 4, (void**)&redo));   // [total (64 bits), count, pad | list]
+    GA_CHECK(redo.get(ctx, "scale_redo", chunk, 8));
     if (mode == GA_SCALE_EACH && !s_dev) GA_CHECK(ctx->scratch_get("scale_scalars", chunk * 32, (void**)&d_scalars));
     if (!i_dev || !o_dev) GA_CHECK(ctx->scratch_get("scale_io", chunk * sizeof(Affine<F>), (void**)&io));
-    total = (uint64_t*)redo;
-    uint32_t *count = redo + 2, *list = redo + 8;
-    struct Drain {   // every return, an error's included, leaves with the stream idle: the caller's buffers outlive the copies
-        hipStream_t st;
-        ~Drain() { hipStreamSynchronize(st); }
-    } drain{st};
+    uint64_t* total = (uint64_t*)redo.words;
+    uint32_t *count = redo.words + 2, *list = redo.list;
+    StreamDrain drain{st};
 
     Fe<FrP> a = fe_zero<FrP>(), b = fe_zero<FrP>();
     if (mode != GA_SCALE_EACH) memcpy(&a, scalars, 32);
@@ -245,18 +234,14 @@ int scale_points_run(Ctx* ctx, const void* points, size_t n, int mode, const voi
     GA_HIP_CHECK(hipMemsetAsync(total, 0, 8, st));
 
     constexpr unsigned T = Table29<F>::THREADS;
-    constexpr unsigned AK = (unsigned)FixedBaseBatch<F>::AFFINE_K;
     for (uint64_t done = 0; done < n; done += chunk) {
         const uint32_t cn = (uint32_t)(n - done < chunk ? n - done : chunk);
         const uint32_t* sc = nullptr;
-        if (mode == GA_SCALE_EACH) {
-            sc = s_dev ? (const uint32_t*)scalars + done * 8 : d_scalars;
-            if (!s_dev) GA_HIP_CHECK(hipMemcpyAsync(d_scalars, (const char*)scalars + done * 32, (size_t)cn * 32, hipMemcpyHostToDevice, st));
-        }
+        if (mode == GA_SCALE_EACH) GA_CHECK(chunk_in(st, s_dev, (const uint32_t*)scalars, done * 8, (uint64_t)cn * 8, d_scalars, &sc));
         // the chunk's points: read where they are on the device, else staged; the staging buffer also takes a host-bound result (the
         // affine kernel is the last reader of nothing but the sums, so input and output may share it -- as they do for out == points)
-        const Affine<F>* src = i_dev ? (const Affine<F>*)points + done : io;
-        if (!i_dev) GA_HIP_CHECK(hipMemcpyAsync(io, (const Affine<F>*)points + done, (size_t)cn * sizeof(Affine<F>), hipMemcpyHostToDevice, st));
+        const Affine<F>* src;
+        GA_CHECK(chunk_in(st, i_dev, (const Affine<F>*)points, done, cn, io, &src));
         GA_HIP_CHECK(hipMemsetAsync(count, 0, 8, st));
         {
             StageTimer tm(ctx, "scale_scalars");
@@ -265,23 +250,17 @@ int scale_points_run(Ctx* ctx, const void* points, size_t n, int mode, const voi
         }
         {
             StageTimer tm(ctx, "scale_ladder");
-            const unsigned all_blocks = (cn + T - 1) / T, blocks = all_blocks < SCALE_MAX_BLOCKS ? all_blocks : SCALE_MAX_BLOCKS, exact_blocks = (cn + 63) / 64;
+            const unsigned blocks = capped_grid(cn, T, SCALE_MAX_BLOCKS), exact_blocks = capped_grid(cn, 64, EC_NTT_EXACT_MAX_BLOCKS);
             if (windowed)
                 hipLaunchKernelGGL((scale_points_window_kernel<F>), dim3(blocks), dim3(T), 0, st, src, (const uint32_t*)canon, cn, table, sums, list, count);
             else
                 hipLaunchKernelGGL((scale_points_plain_kernel<F>), dim3(blocks), dim3(T), 0, st, src, (const uint32_t*)canon, cn, sums, list, count);
-            hipLaunchKernelGGL((scale_points_exact_kernel<F>), dim3(exact_blocks < EC_NTT_EXACT_MAX_BLOCKS ? exact_blocks : EC_NTT_EXACT_MAX_BLOCKS), dim3(64), 0, st, src,
-                               (const uint32_t*)canon, sums, (const uint32_t*)list, (const uint32_t*)count, total);
+            hipLaunchKernelGGL((scale_points_exact_kernel<F>), dim3(exact_blocks), dim3(64), 0, st, src, (const uint32_t*)canon, sums, (const uint32_t*)list,
+                               (const uint32_t*)count, total);
             GA_KERNEL_CHECK();
         }
-        {
-            StageTimer tm(ctx, "scale_affine");
-            const unsigned lanes = (cn + AK - 1) / AK;
-            hipLaunchKernelGGL((fixed_base_affine_kernel<F>), dim3((lanes + 63) / 64), dim3(64), 0, st, (const XYZZ<F>*)sums, cn, o_dev ? done : (uint64_t)0, -1,
-                               o_dev ? (Affine<F>*)out : io);
-            GA_KERNEL_CHECK();
-        }
-        if (!o_dev) GA_HIP_CHECK(hipMemcpyAsync((Affine<F>*)out + done, io, (size_t)cn * sizeof(Affine<F>), hipMemcpyDeviceToHost, st));
+        GA_CHECK(launch_to_affine<F>(ctx, st, "scale_affine", sums, cn, o_dev ? done : 0, -1, o_dev ? (Affine<F>*)out : io));
+        GA_CHECK(chunk_out(st, o_dev, (Affine<F>*)out, done, cn, io));
     }
     GA_HIP_CHECK(hipMemcpyAsync(&h_total, total, 8, hipMemcpyDeviceToHost, st));
     GA_HIP_CHECK(hipStreamSynchronize(st));   // the one synchronisation of a call with everything on the device

@@ -15,7 +15,7 @@
 //        scale_points_exact_kernel     its flagged lanes with the complete formulas.
 //   2. sparse_sums_kernel<F, true>     one lane per segment of terms.  The accumulator stays in registers and starts from the segment's
 //                                      first operand that is not at infinity; every further one is ONE add29 of the affine point
-//                                      (scale_affine_lazy), of its dbl29, or of prod[g], y negated (f29_sub<2>(0, y), before the
+//                                      (affine_to_lazy4), of its dbl29, or of prod[g], y negated (f29_sub<2>(0, y), before the
 //                                      doubling: on a canonical value) for a minus sign.  Nothing is branched on inside the additions:
 //                                      an exceptional one leaves ZZ == 0 (mod p), which is absorbing, so ONE exact test per segment
 //                                      flags it.  A row of at most S terms writes its sum; a longer row writes partial sums, which
@@ -30,13 +30,13 @@
 #pragma once
 #include <vector>
 
-#include "scale_points.hip.h"   // the windowed ladder and its exact redo; scale_affine_lazy, ec_ntt_pack / _unpack; fixed_base_affine_kernel
+#include "csr_plan.hip.h"       // CsrLevels, csr_validate, csr_cut_levels; SPARSE_FINAL
+#include "scale_points.hip.h"   // the windowed ladder and its exact redo; affine_to_lazy4, ec_ntt_pack / _unpack (ec_ntt.hip.h); vec_call.hip.h
 
 namespace ga {
 
 constexpr uint32_t SPARSE_DEFAULT_SEGMENT = 16;   // terms (or partial sums) per lane (GA_SPARSE_SEGMENT): the fastest whole call of the A/B over
                                                   // {8, 16, 32, 64, 128} on a matrix with one 2^20-term row (tools/phase2_init_bench.py)
-constexpr uint32_t SPARSE_FINAL = 1u << 31;       // segment destination: the row's sum (else a partial sum of the next level)
 // term code, word 0: kind in bits 0-1, bit 2 = subtract; word 1: the column (POINT, DOUBLE) or the product index (PRODUCT)
 enum { SPARSE_SKIP = 0, SPARSE_POINT = 1, SPARSE_DOUBLE = 2, SPARSE_PRODUCT = 3, SPARSE_MINUS = 4 };
 
@@ -73,7 +73,7 @@ __device__ __forceinline__ bool sparse_operand(const uint32_t* __restrict__ code
     } else {
         const Affine<F> P = load_pod<Affine<F>>(&points[idx]);
         if (is_inf(P)) return false;
-        e = scale_affine_lazy<F>(P);
+        e = affine_to_lazy4<F>(P);
     }
     if (minus) e.y = f29_sub<2>(Lazy<F>::from_mem(FieldTraits<F>::zero()), e.y);   // 2p - y
     if (kind == SPARSE_DOUBLE) dbl29<F>(e);
@@ -145,12 +145,7 @@ struct SparsePlan {
     std::vector<uint32_t> codes;   // 2 words per term
     std::vector<uint32_t> gen;     // {cid, col} per general term, in product order
     std::vector<uint32_t> mags;    // 8 words per coefficient: min(c, r - c), canonical
-    std::vector<uint32_t> segs;    // 3 words per segment, level after level
-    struct Level {
-        uint64_t first;            // its first segment in `segs`
-        uint32_t nseg, nparts;     // segments; partial sums it writes
-    };
-    std::vector<Level> levels;
+    CsrLevels rows;                // the segments of the row sums, level after level
 };
 
 // coefficient -> (kind, minus); the magnitude into mag[8]
@@ -183,27 +178,8 @@ template <class C>
 int sparse_sums_plan(size_t n_points, const uint64_t* row_start, size_t n_rows, const uint32_t* terms, const void* coeffs, size_t n_coeffs,
                      bool mont, uint32_t S, int cid_order, SparsePlan& plan) {
     typedef typename C::FrP FrP;
-    if (row_start[0] != 0) {
-        set_error("ga_sparse_point_sums: row_start[0] = %llu, not 0", (unsigned long long)row_start[0]);
-        return GA_ERR_INVALID;
-    }
-    for (size_t r = 0; r < n_rows; r++)
-        if (row_start[r + 1] < row_start[r]) {
-            set_error("ga_sparse_point_sums: row_start decreases at row %zu (%llu after %llu)", r, (unsigned long long)row_start[r + 1],
-                      (unsigned long long)row_start[r]);
-            return GA_ERR_INVALID;
-        }
+    GA_CHECK(csr_validate("ga_sparse_point_sums", "points", n_points, row_start, n_rows, terms, n_coeffs));
     const uint64_t nnz = row_start[n_rows];
-    if (nnz >= (1ull << 32)) {
-        set_error("ga_sparse_point_sums: row_start[n_rows] = %llu terms, at most 2^32 - 1 per call", (unsigned long long)nnz);
-        return GA_ERR_INVALID;
-    }
-    for (uint64_t k = 0; k < nnz; k++)
-        if (terms[2 * k] >= n_coeffs || terms[2 * k + 1] >= n_points) {
-            set_error("ga_sparse_point_sums: term %llu = {cid %u, col %u} outside %zu coefficients, %zu points", (unsigned long long)k, terms[2 * k],
-                      terms[2 * k + 1], n_coeffs, n_points);
-            return GA_ERR_INVALID;
-        }
     plan.mags.resize(n_coeffs * 8);
     std::vector<uint32_t> cls(n_coeffs);
     for (size_t i = 0; i < n_coeffs; i++) cls[i] = sparse_classify<FrP>((const char*)coeffs + i * 32, mont, &plan.mags[i * 8]);
@@ -227,34 +203,7 @@ int sparse_sums_plan(size_t n_points, const uint64_t* row_start, size_t n_rows, 
         } else
             plan.codes[2 * k + 1] = col;
     }
-    // level 0: every row; the levels after it: the rows that are still more than one partial sum
-    struct Long {
-        uint32_t row;
-        uint64_t first, count;
-    };
-    std::vector<Long> rows, longer;
-    auto cut = [&](uint32_t row, uint64_t first, uint64_t count, uint32_t& nparts) {
-        if (count <= S) {
-            plan.segs.insert(plan.segs.end(), {(uint32_t)first, (uint32_t)count, SPARSE_FINAL | row});
-            return;
-        }
-        longer.push_back({row, nparts, (count + S - 1) / S});
-        for (uint64_t o = 0; o < count; o += S) plan.segs.insert(plan.segs.end(), {(uint32_t)(first + o), (uint32_t)(count - o < S ? count - o : S), nparts++});
-    };
-    {
-        SparsePlan::Level lv{0, 0, 0};
-        for (size_t r = 0; r < n_rows; r++) cut((uint32_t)r, row_start[r], row_start[r + 1] - row_start[r], lv.nparts);
-        lv.nseg = (uint32_t)(plan.segs.size() / 3);
-        plan.levels.push_back(lv);
-    }
-    while (!longer.empty()) {
-        rows.swap(longer);
-        longer.clear();
-        SparsePlan::Level lv{plan.segs.size() / 3, 0, 0};
-        for (const Long& w : rows) cut(w.row, w.first, w.count, lv.nparts);
-        lv.nseg = (uint32_t)(plan.segs.size() / 3 - lv.first);
-        plan.levels.push_back(lv);
-    }
+    csr_cut_levels(row_start, n_rows, S, plan.rows);
     return GA_OK;
 }
 
@@ -268,25 +217,24 @@ int sparse_sums_run(Ctx* ctx, const void* points, size_t n_points, const uint64_
     SparsePlan plan;
     GA_CHECK(sparse_sums_plan<C>(n_points, row_start, n_rows, terms, coeffs, n_coeffs, (flags & GA_SCALARS_MONTGOMERY) != 0, S, cid_order, plan));
     const uint64_t nnz = plan.codes.size() / 2, ngen = plan.gen.size() / 2;
-    uint64_t chunk = forced_chunk ? forced_chunk : SCALE_DEFAULT_CHUNK;
-    if (chunk > FB_MAX_CHUNK) chunk = FB_MAX_CHUNK;
-    if (chunk > ngen) chunk = ngen;
-    uint64_t parts[2] = {0, 0}, max_seg = chunk;
-    for (size_t l = 0; l < plan.levels.size(); l++) {
-        if (plan.levels[l].nparts > parts[l & 1]) parts[l & 1] = plan.levels[l].nparts;
-        if (plan.levels[l].nseg > max_seg) max_seg = plan.levels[l].nseg;
-    }
+    const std::vector<uint32_t>& h_segs = plan.rows.segs;
+    const uint64_t chunk = clamp_chunk(forced_chunk, SCALE_DEFAULT_CHUNK, ngen);
+    uint64_t parts[2], max_seg = chunk;   // max_seg: the longest redo list, of a pass of products or of a level of segments
+    plan.rows.part_sizes(parts);
+    for (const CsrLevels::Level& lv : plan.rows.levels)
+        if (lv.nseg > max_seg) max_seg = lv.nseg;
     const int logn = (flags & GA_RESULT_BITREVERSED) ? ilog2_u64(n_rows) : -1;
     hipStream_t st = ctx->work_stream();
 
     // the scratch of the whole call first: an allocation failure leaves nothing in flight
     XYZZ<F>*table = nullptr, *prods = nullptr, *part[2] = {nullptr, nullptr}, *sums;
-    uint32_t *codes, *segs, *gen = nullptr, *mags = nullptr, *gs = nullptr, *redo;
+    uint32_t *codes, *segs, *gen = nullptr, *mags = nullptr, *gs = nullptr;
+    RedoList redo;   // header: the call's total (64 bits), the launch's count, pad
     Affine<F>*d_points = nullptr, *d_out = nullptr, *gp = nullptr;
     GA_CHECK(ctx->scratch_get("sparse_codes", nnz * 8, (void**)&codes));
-    GA_CHECK(ctx->scratch_get("sparse_segments", plan.segs.size() * 4, (void**)&segs));
+    GA_CHECK(ctx->scratch_get("sparse_segments", h_segs.size() * 4, (void**)&segs));
     GA_CHECK(ctx->scratch_get("sparse_sums", n_rows * sizeof(XYZZ<F>), (void**)&sums));
-    GA_CHECK(ctx->scratch_get("sparse_redo", (max_seg + 8) * 4, (void**)&redo));   // [total (64 bits), count, pad | list]
+    GA_CHECK(redo.get(ctx, "sparse_redo", max_seg, 8));
     if (ngen) {
         GA_CHECK(ctx->scratch_get("sparse_general", ngen * 8, (void**)&gen));
         GA_CHECK(ctx->scratch_get("sparse_magnitudes", plan.mags.size() * 4, (void**)&mags));
@@ -299,19 +247,16 @@ int sparse_sums_run(Ctx* ctx, const void* points, size_t n_points, const uint64_
         if (parts[b]) GA_CHECK(ctx->scratch_get(b ? "sparse_partial_b" : "sparse_partial_a", parts[b] * sizeof(XYZZ<F>), (void**)&part[b]));
     if (!i_dev) GA_CHECK(ctx->scratch_get("sparse_points", n_points * sizeof(Affine<F>), (void**)&d_points));
     if (!o_dev) GA_CHECK(ctx->scratch_get("sparse_out", n_rows * sizeof(Affine<F>), (void**)&d_out));
-    uint64_t* total = (uint64_t*)redo;
-    uint32_t *count = redo + 2, *list = redo + 8;
-    struct Drain {   // every return, an error's included, leaves with the stream idle: the caller's buffers and the plan outlive the copies
-        hipStream_t st;
-        ~Drain() { hipStreamSynchronize(st); }
-    } drain{st};
+    uint64_t* total = (uint64_t*)redo.words;
+    uint32_t *count = redo.words + 2, *list = redo.list;
+    StreamDrain drain{st};
 
     uint64_t h_total = 0;
     GA_HIP_CHECK(hipMemsetAsync(total, 0, 8, st));
     if (nnz) GA_HIP_CHECK(hipMemcpyAsync(codes, plan.codes.data(), nnz * 8, hipMemcpyHostToDevice, st));
-    GA_HIP_CHECK(hipMemcpyAsync(segs, plan.segs.data(), plan.segs.size() * 4, hipMemcpyHostToDevice, st));
-    if (!i_dev && n_points) GA_HIP_CHECK(hipMemcpyAsync(d_points, points, n_points * sizeof(Affine<F>), hipMemcpyHostToDevice, st));
-    const Affine<F>* src = i_dev ? (const Affine<F>*)points : d_points;
+    GA_HIP_CHECK(hipMemcpyAsync(segs, h_segs.data(), h_segs.size() * 4, hipMemcpyHostToDevice, st));
+    const Affine<F>* src;
+    GA_CHECK(chunk_in(st, i_dev, (const Affine<F>*)points, 0, n_points, d_points, &src));
 
     constexpr unsigned T = Table29<F>::THREADS;
     if (ngen) {
@@ -322,23 +267,22 @@ int sparse_sums_run(Ctx* ctx, const void* points, size_t n_points, const uint64_
         const uint32_t cn = (uint32_t)(ngen - done < chunk ? ngen - done : chunk);
         GA_HIP_CHECK(hipMemsetAsync(count, 0, 8, st));
         StageTimer tm(ctx, "sparse_products");
-        const unsigned all_blocks = (cn + T - 1) / T, blocks = all_blocks < SCALE_MAX_BLOCKS ? all_blocks : SCALE_MAX_BLOCKS, exact_blocks = (cn + 63) / 64;
+        const unsigned blocks = capped_grid(cn, T, SCALE_MAX_BLOCKS), exact_blocks = capped_grid(cn, 64, EC_NTT_EXACT_MAX_BLOCKS);
         hipLaunchKernelGGL((sparse_gather_kernel<F>), dim3((cn + 255) / 256), dim3(256), 0, st, src, (const uint32_t*)(gen + 2 * done), (const uint32_t*)mags, cn, gp, gs);
         hipLaunchKernelGGL((scale_points_window_kernel<F>), dim3(blocks), dim3(T), 0, st, (const Affine<F>*)gp, (const uint32_t*)gs, cn, table, prods + done, list, count);
-        hipLaunchKernelGGL((scale_points_exact_kernel<F>), dim3(exact_blocks < EC_NTT_EXACT_MAX_BLOCKS ? exact_blocks : EC_NTT_EXACT_MAX_BLOCKS), dim3(64), 0, st,
-                           (const Affine<F>*)gp, (const uint32_t*)gs, prods + done, (const uint32_t*)list, (const uint32_t*)count, total);
+        hipLaunchKernelGGL((scale_points_exact_kernel<F>), dim3(exact_blocks), dim3(64), 0, st, (const Affine<F>*)gp, (const uint32_t*)gs, prods + done,
+                           (const uint32_t*)list, (const uint32_t*)count, total);
         GA_KERNEL_CHECK();
     }
-    for (size_t l = 0; l < plan.levels.size(); l++) {
-        const SparsePlan::Level& lv = plan.levels[l];
+    for (size_t l = 0; l < plan.rows.levels.size(); l++) {
+        const CsrLevels::Level& lv = plan.rows.levels[l];
         if (lv.nseg == 0) continue;
         char name[32];
         snprintf(name, sizeof(name), "sparse_sums_%02d", (int)l);
         GA_HIP_CHECK(hipMemsetAsync(count, 0, 8, st));
         StageTimer tm(ctx, name);
         const uint32_t* sg = segs + 3 * lv.first;
-        const unsigned all_blocks = (lv.nseg + T - 1) / T, blocks = all_blocks < SCALE_MAX_BLOCKS ? all_blocks : SCALE_MAX_BLOCKS;
-        const unsigned all_exact = (lv.nseg + 63) / 64, exact_blocks = all_exact < EC_NTT_EXACT_MAX_BLOCKS ? all_exact : EC_NTT_EXACT_MAX_BLOCKS;
+        const unsigned blocks = capped_grid(lv.nseg, T, SCALE_MAX_BLOCKS), exact_blocks = capped_grid(lv.nseg, 64, EC_NTT_EXACT_MAX_BLOCKS);
         XYZZ<F>* to = part[l & 1];
         if (l == 0) {
             hipLaunchKernelGGL((sparse_sums_kernel<F, true>), dim3(blocks), dim3(T), 0, st, sg, lv.nseg, (const uint32_t*)codes, src, (const XYZZ<F>*)prods, to, sums, list, count);
@@ -352,15 +296,8 @@ int sparse_sums_run(Ctx* ctx, const void* points, size_t n_points, const uint64_
         }
         GA_KERNEL_CHECK();
     }
-    {
-        StageTimer tm(ctx, "sparse_affine");
-        constexpr unsigned AK = (unsigned)FixedBaseBatch<F>::AFFINE_K;
-        const unsigned lanes = (unsigned)((n_rows + AK - 1) / AK);
-        hipLaunchKernelGGL((fixed_base_affine_kernel<F>), dim3((lanes + 63) / 64), dim3(64), 0, st, (const XYZZ<F>*)sums, (uint32_t)n_rows, (uint64_t)0, logn,
-                           o_dev ? (Affine<F>*)out : d_out);
-        GA_KERNEL_CHECK();
-    }
-    if (!o_dev) GA_HIP_CHECK(hipMemcpyAsync(out, d_out, n_rows * sizeof(Affine<F>), hipMemcpyDeviceToHost, st));
+    GA_CHECK(launch_to_affine<F>(ctx, st, "sparse_affine", sums, (uint32_t)n_rows, 0, logn, o_dev ? (Affine<F>*)out : d_out));
+    GA_CHECK(chunk_out(st, o_dev, (Affine<F>*)out, 0, n_rows, d_out));
     GA_HIP_CHECK(hipMemcpyAsync(&h_total, total, 8, hipMemcpyDeviceToHost, st));
     GA_HIP_CHECK(hipStreamSynchronize(st));   // the one synchronisation of a call with everything on the device
     if (redone) *redone = h_total;

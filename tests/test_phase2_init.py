@@ -136,7 +136,7 @@ def test_sparse_sums_coefficient_classes(emu_ctx, c, group, mont, sizes=None):
 
 
 # ---- 2. row lengths ---------------------------------------------------------------------------------------------------------------------
-EDGE_LENGTHS = (0, 1, 3, 4, 5, 15, 16, 17, 64, 65, 257)
+EDGE_LENGTHS = (0, 1, 3, 4, 5, 15, 16, 17, 64, 65, 257, 0)   # S = 4: 0, 1, S, S + 1, S^2, S^2 + 1 among them; the first and the last row empty
 
 
 @pytest.mark.parametrize("c,group", PAIRS, ids=PAIR_IDS)

@@ -128,11 +128,11 @@ def test_matvec_coefficient_table(emu_ctx, c, mont):
 @pytest.mark.parametrize("S", [2, 16])
 @pytest.mark.parametrize("c", CURVES, ids=lambda c: c.name)
 def test_matvec_row_lengths(emu_ctx, monkeypatch, c, S):
-    """rows of 0, 1, S - 1, S, S + 1, S^2 and S^2 + 1 terms and one of 5 000 terms with repeated columns: the terms and three levels
-    of partial sums at S = 16 (16^3 < 5 000), thirteen launches at S = 2"""
+    """rows of 0, 1, S - 1, S, S + 1, S^2 and S^2 + 1 terms, one of 5 000 terms with repeated columns and an empty last row (the first
+    is empty too): the terms and three levels of partial sums at S = 16 (16^3 < 5 000), thirteen launches at S = 2"""
     table, x = cases.coeff_table(c), x_values(c)
     rng = pyref.Xoshiro(0x10E5 + c.cid + S)
-    lengths = [0, 1, S - 1, S, S + 1, S * S, S * S + 1, 5000]
+    lengths = [0, 1, S - 1, S, S + 1, S * S, S * S + 1, 5000, 0]
     rows = [[(rng.next() % len(table), rng.next() % NX) for _ in range(n)] for n in lengths]
     levels, n = 1, 5000
     while n > S:
