@@ -85,6 +85,7 @@ _PROTOS = {
     "ga_lagrange_coeffs": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_size_t, C.c_uint, _P]),
     "ga_sparse_point_sums": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_size_t, _P, C.c_size_t, _P, _P, C.c_size_t, C.c_uint, _P, C.POINTER(C.c_uint64)]),
     "ga_check_points": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_size_t, C.c_uint, _P, C.POINTER(C.c_uint64)]),
+    "ga_pairing_check": (C.c_int, [_P, C.c_int, _P, _P, C.c_size_t, _P, C.c_size_t, C.c_uint, _P, _P, C.POINTER(C.c_uint64)]),
     "ga_scale_points": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_size_t, C.c_int, _P, C.c_uint64, C.c_uint, _P, C.POINTER(C.c_uint64)]),
     "ga_fr_lagrange_at": (C.c_int, [_P, C.c_int, C.c_uint64, _P, C.c_size_t, C.c_uint, _P]),
     "ga_fr_sparse_matvec": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, C.c_size_t, _P, _P, C.c_size_t, _P, _P, C.c_size_t, C.c_uint, _P]),

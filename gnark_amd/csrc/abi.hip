@@ -226,6 +226,8 @@ typedef CtxLock Lock;
 //     GA_SPARSE_CHUNK       general terms (products) per pass (0 = 2^20, at most 2^30; tests force a small chunk)
 //     GA_SPARSE_SEGMENT     terms, or partial sums, per lane of the row sums (0 or 1 = 16; tests force 4)
 //     GA_SPARSE_ORDER       0: the products in row order (default); 1: sorted by coefficient id (the A/B of tools/phase2_init_bench.py)
+//   ga_pairing_check
+//     GA_PAIRING_CHUNK      pairs per pass (0 = 2^18, at most 2^30; tests force a small chunk)
 //   ga_fr_sparse_matvec
 //     GA_FR_SPARSE_SEGMENT  terms, or partial sums, per lane: 2 .. 2^20; unset, 0 or 1 = the default (FR_SPARSE_DEFAULT_SEGMENT); a
 //                           larger value is taken as 2^20; tests force 2
@@ -636,6 +638,44 @@ int ga_check_points(ga_ctx* h, int curve, int group, const void* points_affine, 
     const int naive = check_naive_knob();
     const uint64_t forced_chunk = env_u64("GA_CHECK_CHUNK", 0);
     GA_DISPATCH_CURVE(curve, GA_DISPATCH_GROUP(group, return (check_points_run<C, G>(c, points_affine, n, flags, status, out4, naive, forced_chunk))));
+    return GA_OK;
+} GA_ABI_CATCH
+
+// ---- products of pairings (pairing.hip.h) -----------------------------------------------------------------
+int ga_pairing_check(ga_ctx* h, int curve, const void* p_affine, const void* q_affine, size_t n, const uint64_t* group_start, size_t n_groups, unsigned flags,
+                     uint8_t* ok, void* gt, uint64_t* out2) try {
+    GA_ABI_ENTRY();
+    Ctx* c = reinterpret_cast<Ctx*>(h);
+    if (!abi_curve_ok(curve)) return GA_ERR_INVALID;
+    if (n_groups == 0) return GA_OK;
+    if ((uint64_t)n > (1ull << 32) || (uint64_t)n_groups >= (1ull << 31)) {
+        set_error("ga_pairing_check: n = %zu above 2^32 or n_groups = %zu above 2^31 - 1", n, n_groups);
+        return GA_ERR_INVALID;
+    }
+    if (!c || !out2 || (n > 0 && (!p_affine || !q_affine))) {
+        set_error("ga_pairing_check: null argument");
+        return GA_ERR_INVALID;
+    }
+    if (!group_start && n_groups != 1) {
+        set_error("ga_pairing_check: group_start = NULL is one group of all pairs, n_groups = %zu", n_groups);
+        return GA_ERR_INVALID;
+    }
+    if (group_start) {
+        if (group_start[0] != 0 || group_start[n_groups] != n) {
+            set_error("ga_pairing_check: group_start runs from %llu to %llu, not from 0 to n = %zu", (unsigned long long)group_start[0],
+                      (unsigned long long)group_start[n_groups], n);
+            return GA_ERR_INVALID;
+        }
+        for (size_t g = 0; g < n_groups; g++)
+            if (group_start[g + 1] < group_start[g]) {
+                set_error("ga_pairing_check: group_start decreases at group %zu (%llu after %llu)", g, (unsigned long long)group_start[g + 1],
+                          (unsigned long long)group_start[g]);
+                return GA_ERR_INVALID;
+            }
+    }
+    Lock l(c);
+    const uint64_t forced_chunk = env_u64("GA_PAIRING_CHUNK", 0);
+    GA_DISPATCH_CURVE(curve, return (pairing_run<C>(c, p_affine, q_affine, n, group_start, n_groups, flags, ok, gt, out2, forced_chunk)));
     return GA_OK;
 } GA_ABI_CATCH
 

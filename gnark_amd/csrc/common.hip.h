@@ -533,6 +533,10 @@ int check_naive_knob();   // GA_CHECK_NAIVE, for ga_check_points and the key rea
 template <class C, int G>
 int sparse_sums_run(Ctx* ctx, const void* points, size_t n_points, const uint64_t* row_start, size_t n_rows, const uint32_t* terms, const void* coeffs,
                     size_t n_coeffs, unsigned flags, void* out, uint64_t* redone, uint64_t forced_chunk, uint32_t segment, int cid_order);
+// pairing.hip.h: products of pairings over groups of (G1, G2) pairs
+template <class C>
+int pairing_run(Ctx* ctx, const void* p_affine, const void* q_affine, size_t n, const uint64_t* group_start, size_t n_groups, unsigned flags, uint8_t* ok,
+                void* gt, uint64_t* out2, uint64_t forced_chunk);
 // fr_sparse.hip.h: the same matrix applied to a vector of Fr elements, a scale per row class
 template <class C>
 int fr_sparse_run(Ctx* ctx, const void* x, size_t n_cols, const uint64_t* row_start, size_t n_rows, const uint32_t* terms, const void* coeffs,

@@ -165,6 +165,63 @@ def CheckPoints(ctx: Context, curve, group: int, points, n: int | None = None, c
     return res, int(out4[0]), int(out4[1]), int(out4[2]), int(out4[3])
 
 
+def PairingCheck(ctx: Context, curve, P, Q, group_start=None, *, n: int | None = None, want_gt: bool = False, on_device: bool = False):
+    """prod_{i in group g} e(P_i, Q_i) == 1 for every group of a vector of pairs (ga_pairing_check) -- curve.PairingCheck as the
+    Groth16 verifier, pedersen.BatchVerifyMultiVk, kzg.Verify and mpcsetup's SameRatio call it, for many equations in one call.
+
+    P, Q        : (n, affine_words) uint64 arrays of G1Affine / G2Affine images, or both DeviceBuffers of n points (n then comes
+                  from group_start, or from `n`); never written.  (0,0) on either side of a pair contributes 1.  The points are
+                  not validated (CheckPoints does that).
+    group_start : n_groups + 1 offsets (0, ..., n), non-decreasing; None = one group of all pairs.
+    Returns (ok, bad, first), with want_gt=True (ok, gt, bad, first): ok is an (n_groups,) uint8 array of 0 / 1, gt an
+    (n_groups, 12 * fp_words) uint64 array of E12 memory images (the library's own normalisation of e: see include/gnark_amd.h) --
+    with on_device=True both are DeviceBuffers (the caller frees them); bad counts the groups whose product is not 1 and first is
+    the index of the first of them (NONE_BAD if there is none).
+    """
+    cid = curve_id(curve)
+    w1, w2 = affine_words(cid, G1), affine_words(cid, G2)
+    dev = isinstance(P, (DeviceBuffer, int))
+    if dev != isinstance(Q, (DeviceBuffer, int)):
+        raise ValueError("P and Q are both host arrays or both device buffers")
+    gs = None
+    if group_start is not None:
+        gs = np.ascontiguousarray(group_start, dtype=np.uint64).reshape(-1)
+        if gs.size < 1:
+            raise ValueError("group_start holds n_groups + 1 offsets")
+    if not dev:
+        P, Q = as_u64(P, w1), as_u64(Q, w2)
+        if P.shape[0] != Q.shape[0]:
+            raise ValueError("len(P) != len(Q)")
+        n = P.shape[0]
+    elif n is None:
+        if gs is None:
+            raise ValueError("n or group_start is required for device-resident points")
+        n = int(gs[-1])
+    n_groups = 1 if gs is None else gs.size - 1
+    pp, flags = _arg(P, _lib.BASES_ON_DEVICE)
+    qp, _ = _arg(Q, _lib.BASES_ON_DEVICE)
+    wg = 6 * w1   # 12 base-field elements
+    out2 = (C.c_uint64 * 2)(0, NONE_BAD)
+    ok = gt = None
+    try:
+        if on_device:
+            flags |= _lib.RESULT_ON_DEVICE
+            ok = ctx.malloc(max(n_groups, 1))
+            gt = ctx.malloc(max(n_groups, 1) * wg * 8) if want_gt else None
+            okp, gtp = C.c_void_p(ok.ptr), C.c_void_p(gt.ptr if gt else None)
+        else:
+            ok = np.zeros(n_groups, dtype=np.uint8)
+            gt = np.zeros((n_groups, wg), dtype=np.uint64) if want_gt else None
+            okp, gtp = _ptr(ok), (_ptr(gt) if want_gt else C.c_void_p(None))
+        ctx.lib.check(ctx.lib.ga_pairing_check(ctx.handle, cid, pp, qp, n, _ptr(gs) if gs is not None else C.c_void_p(None), n_groups, flags, okp, gtp, out2))
+    except Exception:
+        for b in (ok, gt):
+            if isinstance(b, DeviceBuffer):
+                b.free()
+        raise
+    return (ok, gt, int(out2[0]), int(out2[1])) if want_gt else (ok, int(out2[0]), int(out2[1]))
+
+
 def ScalePoints(ctx: Context, curve, group: int, points, scalars=None, *, scalar=None, powers=None, first: int = 0, n: int | None = None,
                 montgomery: bool = False, out_device: bool = False, in_place: bool = False):
     """out[i] = [s_i] points[i] -- the ScalarMultiplication loops of the Groth16 MPC ceremony (backend/groth16/<curve>/mpcsetup:

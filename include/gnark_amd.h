@@ -56,7 +56,7 @@ extern "C" {
 
 /* flags for ga_msm */
 #define GA_BASES_ON_DEVICE 0x1u        /* `bases` (ga_kzg_to_lagrange_g1, ga_lagrange_coeffs: `powers_affine`; ga_scale_points,
-                                         * ga_sparse_point_sums, ga_check_points: `points_affine`) is a device pointer */
+                                         * ga_sparse_point_sums, ga_check_points: `points_affine`; ga_pairing_check: both point vectors) is a device pointer */
 #define GA_SCALARS_ON_DEVICE 0x2u      /* `scalars` is a device pointer */
 #define GA_TABLE_BATCHED 0x10u         /* ga_msm_table_create: the table will mostly serve ga_msm_table_run_batch (PLONK's grouped
                                          * commitments over the SRS): plan a narrower window -- k bucket sets make the sort keys
@@ -66,7 +66,7 @@ extern "C" {
                                           (ICICLE's AreScalarsMontgomeryForm, icicle.go:861-863,1232) */
 #define GA_RESULT_WINDOW_SUMS 0x8u     /* multi-GPU window sharding: see ga_msm_windows */
 #define GA_RESULT_ON_DEVICE 0x20u      /* ga_batch_scalar_mul, ga_kzg_to_lagrange_g1, ga_lagrange_coeffs, ga_scale_points,
-                                         * ga_sparse_point_sums: `out_affine` (ga_check_points: `status`) is a device pointer */
+                                         * ga_sparse_point_sums: `out_affine` (ga_check_points: `status`; ga_pairing_check: `ok`, `gt`) is a device pointer */
 #define GA_CHECK_CURVE_ONLY 0x80u      /* ga_check_points: the curve equation only (IsOnCurve), no subgroup test */
 #define GA_RESULT_BITREVERSED 0x40u    /* ga_batch_scalar_mul, ga_sparse_point_sums: result i is written at index bitrev(i, log2 n) */
 
@@ -227,6 +227,34 @@ int ga_scale_points(ga_ctx* ctx, int curve, int group, const void* points_affine
 #define GA_POINT_NOT_IN_SUBGROUP 2   /* on the curve, outside the prime-order subgroup */
 int ga_check_points(ga_ctx* ctx, int curve, int group, const void* points_affine, size_t n, unsigned flags,
                     uint8_t* status, uint64_t* out4);
+
+/* ---- products of pairings over groups of (G1, G2) pairs ------------------------------------------------------
+ * ok[g] = 1 iff prod_{i in group g} e(P_i, Q_i) = 1, else 0: one Miller loop per pair, one final exponentiation per group.
+ * replaces: curve.PairingCheck of the Groth16 verifier (backend/groth16/<curve>/verify.go:128-139), pedersen.BatchVerifyMultiVk
+ * (verify.go:104-112), kzg.Verify / BatchVerifyMultiPoints, the SameRatio pairings of mpcsetup's Verify, and -- through `gt` --
+ * vk.Precompute's e(alpha, beta).
+ *   p_affine, q_affine : n G1Affine and n G2Affine memory images; host, or BOTH device with GA_BASES_ON_DEVICE; never written.
+ *   group_start        : n_groups + 1 host offsets, group_start[0] = 0, non-decreasing, group_start[n_groups] = n; NULL = one group
+ *                        of all n pairs (n_groups must then be 1).  An empty group is 1.
+ *   ok                 : n_groups bytes, may be NULL; host, or device with GA_RESULT_ON_DEVICE.
+ *   gt                 : may be NULL; n_groups values of 12 fp.Element images in the order of gnark-crypto's E12 struct (C0.B0.A0,
+ *                        C0.B0.A1, C0.B1.A0, ..., C1.B2.A1), host or device as `ok`: the group's product of Miller values raised to
+ *                        (p^6 - 1)(p^2 + 1) h, with h = 3 (p^4 - p^2 + 1)/r for BLS12-381 and, for BN254, h = l0 + l1 p + l2 p^2 + p^3
+ *                        (l2 = 6x0^2 + 1, l1 = -36x0^3 - 18x0^2 - 12x0 + 1, l0 = -36x0^3 - 30x0^2 - 18x0 - 2: a multiple of
+ *                        (p^4 - p^2 + 1)/r by a cofactor prime to r).  It is the library's own normalisation of e (BN254: the
+ *                        optimal-ate Miller loop over 6x0 + 2; BLS12-381: the loop over |x0|, conjugated): bilinear, non-degenerate
+ *                        and consistent with itself -- what vk.e = e(alpha, beta) needs --, NOT promised to equal gnark-crypto's Pair.
+ *   out2               : host, required: {groups whose product is not 1, index of the first such group or UINT64_MAX}.
+ * The return value says whether the check RAN, not what it found.  A pair with (0,0) on either side contributes 1, as gnark-crypto's
+ * MillerLoop skips it.  Points are NOT validated (ga_check_points does that): a pair with a point off the curve or outside its
+ * subgroup gives an unspecified ok / gt for ITS group only -- never an error, a fault or a hang, never another group's result.
+ * GA_ERR_INVALID, before anything is launched: unknown curve; a null p_affine / q_affine with n > 0; a null out2; a group_start that
+ * breaks the rules above; n above 2^32 (n_groups above 2^31 - 1).  n_groups = 0 is GA_OK and touches nothing.  Device scratch, kept
+ * by the context: one Fp12 (384 / 576 bytes) per pair of a pass of at most GA_PAIRING_CHUNK pairs (default 2^18), one per group,
+ * the partial products of groups longer than 16 pairs, and the staging of host points.  GA_ERR_NOMEM when that does not fit: nothing
+ * is in flight and the context stays usable.  Stages in the profiler: pairing_miller, pairing_product, pairing_final. */
+int ga_pairing_check(ga_ctx* ctx, int curve, const void* p_affine, const void* q_affine, size_t n,
+                     const uint64_t* group_start, size_t n_groups, unsigned flags, uint8_t* ok, void* gt, uint64_t* out2);
 
 /* ---- a sparse Fr matrix applied to a vector of points: the constraint loop of Phase2.Initialize ------------
  * replaces: the loops of Phase2.Initialize in backend/groth16/<curve>/mpcsetup (phase2.go:224-247: every term (coeff, wire) of

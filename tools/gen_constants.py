@@ -13,7 +13,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
-from pyref import BN254, BLS12_381, Fp2Ops, g1_group, g2_group  # noqa: E402
+from pyref import BN254, BLS12_381, Fp2Ops, Fp12Ops, g1_group, g2_group  # noqa: E402
 
 # the curves' seeds (x0 of the BN / BLS12 families): p, r and the cofactors are polynomials in them
 BN254_SEED = 4965661367192848881
@@ -82,6 +82,9 @@ def field_block(name, mod, n64, w, extra=None):
     for k, v in (extra or {}).items():
         if isinstance(v, int) and k.isupper() and k.startswith("I_"):
             out.append(f"    static constexpr int {k[2:]} = {v};")
+        elif isinstance(v, list):
+            rows = ", ".join(arr(x * R % mod, n, w) for x in v)
+            out.append(f"    static constexpr {ty} {k}[{len(v)}][{n}] = {{{rows}}};   // Montgomery form")
         else:
             out.append(f"    static constexpr {ty} {k}[{n}] = {arr(v * R % mod, n, w)};   // Montgomery form")
     out.append("};")
@@ -155,6 +158,29 @@ def endo_constants(c):
     return out
 
 
+def pairing_constants(c):
+    """The Frobenius constants of pairing.hip.h (product header only): in Fp12 = Fp2[w]/(w^6 - xi) the p^k-power Frobenius sends
+    a w^i (a in Fp2) to a^(p^k) g w^i with g = xi^(i (p^k - 1)/6).  FROB1 / FROB3: rows 2(i-1), 2(i-1)+1 are the two Fp halves of g
+    for k = 1 / 3 and i = 1..5; FROB2: row i-1 is g for k = 2, which lies in Fp.  Each is asserted against the p^k-th power of w^i
+    in plain integer polynomial arithmetic (pyref.Fp12Ops)."""
+    p = c.p
+    F2, F12 = Fp2Ops(p), Fp12Ops(c)
+    xi = (F12.a, 1)
+    out = {"FROB1": [], "FROB2": [], "FROB3": []}
+    for k in (1, 2, 3):
+        for i in range(1, 6):
+            g = fp2_pow(F2, xi, i * (p ** k - 1) // 6)
+            wi = [0] * 12
+            wi[i] = 1
+            assert F12.pow(wi, p ** k) == F12.embed_fp2(g, i), (c.name, k, i)
+            if k == 2:
+                assert g[1] == 0
+                out["FROB2"].append(g[0])
+            else:
+                out["FROB%d" % k] += [g[0], g[1]]
+    return out
+
+
 def main():
     hdr = ["// GENERATED by tools/gen_constants.py -- do not edit.", "#pragma once", "#include <stdint.h>", ""]
     prod = list(hdr) + ["namespace ga {", ""]
@@ -165,7 +191,7 @@ def main():
                     "GEN_INV": pow(c.fr_gen, -1, c.r), "I_ADICITY": c.fr_adicity}
         fp_extra = {"G1X": c.g1[0], "G1Y": c.g1[1], "G2X0": c.g2[0][0], "G2X1": c.g2[0][1],
                     "G2Y0": c.g2[1][0], "G2Y1": c.g2[1][1], "B1": c.b, "B2_0": c.b2[0], "B2_1": c.b2[1]}
-        prod.append(field_block(f"{tag}_Fp", c.p, c.fp_limbs, 32, {**fp_extra, **endo_constants(c)}))
+        prod.append(field_block(f"{tag}_Fp", c.p, c.fp_limbs, 32, {**fp_extra, **endo_constants(c), **pairing_constants(c)}))
         prod.append("")
         prod.append(field_block(f"{tag}_Fr", c.r, c.fr_limbs, 32, fr_extra))
         prod.append("")
