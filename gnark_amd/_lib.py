@@ -104,6 +104,8 @@ _PROTOS = {
     "ga_domain_destroy": (None, [_P]),
     "ga_fft": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int]),
     "ga_compute_h": (C.c_int, [_P, _P, _P, _P, C.c_uint64, _P, C.c_int]),
+    "ga_fft_batch": (C.c_int, [_P, _P, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "ga_compute_h_batch": (C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint64, _P, C.c_int]),
     "ga_plonk_quotient": (C.c_int, [_P, _P, C.POINTER(PlonkQuotientIn), _P]),
     "ga_plonk_pk_create": (C.c_int, [_P, _P, C.POINTER(PlonkQuotientIn), C.POINTER(_P)]),
     "ga_plonk_pk_destroy": (None, [_P]),
@@ -127,6 +129,7 @@ _PROTOS = {
     "ga_g16_builder_finish": (C.c_int, [_P, C.c_int32, C.POINTER(_P)]),
     "ga_g16_builder_destroy": (None, [_P]),
     "ga_g16_prove": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, _P, _P, _P]),
+    "ga_g16_prove_batch": (C.c_int, [_P, C.c_uint32, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.c_uint64, C.c_uint64, _P, _P, _P]),
     "ga_g16_prove_oneshot": (C.c_int, [_P, C.POINTER(G16Key), _P, _P, _P, _P, C.c_uint64, C.c_uint64, _P, _P, _P]),
     "ga_g16_prove_partial": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, _P]),
     "ga_g16_finish": (C.c_int, [_P, _P, _P, _P, _P]),

@@ -182,6 +182,10 @@ void Tunables::read_env() {
     put64(g16_table_budget_pct, env_u64("GA_G16_TABLE_BUDGET_PCT", 0));
     put(g16_split, (int)env_u64("GA_G16_SPLIT", 1));
     put(g16_batch_tables, (int)env_u64("GA_G16_BATCH_TABLES", 1));
+    {
+        const uint64_t b = env_u64("GA_G16_BATCH_MAX", 16);
+        put(g16_batch_max, (int)(b < 1 ? 1 : b > 16 ? 16 : b));
+    }
     put(ntt_wave_local, (int)env_u64("GA_NTT_WAVE_LOCAL", 1));
     put(ntt_direct, (int)env_u64("GA_NTT_DIRECT", 1));
     put(table_c, (int)env_u64("GA_TABLE_C", 0));
@@ -1119,6 +1123,31 @@ int ga_fft(ga_domain* dh, void* data, int direction, int decimation, int on_cose
     return GA_OK;
 } GA_ABI_CATCH
 
+// `count` transforms of one size in ONE launch chain (the vector is the grid's y dimension of every pass, ntt.hip.h): what a loop of
+// fft.Domain.FFT / FFTInverse over vectors of one domain does (PLONK's L, R, O and h1..h3, prove.go of backend/plonk; the three
+// chains of computeH, backend/groth16/bn254/prove.go:362-368).  data = count vectors of `cardinality` elements, contiguous.
+int ga_fft_batch(ga_domain* dh, void* data, uint32_t count, int direction, int decimation, int on_coset, int on_device) try {
+    GA_ABI_ENTRY();
+    if (count == 0) return GA_OK;
+    Domain* d = reinterpret_cast<Domain*>(dh);
+    if (!d || !data || (direction != GA_FFT_FORWARD && direction != GA_FFT_INVERSE) || (decimation != GA_DIF && decimation != GA_DIT)) {
+        set_error("ga_fft_batch: bad argument");
+        return GA_ERR_INVALID;
+    }
+    Ctx* c = ntt_domain_ctx(d);
+    Lock l(c);
+    const size_t bytes = (size_t)count * ntt_domain_size(d) * 32;
+    void* dev = data;
+    if (!on_device) {
+        GA_CHECK(c->scratch_get("fft_batch_io", bytes, &dev));
+        GA_HIP_CHECK(hipMemcpyAsync(dev, data, bytes, hipMemcpyHostToDevice, c->stream));
+    }
+    GA_DISPATCH_CURVE(ntt_domain_curve(d), GA_CHECK(ntt_domain_fft<C>(d, dev, direction, decimation, on_coset, count)));
+    if (!on_device) GA_HIP_CHECK(hipMemcpyAsync(data, dev, bytes, hipMemcpyDeviceToHost, c->stream));
+    GA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return GA_OK;
+} GA_ABI_CATCH
+
 static int plonk_args_from(const ga_plonk_quotient_in* in, bool need_fixed, bool need_var, PlonkQuotientArgs* a) {
     memset(a, 0, sizeof(*a));
     if (in->nb_bsb > (uint32_t)PLONK_MAX_BSB) {
@@ -1269,6 +1298,43 @@ int ga_compute_h(ga_domain* dh, const void* a, const void* b, const void* cc, ui
     }
     GA_DISPATCH_CURVE(ntt_domain_curve(d), GA_CHECK(ntt_domain_compute_h<C>(d, da, db, dc)));
     GA_HIP_CHECK(hipMemcpyAsync(h_out, da, full, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+    GA_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return GA_OK;
+} GA_ABI_CATCH
+
+// computeH for `count` solutions of one circuit (a loop of prove.go:346-389 over the solutions): every transform is one batched launch
+// chain and the point-wise step one launch.  a, b, c = [count][n_constraints] contiguous; h_out = [count][cardinality], bit-reversed.
+int ga_compute_h_batch(ga_domain* dh, const void* a, const void* b, const void* cc, uint32_t count, uint64_t n_constraints, void* h_out,
+                       int on_device) try {
+    GA_ABI_ENTRY();
+    if (count == 0) return GA_OK;
+    Domain* d = reinterpret_cast<Domain*>(dh);
+    if (!d || !a || !b || !cc || !h_out || n_constraints > ntt_domain_size(d)) {
+        set_error("ga_compute_h_batch: bad argument (n_constraints must be <= domain cardinality)");
+        return GA_ERR_INVALID;
+    }
+    Ctx* c = ntt_domain_ctx(d);
+    Lock l(c);
+    const uint64_t n = ntt_domain_size(d);
+    const size_t full = n * 32, part = n_constraints * 32;
+    void *da, *db, *dc;
+    GA_CHECK(c->scratch_get("compute_h_batch_a", (size_t)count * full, &da));
+    GA_CHECK(c->scratch_get("compute_h_batch_b", (size_t)count * full, &db));
+    GA_CHECK(c->scratch_get("compute_h_batch_c", (size_t)count * full, &dc));
+    const void* src[3] = {a, b, cc};
+    void* dst[3] = {da, db, dc};
+    const hipMemcpyKind in = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    for (int k = 0; k < 3; k++) {
+        if (part == full) {
+            GA_HIP_CHECK(hipMemcpyAsync(dst[k], src[k], (size_t)count * full, in, c->stream));
+        } else if (part) {   // (rows of n_constraints elements into rows of n)
+            for (uint32_t j = 0; j < count; j++)
+                GA_HIP_CHECK(hipMemcpyAsync((char*)dst[k] + j * full, (const char*)src[k] + j * part, part, in, c->stream));
+        }
+        GA_DISPATCH_CURVE(ntt_domain_curve(d), GA_CHECK(util_pad_fr_batch<C>(c, dst[k], n_constraints, n, count, c->stream)));
+    }
+    GA_DISPATCH_CURVE(ntt_domain_curve(d), GA_CHECK(ntt_domain_compute_h<C>(d, da, db, dc, count)));
+    GA_HIP_CHECK(hipMemcpyAsync(h_out, da, (size_t)count * full, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
     GA_HIP_CHECK(hipStreamSynchronize(c->stream));
     return GA_OK;
 } GA_ABI_CATCH

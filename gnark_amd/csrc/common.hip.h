@@ -158,6 +158,7 @@ struct StageRec {
 //   GA_TABLE_C            force the window width of precomputed tables built from now on (experiments; 0 = planned)
 //   GA_G16_LANES          1: a second concurrent ga_g16_prove caller queues for the device instead of proving on its own lanes
 //   GA_G16_SPLIT          0: a proof keeps its H side (computeH, Z MSM) on the lane of its witness MSMs instead of a partner lane
+//   GA_G16_BATCH_MAX      most solutions ga_g16_prove_batch takes through the device in one pass (1 .. 16, default 16; tests force several chunks)
 //   GA_NTT_WAVE_LOCAL     0: every round of an NTT pass ends in a workgroup barrier (round 3) instead of wave-local exchanges
 //   GA_NTT_DIRECT         0: the first / last round of an NTT pass goes through LDS instead of moving its quads to / from HBM itself
 // (GA_HBM_RESERVE_MB is read once per process by device_malloc: see there.)
@@ -169,6 +170,7 @@ struct Tunables {
     std::atomic<uint64_t> g16_table_budget_pct{0};    // 0 = from the free HBM; else the % of the five tables' bytes precompute = 0 may spend (tests)
     std::atomic<int> g16_lanes{2};
     std::atomic<int> g16_split{1};
+    std::atomic<int> g16_batch_max{16};              // solutions per device pass of ga_g16_prove_batch (1 .. 16)
     std::atomic<int> g16_batch_tables{1};            // 1: the wire-indexed G1 tables of a proof (A, B1, K) in one pass of every MSM kernel
     std::atomic<int> ntt_wave_local{1};
     std::atomic<int> ntt_direct{1};
@@ -463,9 +465,11 @@ template <class C, int G>
 int msm_table_device_batch(Ctx* ctx, const void* d_table, const void* const* d_scalars, int batch, size_t n, bool scalars_mont, int c,
                            void* h_sums);
 // slot 0/1 selects one of two scratch sets (the witness sort shared by several tables stays live in set 1 while set 0 is reused)
+// batch > 1: d_scalars is a host array of `batch` device pointers (msm_prepare); every table walked with *P then gives `batch` sums
 template <class C>
 int msm_prepare_table_scalars(Ctx* ctx, const void* d_scalars, size_t n, bool scalars_mont, int c, MsmPrepared* P, int slot = 0,
-                              int win_lo = 0, int win_hi = -1);
+                              int win_lo = 0, int win_hi = -1, int batch = 1);
+// h_sum: P.nsets XYZZ sums (one, or one per scalar vector of a prepared batch)
 template <class C, int G>
 int msm_table_device_reuse(Ctx* ctx, const void* d_table, const MsmPrepared& P, void* h_sum);
 // the same over 2..4 tables of one shape in ONE pass of every kernel (msm.hip.h): h_sums[i] = the XYZZ sum over tables[i]
@@ -474,10 +478,11 @@ int msm_table_device_reuse_multi(Ctx* ctx, const void* const* tables, int ntab, 
 
 struct Domain;   // ntt.hip.h
 template <class C> int ntt_domain_new(Ctx* ctx, uint64_t n, Domain** out);
-template <class C> int ntt_domain_fft(Domain* d, void* d_data, int direction, int decimation, int on_coset);
-template <class C> int ntt_domain_compute_h(Domain* d, void* d_a, void* d_b, void* d_c);
-template <class C> int ntt_domain_h_chain(Domain* d, void* d_v);                                        // v <- FFT_coset(iFFT(v))
-template <class C> int ntt_domain_h_combine(Domain* d, void* d_a, const void* d_b, const void* d_c);    // a <- h (bit-reversed)
+// (batch: the buffers hold that many vectors of n elements, one after the other; every transform is one launch chain over all of them)
+template <class C> int ntt_domain_fft(Domain* d, void* d_data, int direction, int decimation, int on_coset, uint64_t batch = 1);
+template <class C> int ntt_domain_compute_h(Domain* d, void* d_a, void* d_b, void* d_c, uint64_t batch = 1);
+template <class C> int ntt_domain_h_chain(Domain* d, void* d_v, uint64_t batch = 1);                                        // v <- FFT_coset(iFFT(v))
+template <class C> int ntt_domain_h_combine(Domain* d, void* d_a, const void* d_b, const void* d_c, uint64_t batch = 1);    // a <- h (bit-reversed)
 void ntt_domain_delete(Domain* d);
 // The NTT domain of the last proving key freed on a context stays with the context (like its scratch): a caller that re-pins its key
 // for every proof -- the Go package's default, PinToGPU = false -- gets it back instead of rebuilding 3 GiB of twiddle tables (11 ms
@@ -552,6 +557,12 @@ template <class C> int util_gen_scalars(Ctx* ctx, uint64_t seed, size_t n, void*
 template <class C> int util_fr_dot(Ctx* ctx, const void* d_a, const void* d_b, size_t n, void* h_out);
 template <class C> int util_fr_vec_mul(Ctx* ctx, const void* d_a, const void* d_b, size_t n, void* d_out);
 template <class C> int util_gather_fr(Ctx* ctx, void* d_dst, const void* d_src, const uint32_t* d_idx, size_t n);
+// the same for `count` vectors in one launch (dst / src: count vectors of dst_stride / src_stride elements); and the zero padding of
+// `count` contiguous n-element vectors: elements [from, n) of each <- 0 on `st`
+template <class C>
+int util_gather_fr_batch(Ctx* ctx, void* d_dst, const void* d_src, const uint32_t* d_idx, size_t n, uint32_t count, uint64_t dst_stride,
+                         uint64_t src_stride);
+template <class C> int util_pad_fr_batch(Ctx* ctx, void* d_v, uint64_t from, uint64_t n, uint32_t count, hipStream_t st);
 int util_microbench(Ctx* ctx, char* buf, size_t cap);
 int util_clock_probe(Ctx* ctx, uint32_t micros, double* mhz_out);
 

@@ -32,6 +32,8 @@ namespace ga {
 // z_msm          : MSM over this shard's slice of pk.G1.Z and h                                                prove.go:225-227
 // h_side         : the three chains, each once its vector has landed, h_combine and z_msm on ONE lane
 // HelperThread   : a thread that runs such pieces beside the caller; its result code, error text and exceptions come back in join()
+// prove_batch    : the device part of MANY proofs under one key (ga_g16_prove_batch): chunks of <= 16 solutions, the H side as batched
+//                  transforms, one batch MSM per base vector (vector_msm_batch); finish_batch runs the epilogues side by side
 // prove_partial runs them on one device (witness_msms on the caller's lane, h_helper beside it), prove_multi / MultiProof on several;
 // finish is the host epilogue.
 
@@ -41,6 +43,15 @@ static int check_nb_public(const G16Pk* pk, uint64_t nb_public) {
         set_error("prove: inconsistent sizes (nbWires %llu - nbPublic %llu != len(K) %llu + len(k_remove) %llu)", (unsigned long long)pk->nb_wires,
                   (unsigned long long)nb_public, (unsigned long long)pk->full_len_k, (unsigned long long)pk->len_k_remove);
         return GA_ERR_INVALID;
+    }
+    return GA_OK;
+}
+// a whole proof needs the whole key (`entry`: the entry point refusing)
+static int check_unsharded(const G16Pk* pk, const char* entry) {
+    if (pk->shard_count != 1 || pk->win_count != 1) {
+        set_error("%s: this key holds one share of a sharded key (base range %u/%u, windows %u/%u); use ga_g16_prove_multi or "
+                  "ga_g16_prove_partial + ga_g16_finish", entry, pk->shard_index, pk->shard_count, pk->win_index, pk->win_count);
+        return GA_ERR_STATE;
     }
     return GA_OK;
 }
@@ -548,6 +559,213 @@ static int finish(G16Pk* pk, G16Partials<C> p, const void* r_mont, const void* s
     host_store_affine<F2>(o + sizeof(Affine<F1>), p.bs2);
     host_store_affine<F1>(o + sizeof(Affine<F1>) + sizeof(Affine<F2>), p.krs);
     return GA_OK;
+}
+
+// ---- a batch of proofs under one key (ga_g16_prove_batch) ----------------------------------------------------------------------
+// `count` solutions of one circuit go through the device in chunks of B <= 16.  One chunk, on the caller's lane (lane 0, under the
+// device lock; no partner lane, no input slot, no helper thread for device work):
+//   1. the chunk's W vectors -> one buffer [B][nb_wires], its A, B, C -> three buffers [B][n], zero-padded (one launch per buffer)
+//   2. the H side as BATCHED transforms: three chains, the point-wise step over B * n elements, the last transform -- seven launch
+//      chains per chunk instead of seven per solution (at n = 2^10 a launch is ONE workgroup per vector); h lands in [B][n]
+//   3. one batch MSM per base vector, by its layout (vector_msm_batch): the B scalar vectors share the sort, the task list and every
+//      kernel's tail.  A vector without a table has no batch path and loops vector_msm over the solutions.
+// The host epilogues follow outside the device lock, beside each other (finish_batch).
+
+// most solutions one chunk may hold: the batch MSM's 16 (GA_G16_BATCH_MAX lowers it), what keeps every batched MSM's (scalar, window)
+// pairs inside the 2^31 index space msm_plan_prepare checks, and what the free HBM holds beside the key -- per solution its inputs,
+// (nb_wires + 3n) x 32 B, the gathered scalar vectors, and the MSM scratch (pairs twice over, keys and values, and the task lists:
+// ~24 B per pair of the largest MSM).  Scratch the lane holds already is reused, so it counts as free.  At least 1.
+template <class C>
+static uint32_t batch_chunk_limit(G16Pk* pk) {
+    Ctx* ctx = pk->ctx;
+    uint64_t B = (uint64_t)std::max(1, std::min(16, ctx->tun.g16_batch_max.load(std::memory_order_relaxed)));
+    uint64_t max_pairs = 0, gathered = 0;
+    auto pairs = [&](int c, uint64_t len) {
+        if (len == 0 || c <= 0) return;
+        const uint64_t per = (uint64_t)(C::FrP::BITS / c + 1) * len;
+        max_pairs = std::max(max_pairs, per);
+        B = std::min(B, std::max<uint64_t>(1, ((1ull << 31) - 1) / per));
+    };
+    if (pk->any_wire_indexed()) pairs(pk->c_w, pk->nb_wires);
+    for (int w = 0; w < GA_KEY_NB_VECTORS; w++) {
+        const G16Vec& v = pk->vec[w];
+        if (v.layout == G16Vec::COMPACT_TABLE) pairs(v.c, v.len);
+        if (!v.wire_indexed() && w != GA_KEY_G1_Z && w != GA_KEY_G2_B) gathered += v.len;
+    }
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
+        (void)hipGetLastError();
+        return (uint32_t)B;
+    }
+    uint64_t avail = free_b;
+    {
+        std::lock_guard<std::mutex> g(ctx->scratch_mu);
+        for (const auto& kv : ctx->scratch)
+            if (kv.second.lane == 0) avail += kv.second.bytes;
+    }
+    const uint64_t per_solution = (pk->nb_wires + 3 * pk->n + gathered) * 32 + max_pairs * 24;
+    B = std::min(B, std::max<uint64_t>(1, avail / 2 / std::max<uint64_t>(per_solution, 1)));
+    return (uint32_t)B;
+}
+
+// The MSMs over base vector `which` for the B solutions of a chunk, into out[0..B): solution j's scalars are the v.len (wire-indexed:
+// nb_wires) elements at d_scalars + j * stride elements.
+//   WIRE_TABLE    the table walks `shared_sort`, the digits + sort of the B witnesses, made once per chunk
+//   COMPACT_TABLE one batch MSM over the B scalar vectors (what msm_table_device_batch does); the prepared digits stay in `reuse`,
+//                 and a vector that finds live ones of its own width and length there (G2.B after G1.B) walks its table with them
+//   PLAIN         no batch path exists for raw bases: vector_msm per solution
+template <class C, int G>
+static int vector_msm_batch(G16Pk* pk, int which, uint32_t B, const void* d_scalars, uint64_t stride, const MsmPrepared* shared_sort,
+                            PrepSlot* reuse, XYZZ<typename GroupField<C, G>::F>* out) {
+    Ctx* ctx = pk->ctx;
+    const G16Vec& v = pk->vec[which];
+    for (uint32_t j = 0; j < B; j++) out[j] = xyzz_inf<typename GroupField<C, G>::F>();
+    switch (v.layout) {
+    case G16Vec::WIRE_TABLE:
+        return shared_sort ? msm_table_device_reuse<C, G>(ctx, v.d, *shared_sort, out) : GA_OK;
+    case G16Vec::COMPACT_TABLE: {
+        if (v.len == 0) return GA_OK;
+        PrepSlot own;
+        PrepSlot& p = reuse ? *reuse : own;
+        if (!(p.live && p.prep.c == v.c && p.prep.n == v.len && p.prep.nsets == (int)B)) {
+            std::vector<const void*> ptrs(B);
+            for (uint32_t j = 0; j < B; j++) ptrs[j] = (const char*)d_scalars + (uint64_t)j * stride * 32;
+            p.live = false;
+            GA_CHECK(msm_prepare_table_scalars<C>(ctx, B == 1 ? ptrs[0] : (const void*)ptrs.data(), v.len, true, v.c, &p.prep, 0, 0, -1, (int)B));
+            p.live = true;
+        }
+        return msm_table_device_reuse<C, G>(ctx, v.d, p.prep, out);
+    }
+    default:
+        for (uint32_t j = 0; j < B; j++)
+            GA_CHECK((vector_msm<C, G>(pk, which, (const char*)d_scalars + (uint64_t)j * stride * 32, nullptr, nullptr, &out[j])));
+        return GA_OK;
+    }
+}
+
+// one chunk of B <= 16 solutions: the schedule above.  GA_ERR_NOMEM when the chunk's scratch does not fit (the caller halves B).
+template <class C>
+static int prove_batch_chunk(G16Pk* pk, uint32_t B, const void* const* w, const void* const* a, const void* const* b, const void* const* c,
+                             uint64_t n_constraints, uint64_t nb_public, G16Partials<C>* out) {
+    typedef Fe<typename C::FpP> F1;
+    typedef Fe2<typename C::FpP> F2;
+    Ctx* ctx = pk->ctx;
+    hipStream_t st = ctx->work_stream();
+    const G16Vec &va = pk->vec[GA_KEY_G1_A], &vb = pk->vec[GA_KEY_G1_B], &vk = pk->vec[GA_KEY_G1_K], &vb2 = pk->vec[GA_KEY_G2_B],
+                 &vz = pk->vec[GA_KEY_G1_Z];
+    const uint64_t nw = pk->nb_wires, n = pk->n;
+    // 1. inputs (scratch names of the batch path's own: the input slots belong to ga_g16_prove's callers)
+    void *d_w, *d_h[3];
+    GA_CHECK(ctx->scratch_get("g16b_w", (size_t)B * nw * 32 + 32, &d_w));
+    static const char* const h_names[3] = {"g16b_a", "g16b_b", "g16b_c"};
+    for (int k = 0; k < 3; k++) GA_CHECK(ctx->scratch_get(h_names[k], (size_t)B * n * 32, &d_h[k]));
+    {
+        StageTimer tm(ctx, "g16_h2d_batch");
+        const void* const* src[3] = {a, b, c};
+        for (uint32_t j = 0; j < B; j++)
+            if (nw) GA_HIP_CHECK(ctx->h2d_pageable((char*)d_w + (uint64_t)j * nw * 32, w[j], nw * 32, st, /*prio=*/0));
+        for (int k = 0; k < 3; k++) {
+            for (uint32_t j = 0; j < B; j++)
+                if (n_constraints) GA_HIP_CHECK(ctx->h2d_pageable((char*)d_h[k] + (uint64_t)j * n * 32, src[k][j], n_constraints * 32, st));
+            GA_CHECK(util_pad_fr_batch<C>(ctx, d_h[k], n_constraints, n, B, st));
+        }
+    }
+    // 2. the H side (prove.go:346-389 for every solution): h in d_h[0], [B][n], bit-reversed like pk.G1.Z
+    for (int k = 0; k < 3; k++) GA_CHECK(ntt_domain_h_chain<C>(pk->dom, d_h[k], B));
+    GA_CHECK(ntt_domain_h_combine<C>(pk->dom, d_h[0], d_h[1], d_h[2], B));
+    // 3. the MSMs.  Digits + sort of the B witnesses once (scratch set 1), walked by every wire-indexed table
+    MsmPrepared prep_w;
+    const MsmPrepared* shared = nullptr;
+    if (pk->any_wire_indexed() && nw) {
+        std::vector<const void*> ptrs(B);
+        for (uint32_t j = 0; j < B; j++) ptrs[j] = (const char*)d_w + (uint64_t)j * nw * 32;
+        GA_CHECK(msm_prepare_table_scalars<C>(ctx, B == 1 ? ptrs[0] : (const void*)ptrs.data(), nw, true, pk->c_w, &prep_w, 1, 0, -1, (int)B));
+        shared = &prep_w;
+    }
+    // wire filtering (prove.go:147-168) of the B witnesses for the vectors that are not walked by wire id; K's scalars are W[nbPublic:],
+    // gathered through the remove list when commitments leave wires out (prove.go:231-235)
+    void *d_wa = nullptr, *d_wb = nullptr;
+    const void* d_wk = (const char*)d_w + (nb_public + vk.off) * 32;
+    uint64_t k_stride = nw;
+    if (!va.wire_indexed()) {
+        GA_CHECK(ctx->scratch_get("g16b_wa", (size_t)B * va.len * 32 + 32, &d_wa));
+        GA_CHECK(util_gather_fr_batch<C>(ctx, d_wa, d_w, va.idx, va.len, B, va.len, nw));
+    }
+    if (!vb.wire_indexed() || !vb2.wire_indexed()) {
+        GA_CHECK(ctx->scratch_get("g16b_wb", (size_t)B * vb.len * 32 + 32, &d_wb));
+        GA_CHECK(util_gather_fr_batch<C>(ctx, d_wb, d_w, vb.idx, vb.len, B, vb.len, nw));
+    }
+    if (!vk.wire_indexed() && vk.idx) {
+        void* g;
+        GA_CHECK(ctx->scratch_get("g16b_wk", (size_t)B * vk.len * 32 + 32, &g));
+        GA_CHECK(util_gather_fr_batch<C>(ctx, g, d_w, vk.idx, vk.len, B, vk.len, nw));
+        d_wk = g;
+        k_stride = vk.len;
+    }
+    std::vector<XYZZ<F1>> s1(B), sz(B);
+    std::vector<XYZZ<F2>> s2(B);
+    PrepSlot wb;   // G1.B's digits, for G2.B
+    GA_CHECK((vector_msm_batch<C, GA_G1>(pk, GA_KEY_G1_A, B, d_wa, va.len, shared, nullptr, s1.data())));
+    for (uint32_t j = 0; j < B; j++) out[j].ar = s1[j];
+    GA_CHECK((vector_msm_batch<C, GA_G1>(pk, GA_KEY_G1_B, B, d_wb, vb.len, shared, &wb, s1.data())));
+    for (uint32_t j = 0; j < B; j++) out[j].bs1 = s1[j];
+    GA_CHECK((vector_msm_batch<C, GA_G2>(pk, GA_KEY_G2_B, B, d_wb, vb.len, shared, &wb, s2.data())));
+    for (uint32_t j = 0; j < B; j++) out[j].bs2 = s2[j];
+    GA_CHECK((vector_msm_batch<C, GA_G1>(pk, GA_KEY_G1_K, B, d_wk, k_stride, shared, nullptr, s1.data())));
+    for (uint32_t j = 0; j < B; j++) sz[j] = xyzz_inf<F1>();
+    if (vz.len) GA_CHECK((vector_msm_batch<C, GA_G1>(pk, GA_KEY_G1_Z, B, (const char*)d_h[0] + vz.off * 32, n, nullptr, nullptr, sz.data())));
+    for (uint32_t j = 0; j < B; j++) out[j].krs = add(s1[j], sz[j]);
+    GA_HIP_CHECK(hipStreamSynchronize(st));   // (every MSM returns synchronised; a chunk whose vectors are all empty has only copies in flight)
+    return GA_OK;
+}
+
+// the device part of `count` proofs: chunks of at most batch_chunk_limit solutions; a chunk of more than one solution that does not
+// get its scratch is halved and tried again, GA_ERR_NOMEM is returned for a chunk of one only
+template <class C>
+static int prove_batch(G16Pk* pk, uint32_t count, const void* const* w, const void* const* a, const void* const* b, const void* const* c,
+                       uint64_t n_constraints, uint64_t nb_public, G16Partials<C>* partials) {
+    Ctx* ctx = pk->ctx;
+    uint32_t B = batch_chunk_limit<C>(pk);
+    for (uint32_t done = 0; done < count;) {
+        const uint32_t cur = std::min(B, count - done);
+        const int rc = prove_batch_chunk<C>(pk, cur, w + done, a + done, b + done, c + done, n_constraints, nb_public, partials + done);
+        if (rc != GA_OK) {
+            hipStreamSynchronize(ctx->work_stream());   // nothing of the failed chunk is in flight when it is tried again or given up
+            if (rc != GA_ERR_NOMEM || cur == 1) return rc;
+            B = cur / 2;
+            continue;
+        }
+        done += cur;
+    }
+    return GA_OK;
+}
+
+// The host epilogues of a batch (finish, ~0.6 ms of host arithmetic each) beside each other on min(count, 8) threads, the caller's
+// among them: thread t takes proofs t, t + T, ...  They run outside the device lock and touch no device; the threads carry lane 1's
+// number only so that finish's stage timer, which belongs to lane 0 and the device lock, stays out of it.  serial (the profiler is
+// on and the caller still holds the device lock): one after the other on the calling thread, recorded as stages.
+template <class C>
+static int finish_batch(G16Pk* pk, const std::vector<G16Partials<C>>& parts, const void* r, const void* s, void* proofs_out, bool serial) {
+    typedef Fe<typename C::FpP> F1;
+    typedef Fe2<typename C::FpP> F2;
+    const uint32_t count = (uint32_t)parts.size();
+    const size_t proof_bytes = 2 * sizeof(Affine<F1>) + sizeof(Affine<F2>);
+    const uint32_t T = serial ? 1u : std::min<uint32_t>(count, 8u);
+    auto share = [&](uint32_t t) -> int {
+        for (uint32_t j = t; j < count; j += T)
+            GA_CHECK(finish<C>(pk, parts[j], (const char*)r + (size_t)j * 32, (const char*)s + (size_t)j * 32, (char*)proofs_out + (size_t)j * proof_bytes));
+        return GA_OK;
+    };
+    if (serial) return share(0);
+    std::vector<HelperThread> threads(T);
+    for (uint32_t t = 1; t < T; t++) threads[t].start(pk->ctx, 1, [&share, t] { return share(t); });
+    threads[0].run_here(pk->ctx, 1, [&share] { return share(0); });
+    int rc = GA_OK;
+    for (uint32_t t = T; t-- > 0;) {
+        const int rc_t = threads[t].join();
+        if (rc_t != GA_OK) rc = rc_t;
+    }
+    return rc;
 }
 
 // BSB22: commitment_i = <values, Basis_i> (pedersen Commit, prove.go:84) and its proof of knowledge <values, BasisExpSigma_i>
@@ -1126,11 +1344,7 @@ static int g16_prove_impl(ga_g16_pk* p, const void* w, const void* a, const void
         return GA_ERR_INVALID;
     }
     GA_PK_USE(pk, "ga_g16_prove");
-    if (pk->shard_count != 1 || pk->win_count != 1) {
-        set_error("ga_g16_prove: this key holds one share of a sharded key (base range %u/%u, windows %u/%u); use ga_g16_prove_multi or "
-                  "ga_g16_prove_partial + ga_g16_finish", pk->shard_index, pk->shard_count, pk->win_index, pk->win_count);
-        return GA_ERR_STATE;
-    }
+    GA_CHECK(check_unsharded(pk, "ga_g16_prove"));
     // Two callers may be inside at once (two goroutines proving on one device).  The first holds the device lock and works on
     // lanes 0/1 (witness MSMs / H side, prove_partial).  The second finds the device busy and computes its proof on lanes 2/3 --
     // own streams, own scratch namespaces -- so the two proofs run CONCURRENTLY: uploads hide behind the other proof's kernels
@@ -1401,6 +1615,43 @@ int ga_g16_prove(ga_g16_pk* p, const void* w, const void* a, const void* b, cons
                  uint64_t nb_public, const void* r, const void* s, void* proof_out) try {
     GA_ABI_ENTRY();
     return g16_prove_impl(p, w, a, b, c, n_constraints, nb_public, r, s, proof_out);
+} GA_ABI_CATCH
+
+// `count` proofs under one key: a loop of groth16.Prove over one ProvingKey (prove.go:130-315; the reference has no batch entry
+// point) as one caller of the device -- prove_batch on lane 0 under the device lock, then the epilogues outside it (finish_batch).  A
+// ga_g16_prove arriving meanwhile finds the device busy and proves on lanes 2/3 as beside any other proof.
+int ga_g16_prove_batch(ga_g16_pk* p, uint32_t count, const void* const* w, const void* const* a, const void* const* b, const void* const* c,
+                       uint64_t n_constraints, uint64_t nb_public, const void* r, const void* s, void* proofs_out) try {
+    GA_ABI_ENTRY();
+    if (count == 0) return GA_OK;
+    G16Pk* pk = reinterpret_cast<G16Pk*>(p);
+    if (!pk || !w || !a || !b || !c || !r || !s || !proofs_out) {
+        set_error("ga_g16_prove_batch: null argument");
+        return GA_ERR_INVALID;
+    }
+    for (uint32_t j = 0; j < count; j++)
+        if (!w[j] || !a[j] || !b[j] || !c[j]) {
+            set_error("ga_g16_prove_batch: null pointer in solution %u (%s[%u])", j, !w[j] ? "w" : !a[j] ? "a" : !b[j] ? "b" : "c", j);
+            return GA_ERR_INVALID;
+        }
+    GA_PK_USE(pk, "ga_g16_prove_batch");
+    GA_CHECK(check_unsharded(pk, "ga_g16_prove_batch"));
+    GA_CHECK(check_nb_constraints(pk, n_constraints));
+    GA_CHECK(check_nb_public(pk, nb_public));
+    Ctx* ctx = pk->ctx;
+    GA_DISPATCH_CURVE(pk->curve, {
+        std::vector<G16Partials<C>> parts(count);
+        {
+            std::unique_lock<std::mutex> dev(ctx->mu);
+            hipSetDevice(ctx->device);
+            ctx->tun.read_env();
+            GA_CHECK(prove_batch<C>(pk, count, w, a, b, c, n_constraints, nb_public, parts.data()));
+            // (the stage list of the profiler is guarded by the device lock)
+            if (ctx->profiling) return finish_batch<C>(pk, parts, r, s, proofs_out, /*serial=*/true);
+        }
+        return finish_batch<C>(pk, parts, r, s, proofs_out, /*serial=*/false);
+    });
+    return GA_OK;
 } GA_ABI_CATCH
 
 // One proof on a key that is NOT kept on the device (the Go package's default, PinToGPU = false, as icicle.go:797-805): the key

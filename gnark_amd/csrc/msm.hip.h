@@ -155,8 +155,8 @@ int msm_table_device_reuse_multi(Ctx* ctx, const void* const* tables, int ntab, 
 // group-independent preparation callable from translation units that do not include this header (groth16.hip)
 template <class C>
 int msm_prepare_table_scalars(Ctx* ctx, const void* d_scalars, size_t n, bool scalars_mont, int c, MsmPrepared* P, int slot, int win_lo,
-                              int win_hi) {
-    return msm_prepare<typename C::FrP>(ctx, d_scalars, n, scalars_mont, c, win_lo, win_hi, true, P, slot);
+                              int win_hi, int batch) {
+    return msm_prepare<typename C::FrP>(ctx, d_scalars, n, scalars_mont, c, win_lo, win_hi, true, P, slot, batch);
 }
 
 template <class C, int G>

@@ -8,5 +8,5 @@ template int msm_table_device_reuse_multi<Bn254, GA_G1>(Ctx*, const void* const*
 template int msm_table_device_batch<Bn254, GA_G1>(Ctx*, const void*, const void* const*, int, size_t, bool, int, void*);
 template int msm_table_build<Bn254, GA_G1>(Ctx*, const void*, size_t, int, void*);
 template size_t msm_table_point_bytes<Bn254, GA_G1>();
-template int msm_prepare_table_scalars<Bn254>(Ctx*, const void*, size_t, bool, int, MsmPrepared*, int, int, int);
+template int msm_prepare_table_scalars<Bn254>(Ctx*, const void*, size_t, bool, int, MsmPrepared*, int, int, int, int);
 }  // namespace ga

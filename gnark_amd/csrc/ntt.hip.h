@@ -34,6 +34,7 @@ namespace ga {
 constexpr int NTT_LG_TILE = 10;               // 1024 elements = 32 KiB of LDS per workgroup
 constexpr int NTT_THREADS = 256;
 constexpr int NTT_POW_LO_BITS = 12;
+constexpr uint64_t NTT_MAX_GRID_Y = 65535;    // vectors of a batch per launch (the grid's y limit)
 
 struct NttScale {
     int mode;                 // 0 none, 1 constant only, 2 power tables (lo*hi), constant folded into lo
@@ -172,6 +173,10 @@ ntt_pass29r4_kernel(uint32_t* data, const uint32_t* src, const uint32_t* __restr
     LdsTile29<FrP> T{lds};
     const uint32_t tile_elems = 1u << lg_tile;
     const uint64_t tile = blockIdx.x;
+    // a batch: grid row y transforms vector y of `data` (and of `src`), n contiguous elements each; tables, plan and scale factors
+    // are the same for every vector, so nothing below depends on y
+    data += ((uint64_t)blockIdx.y << logn) * 8;
+    src += ((uint64_t)blockIdx.y << logn) * 8;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
     const bool unit_ok = (flags & NTT_F_UNIT) != 0;
     const bool wl = lg_tile == NTT_LG_TILE && (flags & NTT_F_WAVE_LOCAL) != 0;
@@ -514,9 +519,11 @@ inline std::vector<NttPass> ntt_plan(int logn) {
 
 template <class FrP>
 int ntt_run(Domain* d, uint32_t* d_data, bool inverse, bool dit, const NttScale& pre_first, const NttScale& post_last,
-            const uint32_t* d_src = nullptr, const uint32_t* coset_table = nullptr) {
+            const uint32_t* d_src = nullptr, const uint32_t* coset_table = nullptr, uint64_t batch = 1) {
     // coset_table != nullptr: a stacked table with the coset generator folded in (forward, bit-reversed -> natural only)
     // d_src != nullptr: out-of-place transform (the first pass reads d_src, every pass writes d_data; d_src is left untouched)
+    // batch: d_data (and d_src) hold `batch` vectors of n elements each, contiguous; every pass is ONE launch over all of them, the
+    // vector is the grid's y dimension (at most NTT_MAX_GRID_Y rows per launch: a larger batch takes several launches per pass)
     Ctx* ctx = d->ctx;
     const uint32_t* tw = coset_table ? coset_table : dit ? (inverse ? d->d_ts_inv : d->d_ts) : (inverse ? d->d_tb_inv : d->d_tb);
     const int flags = (coset_table ? 0 : NTT_F_UNIT) | (ctx->tun.ntt_wave_local ? NTT_F_WAVE_LOCAL : 0) | (ctx->tun.ntt_direct ? NTT_F_DIRECT : 0);
@@ -531,12 +538,17 @@ int ntt_run(Domain* d, uint32_t* d_data, bool inverse, bool dit, const NttScale&
         const NttScale& post = (p == np - 1) ? post_last : none;
         const uint32_t* src = (p == 0 && d_src) ? d_src : d_data;
         StageTimer st(ctx, dit ? "ntt_pass_dit" : "ntt_pass_dif");
-        if (dit)
-            hipLaunchKernelGGL((ntt_pass29r4_kernel<FrP, true>), dim3((unsigned)tiles), dim3(NTT_THREADS), 0, ctx->work_stream(),
-                               d_data, src, tw, d->logn, lg_tile, ps.s_lo, ps.K, ps.lc, pre, post, flags);
-        else
-            hipLaunchKernelGGL((ntt_pass29r4_kernel<FrP, false>), dim3((unsigned)tiles), dim3(NTT_THREADS), 0, ctx->work_stream(),
-                               d_data, src, tw, d->logn, lg_tile, ps.s_lo, ps.K, ps.lc, pre, post, flags);
+        for (uint64_t v0 = 0; v0 < batch; v0 += NTT_MAX_GRID_Y) {
+            const unsigned rows = (unsigned)(batch - v0 < NTT_MAX_GRID_Y ? batch - v0 : NTT_MAX_GRID_Y);
+            uint32_t* const out = d_data + v0 * d->n * 8;
+            const uint32_t* const in = src + v0 * d->n * 8;
+            if (dit)
+                hipLaunchKernelGGL((ntt_pass29r4_kernel<FrP, true>), dim3((unsigned)tiles, rows), dim3(NTT_THREADS), 0, ctx->work_stream(),
+                                   out, in, tw, d->logn, lg_tile, ps.s_lo, ps.K, ps.lc, pre, post, flags);
+            else
+                hipLaunchKernelGGL((ntt_pass29r4_kernel<FrP, false>), dim3((unsigned)tiles, rows), dim3(NTT_THREADS), 0, ctx->work_stream(),
+                                   out, in, tw, d->logn, lg_tile, ps.s_lo, ps.K, ps.lc, pre, post, flags);
+        }
         GA_KERNEL_CHECK();
     }
     return GA_OK;
@@ -565,55 +577,59 @@ inline NttScale scale_pow(const uint32_t* lo, const uint32_t* hi, bool bitrev) {
 
 // gnark semantics wrapper: see header comment
 template <class FrP>
-int ntt_fft(Domain* d, uint32_t* d_data, int direction, int decimation, int on_coset) {
-    if (d->logn == 0) return GA_OK;
+int ntt_fft(Domain* d, uint32_t* d_data, int direction, int decimation, int on_coset, uint64_t batch = 1) {
+    if (d->logn == 0 || batch == 0) return GA_OK;
     bool inverse = direction == GA_FFT_INVERSE;
     bool dit = decimation == GA_DIT;
     NttScale pre = scale_none(), post = scale_none();
     if (!inverse) {
         if (on_coset && dit)   // the coset lives in the twiddle table: no scaling pass
-            return ntt_run<FrP>(d, d_data, false, true, pre, post, nullptr, d->d_ts_g);
+            return ntt_run<FrP>(d, d_data, false, true, pre, post, nullptr, d->d_ts_g, batch);
         if (on_coset) pre = scale_pow(d->d_g_lo, d->d_g_hi, /*bitrev=*/false);
     } else {
         if (on_coset) post = scale_pow(d->d_gi_lo, d->d_gi_hi, /*bitrev=*/!dit);
         else post = scale_const(d->ninv);
     }
-    return ntt_run<FrP>(d, d_data, inverse, dit, pre, post);
+    return ntt_run<FrP>(d, d_data, inverse, dit, pre, post, nullptr, nullptr, batch);
 }
 
 // computeH in two pieces, so that a multi-GPU proof can run the three chains on different devices:
 //   chain(v)        : v <- FFT_coset(iFFT(v))       per input vector a, b, c   (prove.go:362-368)
 //   combine(a,b,c)  : a <- iFFT_coset((a*b - c) * den)   bit-reversed h        (prove.go:377-386)
-// Buffers hold exactly n elements each (already zero-padded).
+// Buffers hold exactly n elements each (already zero-padded) -- or, for a batch, `batch` such vectors one after the other: every
+// transform is then one launch chain over all of them and the point-wise step one launch over batch * n elements.
 template <class FrP>
-int ntt_compute_h_chain(Domain* d, uint32_t* d_v) {
-    if (d->logn == 0) return GA_OK;   // n = 1: iFFT and coset FFT are identities
+int ntt_compute_h_chain(Domain* d, uint32_t* d_v, uint64_t batch = 1) {
+    if (d->logn == 0 || batch == 0) return GA_OK;   // n = 1: iFFT and coset FFT are identities
     // n * FFT_coset(iFFT(v)) without a single scaling multiplication: the inverse transform leaves its 1/n out (the point-wise step
     // of ntt_compute_h_combine absorbs it: the chains are only ever consumed there) and the forward one runs over the coset table
-    GA_CHECK(ntt_run<FrP>(d, d_v, /*inverse=*/true, /*dit=*/false, scale_none(), scale_none()));
-    return ntt_run<FrP>(d, d_v, /*inverse=*/false, /*dit=*/true, scale_none(), scale_none(), nullptr, d->d_ts_g);
+    GA_CHECK(ntt_run<FrP>(d, d_v, /*inverse=*/true, /*dit=*/false, scale_none(), scale_none(), nullptr, nullptr, batch));
+    return ntt_run<FrP>(d, d_v, /*inverse=*/false, /*dit=*/true, scale_none(), scale_none(), nullptr, d->d_ts_g, batch);
 }
 
 template <class FrP>
-int ntt_compute_h_combine(Domain* d, uint32_t* d_a, const uint32_t* d_b, const uint32_t* d_c) {
+int ntt_compute_h_combine(Domain* d, uint32_t* d_a, const uint32_t* d_b, const uint32_t* d_c, uint64_t batch = 1) {
     Ctx* ctx = d->ctx;
+    if (batch == 0) return GA_OK;
     {
         StageTimer st(ctx, "h_pointwise");
         NttScale den = scale_const(d->den_n2), cn = scale_const(d->n_mont);   // a, b, c are n * (the reference's vectors)
-        unsigned blocks = d->logn == 0 ? 1u : (unsigned)((d->n + 255) / 256);
-        hipLaunchKernelGGL((ntt_pointwise_h_kernel<FrP>), dim3(blocks), dim3(d->logn == 0 ? 64 : 256), 0, ctx->work_stream(), d_a, d_b, d_c, d->n, den, cn);
+        const uint64_t total = batch * d->n;   // (the constants are the same for every vector of a batch)
+        const bool one = total == 1;
+        unsigned blocks = one ? 1u : (unsigned)((total + 255) / 256);
+        hipLaunchKernelGGL((ntt_pointwise_h_kernel<FrP>), dim3(blocks), dim3(one ? 64 : 256), 0, ctx->work_stream(), d_a, d_b, d_c, total, den, cn);
         GA_KERNEL_CHECK();
     }
     if (d->logn == 0) return GA_OK;
-    return ntt_fft<FrP>(d, d_a, GA_FFT_INVERSE, GA_DIF, 1);
+    return ntt_fft<FrP>(d, d_a, GA_FFT_INVERSE, GA_DIF, 1, batch);
 }
 
-// computeH on device buffers of exactly n elements each (already zero-padded); result in d_a (bit-reversed)
+// computeH on device buffers of exactly n elements each (already zero-padded), `batch` of them per buffer; result in d_a (bit-reversed)
 template <class FrP>
-int ntt_compute_h(Domain* d, uint32_t* d_a, uint32_t* d_b, uint32_t* d_c) {
+int ntt_compute_h(Domain* d, uint32_t* d_a, uint32_t* d_b, uint32_t* d_c, uint64_t batch = 1) {
     uint32_t* v[3] = {d_a, d_b, d_c};
-    for (int k = 0; k < 3; k++) GA_CHECK(ntt_compute_h_chain<FrP>(d, v[k]));
-    return ntt_compute_h_combine<FrP>(d, d_a, d_b, d_c);
+    for (int k = 0; k < 3; k++) GA_CHECK(ntt_compute_h_chain<FrP>(d, v[k], batch));
+    return ntt_compute_h_combine<FrP>(d, d_a, d_b, d_c, batch);
 }
 
 // The stacked forward table of the domain with the coset `shift` folded in (layout and derivation: ntt_twiddle_kernel): a

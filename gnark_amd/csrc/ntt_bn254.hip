@@ -14,19 +14,19 @@ int ntt_domain_new<Bn254>(Ctx* ctx, uint64_t n, Domain** out) {
     return GA_OK;
 }
 template <>
-int ntt_domain_fft<Bn254>(Domain* d, void* d_data, int direction, int decimation, int on_coset) {
-    return ntt_fft<Bn254::FrP>(d, (uint32_t*)d_data, direction, decimation, on_coset);
+int ntt_domain_fft<Bn254>(Domain* d, void* d_data, int direction, int decimation, int on_coset, uint64_t batch) {
+    return ntt_fft<Bn254::FrP>(d, (uint32_t*)d_data, direction, decimation, on_coset, batch);
 }
 template <>
-int ntt_domain_h_chain<Bn254>(Domain* d, void* d_v) {
-    return ntt_compute_h_chain<Bn254::FrP>(d, (uint32_t*)d_v);
+int ntt_domain_h_chain<Bn254>(Domain* d, void* d_v, uint64_t batch) {
+    return ntt_compute_h_chain<Bn254::FrP>(d, (uint32_t*)d_v, batch);
 }
 template <>
-int ntt_domain_h_combine<Bn254>(Domain* d, void* d_a, const void* d_b, const void* d_c) {
-    return ntt_compute_h_combine<Bn254::FrP>(d, (uint32_t*)d_a, (const uint32_t*)d_b, (const uint32_t*)d_c);
+int ntt_domain_h_combine<Bn254>(Domain* d, void* d_a, const void* d_b, const void* d_c, uint64_t batch) {
+    return ntt_compute_h_combine<Bn254::FrP>(d, (uint32_t*)d_a, (const uint32_t*)d_b, (const uint32_t*)d_c, batch);
 }
 template <>
-int ntt_domain_compute_h<Bn254>(Domain* d, void* d_a, void* d_b, void* d_c) {
-    return ntt_compute_h<Bn254::FrP>(d, (uint32_t*)d_a, (uint32_t*)d_b, (uint32_t*)d_c);
+int ntt_domain_compute_h<Bn254>(Domain* d, void* d_a, void* d_b, void* d_c, uint64_t batch) {
+    return ntt_compute_h<Bn254::FrP>(d, (uint32_t*)d_a, (uint32_t*)d_b, (uint32_t*)d_c, batch);
 }
 }  // namespace ga

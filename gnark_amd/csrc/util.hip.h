@@ -84,6 +84,30 @@ __global__ void gather_fr_kernel(uint32_t* __restrict__ dst, const uint32_t* __r
     d[i * 2 + half] = s[(uint64_t)idx[i] * 2 + half];
 }
 
+// the same gather for the vectors of a batch in one launch: vector y of the grid reads src + y * src_stride elements and writes
+// dst + y * dst_stride elements through the ONE index list (the wire filtering of `count` witnesses of one circuit)
+template <class C>
+__global__ void gather_fr_batch_kernel(uint32_t* __restrict__ dst, const uint32_t* __restrict__ src, const uint32_t* __restrict__ idx,
+                                       uint64_t n, uint64_t dst_stride, uint64_t src_stride) {
+    uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint64_t i = t >> 1, half = t & 1;
+    if (i >= n) return;
+    const u32x4* s = reinterpret_cast<const u32x4*>(src) + (uint64_t)blockIdx.y * src_stride * 2;
+    u32x4* d = reinterpret_cast<u32x4*>(dst) + (uint64_t)blockIdx.y * dst_stride * 2;
+    d[i * 2 + half] = s[(uint64_t)idx[i] * 2 + half];
+}
+
+// zero padding of the vectors of a batch: elements [from, n) of vector y (n elements each, contiguous) <- 0; two lanes per element
+template <class C>
+__global__ void pad_fr_batch_kernel(uint32_t* __restrict__ v, uint64_t from, uint64_t n) {
+    uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint64_t i = from + (t >> 1), half = t & 1;
+    if (i >= n) return;
+    u32x4 z;
+    z.x = z.y = z.z = z.w = 0u;
+    reinterpret_cast<u32x4*>(v)[((uint64_t)blockIdx.y * n + i) * 2 + half] = z;
+}
+
 template <class C, int G>
 int util_gen_bases(Ctx* ctx, uint64_t seed, size_t n, void* d_bases, void* d_dlogs, uint64_t first) {
     if (n == 0) return GA_OK;
@@ -140,6 +164,37 @@ int util_gather_fr(Ctx* ctx, void* d_dst, const void* d_src, const uint32_t* d_i
     StageTimer tm(ctx, "gather_fr");
     hipLaunchKernelGGL((gather_fr_kernel<C>), dim3((unsigned)((2 * n + 255) / 256)), dim3(256), 0, ctx->work_stream(), (uint32_t*)d_dst,
                        (const uint32_t*)d_src, d_idx, (uint64_t)n);
+    GA_KERNEL_CHECK();
+    return GA_OK;
+}
+
+constexpr uint32_t UTIL_MAX_GRID_Y = 65535;   // vectors of a batch per launch (the grid's y limit)
+
+// dst[v][i] = src[v][idx[i]] for v < count: dst holds count vectors of dst_stride elements, src count vectors of src_stride elements
+template <class C>
+int util_gather_fr_batch(Ctx* ctx, void* d_dst, const void* d_src, const uint32_t* d_idx, size_t n, uint32_t count, uint64_t dst_stride,
+                         uint64_t src_stride) {
+    if (n == 0 || count == 0) return GA_OK;
+    StageTimer tm(ctx, "gather_fr");
+    for (uint32_t v0 = 0; v0 < count; v0 += UTIL_MAX_GRID_Y) {
+        const uint32_t rows = count - v0 < UTIL_MAX_GRID_Y ? count - v0 : UTIL_MAX_GRID_Y;
+        hipLaunchKernelGGL((gather_fr_batch_kernel<C>), dim3((unsigned)((2 * n + 255) / 256), rows), dim3(256), 0, ctx->work_stream(),
+                           (uint32_t*)d_dst + (uint64_t)v0 * dst_stride * 8, (const uint32_t*)d_src + (uint64_t)v0 * src_stride * 8, d_idx,
+                           (uint64_t)n, dst_stride, src_stride);
+    }
+    GA_KERNEL_CHECK();
+    return GA_OK;
+}
+
+// elements [from, n) of each of the `count` contiguous n-element vectors at d_v <- 0 on `st` (computeH's padding, prove.go:356-359)
+template <class C>
+int util_pad_fr_batch(Ctx* ctx, void* d_v, uint64_t from, uint64_t n, uint32_t count, hipStream_t st) {
+    if (from >= n || count == 0) return GA_OK;
+    for (uint32_t v0 = 0; v0 < count; v0 += UTIL_MAX_GRID_Y) {
+        const uint32_t rows = count - v0 < UTIL_MAX_GRID_Y ? count - v0 : UTIL_MAX_GRID_Y;
+        hipLaunchKernelGGL((pad_fr_batch_kernel<C>), dim3((unsigned)((2 * (n - from) + 255) / 256), rows), dim3(256), 0, st,
+                           (uint32_t*)d_v + (uint64_t)v0 * n * 8, from, n);
+    }
     GA_KERNEL_CHECK();
     return GA_OK;
 }

@@ -45,6 +45,40 @@ class Domain:
     def FFTInverse(self, a, decimation: int, on_coset: bool = False):
         return self._run(a, _lib.FFT_INVERSE, decimation, on_coset)
 
+    def _run_batch(self, a2d, direction, decimation, on_coset, count):
+        n = self.Cardinality
+        if isinstance(a2d, DeviceBuffer):
+            if count is None:
+                count = a2d.nbytes // (n * 32)
+            if count * n * 32 > a2d.nbytes:
+                raise ValueError(f"{count} vectors of {n} elements do not fit a device buffer of {a2d.nbytes} bytes")
+            self.ctx.lib.check(self.ctx.lib.ga_fft_batch(self.handle, C.c_void_p(a2d.ptr), count, direction, decimation, int(on_coset), 1))
+            return a2d
+        a = np.ascontiguousarray(a2d, dtype=np.uint64)
+        if a.ndim != 3 or a.shape[1:] != (n, 4) or (count is not None and count != a.shape[0]):
+            raise ValueError(f"expected a (count, {n}, 4) uint64 array, got shape {a.shape}")
+        out = a.copy()
+        self.ctx.lib.check(self.ctx.lib.ga_fft_batch(self.handle, _ptr(out), out.shape[0], direction, decimation, int(on_coset), 0))
+        return out
+
+    def FFTBatch(self, a2d, decimation: int, on_coset: bool = False, count=None):
+        """FFT of every vector of a2d, a (count, Cardinality, 4) array or a DeviceBuffer of `count` contiguous vectors (default: as many
+        as the buffer holds), in one call: every pass of the transform is one launch over all of them (ga_fft_batch)."""
+        return self._run_batch(a2d, _lib.FFT_FORWARD, decimation, on_coset, count)
+
+    def FFTInverseBatch(self, a2d, decimation: int, on_coset: bool = False, count=None):
+        return self._run_batch(a2d, _lib.FFT_INVERSE, decimation, on_coset, count)
+
+    def compute_h_batch(self, A, B, C_) -> np.ndarray:
+        """computeH for every solution of a batch (ga_compute_h_batch): A, B, C_ are (count, #constraints, 4) arrays; returns the
+        (count, Cardinality, 4) array of the h vectors, each as compute_h's for its triple."""
+        A, B, C_ = (np.ascontiguousarray(v, dtype=np.uint64) for v in (A, B, C_))
+        if A.ndim != 3 or A.shape[2] != 4 or not (A.shape == B.shape == C_.shape):
+            raise ValueError("A, B, C must be (count, n_constraints, 4) uint64 arrays of one shape")
+        out = np.zeros((A.shape[0], self.Cardinality, 4), dtype=np.uint64)
+        self.ctx.lib.check(self.ctx.lib.ga_compute_h_batch(self.handle, _ptr(A), _ptr(B), _ptr(C_), A.shape[0], A.shape[1], _ptr(out), 0))
+        return out
+
     def compute_h(self, a, b, c) -> np.ndarray:
         """computeH (prove.go:346-389): a, b, c are the solver's A, B, C (len = #constraints <= n)."""
         a, b, c = as_u64(a, 4), as_u64(b, 4), as_u64(c, 4)

@@ -295,6 +295,33 @@ def Prove(pk: ProvingKey, solution: Solution, nb_public: int, r: np.ndarray, s: 
     return Proof(pk.curve, out[: 2 * fp].copy(), out[2 * fp: 6 * fp].copy(), out[6 * fp:].copy(), lib)
 
 
+def ProveBatch(pk: ProvingKey, solutions, nb_public: int, rs, ss) -> list:
+    """One proof per solution under one key in one device pass (ga_g16_prove_batch): what a loop of Prove over `solutions` returns,
+    byte for byte, with proof j randomised by (rs[j], ss[j]).  The reference has no batch entry point (a loop of groth16.Prove,
+    prove.go:130-315); this is for callers that prove many instances of one small circuit."""
+    if pk.handle is None:
+        raise _lib.GnarkAmdError("proving key has been freed")
+    count = len(solutions)
+    fp = FP_LIMBS[pk.curve]
+    if count == 0:
+        return []
+    vecs = [[as_u64(x, 4) for x in (sol.W, sol.A, sol.B, sol.C)] for sol in solutions]   # (kept alive until the call returns)
+    nc = vecs[0][1].shape[0]
+    for W, A, B, Cc in vecs:
+        if W.shape[0] != pk.nb_wires:
+            raise ValueError(f"len(W)={W.shape[0]} != nbWires={pk.nb_wires}")
+        if not (A.shape == B.shape == Cc.shape) or A.shape[0] != nc:
+            raise ValueError("A, B, C of every solution must have the same length")
+    rs, ss = as_u64(np.asarray(rs).reshape(-1, 4), 4), as_u64(np.asarray(ss).reshape(-1, 4), 4)
+    if rs.shape[0] != count or ss.shape[0] != count:
+        raise ValueError(f"{count} solutions need {count} values of r and of s each")
+    ptrs = [(C.c_void_p * count)(*[v[k].ctypes.data for v in vecs]) for k in range(4)]
+    out = np.zeros((count, 8 * fp), dtype=np.uint64)
+    lib = pk.ctx.lib
+    lib.check(lib.ga_g16_prove_batch(pk.handle, count, ptrs[0], ptrs[1], ptrs[2], ptrs[3], nc, nb_public, _ptr(rs), _ptr(ss), _ptr(out)))
+    return [Proof(pk.curve, o[: 2 * fp].copy(), o[2 * fp: 6 * fp].copy(), o[6 * fp:].copy(), lib) for o in out]
+
+
 def ProveOneShot(ctx: Context, curve, solution: Solution, nb_public: int, r, s, *, domain_cardinality, alpha1, beta1, delta1, A, B, Z, K,
                  beta2, delta2, B2, infinityA, infinityB, k_remove=()) -> Proof:
     """groth16.Prove with the key NOT kept on the device (the reference's and the Go package's default, PinToGPU = false,

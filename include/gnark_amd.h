@@ -376,12 +376,24 @@ void ga_domain_destroy(ga_domain* d);
  * (inverse includes the 1/n factor); decimation: GA_DIF / GA_DIT; on_coset: fft.OnCoset() with the domain's
  * FrMultiplicativeGen (5 for BN254, 7 for BLS12-381).  data is a host pointer unless on_device != 0. */
 int ga_fft(ga_domain* d, void* data, int direction, int decimation, int on_coset, int on_device);
+/* `count` transforms of one size in one call: data = count vectors of `cardinality` fr elements, contiguous; the other arguments
+ * as ga_fft's, the same for every vector.  Replaces a loop of fft.Domain.FFT / FFTInverse over vectors of one domain (the three
+ * chains of computeH, prove.go:362-368; PLONK's L, R, O and h1..h3): every pass of the transform is ONE launch over all the
+ * vectors, so small transforms (one workgroup per launch at 2^10) fill the device together.  Vector j's result is ga_fft's on vector
+ * j alone, bit for bit.  count = 0 is GA_OK and touches nothing. */
+int ga_fft_batch(ga_domain* d, void* data, uint32_t count, int direction, int decimation, int on_coset, int on_device);
 
 /* computeH (prove.go:346-389 / icicle.go:1391-1488): h = coefficients of (A*B - C)/(X^n - 1) in bit-reversed
  * order.  a,b,c hold n_constraints fr elements (Montgomery), zero-padded internally to the domain size;
  * h_out receives cardinality elements.  Pointers are host unless on_device != 0 (then a is clobbered). */
 int ga_compute_h(ga_domain* d, const void* a, const void* b, const void* c, uint64_t n_constraints,
                  void* h_out, int on_device);
+/* computeH for `count` solutions of one circuit (a loop of prove.go:346-389 over the solutions): a, b, c = [count][n_constraints]
+ * contiguous; h_out = [count][cardinality], each h as ga_compute_h's for its triple, bit for bit.  The seven transforms are batched
+ * launch chains (ga_fft_batch) and the point-wise step is one launch.  Pointers are host unless on_device != 0 (a, b, c are left
+ * untouched either way).  count = 0 is GA_OK and touches nothing. */
+int ga_compute_h_batch(ga_domain* d, const void* a, const void* b, const void* c, uint32_t count, uint64_t n_constraints,
+                       void* h_out, int on_device);
 
 /* ---- PLONK: quotient and grand product on the device ---------------------------------------
  * replaces: (*instance).computeNumerator + divideByZH (backend/plonk/bn254/prove.go:841-1123,1287-1350; the "we do **a lot** of
@@ -539,6 +551,26 @@ void ga_g16_builder_destroy(ga_g16_builder* b);
  * All pointers are host pointers. */
 int ga_g16_prove(ga_g16_pk* pk, const void* w, const void* a, const void* b, const void* c,
                  uint64_t n_constraints, uint64_t nb_public, const void* r, const void* s, void* proof_out);
+
+/* `count` proofs under one key in one device pass: what a loop of groth16.Prove over one ProvingKey computes (prove.go:130-315; the
+ * reference has no batch entry point).  For callers that prove many instances of one small circuit, where a single proof is bound by
+ * launch chains and host round trips, not by device work.
+ *   w, a, b, c: host arrays of `count` host pointers (as ga_msm_table_run_batch takes its scalars): w[j] -> nb_wires elements,
+ *               a[j], b[j], c[j] -> n_constraints elements each
+ *   r, s      : count fr elements each (Montgomery): the randomness of proof j is (r[j], s[j])
+ *   proofs_out: count images Ar | Bs | Krs as ga_g16_prove writes one; proof j is byte-identical to ga_g16_prove's for solution j
+ * Solutions go through the device in chunks of at most 16 (GA_G16_BATCH_MAX; fewer when the (scalar, window) pair space or the free
+ * HBM asks for it; `count` itself is not limited): the H side of a chunk runs as batched transforms, every MSM over a precomputed
+ * table takes the chunk's scalar vectors in one pass, and the host epilogues run beside each other on up to 8 threads.  A base vector
+ * WITHOUT a table (a key pinned with precompute = -1, or a partial table set) has no batch path: its MSMs are looped over the
+ * solutions -- a batch on such a key is correct, not fast.  The call holds the device like one ga_g16_prove caller (lanes 0/1);
+ * a concurrent ga_g16_prove runs beside it on lanes 2/3.  A key that holds a share of a sharded key is refused (GA_ERR_STATE); a
+ * null pointer anywhere (the message names the index), n_constraints above the cardinality or an nb_public the key contradicts is
+ * GA_ERR_INVALID, decided before any device work.  On an error the contents of proofs_out are unspecified; the context and the key
+ * stay usable.  count = 0 is GA_OK and touches nothing. */
+int ga_g16_prove_batch(ga_g16_pk* pk, uint32_t count, const void* const* w, const void* const* a, const void* const* b,
+                       const void* const* c, uint64_t n_constraints, uint64_t nb_public, const void* r, const void* s,
+                       void* proofs_out);
 
 /* Multi-GPU proving with a key sharded by base-point range (one context + one shard per GPU, every rank gets the whole
  * solution): ga_g16_prove_partial runs computeH and the five MSMs over this shard and returns the sums BEFORE
