@@ -235,6 +235,14 @@ typedef CtxLock Lock;
 //   ga_fr_sparse_matvec
 //     GA_FR_SPARSE_SEGMENT  terms, or partial sums, per lane: 2 .. 2^20; unset, 0 or 1 = the default (FR_SPARSE_DEFAULT_SEGMENT); a
 //                           larger value is taken as 2^20; tests force 2
+//   ga_plonk_build_z_batch, ga_plonk_quotient_pinned_batch, ga_kzg_open_batch
+//     GA_PLONK_BATCH_MAX    most proofs per device pass (1 .. 16, default 16 = the limit of the batched table MSM; tests force several passes)
+//     GA_PLONK_SCAN_THREADS threads a segmented scan aims at when it chooses its chunk of 8 .. 256 elements (default 2^13; 0 = default;
+//                           tests force small values so that sizes of a few hundred elements take every chunk width)
+static PlonkBatchKnobs env_plonk_batch_knobs() {
+    const uint64_t b = env_u64("GA_PLONK_BATCH_MAX", PLONK_BATCH_LIMIT), t = env_u64("GA_PLONK_SCAN_THREADS", 0);
+    return PlonkBatchKnobs{(uint32_t)(b < 1 ? 1 : b > PLONK_BATCH_LIMIT ? PLONK_BATCH_LIMIT : b), t ? t : 8192};
+}
 static uint32_t env_segment(const char* name) {   // the two segment knobs, capped
     const uint64_t v = env_u64(name, 0);
     return (uint32_t)(v < (1u << 20) ? v : (1u << 20));
@@ -1048,6 +1056,76 @@ int ga_kzg_open(ga_msm_table* th, const void* poly, size_t n, unsigned flags, co
     return GA_OK;
 } GA_ABI_CATCH
 
+// kzg.Open for `count` polynomials of one length over one SRS: per pass of at most GA_PLONK_BATCH_MAX items the divisions by
+// (X - z_j) are one launch chain (plonk_batch.hip.h) and the quotients one batched table MSM
+int ga_kzg_open_batch(ga_msm_table* th, const void* const* polys, size_t n, uint32_t count, unsigned flags, const void* points,
+                      void* claimed_values_out, void* h_out) try {
+    GA_ABI_ENTRY();
+    if (count == 0) return GA_OK;
+    MsmTable* t = reinterpret_cast<MsmTable*>(th);
+    if (!t || !polys || !points || !claimed_values_out || !h_out || n == 0) {
+        set_error("ga_kzg_open_batch: null argument or empty polynomial");
+        return GA_ERR_INVALID;
+    }
+    for (uint32_t j = 0; j < count; j++)
+        if (!polys[j]) {
+            set_error("ga_kzg_open_batch: polys[%u] is null", j);
+            return GA_ERR_INVALID;
+        }
+    if (t->group != GA_G1 || n - 1 > t->n) {
+        set_error("ga_kzg_open_batch: the SRS table must be G1 and hold at least len(p) - 1 = %zu points (it has %zu)", n - 1, t->n);
+        return GA_ERR_INVALID;
+    }
+    Ctx* c = t->ctx;
+    Lock l(c);
+    const PlonkBatchKnobs knobs = env_plonk_batch_knobs();
+    uint32_t batch_max = knobs.batch_max;
+    while (batch_max > 1 && (uint64_t)batch_max * t->nwin * t->n >= (1ull << 31)) batch_max--;   // the pair index space of one batched MSM
+    if ((uint64_t)batch_max * t->nwin * t->n >= (1ull << 31)) {
+        set_error("ga_kzg_open_batch: %d windows x %zu points exceed the 2^31 pair index space of the batched table MSM", t->nwin, (size_t)t->n);
+        return GA_ERR_INVALID;
+    }
+    const bool on_device = (flags & GA_SCALARS_ON_DEVICE) != 0;
+    const size_t qn = n > t->n ? n : t->n;   // a row of quotients: the table's n scalars (zero beyond the n - 1 coefficients)
+    GA_DISPATCH_CURVE(t->curve, {
+        typedef typename GroupField<C, GA_G1>::F F;
+        char *in = nullptr, *q = nullptr, *vals = nullptr;
+        auto reserve = [&](uint32_t cnt) -> int {
+            GA_CHECK(c->scratch_get("kzg_b_in", on_device ? 256 : (size_t)cnt * n * 32, (void**)&in));
+            GA_CHECK(c->scratch_get("kzg_b_quotient", (size_t)cnt * qn * 32, (void**)&q));
+            GA_CHECK(c->scratch_get("kzg_b_values", (size_t)cnt * 32, (void**)&vals));
+            return GA_OK;
+        };
+        std::vector<XYZZ<F>> sums(PLONK_BATCH_LIMIT);
+        std::vector<uint32_t> stage;   // the division's small upload; read before the MSM of its pass has returned
+        // (the division and the MSM get their own scratch inside the pass: plonk_batch_chunks halves a pass that fails there as well)
+        auto pass = [&](uint32_t first, uint32_t cnt) -> int {
+            const void *dpoly[PLONK_BATCH_LIMIT], *dquot[PLONK_BATCH_LIMIT];
+            for (uint32_t j = 0; j < cnt; j++) {
+                dpoly[j] = polys[first + j];
+                if (!on_device) {
+                    GA_HIP_CHECK(hipMemcpyAsync(in + (size_t)j * n * 32, polys[first + j], n * 32, hipMemcpyHostToDevice, c->stream));
+                    dpoly[j] = in + (size_t)j * n * 32;
+                }
+                dquot[j] = q + (size_t)j * qn * 32;
+            }
+            GA_HIP_CHECK(hipMemsetAsync(q, 0, (size_t)cnt * qn * 32, c->stream));
+            GA_CHECK(kzg_domain_divide_batch<C>(c, dpoly, n, cnt, (const char*)points + (size_t)first * 32, q, qn, vals, knobs.scan_threads, &stage));
+            // the claimed values leave in one copy ahead of the MSM, whose synchronisation (it returns its sums) completes it
+            GA_HIP_CHECK(hipMemcpyAsync((char*)claimed_values_out + (size_t)first * 32, vals, (size_t)cnt * 32, hipMemcpyDeviceToHost, c->stream));
+            GA_CHECK((msm_table_device_batch<C, GA_G1>(c, t->d_table, dquot, (int)cnt, t->n, true, t->c, sums.data())));
+            for (uint32_t j = 0; j < cnt; j++) host_store_jac<F>((char*)h_out + (size_t)(first + j) * sizeof(Jac<F>), sums[j]);
+            return GA_OK;
+        };
+        const int rc = plonk_batch_chunks(count, batch_max, reserve, pass);
+        if (rc != GA_OK) {
+            hipStreamSynchronize(c->stream);   // `stage` and the caller's polynomials: no copy from them may still be queued
+            return rc;
+        }
+    });
+    return GA_OK;
+} GA_ABI_CATCH
+
 // ---- host group helpers ---------------------------------------------------------------------------------
 int ga_jac_add(int curve, int group, const void* a, const void* b, void* out) try {
     GA_ABI_ENTRY();
@@ -1260,6 +1338,55 @@ int ga_plonk_build_z(ga_domain* dh0, const void* lv, const void* rv, const void*
             }
     }
     GA_DISPATCH_CURVE(ntt_domain_curve(d0), GA_CHECK(plonk_domain_build_z<C>(d0, lv, rv, ov, permutation, beta, gamma, on_device != 0, z_out)));
+    return GA_OK;
+} GA_ABI_CATCH
+
+int ga_plonk_build_z_batch(ga_domain* dh0, const void* lv, const void* rv, const void* ov, const int64_t* permutation, const void* betas,
+                           const void* gammas, uint32_t count, int on_device, void* z_out) try {
+    GA_ABI_ENTRY();
+    if (count == 0) return GA_OK;
+    Domain* d0 = reinterpret_cast<Domain*>(dh0);
+    if (!d0 || !lv || !rv || !ov || !permutation || !betas || !gammas || !z_out) {
+        set_error("ga_plonk_build_z_batch: null argument");
+        return GA_ERR_INVALID;
+    }
+    Ctx* c = ntt_domain_ctx(d0);
+    Lock l(c);
+    if (!on_device) {
+        const uint64_t n3 = 3 * ntt_domain_size(d0);
+        for (uint64_t i = 0; i < n3; i++)
+            if (permutation[i] < 0 || (uint64_t)permutation[i] >= n3) {
+                set_error("ga_plonk_build_z_batch: permutation[%llu] = %lld is outside [0, 3n)", (unsigned long long)i, (long long)permutation[i]);
+                return GA_ERR_INVALID;
+            }
+    }
+    const PlonkBatchKnobs knobs = env_plonk_batch_knobs();
+    GA_DISPATCH_CURVE(ntt_domain_curve(d0), GA_CHECK(plonk_domain_build_z_batch<C>(d0, lv, rv, ov, permutation, betas, gammas, count, knobs,
+                                                                                  on_device != 0, z_out)));
+    return GA_OK;
+} GA_ABI_CATCH
+
+int ga_plonk_quotient_pinned_batch(ga_plonk_pk* p, const ga_plonk_quotient_in* ins, uint32_t count, void* h_out) try {
+    GA_ABI_ENTRY();
+    if (count == 0) return GA_OK;
+    PlonkFixed* fx = reinterpret_cast<PlonkFixed*>(p);
+    if (!fx || !ins || !h_out) {
+        set_error("ga_plonk_quotient_pinned_batch: null argument");
+        return GA_ERR_INVALID;
+    }
+    Domain* d0 = plonk_fixed_domain0(fx);
+    Ctx* c = ntt_domain_ctx(d0);
+    Lock l(c);
+    std::vector<PlonkQuotientArgs> a(count);
+    for (uint32_t j = 0; j < count; j++) {
+        if (ins[j].nb_bsb != ins[0].nb_bsb || ins[j].lagrange_mask != ins[0].lagrange_mask || ins[j].flags != ins[0].flags) {
+            set_error("ga_plonk_quotient_pinned_batch: ins[%u] differs from ins[0] in nb_bsb, lagrange_mask or flags", j);
+            return GA_ERR_INVALID;
+        }
+        GA_CHECK(plonk_args_from(&ins[j], false, true, &a[j]));
+    }
+    const PlonkBatchKnobs knobs = env_plonk_batch_knobs();
+    GA_DISPATCH_CURVE(ntt_domain_curve(d0), GA_CHECK(plonk_domain_quotient_pinned_batch<C>(fx, a.data(), count, knobs, h_out)));
     return GA_OK;
 } GA_ABI_CATCH
 

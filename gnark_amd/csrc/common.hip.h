@@ -515,6 +515,55 @@ template <class C> int plonk_domain_build_z(Domain* d0, const void* L, const voi
 template <class C> int fr_vec_batch_inverse(Ctx* ctx, void* v, uint64_t n, bool on_device);
 template <class C> int fr_vec_lincomb(Ctx* ctx, uint64_t n, int k, const void* const* vecs, const void* scalars, void* out, bool on_device);
 template <class C> int kzg_domain_divide(Ctx* ctx, const void* d_poly, uint64_t n, const void* z_mont, void* d_quot, void* value_out);
+// The batched forms (plonk_batch.hip.h): `count` proofs of ONE circuit, at most knobs.batch_max (1 .. PLONK_BATCH_LIMIT) per device pass,
+// the proof in the grid's y dimension; a pass that does not fit the scratch is retried with fewer proofs.  Row j of every output is the
+// single call's result on item j.  args[j] differ in the per-proof pointers only (the entry point checked nb_bsb, mask and flags).
+constexpr uint32_t PLONK_BATCH_LIMIT = 16;   // = the most vectors of one batched table MSM (ga_msm_table_run_batch)
+struct PlonkBatchKnobs {          // as the entry point read them (abi.hip has the table)
+    uint32_t batch_max;           // GA_PLONK_BATCH_MAX
+    uint64_t scan_threads;        // GA_PLONK_SCAN_THREADS: threads a segmented scan aims at (plonk_scan_chunk)
+};
+// elements per thread of a segmented scan (a power of two, 8 .. 256) for `total` elements: about `threads` threads (2^13) where the
+// batch allows it -- 256 (the single call's PROD_CHUNK / SUM_CHUNK) leaves 64 threads for sixteen proofs of 2^10
+inline uint64_t plonk_scan_chunk(uint64_t total, uint64_t threads) {
+    uint64_t c = 8;
+    while (c < 256 && total / c > threads) c <<= 1;
+    return c;
+}
+// pass(first, cnt) over [0, count) in passes of at most batch_max proofs, after reserve(cnt) has obtained the scratch of a pass of cnt.
+// A reservation or a pass that fails with GA_ERR_NOMEM is retried with half as many proofs, down to one (a pass writes its outputs
+// last, so it can be run again); whatever sizes a buffer by the pass size is therefore decided in reserve, never in pass.
+template <class Reserve, class Pass>
+int plonk_batch_chunks(uint32_t count, uint32_t batch_max, Reserve reserve, Pass pass) {
+    uint32_t chunk = batch_max < 1 ? 1 : batch_max > PLONK_BATCH_LIMIT ? PLONK_BATCH_LIMIT : batch_max;
+    if (chunk > count) chunk = count;
+    bool reserved = false;
+    for (uint32_t first = 0; first < count;) {
+        const uint32_t cnt = count - first < chunk ? count - first : chunk;
+        int rc = reserved ? GA_OK : reserve(chunk);
+        reserved = rc == GA_OK;
+        if (rc == GA_OK) rc = pass(first, cnt);
+        if (rc == GA_OK) {
+            first += cnt;
+            continue;
+        }
+        if (rc != GA_ERR_NOMEM || chunk == 1) return rc;
+        chunk = (chunk + 1) / 2;
+        reserved = false;
+    }
+    return GA_OK;
+}
+template <class C> int plonk_domain_build_z_batch(Domain* d0, const void* L, const void* R, const void* O, const int64_t* perm, const void* betas,
+                                                  const void* gammas, uint32_t count, PlonkBatchKnobs knobs, bool on_device, void* z_out);
+template <class C> int plonk_domain_quotient_pinned_batch(PlonkFixed* fx, const PlonkQuotientArgs* args, uint32_t count, PlonkBatchKnobs knobs,
+                                                          void* h_out);
+// One pass of kzg.Open's division for count <= PLONK_BATCH_LIMIT polynomials of n coefficients (d_polys: host array of device pointers;
+// points: host): row j of d_quot (rows of quot_stride >= n elements, zeroed by the caller) receives the n - 1 quotient coefficients,
+// d_values[j] = p_j(points[j]).  Nothing is synchronised: the caller's MSM over d_quot follows on the same stream, and `stage` (the
+// host side of the one small upload) is the caller's, alive until that MSM has returned.
+template <class C> int kzg_domain_divide_batch(Ctx* ctx, const void* const* d_polys, uint64_t n, uint32_t count, const void* points,
+                                               void* d_quot, uint64_t quot_stride, void* d_values, uint64_t scan_threads,
+                                               std::vector<uint32_t>* stage);
 
 // ---- the point and Fr vector calls; explicitly instantiated in <call>_<curve>[_g<k>].hip.  Operands are host or device pointers per
 // the GA_*_ON_DEVICE flags; the trailing arguments are the run-time knobs as the entry point read them (abi.hip has the table)

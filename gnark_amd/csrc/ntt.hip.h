@@ -684,13 +684,14 @@ Fe<FrP> ntt_root_of_unity(int logn, bool inverse = false) {
 }
 
 // Host words of the two-level power table of `base` with first factor c0 that covers exponents below n: 2^NTT_POW_LO_BITS entries
-// lo[k] = c0 * base^k, then max(n >> NTT_POW_LO_BITS, 1) entries hi[k] = base^(k << NTT_POW_LO_BITS).  hat: entries in the hat
+// lo[k] = c0 * base^k, then ceil(n / 2^NTT_POW_LO_BITS) (at least one) entries hi[k] = base^(k << NTT_POW_LO_BITS).  hat: entries in the hat
 // domain (scale tables of the pass kernels: NttScale), else in plain Montgomery form (plonk_point)
 template <class FrP>
 std::vector<uint32_t> ntt_pow_table_host(const Fe<FrP>& base, const Fe<FrP>& c0, uint64_t n, bool hat) {
     typedef Fe<FrP> F;
     const uint64_t nlo = 1ull << NTT_POW_LO_BITS;
-    const uint64_t nhi = (n >> NTT_POW_LO_BITS) ? (n >> NTT_POW_LO_BITS) : 1;
+    // (n is not always a power of two: kzg_divide_by_linear's blinded polynomials have n + 2 or n + 3 coefficients)
+    const uint64_t nhi = n > nlo ? ((n - 1) >> NTT_POW_LO_BITS) + 1 : 1;
     std::vector<uint32_t> buf((nlo + nhi) * 8);
     F acc = c0;
     for (uint64_t k = 0; k < nlo; k++) {

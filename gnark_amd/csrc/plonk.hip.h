@@ -89,16 +89,32 @@ __global__ void fr_batch_inverse_kernel(uint32_t* __restrict__ v, uint32_t* __re
 
 // allConstraints of prove.go:950-981 at point j of the current coset, times 1/(X^n-1) on this coset (divideByZH,
 // prove.go:1311-1316), stored where the big inverse DIT expects evaluation rho*j + i: block*n + bitrev_n(j) (prove.go:1073).
+// (the expression itself is plonk_constraints_at: the batched kernel of plonk_batch.hip.h evaluates the same one with the proof in
+// the grid's y dimension.  proofs / stride: the ids of the bit set `proofs` are read `stride` words further on, 0 / 0 here.
+// Declared first and DEFINED AFTER the kernel, here and for the lazy variant: tests/test_lazy_bounds.py reads the subtraction
+// constants of the expression from the text that follows the kernel's signature, and the expression should stay where it finds it)
+template <class FrP>
+__device__ __forceinline__ void plonk_constraints_at(const PlonkPtrs& P, uint64_t proofs, uint64_t stride, const PlonkConsts& K,
+                                                     const uint32_t* __restrict__ x_lo, const uint32_t* __restrict__ x_hi, int lo_bits,
+                                                     const uint32_t* __restrict__ inv_xm1, uint32_t* __restrict__ out_block, uint64_t n, int logn,
+                                                     uint64_t j);
 template <class FrP>
 __global__ void __launch_bounds__(128)
 plonk_constraints_kernel(PlonkPtrs P, PlonkConsts K, const uint32_t* __restrict__ x_lo, const uint32_t* __restrict__ x_hi, int lo_bits,
                          const uint32_t* __restrict__ inv_xm1, uint32_t* __restrict__ out_block, uint64_t n, int logn) {
-    typedef Fe<FrP> F;
     uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n) return;
+    plonk_constraints_at<FrP>(P, 0, 0, K, x_lo, x_hi, lo_bits, inv_xm1, out_block, n, logn, j);
+}
+template <class FrP>
+__device__ __forceinline__ void plonk_constraints_at(const PlonkPtrs& P, uint64_t proofs, uint64_t stride, const PlonkConsts& K,
+                                                     const uint32_t* __restrict__ x_lo, const uint32_t* __restrict__ x_hi, int lo_bits,
+                                                     const uint32_t* __restrict__ inv_xm1, uint32_t* __restrict__ out_block, uint64_t n, int logn,
+                                                     uint64_t j) {
+    typedef Fe<FrP> F;
     // ~45 products per point against 14 x 32 B of loads: one shared out-of-line multiply keeps the kernel small
     auto mul = [](const F& u, const F& v) { return mul_val(u, v); };
-    auto at = [&](int id, uint64_t idx) { return load_fe<FrP>(P.p[id] + idx * 8); };
+    auto at = [&](int id, uint64_t idx) { return load_fe<FrP>(P.p[id] + ((proofs >> id) & 1 ? stride : 0) + idx * 8); };
     const F x = plonk_point<FrP>(x_lo, x_hi, lo_bits, j);
     const F xw = mul(x, plonk_c<FrP>(K.omega));   // next point of the coset: ZS is Z shifted by one (prove.go:602,972)
     const F beta = plonk_c<FrP>(K.beta), gamma = plonk_c<FrP>(K.gamma), alpha = plonk_c<FrP>(K.alpha);
@@ -154,16 +170,28 @@ __device__ __forceinline__ F29<FrP> plonk_shl5(const F29<FrP>& a) {   // 32 a fo
     r.l[NL - 1] = (a.l[NL - 1] << 5) | (a.l[NL - 2] >> (L - 5));
     return r;
 }
+template <class FrP>   // (the expression, after the kernel: shared with the batched kernel like plonk_constraints_at)
+__device__ __forceinline__ void plonk_constraints29_at(const PlonkPtrs& P, uint64_t proofs, uint64_t stride, const PlonkConsts& K,
+                                                       const uint32_t* __restrict__ x_lo, const uint32_t* __restrict__ x_hi, int lo_bits,
+                                                       const uint32_t* __restrict__ inv_xm1, uint32_t* __restrict__ out_block, uint64_t n, int logn,
+                                                       uint64_t j);
 template <class FrP>
 __global__ void __launch_bounds__(128)
 plonk_constraints29_kernel(PlonkPtrs P, PlonkConsts K, const uint32_t* __restrict__ x_lo, const uint32_t* __restrict__ x_hi, int lo_bits,
                            const uint32_t* __restrict__ inv_xm1, uint32_t* __restrict__ out_block, uint64_t n, int logn) {
+    uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    plonk_constraints29_at<FrP>(P, 0, 0, K, x_lo, x_hi, lo_bits, inv_xm1, out_block, n, logn, j);
+}
+template <class FrP>
+__device__ __forceinline__ void plonk_constraints29_at(const PlonkPtrs& P, uint64_t proofs, uint64_t stride, const PlonkConsts& K,
+                                                       const uint32_t* __restrict__ x_lo, const uint32_t* __restrict__ x_hi, int lo_bits,
+                                                       const uint32_t* __restrict__ inv_xm1, uint32_t* __restrict__ out_block, uint64_t n, int logn,
+                                                       uint64_t j) {
     static_assert(Radix<FrP>::NL * Radix<FrP>::L - 32 * FrP::N == 5 && Radix<FrP>::NL * Radix<FrP>::L - FrP::BITS >= 7,
                   "the shift-by-5 products and the bounds of tools/lazy_bounds.py need nine 29-bit limbs over a <= 254-bit modulus");
     typedef F29<FrP> E;
-    uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    auto at = [&](int id, uint64_t idx) { return f29_unpack(load_fe<FrP>(P.p[id] + idx * 8)); };   // canonical
+    auto at = [&](int id, uint64_t idx) { return f29_unpack(load_fe<FrP>(P.p[id] + ((proofs >> id) & 1 ? stride : 0) + idx * 8)); };   // canonical
     auto cst = [&](const uint32_t* w) { return f29_unpack(plonk_c<FrP>(w)); };                       // canonical
     auto mulc = [&](int sh_id, const E& v) { return f29_mul(cst(K.sh[sh_id]), v); };                 // constant x anything below 2^261
     auto mulv = [&](const E& small, const E& v) { return f29_mul(plonk_shl5<FrP>(small), v); };      // `small` below 2^256
@@ -333,6 +361,38 @@ void plonk_put(uint32_t* dst, const Fe<FrP>& v) {
     memcpy(dst, v.l, 32);
 }
 
+// The constants of the constraint kernels, in two steps shared by the single and the batched drivers (their outputs must agree bit
+// for bit): what depends on the coset alone -- cexp = coset^n - 1 (prove.go:999-1000) --, then a proof's challenges, its blinding
+// coefficients times cexp, and the images sh[] = 32 c mod r of the constants the lazy kernel multiplies by
+template <class FrP>
+void plonk_coset_consts(PlonkConsts& K, const Domain* d0, const Fe<FrP>& cexp) {
+    const Fe<FrP> g = fe_const<FrP>(FrP::GEN);
+    plonk_put(K.cs, g);   // prove.go:891-893
+    plonk_put(K.css, sqr(g));
+    memcpy(K.omega, d0->w, 32);
+    plonk_put(K.lone, mul(cexp, plonk_ld<FrP>(d0->ninv_mont)));
+    plonk_put(K.zh_inv, inv(cexp));
+}
+template <class FrP>
+void plonk_proof_consts(PlonkConsts& K, const PlonkQuotientArgs& A, const Fe<FrP>& cexp) {
+    typedef Fe<FrP> F;
+    plonk_put(K.alpha, plonk_ld<FrP>(A.alpha));
+    plonk_put(K.beta, plonk_ld<FrP>(A.beta));
+    plonk_put(K.gamma, plonk_ld<FrP>(A.gamma));
+    for (int k = 0; k < 2; k++) {
+        plonk_put(K.bl[k], mul(plonk_ld<FrP>(A.bl, k), cexp));
+        plonk_put(K.br[k], mul(plonk_ld<FrP>(A.br, k), cexp));
+        plonk_put(K.bo[k], mul(plonk_ld<FrP>(A.bo, k), cexp));
+    }
+    for (int k = 0; k < 3; k++) plonk_put(K.bz[k], mul(plonk_ld<FrP>(A.bz, k), cexp));
+    const uint32_t* src[11] = {K.omega, K.bl[1], K.br[1], K.bo[1], K.bz[2], K.beta, K.cs, K.css, K.lone, K.alpha, K.zh_inv};   // (index = PSH_*)
+    for (int q = 0; q < 11; q++) {   // 32 c mod r: five modular doublings each
+        F v = plonk_ld<FrP>(src[q]);
+        for (int k = 0; k < 5; k++) v = add(v, v);
+        plonk_put(K.sh[q], v);
+    }
+}
+
 // Circuit-constant part of the quotient, pinned in HBM (the "huge memory footprint" precomputation prove.go:1030-1034 decides
 // against on a CPU): the evaluations of Ql, Qr, Qm, Qo, S1, S2, S3 and every Qcp on each of the rho cosets, and 1/(x-1) on
 // each coset -- (7 + k + 1) * rho * n * 32 B, 4.3 GB at n = 2^22.  Per proof only L, R, O, Z, Qk and the BSB22 commitment
@@ -432,34 +492,14 @@ struct PlonkRun {
         const F g = fe_const<FrP>(FrP::GEN);
         coset = mul(coset, i == 0 ? g : plonk_ld<FrP>(d1->w));
         cexp = sub(plonk_host_pow<FrP>(coset, n), fe_one<FrP>());   // (coset^n - 1), prove.go:999-1000
-        plonk_put(K.cs, g);   // prove.go:891-893
-        plonk_put(K.css, sqr(g));
-        memcpy(K.omega, d0->w, 32);
-        plonk_put(K.lone, mul(cexp, plonk_ld<FrP>(d0->ninv_mont)));
-        plonk_put(K.zh_inv, inv(cexp));
+        plonk_coset_consts<FrP>(K, d0, cexp);
         GA_CHECK(ntt_coset_table<FrP>(d0, coset, &coset_tw));
         return plonk_pow_tables<FrP>(ctx, "plonk_x_tab", plonk_ld<FrP>(d0->w), coset, n, &x_lo, &x_hi);
     }
 
     // the proof's constants on the current coset, after begin_coset: the challenges, the blinding coefficients times (coset^n - 1),
     // and the images sh[] of the constants the lazy constraint kernel multiplies by
-    void proof_consts(const PlonkQuotientArgs& A) {
-        plonk_put(K.alpha, plonk_ld<FrP>(A.alpha));
-        plonk_put(K.beta, plonk_ld<FrP>(A.beta));
-        plonk_put(K.gamma, plonk_ld<FrP>(A.gamma));
-        for (int k = 0; k < 2; k++) {
-            plonk_put(K.bl[k], mul(plonk_ld<FrP>(A.bl, k), cexp));
-            plonk_put(K.br[k], mul(plonk_ld<FrP>(A.br, k), cexp));
-            plonk_put(K.bo[k], mul(plonk_ld<FrP>(A.bo, k), cexp));
-        }
-        for (int k = 0; k < 3; k++) plonk_put(K.bz[k], mul(plonk_ld<FrP>(A.bz, k), cexp));
-        const uint32_t* src[11] = {K.omega, K.bl[1], K.br[1], K.bo[1], K.bz[2], K.beta, K.cs, K.css, K.lone, K.alpha, K.zh_inv};   // (index = PSH_*)
-        for (int q = 0; q < 11; q++) {   // 32 c mod r: five modular doublings each
-            F v = plonk_ld<FrP>(src[q]);
-            for (int k = 0; k < 5; k++) v = add(v, v);
-            plonk_put(K.sh[q], v);
-        }
-    }
+    void proof_consts(const PlonkQuotientArgs& A) { plonk_proof_consts<FrP>(K, A, cexp); }
 
     // dst = evaluations of polynomial p on the current coset: one out-of-place forward DIT over the coset's twiddle table
     int eval_on_coset(int p, uint32_t* dst) {

@@ -449,6 +449,22 @@ class PrecomputedBases:
         self.ctx.lib.check(self.ctx.lib.ga_kzg_open(self.handle, pp, n, f, _ptr(z), _ptr(val), _ptr(out)))
         return val, out
 
+    def KzgOpenBatch(self, polys, points):
+        """kzg.Open for many polynomials of one length over this SRS in one call (ga_kzg_open_batch): polys is a sequence of
+        coefficient arrays (host) or a (count, n, 4) array, points (count, 4).  Returns (ClaimedValues (count, 4), H (count, jac_words));
+        item j is KzgOpen(polys[j], points[j])."""
+        ps = [as_u64(np.asarray(p).reshape(-1, 4), 4) for p in polys]
+        count = len(ps)
+        z = as_u64(np.asarray(points).reshape(-1, 4), 4)
+        if z.shape[0] != count or any(p.shape != ps[0].shape for p in ps):
+            raise ValueError("one point per polynomial, polynomials of equal length")
+        vals = np.zeros((count, 4), dtype=np.uint64)
+        out = np.zeros((count, jac_words(self.curve, self.group)), dtype=np.uint64)
+        if count:
+            arr = (C.c_void_p * count)(*[p.ctypes.data for p in ps])
+            self.ctx.lib.check(self.ctx.lib.ga_kzg_open_batch(self.handle, arr, ps[0].shape[0], count, 0, _ptr(z), _ptr(vals), _ptr(out)))
+        return vals, out
+
     def free(self):
         if self.handle:
             self.ctx.lib.ga_msm_table_destroy(self.handle)

@@ -91,6 +91,34 @@ class ProvingKey:
         lib.check(lib.ga_plonk_quotient_pinned(self.handle, C.byref(a), _ptr(out)))
         return out
 
+    def ComputeQuotientBatch(self, proofs, lagrange=()):
+        """s.h of many proofs of this circuit in one call (ga_plonk_quotient_pinned_batch).  proofs: a list of dicts
+        {polys, pi2, bp, alpha, beta, gamma} with the arguments of ComputeQuotient; `lagrange` holds for all of them.
+        Returns (count, rho*n, 4); block j is ComputeQuotient(**proofs[j], lagrange=lagrange)."""
+        lib = self.d0.ctx.lib
+        count, n = len(proofs), self.d0.Cardinality
+        keep = []
+        ins = (_lib.PlonkQuotientIn * max(count, 1))()
+        for a, pr in zip(ins, proofs):
+            pi2 = pr.get("pi2", ())
+            if len(pi2) != self.nb_bsb:
+                raise ValueError("one committed polynomial per Qcp")
+            a.nb_bsb = self.nb_bsb
+            _fill(a, PROOF_IDS, pr["polys"], lagrange, n, keep)
+            if pi2:
+                a.pi2 = _ptr_array(pi2, n, keep)
+            for k, cnt in (("Bl", 2), ("Br", 2), ("Bo", 2), ("Bz", 3)):
+                v = as_u64(np.asarray(pr["bp"][k]).reshape(cnt, 4), 4)
+                keep.append(v)
+                setattr(a, k.lower(), v.ctypes.data)
+            for k in ("alpha", "beta", "gamma"):
+                v = as_u64(np.asarray(pr[k]).reshape(1, 4), 4)
+                keep.append(v)
+                setattr(a, k, v.ctypes.data)
+        out = np.zeros((count, self.d1.Cardinality, 4), dtype=np.uint64)
+        lib.check(lib.ga_plonk_quotient_pinned_batch(self.handle, ins, count, _ptr(out)))
+        return out
+
     def close(self):
         if self.handle:
             self.d0.ctx.lib.ga_plonk_pk_destroy(self.handle)
@@ -148,6 +176,22 @@ def BuildRatioCopyConstraint(domain0: Domain, L, R, O, permutation, beta, gamma)
     b, g = as_u64(np.asarray(beta).reshape(1, 4), 4), as_u64(np.asarray(gamma).reshape(1, 4), 4)
     out = np.zeros((n, 4), dtype=np.uint64)
     lib.check(lib.ga_plonk_build_z(domain0.handle, _ptr(L), _ptr(R), _ptr(O), _ptr(perm), _ptr(b), _ptr(g), 0, _ptr(out)))
+    return out
+
+
+def BuildRatioCopyConstraintBatch(domain0: Domain, L, R, O, permutation, betas, gammas) -> np.ndarray:
+    """iop.BuildRatioCopyConstraint for many proofs of one circuit in one call (ga_plonk_build_z_batch): L, R, O of shape (count, n, 4),
+    betas, gammas (count, 4), one permutation.  Returns Z (count, n, 4); row j is BuildRatioCopyConstraint on item j."""
+    lib = domain0.ctx.lib
+    n = domain0.Cardinality
+    L, R, O = (as_u64(np.asarray(x).reshape(-1, n, 4)) for x in (L, R, O))
+    count = L.shape[0]
+    perm = np.ascontiguousarray(permutation, dtype=np.int64)
+    b, g = as_u64(np.asarray(betas).reshape(-1, 4), 4), as_u64(np.asarray(gammas).reshape(-1, 4), 4)
+    if perm.shape != (3 * n,) or R.shape != L.shape or O.shape != L.shape or b.shape[0] != count or g.shape[0] != count:
+        raise ValueError("L, R, O need (count, n) evaluations each, the permutation 3n entries, one beta and gamma per proof")
+    out = np.zeros((count, n, 4), dtype=np.uint64)
+    lib.check(lib.ga_plonk_build_z_batch(domain0.handle, _ptr(L), _ptr(R), _ptr(O), _ptr(perm), _ptr(b), _ptr(g), count, 0, _ptr(out)))
     return out
 
 

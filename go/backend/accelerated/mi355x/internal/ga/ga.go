@@ -619,6 +619,30 @@ func (t *Table) Open(poly unsafe.Pointer, n uint64, point, claimedOut, hOutJac u
 	})
 }
 
+// OpenBatch is kzg.Open for len(polys) polynomials of n coefficients each over the pinned SRS in one call (ga_kzg_open_batch):
+// points and claimedOut hold one fr element per polynomial, hOutJacs one Jacobian point.  The pointer array handed to C lives in C
+// memory for the duration of the call and every polynomial is pinned.
+func (t *Table) OpenBatch(polys []unsafe.Pointer, n uint64, points, claimedOut, hOutJacs unsafe.Pointer) error {
+	k := len(polys)
+	if k == 0 {
+		return nil
+	}
+	a := (*unsafe.Pointer)(C.malloc(C.size_t(k) * C.size_t(unsafe.Sizeof(uintptr(0)))))
+	defer C.free(unsafe.Pointer(a))
+	arr := unsafe.Slice(a, k)
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	for i, p := range polys {
+		if p != nil {
+			pin.Pin(p)
+		}
+		arr[i] = p
+	}
+	return call("ga_kzg_open_batch", func() C.int {
+		return C.ga_kzg_open_batch(t.h, a, C.size_t(n), C.uint32_t(k), C.uint(ScalarsMontgomery), points, claimedOut, hOutJacs)
+	})
+}
+
 // Free releases the table.
 func (t *Table) Free() {
 	if t != nil && t.h != nil {
@@ -686,6 +710,15 @@ func (d *Domain) BuildZ(l, r, o unsafe.Pointer, permutation []int64, beta, gamma
 	return call("ga_plonk_build_z", func() C.int { return C.ga_plonk_build_z(d.h, l, r, o, p, beta, gamma, 0, zOut) })
 }
 
+// BuildZBatch is iop.BuildRatioCopyConstraint for count proofs of one circuit in one call (ga_plonk_build_z_batch): l, r, o and zOut
+// hold count vectors of Cardinality fr elements each, contiguous; betas and gammas count fr elements; the permutation is shared.
+func (d *Domain) BuildZBatch(l, r, o unsafe.Pointer, permutation []int64, betas, gammas unsafe.Pointer, count int, zOut unsafe.Pointer) error {
+	p := (*C.int64_t)(unsafe.Pointer(unsafe.SliceData(permutation)))
+	return call("ga_plonk_build_z_batch", func() C.int {
+		return C.ga_plonk_build_z_batch(d.h, l, r, o, p, betas, gammas, C.uint32_t(count), 0, zOut)
+	})
+}
+
 // Free releases the domain.
 func (d *Domain) Free() {
 	if d != nil && d.h != nil {
@@ -706,6 +739,15 @@ type QuotientInput struct {
 
 func (in *QuotientInput) toC(p *runtime.Pinner) (*C.ga_plonk_quotient_in, func()) {
 	q := (*C.ga_plonk_quotient_in)(C.calloc(1, C.size_t(unsafe.Sizeof(C.ga_plonk_quotient_in{}))))
+	free := in.fillC(q, p)
+	return q, func() {
+		free()
+		C.free(unsafe.Pointer(q))
+	}
+}
+
+// fillC writes the input into a zeroed struct in C memory; the returned function frees the pointer arrays it allocated.
+func (in *QuotientInput) fillC(q *C.ga_plonk_quotient_in, p *runtime.Pinner) func() {
 	pin := func(x unsafe.Pointer) unsafe.Pointer {
 		if x != nil {
 			p.Pin(x)
@@ -734,11 +776,10 @@ func (in *QuotientInput) toC(p *runtime.Pinner) (*C.ga_plonk_quotient_in, func()
 	}
 	q.qcp = ptrArray(in.Qcp)
 	q.pi2 = ptrArray(in.Pi2)
-	return q, func() {
+	return func() {
 		for _, f := range frees {
 			C.free(f)
 		}
-		C.free(unsafe.Pointer(q))
 	}
 }
 
@@ -776,6 +817,27 @@ func (k *PlonkKey) Quotient(in *QuotientInput, hOut unsafe.Pointer) error {
 	q, free := in.toC(&p)
 	defer free()
 	return call("ga_plonk_quotient_pinned", func() C.int { return C.ga_plonk_quotient_pinned(k.h, q, hOut) })
+}
+
+// QuotientBatch computes the quotients of len(ins) proofs of this key's circuit in one call (ga_plonk_quotient_pinned_batch): every
+// input must carry the same LagrangeMask and as many Pi2 as the key has Qcp; hOut receives len(ins) blocks of rho*n fr elements.
+func (k *PlonkKey) QuotientBatch(ins []*QuotientInput, hOut unsafe.Pointer) error {
+	if len(ins) == 0 {
+		return nil
+	}
+	var p runtime.Pinner
+	defer p.Unpin()
+	size := unsafe.Sizeof(C.ga_plonk_quotient_in{})
+	arr := (*C.ga_plonk_quotient_in)(C.calloc(C.size_t(len(ins)), C.size_t(size)))
+	defer C.free(unsafe.Pointer(arr))
+	qs := unsafe.Slice(arr, len(ins))
+	for i, in := range ins {
+		free := in.fillC(&qs[i], &p)
+		defer free()
+	}
+	return call("ga_plonk_quotient_pinned_batch", func() C.int {
+		return C.ga_plonk_quotient_pinned_batch(k.h, arr, C.uint32_t(len(ins)), hOut)
+	})
 }
 
 // Free releases the pinned evaluations.

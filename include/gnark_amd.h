@@ -437,6 +437,47 @@ int ga_plonk_build_z(ga_domain* domain0, const void* l, const void* r, const voi
  * by the table MSM.  srs: ga_msm_table over pk.Kzg.G1 with at least len(p) - 1 points; poly: n fr coefficients (Montgomery; device
  * pointer with GA_SCALARS_ON_DEVICE); point, claimed_value_out: fr Montgomery; h_out: G1Jac. */
 int ga_kzg_open(ga_msm_table* srs, const void* poly, size_t n, unsigned flags, const void* point, void* claimed_value_out, void* h_out);
+
+/* ---- PLONK: the same three calls for MANY proofs of ONE circuit (one key, many witnesses) -------------------------------------
+ * A proof of 2^10 .. 2^16 gates cannot fill the device: each of the calls above is a chain of small launches with host-built
+ * tables and a closing synchronisation, paid once per proof by a service that proves per-transaction instances under one key.
+ * The batched forms take `count` proofs per call; the proof is the grid's y dimension of every kernel, the per-proof challenges
+ * and blinding terms come from a device array, the scans are segmented per proof and the power tables are built on the device.
+ * (Wire and quotient commitments of a batch already have ga_msm_table_run_batch, the transforms ga_fft_batch.)
+ * Measured on one MI355X, 16 proofs, operands on the device, against a loop of the single calls (profiles/plonk_batch.json): the three
+ * calls together take 0.13 ms per proof against 3.07 at 2^10 gates (BN254), 0.60 against 4.06 at 2^16; none is slower than its loop.
+ * Shared rules:
+ *   - count = 0 is GA_OK and touches nothing;
+ *   - GA_ERR_INVALID, with ga_last_error text, before anything is launched: a null pointer, structs that disagree, and whatever
+ *     the single call refuses;
+ *   - the proofs go through the device in passes of at most GA_PLONK_BATCH_MAX (environment, 1 .. 16, default 16: the limit of
+ *     ga_msm_table_run_batch); a pass that runs out of device memory, when it reserves its scratch or later, is run again with half
+ *     as many proofs (its outputs are written last), and GA_ERR_NOMEM comes back only when one proof does not fit; the context stays
+ *     usable after it.  One host synchronisation per pass -- an opening's is the one of its table MSM -- and one more per call where
+ *     a device-resident permutation is range-checked;
+ *   - GA_ERR_HIP for a failed launch or copy; no exception crosses the call (an allocation failure on the host is GA_ERR_NOMEM).
+ *
+ * ga_plonk_build_z_batch replaces a loop over proofs of iop.BuildRatioCopyConstraint (call site backend/plonk/bn254/prove.go:645-655).
+ * l, r, o = [count][n] evaluations on domain0 (regular order), contiguous; permutation: 3n int64, shared (s.trace.S); betas, gammas:
+ * count fr each (Montgomery, HOST memory always); z_out = [count][n].  on_device: l, r, o, permutation and z_out are device pointers.
+ * Row j is ga_plonk_build_z's result for (l[j], r[j], o[j], betas[j], gammas[j]), bit for bit.  A permutation entry outside [0, 3n)
+ * is GA_ERR_INVALID (checked on the host, or by a kernel for a device-resident permutation), as in the single call. */
+int ga_plonk_build_z_batch(ga_domain* domain0, const void* l, const void* r, const void* o, const int64_t* permutation,
+                           const void* betas, const void* gammas, uint32_t count, int on_device, void* z_out);
+/* ga_plonk_quotient_pinned_batch replaces a loop over proofs of computeNumerator + divideByZH (prove.go:841-1123,1287-1350).
+ * ins: count structs, each read as ga_plonk_quotient_pinned reads its `in`; all must carry the same nb_bsb (the key's), lagrange_mask
+ * and flags, else GA_ERR_INVALID.  h_out = [count][rho*n] (a device pointer with GA_PLONK_ON_DEVICE); block j is
+ * ga_plonk_quotient_pinned(pk, &ins[j]) bit for bit.  Per coset ONE coset transform covers the count * (5 + nb_bsb) per-proof
+ * polynomials, and ONE inverse transform of size rho*n covers the count quotients. */
+int ga_plonk_quotient_pinned_batch(ga_plonk_pk* pk, const ga_plonk_quotient_in* ins, uint32_t count, void* h_out);
+/* ga_kzg_open_batch replaces a loop over proofs of kzg.Open (call sites prove.go:681,788,827).  polys: count pointers to n fr
+ * coefficients each (all host, or all device with GA_SCALARS_ON_DEVICE); points: count fr (Montgomery, host); claimed_values_out:
+ * count fr (host); h_out: count G1Jac (host).  Item j is ga_kzg_open's result for (polys[j], points[j]): the claimed value bit for
+ * bit, H the same group element (a Jacobian representative, as everywhere).  The count quotients go through the batched table MSM
+ * in one pass.  GA_ERR_INVALID: a null entry of polys, n = 0, a table that is not G1 or holds fewer than n - 1 points, or count
+ * passes of the table's size beyond the 2^31 pair index space of ga_msm_table_run_batch. */
+int ga_kzg_open_batch(ga_msm_table* srs, const void* const* polys, size_t n, uint32_t count, unsigned flags, const void* points,
+                      void* claimed_values_out, void* h_out);
 /* out[i] = sum_{j<k} scalars[j] * vecs[j][i], k <= 16 per call: the polynomial folding of kzg.BatchOpenSinglePoint and the
  * linear combinations of innerComputeLinearizedPoly (backend/plonk/bn254/prove.go:1352-1460) in one pass.  scalars: k fr
  * (Montgomery, host); vecs/out: n fr each, all host or all device (on_device). */
