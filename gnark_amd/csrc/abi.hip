@@ -237,6 +237,8 @@ typedef CtxLock Lock;
 //                           larger value is taken as 2^20; tests force 2
 //   ga_plonk_build_z_batch, ga_plonk_quotient_pinned_batch, ga_kzg_open_batch
 //     GA_PLONK_BATCH_MAX    most proofs per device pass (1 .. 16, default 16 = the limit of the batched table MSM; tests force several passes)
+//   the same three, and the single calls that are their one-proof case: ga_plonk_build_z, ga_plonk_quotient_pinned, ga_kzg_open,
+//   ga_fr_poly_evaluate
 //     GA_PLONK_SCAN_THREADS threads a segmented scan aims at when it chooses its chunk of 8 .. 256 elements (default 2^13; 0 = default;
 //                           tests force small values so that sizes of a few hundred elements take every chunk width)
 static PlonkBatchKnobs env_plonk_batch_knobs() {
@@ -264,6 +266,16 @@ static bool abi_range_ok(size_t n, uint64_t first) {
     if ((uint64_t)n <= (1ull << 32) && (n == 0 || first <= UINT64_MAX - (uint64_t)n + 1)) return true;
     set_error("%s: n = %zu above 2^32, or first + n above 2^64", current_entry(), n);
     return false;
+}
+
+// a host-resident PLONK permutation: every entry in [0, 3n) (a device-resident one is checked by the driver, plonk_build_z)
+static bool abi_permutation_ok(const int64_t* permutation, uint64_t n3) {
+    for (uint64_t i = 0; i < n3; i++)
+        if (permutation[i] < 0 || (uint64_t)permutation[i] >= n3) {
+            set_error("%s: permutation[%llu] = %lld is outside [0, 3n)", current_entry(), (unsigned long long)i, (long long)permutation[i]);
+            return false;
+        }
+    return true;
 }
 
 // Bring inputs to the device when they are host pointers.
@@ -1022,7 +1034,8 @@ int ga_fr_poly_evaluate(ga_ctx* h, int curve, const void* poly, uint64_t n, cons
     GA_CHECK(sp.stage(poly, n * 32, on_device));
     void* q;
     GA_CHECK(c->scratch_get("kzg_quotient", n * 32, &q));
-    GA_DISPATCH_CURVE(curve, GA_CHECK(kzg_domain_divide<C>(c, sp.dev, n, point, q, value_out)));
+    const uint64_t scan_threads = env_plonk_batch_knobs().scan_threads;
+    GA_DISPATCH_CURVE(curve, GA_CHECK(kzg_domain_divide<C>(c, sp.dev, n, point, q, value_out, scan_threads)));
     return GA_OK;
 } GA_ABI_CATCH
 
@@ -1040,6 +1053,7 @@ int ga_kzg_open(ga_msm_table* th, const void* poly, size_t n, unsigned flags, co
     }
     Ctx* c = t->ctx;
     Lock l(c);
+    const uint64_t scan_threads = env_plonk_batch_knobs().scan_threads;
     GA_DISPATCH_CURVE(t->curve, {
         typedef typename GroupField<C, GA_G1>::F F;
         Staged sp{c};
@@ -1048,7 +1062,7 @@ int ga_kzg_open(ga_msm_table* th, const void* poly, size_t n, unsigned flags, co
         void* q;
         GA_CHECK(c->scratch_get("kzg_quotient", qn * 32, &q));
         GA_HIP_CHECK(hipMemsetAsync(q, 0, qn * 32, c->stream));
-        GA_CHECK(kzg_domain_divide<C>(c, sp.dev, n, point, q, claimed_value_out));
+        GA_CHECK(kzg_domain_divide<C>(c, sp.dev, n, point, q, claimed_value_out, scan_threads));
         XYZZ<F> sum;
         GA_CHECK((msm_table_device<C, GA_G1>(c, t->d_table, q, t->n, true, t->c, &sum)));
         host_store_jac<F>(h_out, sum);
@@ -1315,7 +1329,8 @@ int ga_plonk_quotient_pinned(ga_plonk_pk* p, const ga_plonk_quotient_in* in, voi
     Lock l(c);
     PlonkQuotientArgs a;
     GA_CHECK(plonk_args_from(in, false, true, &a));
-    GA_DISPATCH_CURVE(ntt_domain_curve(d0), GA_CHECK(plonk_domain_quotient_pinned<C>(fx, a, h_out)));
+    const uint64_t scan_threads = env_plonk_batch_knobs().scan_threads;
+    GA_DISPATCH_CURVE(ntt_domain_curve(d0), GA_CHECK(plonk_domain_quotient_pinned<C>(fx, a, scan_threads, h_out)));
     return GA_OK;
 } GA_ABI_CATCH
 
@@ -1329,15 +1344,10 @@ int ga_plonk_build_z(ga_domain* dh0, const void* lv, const void* rv, const void*
     }
     Ctx* c = ntt_domain_ctx(d0);
     Lock l(c);
-    if (!on_device) {
-        const uint64_t n3 = 3 * ntt_domain_size(d0);
-        for (uint64_t i = 0; i < n3; i++)
-            if (permutation[i] < 0 || (uint64_t)permutation[i] >= n3) {
-                set_error("ga_plonk_build_z: permutation[%llu] = %lld is outside [0, 3n)", (unsigned long long)i, (long long)permutation[i]);
-                return GA_ERR_INVALID;
-            }
-    }
-    GA_DISPATCH_CURVE(ntt_domain_curve(d0), GA_CHECK(plonk_domain_build_z<C>(d0, lv, rv, ov, permutation, beta, gamma, on_device != 0, z_out)));
+    if (!on_device && !abi_permutation_ok(permutation, 3 * ntt_domain_size(d0))) return GA_ERR_INVALID;
+    const uint64_t scan_threads = env_plonk_batch_knobs().scan_threads;
+    GA_DISPATCH_CURVE(ntt_domain_curve(d0),
+                      GA_CHECK(plonk_domain_build_z<C>(d0, lv, rv, ov, permutation, beta, gamma, scan_threads, on_device != 0, z_out)));
     return GA_OK;
 } GA_ABI_CATCH
 
@@ -1352,14 +1362,7 @@ int ga_plonk_build_z_batch(ga_domain* dh0, const void* lv, const void* rv, const
     }
     Ctx* c = ntt_domain_ctx(d0);
     Lock l(c);
-    if (!on_device) {
-        const uint64_t n3 = 3 * ntt_domain_size(d0);
-        for (uint64_t i = 0; i < n3; i++)
-            if (permutation[i] < 0 || (uint64_t)permutation[i] >= n3) {
-                set_error("ga_plonk_build_z_batch: permutation[%llu] = %lld is outside [0, 3n)", (unsigned long long)i, (long long)permutation[i]);
-                return GA_ERR_INVALID;
-            }
-    }
+    if (!on_device && !abi_permutation_ok(permutation, 3 * ntt_domain_size(d0))) return GA_ERR_INVALID;
     const PlonkBatchKnobs knobs = env_plonk_batch_knobs();
     GA_DISPATCH_CURVE(ntt_domain_curve(d0), GA_CHECK(plonk_domain_build_z_batch<C>(d0, lv, rv, ov, permutation, betas, gammas, count, knobs,
                                                                                   on_device != 0, z_out)));

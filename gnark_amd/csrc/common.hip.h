@@ -507,24 +507,21 @@ struct PlonkQuotientArgs {
 struct PlonkFixed;   // plonk.hip.h: the circuit-constant coset evaluations pinned in HBM
 template <class C> int plonk_domain_quotient(Domain* d0, Domain* d1, const PlonkQuotientArgs& args, void* h_out);
 template <class C> int plonk_domain_fixed_create(Domain* d0, Domain* d1, const PlonkQuotientArgs& args, PlonkFixed** out);
-template <class C> int plonk_domain_quotient_pinned(PlonkFixed* fx, const PlonkQuotientArgs& args, void* h_out);
 void plonk_fixed_delete(PlonkFixed* fx);
 Domain* plonk_fixed_domain0(PlonkFixed* fx);
-template <class C> int plonk_domain_build_z(Domain* d0, const void* L, const void* R, const void* O, const int64_t* perm, const void* beta,
-                                            const void* gamma, bool on_device, void* z_out);
 template <class C> int fr_vec_batch_inverse(Ctx* ctx, void* v, uint64_t n, bool on_device);
 template <class C> int fr_vec_lincomb(Ctx* ctx, uint64_t n, int k, const void* const* vecs, const void* scalars, void* out, bool on_device);
-template <class C> int kzg_domain_divide(Ctx* ctx, const void* d_poly, uint64_t n, const void* z_mont, void* d_quot, void* value_out);
-// The batched forms (plonk_batch.hip.h): `count` proofs of ONE circuit, at most knobs.batch_max (1 .. PLONK_BATCH_LIMIT) per device pass,
-// the proof in the grid's y dimension; a pass that does not fit the scratch is retried with fewer proofs.  Row j of every output is the
-// single call's result on item j.  args[j] differ in the per-proof pointers only (the entry point checked nb_bsb, mask and flags).
+// The grand product, the quotient over a pinned key and kzg.Open's division (plonk_batch.hip.h): `count` proofs of ONE circuit, at most
+// knobs.batch_max (1 .. PLONK_BATCH_LIMIT) per device pass, the proof in the grid's y dimension; a pass that does not fit the scratch is
+// retried with fewer proofs.  Row j of every output depends on item j alone; the single calls below are count = 1.  args[j] differ in
+// the per-proof pointers only (the entry point checked nb_bsb, mask and flags).
 constexpr uint32_t PLONK_BATCH_LIMIT = 16;   // = the most vectors of one batched table MSM (ga_msm_table_run_batch)
 struct PlonkBatchKnobs {          // as the entry point read them (abi.hip has the table)
     uint32_t batch_max;           // GA_PLONK_BATCH_MAX
     uint64_t scan_threads;        // GA_PLONK_SCAN_THREADS: threads a segmented scan aims at (plonk_scan_chunk)
 };
 // elements per thread of a segmented scan (a power of two, 8 .. 256) for `total` elements: about `threads` threads (2^13) where the
-// batch allows it -- 256 (the single call's PROD_CHUNK / SUM_CHUNK) leaves 64 threads for sixteen proofs of 2^10
+// batch allows it -- 256 throughout would leave 64 threads for sixteen proofs of 2^10
 inline uint64_t plonk_scan_chunk(uint64_t total, uint64_t threads) {
     uint64_t c = 8;
     while (c < 256 && total / c > threads) c <<= 1;
@@ -564,6 +561,41 @@ template <class C> int plonk_domain_quotient_pinned_batch(PlonkFixed* fx, const 
 template <class C> int kzg_domain_divide_batch(Ctx* ctx, const void* const* d_polys, uint64_t n, uint32_t count, const void* points,
                                                void* d_quot, uint64_t quot_stride, void* d_values, uint64_t scan_threads,
                                                std::vector<uint32_t>* stage);
+// One proof: the calls above with count = 1 (scan_threads as the entry point read it, like knobs.scan_threads).
+template <class C>
+int plonk_domain_build_z(Domain* d0, const void* L, const void* R, const void* O, const int64_t* perm, const void* beta, const void* gamma,
+                         uint64_t scan_threads, bool on_device, void* z_out) {
+    return plonk_domain_build_z_batch<C>(d0, L, R, O, perm, beta, gamma, 1, PlonkBatchKnobs{1, scan_threads}, on_device, z_out);
+}
+template <class C>
+int plonk_domain_quotient_pinned(PlonkFixed* fx, const PlonkQuotientArgs& args, uint64_t scan_threads, void* h_out) {
+    return plonk_domain_quotient_pinned_batch<C>(fx, &args, 1, PlonkBatchKnobs{1, scan_threads}, h_out);
+}
+// d_quot (device, n elements: n - 1 quotient coefficients then a zero) and *value_out (host, Montgomery) = p(z) from d_poly (device, n
+// coefficients); n = 0 is the zero polynomial: the value 0 and no quotient.  Synchronises.
+template <class C>
+int kzg_domain_divide(Ctx* ctx, const void* d_poly, uint64_t n, const void* z_mont, void* d_quot, void* value_out, uint64_t scan_threads) {
+    if (n == 0) {
+        memset(value_out, 0, 32);
+        return GA_OK;
+    }
+    std::vector<uint32_t> stage;   // read by an upload that the synchronisation below completes
+    auto run = [&]() -> int {
+        void* d_value;
+        GA_CHECK(ctx->scratch_get("kzg_b_values", 32, &d_value));
+        GA_HIP_CHECK(hipMemsetAsync((char*)d_quot + (n - 1) * 32, 0, 32, ctx->stream));
+        GA_CHECK(kzg_domain_divide_batch<C>(ctx, &d_poly, n, 1, z_mont, d_quot, n, d_value, scan_threads, &stage));
+        GA_HIP_CHECK(hipMemcpyAsync(value_out, d_value, 32, hipMemcpyDeviceToHost, ctx->stream));
+        return GA_OK;
+    };
+    const int rc = run();
+    if (rc != GA_OK) {
+        hipStreamSynchronize(ctx->stream);
+        return rc;
+    }
+    GA_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return GA_OK;
+}
 
 // ---- the point and Fr vector calls; explicitly instantiated in <call>_<curve>[_g<k>].hip.  Operands are host or device pointers per
 // the GA_*_ON_DEVICE flags; the trailing arguments are the run-time knobs as the entry point read them (abi.hip has the table)

@@ -10,6 +10,11 @@
 // at its bit-reversed slot, and the final inverse coset transform of size rho*n produces h in canonical order.
 // 1/(x-1) for L1 comes from a batched Montgomery-trick inversion kernel (the reference's batchInvert, prove.go:1134-1147).
 // Field elements are mathematically unique, so the coefficients equal the reference's bit for bit.
+//
+// The grand product, the quotient over a pinned key and the division of kzg.Open have ONE implementation each, for `count` proofs of
+// one circuit per device pass (the drivers of plonk_batch.hip.h; a single proof is count = 1).  The kernels below therefore carry the
+// proof in the grid's y dimension (or as a segment of a flat index), read a proof's challenges from a device array, and every power
+// table is built on the device.  Every stored field element is fully reduced, so a result does not depend on how a scan associates.
 #pragma once
 #include "ntt.hip.h"
 #include <algorithm>
@@ -32,7 +37,7 @@ struct PlonkConsts {
     uint32_t lone[8];      // (coset^n - 1) / n
     uint32_t omega[8];     // generator of the small domain
     uint32_t zh_inv[8];    // 1 / (coset^n - 1): divideByZH's factor for this coset (prove.go:1327-1350)
-    // 32 * c mod r of the constants that the lazy constraint kernel multiplies by (plonk_constraints29_kernel): a product of limb
+    // 32 * c mod r of the constants that the lazy constraint kernel multiplies by (plonk_constraints29_at): a product of limb
     // vectors divides by 2^261 where the memory format wants 2^256, so one factor carries the 2^5
     uint32_t sh[11][8];
 };
@@ -52,6 +57,58 @@ __device__ __forceinline__ Fe<FrP> plonk_point(const uint32_t* lo, const uint32_
     Fe<FrP> a = load_fe<FrP>(lo + (j & ((1ull << lo_bits) - 1)) * 8);
     uint64_t h = j >> lo_bits;
     return h ? mul(a, load_fe<FrP>(hi + h * 8)) : a;
+}
+
+// ---- power tables on the device ------------------------------------------------------------------------------------------------
+// Table t (grid row y) of `bases` = (base_t, c0_t): the two-level table plonk_point reads, lo[k] = c0 * base^k for k < 2^lo_bits and
+// hi[k] = base^(k << lo_bits) for k < nhi, (2^lo_bits + nhi) elements per table (the layout of ntt_pow_table_host).  One thread per
+// entry, square-and-multiply on the entry's exponent: at most 2 * 64 products, no dependence between threads.
+template <class FrP>
+__global__ void fr_pow_tables_kernel(const uint32_t* __restrict__ bases, uint32_t* __restrict__ tabs, int lo_bits, uint64_t nhi) {
+    const uint64_t nlo = 1ull << lo_bits;
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nlo + nhi) return;
+    const uint32_t* b = bases + (size_t)blockIdx.y * 16;
+    Fe<FrP> a = load_fe<FrP>(b);
+    const bool low = k < nlo;
+    uint64_t e = low ? k : (k - nlo) << lo_bits;
+    Fe<FrP> r = low ? load_fe<FrP>(b + 8) : fe_one<FrP>();
+    while (e) {
+        if (e & 1) r = mul_val(r, a);
+        a = mul_val(a, a);
+        e >>= 1;
+    }
+    store_fe(tabs + ((size_t)blockIdx.y * (nlo + nhi) + k) * 8, r);
+}
+
+// `ntab` tables that cover exponents below n, from host pairs (base, c0), into scratch `key` (pairs first, then the tables): one small
+// upload from `stage` -- which the caller keeps alive until its synchronisation -- and one launch.
+template <class FrP>
+struct PowTables {
+    uint32_t *bases = nullptr, *tabs = nullptr;   // [ntab] (base, c0), [ntab] tables
+    uint64_t words = 0;                           // per table
+    uint32_t* lo(uint64_t t) const { return tabs + t * words; }
+    uint32_t* hi(uint64_t t) const { return tabs + t * words + ((size_t)8 << NTT_POW_LO_BITS); }
+    static uint64_t nhi_of(uint64_t n) { return n ? ((n - 1) >> NTT_POW_LO_BITS) + 1 : 1; }
+    static size_t bytes(uint64_t ntab, uint64_t n) { return (size_t)ntab * (64 + (((size_t)1 << NTT_POW_LO_BITS) + nhi_of(n)) * 32); }
+    int build(Ctx* ctx, const char* key, const std::vector<uint32_t>& stage, uint64_t ntab, uint64_t n) {
+        const uint64_t nhi = nhi_of(n), per = (1ull << NTT_POW_LO_BITS) + nhi;
+        uint32_t* d;
+        GA_CHECK(ctx->scratch_get(key, bytes(ntab, n), (void**)&d));
+        GA_HIP_CHECK(hipMemcpyAsync(d, stage.data(), ntab * 64, hipMemcpyHostToDevice, ctx->stream));
+        bases = d;
+        tabs = d + ntab * 16;
+        words = per * 8;
+        hipLaunchKernelGGL((fr_pow_tables_kernel<FrP>), dim3((unsigned)((per + 255) / 256), (unsigned)ntab), dim3(256), 0, ctx->stream, d, tabs,
+                           NTT_POW_LO_BITS, nhi);
+        GA_KERNEL_CHECK();
+        return GA_OK;
+    }
+};
+template <class FrP>
+void pow_pair(std::vector<uint32_t>& stage, const Fe<FrP>& base, const Fe<FrP>& c0) {
+    stage.insert(stage.end(), base.l, base.l + 8);
+    stage.insert(stage.end(), c0.l, c0.l + 8);
 }
 
 template <class FrP>
@@ -87,25 +144,17 @@ __global__ void fr_batch_inverse_kernel(uint32_t* __restrict__ v, uint32_t* __re
     }
 }
 
+// threads of fr_batch_inverse_kernel over `total` elements, for every caller: each pays one field inversion (~ 400 products) beside
+// three products per element, so 16 .. 64 elements per thread; 64 throughout would leave sixteen proofs of 2^10 on 256 threads
+inline uint64_t plonk_inverse_threads(uint64_t total) {
+    const uint64_t per = total >= (1ull << 20) ? 64 : total >= (1ull << 17) ? 32 : 16;
+    return (total + per - 1) / per;
+}
+
 // allConstraints of prove.go:950-981 at point j of the current coset, times 1/(X^n-1) on this coset (divideByZH,
 // prove.go:1311-1316), stored where the big inverse DIT expects evaluation rho*j + i: block*n + bitrev_n(j) (prove.go:1073).
-// (the expression itself is plonk_constraints_at: the batched kernel of plonk_batch.hip.h evaluates the same one with the proof in
-// the grid's y dimension.  proofs / stride: the ids of the bit set `proofs` are read `stride` words further on, 0 / 0 here.
-// Declared first and DEFINED AFTER the kernel, here and for the lazy variant: tests/test_lazy_bounds.py reads the subtraction
-// constants of the expression from the text that follows the kernel's signature, and the expression should stay where it finds it)
-template <class FrP>
-__device__ __forceinline__ void plonk_constraints_at(const PlonkPtrs& P, uint64_t proofs, uint64_t stride, const PlonkConsts& K,
-                                                     const uint32_t* __restrict__ x_lo, const uint32_t* __restrict__ x_hi, int lo_bits,
-                                                     const uint32_t* __restrict__ inv_xm1, uint32_t* __restrict__ out_block, uint64_t n, int logn,
-                                                     uint64_t j);
-template <class FrP>
-__global__ void __launch_bounds__(128)
-plonk_constraints_kernel(PlonkPtrs P, PlonkConsts K, const uint32_t* __restrict__ x_lo, const uint32_t* __restrict__ x_hi, int lo_bits,
-                         const uint32_t* __restrict__ inv_xm1, uint32_t* __restrict__ out_block, uint64_t n, int logn) {
-    uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    plonk_constraints_at<FrP>(P, 0, 0, K, x_lo, x_hi, lo_bits, inv_xm1, out_block, n, logn, j);
-}
+// proofs / stride: the polynomials whose id is in the bit set `proofs` are read `stride` words further on (a proof's own polynomials,
+// plonk_constraints_kernel below).
 template <class FrP>
 __device__ __forceinline__ void plonk_constraints_at(const PlonkPtrs& P, uint64_t proofs, uint64_t stride, const PlonkConsts& K,
                                                      const uint32_t* __restrict__ x_lo, const uint32_t* __restrict__ x_hi, int lo_bits,
@@ -170,19 +219,6 @@ __device__ __forceinline__ F29<FrP> plonk_shl5(const F29<FrP>& a) {   // 32 a fo
     r.l[NL - 1] = (a.l[NL - 1] << 5) | (a.l[NL - 2] >> (L - 5));
     return r;
 }
-template <class FrP>   // (the expression, after the kernel: shared with the batched kernel like plonk_constraints_at)
-__device__ __forceinline__ void plonk_constraints29_at(const PlonkPtrs& P, uint64_t proofs, uint64_t stride, const PlonkConsts& K,
-                                                       const uint32_t* __restrict__ x_lo, const uint32_t* __restrict__ x_hi, int lo_bits,
-                                                       const uint32_t* __restrict__ inv_xm1, uint32_t* __restrict__ out_block, uint64_t n, int logn,
-                                                       uint64_t j);
-template <class FrP>
-__global__ void __launch_bounds__(128)
-plonk_constraints29_kernel(PlonkPtrs P, PlonkConsts K, const uint32_t* __restrict__ x_lo, const uint32_t* __restrict__ x_hi, int lo_bits,
-                           const uint32_t* __restrict__ inv_xm1, uint32_t* __restrict__ out_block, uint64_t n, int logn) {
-    uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    plonk_constraints29_at<FrP>(P, 0, 0, K, x_lo, x_hi, lo_bits, inv_xm1, out_block, n, logn, j);
-}
 template <class FrP>
 __device__ __forceinline__ void plonk_constraints29_at(const PlonkPtrs& P, uint64_t proofs, uint64_t stride, const PlonkConsts& K,
                                                        const uint32_t* __restrict__ x_lo, const uint32_t* __restrict__ x_hi, int lo_bits,
@@ -231,27 +267,57 @@ __device__ __forceinline__ void plonk_constraints29_at(const PlonkPtrs& P, uint6
     store_fe(out_block + bitrev64(j, logn) * 8, f29_pack_canonical(f29_reduce_3p(res)));
 }
 
-// out[bitrev(i)] = in[i]
+// The constraint launch, with the proof in blockIdx.y: proof j reads its constants from K[j], its own polynomials (the ids of
+// B.proofs) `stride` words after proof 0's, and writes its block of its own h, out_stride words after proof 0's; whatever else it
+// reads (pinned evaluations, 1/(x - 1), the coset's points) is shared.  LAZY: the expression on unreduced limbs, BN254; BLS12-381's
+// 255-bit Fr leaves 6 spare bits and stays packed.
+template <class FrP>
+constexpr bool PLONK_LAZY = Radix<FrP>::NL * Radix<FrP>::L - FrP::BITS >= 7;
+struct PlonkBatchPtrs {
+    PlonkPtrs P;       // proof 0
+    uint64_t proofs;   // bit id: a per-proof polynomial
+    uint64_t stride;   // words from a proof's polynomial to the next proof's
+};
+template <class FrP, bool LAZY>
+__global__ void __launch_bounds__(128)
+plonk_constraints_kernel(PlonkBatchPtrs B, const PlonkConsts* __restrict__ K, const uint32_t* __restrict__ x_lo,
+                         const uint32_t* __restrict__ x_hi, int lo_bits, const uint32_t* __restrict__ inv_xm1,
+                         uint32_t* __restrict__ out, uint64_t out_stride, uint64_t n, int logn) {
+    uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const uint64_t proof = blockIdx.y;
+    if constexpr (LAZY)
+        plonk_constraints29_at<FrP>(B.P, B.proofs, proof * B.stride, K[proof], x_lo, x_hi, lo_bits, inv_xm1, out + proof * out_stride, n, logn, j);
+    else
+        plonk_constraints_at<FrP>(B.P, B.proofs, proof * B.stride, K[proof], x_lo, x_hi, lo_bits, inv_xm1, out + proof * out_stride, n, logn, j);
+}
+
+// out[v][bitrev(i)] = in[v][i] for the vectors v = blockIdx.y
 template <class FrP>
 __global__ void fr_bitrev_copy_kernel(uint32_t* __restrict__ out, const uint32_t* __restrict__ in, uint64_t n, int logn) {
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    store_fe(out + bitrev64(i, logn) * 8, load_fe<FrP>(in + i * 8));
+    const size_t row = (size_t)blockIdx.y * n * 8;
+    store_fe(out + row + bitrev64(i, logn) * 8, load_fe<FrP>(in + row + i * 8));
 }
 
 // ---- grand product (iop.BuildRatioCopyConstraint) --------------------------------------------------------------------
 // ratio[i] = prod_k (e_k[i] + beta*id_k(i) + gamma) and its denominator prod_k (e_k[i] + beta*id(perm[k*n+i]) + gamma)
+// for the proof blockIdx.y: L, R, O, num, den are [count][n]; bg[proof] = (beta, gamma); the identity tables, the coset shifts and
+// the permutation are the circuit's
 template <class FrP>
 __global__ void plonk_ratio_terms_kernel(const uint32_t* __restrict__ L, const uint32_t* __restrict__ R, const uint32_t* __restrict__ O,
                                          const int64_t* __restrict__ perm, const uint32_t* __restrict__ w_lo,
-                                         const uint32_t* __restrict__ w_hi, int lo_bits, PlonkConsts K, uint32_t* __restrict__ num,
-                                         uint32_t* __restrict__ den, uint64_t n) {
+                                         const uint32_t* __restrict__ w_hi, int lo_bits, const uint32_t* __restrict__ bg,
+                                         const uint32_t* __restrict__ shifts, uint32_t* __restrict__ num, uint32_t* __restrict__ den,
+                                         uint64_t n) {
     typedef Fe<FrP> F;
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const F beta = plonk_c<FrP>(K.beta), gamma = plonk_c<FrP>(K.gamma);
-    const F shift[3] = {fe_one<FrP>(), plonk_c<FrP>(K.cs), plonk_c<FrP>(K.css)};
-    const uint32_t* e[3] = {L, R, O};
+    const size_t row = (size_t)blockIdx.y * n * 8;
+    const F beta = load_fe<FrP>(bg + (size_t)blockIdx.y * 16), gamma = load_fe<FrP>(bg + (size_t)blockIdx.y * 16 + 8);
+    const F shift[3] = {fe_one<FrP>(), load_fe<FrP>(shifts), load_fe<FrP>(shifts + 8)};
+    const uint32_t* e[3] = {L + row, R + row, O + row};
     auto idv = [&](uint64_t pos) {   // evaluation of the identity permutation at flat position pos: u^(pos / n) * w^(pos % n)
         uint64_t k = pos / n, j = pos % n;
         F w = plonk_point<FrP>(w_lo, w_hi, lo_bits, j);
@@ -263,35 +329,36 @@ __global__ void plonk_ratio_terms_kernel(const uint32_t* __restrict__ L, const u
         a = mul(a, add(v, mul(beta, idv((uint64_t)k * n + i))));
         b = mul(b, add(v, mul(beta, idv((uint64_t)perm[(uint64_t)k * n + i]))));
     }
-    store_fe(num + i * 8, a);
-    store_fe(den + i * 8, b);
+    store_fe(num + row + i * 8, a);
+    store_fe(den + row + i * 8, b);
 }
 
-// exclusive prefix product over n elements, three phases: per-chunk products, scan of the chunk products (one block),
-// per-chunk rescan with the carried-in prefix.  z[0] = 1, z[i] = prod_{t<i} r[t].
-constexpr int PROD_CHUNK = 256;
+// Segmented exclusive prefix product, z[p][0] = 1, z[p][i] = prod_{t<i} num[p][t] * den_inv[p][t], in three phases -- per-chunk
+// products, a scan of the chunk products, a per-chunk rescan with the carried-in prefix -- with the segment = the proof: `chunk`
+// divides n (both powers of two, chunk <= n), so a chunk never spans two proofs and a proof has cpp = n / chunk chunk products,
+// scanned by one block per proof (blockIdx.y).
 template <class FrP>
 __global__ void fr_chunk_product_kernel(const uint32_t* __restrict__ num, const uint32_t* __restrict__ den_inv,
-                                        uint32_t* __restrict__ chunk_prod, uint64_t n) {
-    uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t lo = c * PROD_CHUNK;
-    if (lo >= n) return;
-    uint64_t hi = lo + PROD_CHUNK < n ? lo + PROD_CHUNK : n;
+                                        uint32_t* __restrict__ chunk_prod, uint64_t total, uint64_t chunk) {
+    const uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t lo = c * chunk;
+    if (lo >= total) return;
     Fe<FrP> acc = fe_one<FrP>();
-    for (uint64_t i = lo; i < hi; i++) acc = mul(acc, mul(load_fe<FrP>(num + i * 8), load_fe<FrP>(den_inv + i * 8)));
+    for (uint64_t i = lo; i < lo + chunk; i++) acc = mul(acc, mul(load_fe<FrP>(num + i * 8), load_fe<FrP>(den_inv + i * 8)));
     store_fe(chunk_prod + c * 8, acc);
 }
 template <class FrP>
-__global__ void __launch_bounds__(256) fr_chunk_scan_kernel(uint32_t* __restrict__ chunk_prod, uint64_t nchunks) {
-    // one block: each thread multiplies a contiguous segment of chunk products, the 256 segment products are scanned in LDS
-    // (Hillis-Steele, 8 steps), then every thread rewrites its segment as exclusive prefixes
+__global__ void __launch_bounds__(256) fr_chunk_scan_kernel(uint32_t* __restrict__ chunk_prod, uint64_t cpp) {
+    // the cpp chunk products of proof blockIdx.y: each thread multiplies a contiguous segment of them, the 256 segment products are
+    // scanned in LDS (Hillis-Steele, 8 steps), then every thread rewrites its segment as exclusive prefixes
     __shared__ uint32_t sh[256 * 8];
+    uint32_t* cp = chunk_prod + (size_t)blockIdx.y * cpp * 8;
     const uint32_t tid = threadIdx.x;
-    const uint64_t seg = (nchunks + 255) / 256;
-    const uint64_t lo = (uint64_t)tid * seg < nchunks ? (uint64_t)tid * seg : nchunks;
-    const uint64_t hi = lo + seg < nchunks ? lo + seg : nchunks;
+    const uint64_t seg = (cpp + 255) / 256;
+    const uint64_t lo = (uint64_t)tid * seg < cpp ? (uint64_t)tid * seg : cpp;
+    const uint64_t hi = lo + seg < cpp ? lo + seg : cpp;
     Fe<FrP> acc = fe_one<FrP>();
-    for (uint64_t c = lo; c < hi; c++) acc = mul_val(acc, load_fe<FrP>(chunk_prod + c * 8));
+    for (uint64_t c = lo; c < hi; c++) acc = mul_val(acc, load_fe<FrP>(cp + c * 8));
     store_fe(sh + tid * 8, acc);
     __syncthreads();
     for (uint32_t off = 1; off < 256; off <<= 1) {
@@ -303,40 +370,114 @@ __global__ void __launch_bounds__(256) fr_chunk_scan_kernel(uint32_t* __restrict
     }
     acc = tid ? load_fe<FrP>(sh + (tid - 1) * 8) : fe_one<FrP>();
     for (uint64_t c = lo; c < hi; c++) {
-        Fe<FrP> p = load_fe<FrP>(chunk_prod + c * 8);
-        store_fe(chunk_prod + c * 8, acc);
+        Fe<FrP> p = load_fe<FrP>(cp + c * 8);
+        store_fe(cp + c * 8, acc);
         acc = mul_val(acc, p);
     }
 }
 template <class FrP>
 __global__ void fr_chunk_apply_kernel(const uint32_t* __restrict__ num, const uint32_t* __restrict__ den_inv,
-                                      const uint32_t* __restrict__ chunk_prefix, uint32_t* __restrict__ z, uint64_t n) {
-    uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t lo = c * PROD_CHUNK;
-    if (lo >= n) return;
-    uint64_t hi = lo + PROD_CHUNK < n ? lo + PROD_CHUNK : n;
+                                      const uint32_t* __restrict__ chunk_prefix, uint32_t* __restrict__ z, uint64_t total, uint64_t chunk) {
+    const uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t lo = c * chunk;
+    if (lo >= total) return;
     Fe<FrP> acc = load_fe<FrP>(chunk_prefix + c * 8);
-    for (uint64_t i = lo; i < hi; i++) {
+    for (uint64_t i = lo; i < lo + chunk; i++) {
         store_fe(z + i * 8, acc);
         acc = mul(acc, mul(load_fe<FrP>(num + i * 8), load_fe<FrP>(den_inv + i * 8)));
     }
 }
 
-// ---- host side -----------------------------------------------------------------------------------------------------
-
-// two-level power table of `base` with first factor c0 in plain Montgomery form (ntt_pow_table_host), uploaded into scratch `key`
+// ---- kzg.Open: p(z) and the coefficients of (p(X) - p(z)) / (X - z) -----------------------------------------------------
+// gnark-crypto's dividePolyByXminusA is a sequential Horner recurrence q_{k-1} = p_k + z*q_k (call sites
+// backend/plonk/bn254/prove.go:681,788,827).  Unrolled, q_k = z^-(k+1) * sum_{j>k} p_j z^j: an element-wise scaling by z^j, a
+// suffix SUM (field additions only, three-phase scan) and an element-wise scaling by z^-(k+1); p(z) is the total sum.  Item j is grid
+// row j of the element-wise kernels and a segment of cpp = ceil(n / chunk) chunks of the scan (n is not a power of two: n + 2, n + 3)
+struct KzgBatchPtrs {
+    const uint32_t* p[PLONK_BATCH_LIMIT];
+};
 template <class FrP>
-int plonk_pow_tables(Ctx* ctx, const char* key, const Fe<FrP>& base, const Fe<FrP>& c0, uint64_t n, uint32_t** d_lo, uint32_t** d_hi) {
-    const std::vector<uint32_t> buf = ntt_pow_table_host<FrP>(base, c0, n, /*hat=*/false);
-    void* d;
-    GA_CHECK(ctx->scratch_get(key, buf.size() * 4, &d));
-    // the staging vector dies at return: synchronous copy (pageable memory)
-    GA_HIP_CHECK(hipMemcpyAsync(d, buf.data(), buf.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    GA_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    *d_lo = (uint32_t*)d;
-    *d_hi = (uint32_t*)d + ((size_t)8 << NTT_POW_LO_BITS);
-    return GA_OK;
+__global__ void kzg_scale_kernel(KzgBatchPtrs in, uint32_t* __restrict__ t, const uint32_t* __restrict__ tabs, uint64_t tab_words,
+                                 int lo_bits, uint64_t n) {
+    // t[j][i] = p_j[i] * z_j^i (table 2j)
+    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t* lo = tabs + (size_t)(2 * blockIdx.y) * tab_words;
+    store_fe(t + ((size_t)blockIdx.y * n + i) * 8,
+             mul(load_fe<FrP>(in.p[blockIdx.y] + i * 8), plonk_point<FrP>(lo, lo + ((size_t)8 << lo_bits), lo_bits, i)));
 }
+template <class FrP>
+__global__ void fr_chunk_sum_kernel(const uint32_t* __restrict__ t, uint32_t* __restrict__ chunk_sum, uint64_t n, uint64_t chunk,
+                                    uint64_t cpp, uint64_t nchunks) {
+    const uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= nchunks) return;
+    const uint64_t row = (c / cpp) * n, lo = (c % cpp) * chunk;
+    const uint64_t hi = lo + chunk < n ? lo + chunk : n;
+    Fe<FrP> acc = fe_zero<FrP>();
+    for (uint64_t i = lo; i < hi; i++) acc = add(acc, load_fe<FrP>(t + (row + i) * 8));
+    store_fe(chunk_sum + c * 8, acc);
+}
+template <class FrP>
+__global__ void __launch_bounds__(256) fr_chunk_suffix_scan_kernel(uint32_t* __restrict__ chunk_sum, uint64_t cpp) {
+    // chunk_sum[c] <- sum of the chunks AFTER c (exclusive suffix sum) over the cpp chunk sums of item blockIdx.y; segment per thread + LDS scan
+    __shared__ uint32_t sh[256 * 8];
+    uint32_t* cs = chunk_sum + (size_t)blockIdx.y * cpp * 8;
+    const uint32_t tid = threadIdx.x;
+    const uint64_t seg = (cpp + 255) / 256;
+    const uint64_t lo = (uint64_t)tid * seg < cpp ? (uint64_t)tid * seg : cpp;
+    const uint64_t hi = lo + seg < cpp ? lo + seg : cpp;
+    Fe<FrP> acc = fe_zero<FrP>();
+    for (uint64_t c = lo; c < hi; c++) acc = add(acc, load_fe<FrP>(cs + c * 8));
+    store_fe(sh + tid * 8, acc);
+    __syncthreads();
+    for (uint32_t off = 1; off < 256; off <<= 1) {   // inclusive suffix scan over the 256 segment sums
+        Fe<FrP> v = load_fe<FrP>(sh + tid * 8);
+        if (tid + off < 256) v = add(v, load_fe<FrP>(sh + (tid + off) * 8));
+        __syncthreads();
+        store_fe(sh + tid * 8, v);
+        __syncthreads();
+    }
+    acc = tid + 1 < 256 ? load_fe<FrP>(sh + (tid + 1) * 8) : fe_zero<FrP>();   // everything after this thread's segment
+    for (uint64_t c = hi; c-- > lo;) {
+        Fe<FrP> v = load_fe<FrP>(cs + c * 8);
+        store_fe(cs + c * 8, acc);
+        acc = add(acc, v);
+    }
+}
+template <class FrP>
+__global__ void fr_chunk_suffix_apply_kernel(uint32_t* __restrict__ t, const uint32_t* __restrict__ chunk_after, uint64_t n, uint64_t chunk,
+                                             uint64_t cpp, uint64_t nchunks) {
+    // t[j][i] <- sum_{i' >= i} t[j][i']  (inclusive suffix sum per item)
+    const uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= nchunks) return;
+    const uint64_t row = (c / cpp) * n, lo = (c % cpp) * chunk;
+    const uint64_t hi = lo + chunk < n ? lo + chunk : n;
+    Fe<FrP> acc = load_fe<FrP>(chunk_after + c * 8);
+    for (uint64_t i = hi; i-- > lo;) {
+        acc = add(acc, load_fe<FrP>(t + (row + i) * 8));
+        store_fe(t + (row + i) * 8, acc);
+    }
+}
+template <class FrP>
+__global__ void kzg_quotient_kernel(KzgBatchPtrs in, const uint32_t* __restrict__ t, const uint32_t* __restrict__ bases,
+                                    const uint32_t* __restrict__ tabs, uint64_t tab_words, int lo_bits, uint64_t n,
+                                    uint32_t* __restrict__ quot, uint64_t quot_stride, uint32_t* __restrict__ values) {
+    // q_j[i] = S_j[i + 1] * z_j^-(i + 1) (table 2j + 1), or p_j[i + 1] where z_j = 0; values[j] = S_j[0] = p_j(z_j)
+    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t* tj = t + (size_t)blockIdx.y * n * 8;
+    if (i == 0) store_fe(values + (size_t)blockIdx.y * 8, load_fe<FrP>(tj));
+    if (i + 1 >= n) return;
+    Fe<FrP> q;
+    if (is_zero(load_fe<FrP>(bases + (size_t)(2 * blockIdx.y) * 16))) {
+        q = load_fe<FrP>(in.p[blockIdx.y] + (i + 1) * 8);
+    } else {
+        const uint32_t* lo = tabs + (size_t)(2 * blockIdx.y + 1) * tab_words;
+        q = mul(load_fe<FrP>(tj + (i + 1) * 8), plonk_point<FrP>(lo, lo + ((size_t)8 << lo_bits), lo_bits, i + 1));
+    }
+    store_fe(quot + (size_t)blockIdx.y * quot_stride * 8 + i * 8, q);
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------
 
 template <class FrP>
 Fe<FrP> plonk_host_pow(Fe<FrP> a, uint64_t e) {
@@ -361,8 +502,7 @@ void plonk_put(uint32_t* dst, const Fe<FrP>& v) {
     memcpy(dst, v.l, 32);
 }
 
-// The constants of the constraint kernels, in two steps shared by the single and the batched drivers (their outputs must agree bit
-// for bit): what depends on the coset alone -- cexp = coset^n - 1 (prove.go:999-1000) --, then a proof's challenges, its blinding
+// The constants of the constraint kernel, in two steps: what depends on the coset alone -- cexp = coset^n - 1 (prove.go:999-1000) --, then a proof's challenges, its blinding
 // coefficients times cexp, and the images sh[] = 32 c mod r of the constants the lazy kernel multiplies by
 template <class FrP>
 void plonk_coset_consts(PlonkConsts& K, const Domain* d0, const Fe<FrP>& cexp) {
@@ -425,35 +565,76 @@ inline std::vector<int> plonk_ids(int np, bool fixed) {
     return ids;
 }
 
-// One call of a driver below: the checked shape, the scratch buffers, the coset being worked on, and the stages as members.  A
-// driver calls begin once, to_canonical per polynomial it owns, then per coset begin_coset followed by the stages it needs (every
-// launch of a coset reads the coset's tables: x_lo / x_hi live in one scratch buffer that the next begin_coset overwrites after
-// its synchronisation).
+// What every quotient driver needs of the rho cosets g * w1^i of the big domain (shifters, prove.go:936-941,998), made once per call:
+// coset^n - 1 (prove.go:999-1000), the constants that depend on the coset alone (one inversion per coset), the twiddle table that
+// carries the shift -- kept per domain and coset, so a forward transform scales nothing (prove.go:1033-1058) -- and, on the device,
+// the tables of the points coset * w0^j: one small upload out of `stage` and one launch for all cosets.  The owner keeps this object
+// alive until it has synchronised.
+template <class FrP>
+struct PlonkCosets {
+    uint64_t rho = 0;
+    std::vector<Fe<FrP>> cexp;
+    std::vector<PlonkConsts> K;
+    std::vector<const uint32_t*> tw;
+    std::vector<uint32_t> stage;
+    PowTables<FrP> x;
+
+    int build(Domain* d0, Domain* d1, uint32_t nb_bsb) {
+        const uint64_t n = d0->n;
+        if (n < 2 || d1->n < n || d1->n % n != 0 || nb_bsb > (uint32_t)PLONK_MAX_BSB || d1->ctx != d0->ctx) {
+            set_error("plonk: need n >= 2, |domain1| a multiple of |domain0|, at most %d BSB22 gates", PLONK_MAX_BSB);
+            return GA_ERR_INVALID;
+        }
+        rho = d1->n / n;
+        cexp.resize(rho), K.resize(rho), tw.resize(rho);
+        Fe<FrP> coset = fe_one<FrP>();
+        for (uint64_t i = 0; i < rho; i++) {
+            coset = mul(coset, i == 0 ? fe_const<FrP>(FrP::GEN) : plonk_ld<FrP>(d1->w));
+            cexp[i] = sub(plonk_host_pow<FrP>(coset, n), fe_one<FrP>());
+            memset(&K[i], 0, sizeof(PlonkConsts));
+            plonk_coset_consts<FrP>(K[i], d0, cexp[i]);
+            GA_CHECK(ntt_coset_table<FrP>(d0, coset, &tw[i]));
+            pow_pair<FrP>(stage, plonk_ld<FrP>(d0->w), coset);
+        }
+        return x.build(d0->ctx, "plonk_qb_xtab", stage, rho, n);
+    }
+    // where the constraints of coset i go: bitrev_N(rho*j + i) = bitrev_rho(i)*n + bitrev_n(j)
+    uint64_t block(uint64_t i) const {
+        const int logrho = ilog2_u64(rho);
+        uint64_t b = 0;
+        for (int k = 0; k < logrho; k++) b |= ((i >> k) & 1) << (logrho - 1 - k);
+        return b;
+    }
+};
+
+// One call of ga_plonk_quotient (every polynomial per call) or ga_plonk_pk_create: the checked shape, the scratch buffers and the
+// stages as members.  A driver calls begin once, to_canonical per polynomial it owns, proof_consts if it evaluates constraints, then
+// per coset the stages it needs.  (The quotient over a pinned key is plonk_quotient_pinned of plonk_batch.hip.h.)
 template <class FrP>
 struct PlonkRun {
-    typedef Fe<FrP> F;
-    Ctx* ctx;
+    Ctx* ctx = nullptr;
     Domain *d0, *d1;
     hipStream_t st;
     uint64_t n, rho;
     int np;
     unsigned blocks;                               // of 256 threads over n
     uint32_t *canon, *work, *invb, *tmpb, *cres;   // [np][n] canonical bit-reversed, [np][n] coset evaluations, [n], [n], [rho*n]
-    F coset, cexp;                                 // the current coset: its shift g * w1^i and coset^n - 1,
-    const uint32_t* coset_tw;                      // the ntt_coset_table of the shift,
-    uint32_t *x_lo, *x_hi;                         // the power table of its points coset * w0^j,
-    PlonkConsts K;                                 // the constants
-    PlonkPtrs P;                                   // and where the constraint kernel reads each polynomial: work_of(p) unless a driver says otherwise
+    PlonkCosets<FrP> cosets;
+    std::vector<PlonkConsts> hK;                   // [rho]: the proof's constants on every coset, and their place on the device
+    PlonkConsts* dK;
+    PlonkBatchPtrs B;                              // where the constraint kernel reads each polynomial: work_of(p), no per-proof stride
     uint32_t* canon_of(int p) const { return canon + (size_t)p * n * 8; }
     uint32_t* work_of(int p) const { return work + (size_t)p * n * 8; }
 
+    // cosets.stage and hK die with the run: no copy from them may still be queued when a driver returns early
+    ~PlonkRun() {
+        if (ctx) hipStreamSynchronize(st);
+    }
+
     int begin(Domain* dom0, Domain* dom1, uint32_t nb_bsb) {
         d0 = dom0, d1 = dom1, ctx = d0->ctx, st = ctx->stream, n = d0->n;
-        if (n < 2 || d1->n < n || d1->n % n != 0 || nb_bsb > (uint32_t)PLONK_MAX_BSB || d1->ctx != ctx) {
-            set_error("plonk: need n >= 2, |domain1| a multiple of |domain0|, at most %d BSB22 gates", PLONK_MAX_BSB);
-            return GA_ERR_INVALID;
-        }
-        rho = d1->n / n;
+        GA_CHECK(cosets.build(d0, d1, nb_bsb));
+        rho = cosets.rho;
         np = PLONK_NB_FIXED + 2 * (int)nb_bsb;
         blocks = (unsigned)((n + 255) / 256);
         GA_CHECK(ctx->scratch_get("plonk_canon", (size_t)np * n * 32, (void**)&canon));
@@ -461,11 +642,10 @@ struct PlonkRun {
         GA_CHECK(ctx->scratch_get("plonk_inv", n * 32, (void**)&invb));
         GA_CHECK(ctx->scratch_get("plonk_tmp", n * 32, (void**)&tmpb));
         GA_CHECK(ctx->scratch_get("plonk_cres", d1->n * 32, (void**)&cres));
-        coset = fe_one<FrP>();
-        memset(&K, 0, sizeof(K));
-        memset(&P, 0, sizeof(P));
-        P.nb_bsb = (int)nb_bsb;
-        for (int p = 0; p < np; p++) P.p[p] = work_of(p);
+        GA_CHECK(ctx->scratch_get("plonk_qb_consts", rho * sizeof(PlonkConsts), (void**)&dK));
+        memset(&B, 0, sizeof(B));
+        B.P.nb_bsb = (int)nb_bsb;
+        for (int p = 0; p < np; p++) B.P.p[p] = work_of(p);
         return GA_OK;
     }
 
@@ -485,49 +665,34 @@ struct PlonkRun {
         return GA_OK;
     }
 
-    // Coset i (cosets are begun in order): the shift g * w1^i (shifters, prove.go:936-941,998), its twiddle table -- kept per domain
-    // and coset, so a forward transform scales nothing (prove.go:1033-1058) -- the table of its points, uploaded synchronously,
-    // and the proof-independent constants cs, css, omega, lone, zh_inv
-    int begin_coset(uint64_t i) {
-        const F g = fe_const<FrP>(FrP::GEN);
-        coset = mul(coset, i == 0 ? g : plonk_ld<FrP>(d1->w));
-        cexp = sub(plonk_host_pow<FrP>(coset, n), fe_one<FrP>());   // (coset^n - 1), prove.go:999-1000
-        plonk_coset_consts<FrP>(K, d0, cexp);
-        GA_CHECK(ntt_coset_table<FrP>(d0, coset, &coset_tw));
-        return plonk_pow_tables<FrP>(ctx, "plonk_x_tab", plonk_ld<FrP>(d0->w), coset, n, &x_lo, &x_hi);
+    // the proof's constants on every coset (the challenges, the blinding coefficients times (coset^n - 1), the images sh[]), uploaded once
+    int proof_consts(const PlonkQuotientArgs& A) {
+        hK = cosets.K;
+        for (uint64_t i = 0; i < rho; i++) plonk_proof_consts<FrP>(hK[i], A, cosets.cexp[i]);
+        GA_HIP_CHECK(hipMemcpyAsync(dK, hK.data(), rho * sizeof(PlonkConsts), hipMemcpyHostToDevice, st));
+        return GA_OK;
     }
 
-    // the proof's constants on the current coset, after begin_coset: the challenges, the blinding coefficients times (coset^n - 1),
-    // and the images sh[] of the constants the lazy constraint kernel multiplies by
-    void proof_consts(const PlonkQuotientArgs& A) { plonk_proof_consts<FrP>(K, A, cexp); }
-
-    // dst = evaluations of polynomial p on the current coset: one out-of-place forward DIT over the coset's twiddle table
-    int eval_on_coset(int p, uint32_t* dst) {
-        return ntt_run<FrP>(d0, dst, /*inverse=*/false, /*dit=*/true, scale_none(), scale_none(), canon_of(p), coset_tw);
+    // dst = evaluations of polynomial p on coset i: one out-of-place forward DIT over the coset's twiddle table
+    int eval_on_coset(uint64_t i, int p, uint32_t* dst) {
+        return ntt_run<FrP>(d0, dst, /*inverse=*/false, /*dit=*/true, scale_none(), scale_none(), canon_of(p), cosets.tw[i]);
     }
 
-    // out[j] = 1 / (x_j - 1) over the current coset
-    int inv_x_minus_one(uint32_t* out) {
+    // out[j] = 1 / (x_j - 1) over coset i
+    int inv_x_minus_one(uint64_t i, uint32_t* out) {
         StageTimer tm(ctx, "plonk_batch_inverse");
-        hipLaunchKernelGGL((plonk_x_minus_one_kernel<FrP>), dim3(blocks), dim3(256), 0, st, out, x_lo, x_hi, NTT_POW_LO_BITS, n);
-        const uint64_t threads = n < 65536 ? (n + 63) / 64 : n / 64;   // >= 64 elements per thread amortise the inversion
-        hipLaunchKernelGGL((fr_batch_inverse_kernel<FrP>), dim3((unsigned)((threads + 63) / 64)), dim3(64), 0, st, out, tmpb, n);
+        hipLaunchKernelGGL((plonk_x_minus_one_kernel<FrP>), dim3(blocks), dim3(256), 0, st, out, cosets.x.lo(i), cosets.x.hi(i), NTT_POW_LO_BITS, n);
+        hipLaunchKernelGGL((fr_batch_inverse_kernel<FrP>), dim3((unsigned)((plonk_inverse_threads(n) + 63) / 64)), dim3(64), 0, st, out, tmpb, n);
         GA_KERNEL_CHECK();
         return GA_OK;
     }
 
-    // the constraints of coset i, from the evaluations P and 1/(x-1), into their block of cres
-    int constraints(const uint32_t* inv_xm1, uint64_t i) {
+    // the constraints of coset i, from the evaluations B.P and 1/(x-1), into their block of cres (one proof: grid y = 1)
+    int constraints(uint64_t i, const uint32_t* inv_xm1) {
         StageTimer tm(ctx, "plonk_constraints");
-        const int logrho = ilog2_u64(rho);
-        uint64_t block = 0;   // bitrev_N(rho*j + i) = bitrev_rho(i)*n + bitrev_n(j)
-        for (int b = 0; b < logrho; b++) block |= ((i >> b) & 1) << (logrho - 1 - b);
-        auto kernel = [] {   // BN254: lazy representation; BLS12-381's 255-bit Fr leaves 6 spare bits: packed
-            if constexpr (Radix<FrP>::NL * Radix<FrP>::L - FrP::BITS >= 7) return plonk_constraints29_kernel<FrP>;
-            else return plonk_constraints_kernel<FrP>;
-        }();
-        hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, st, P, K, x_lo, x_hi, NTT_POW_LO_BITS, inv_xm1,
-                           cres + block * n * 8, n, d0->logn);
+        hipLaunchKernelGGL((plonk_constraints_kernel<FrP, PLONK_LAZY<FrP>>), dim3((unsigned)((n + 127) / 128), 1), dim3(128), 0, st, B,
+                           (const PlonkConsts*)(dK + i), cosets.x.lo(i), cosets.x.hi(i), NTT_POW_LO_BITS, inv_xm1,
+                           cres + cosets.block(i) * n * 8, (uint64_t)0, n, d0->logn);
         GA_KERNEL_CHECK();
         return GA_OK;
     }
@@ -544,19 +709,17 @@ struct PlonkRun {
     }
 };
 
-// ---- the three drivers -------------------------------------------------------------------------------------------------
 // Every polynomial per call.
 template <class FrP>
 int plonk_quotient(Domain* d0, Domain* d1, const PlonkQuotientArgs& A, void* h_out) {
     PlonkRun<FrP> R;
     GA_CHECK(R.begin(d0, d1, A.nb_bsb));
     for (int p = 0; p < R.np; p++) GA_CHECK(R.to_canonical(A, p));
+    GA_CHECK(R.proof_consts(A));
     for (uint64_t i = 0; i < R.rho; i++) {
-        GA_CHECK(R.begin_coset(i));
-        R.proof_consts(A);
-        for (int p = 0; p < R.np; p++) GA_CHECK(R.eval_on_coset(p, R.work_of(p)));
-        GA_CHECK(R.inv_x_minus_one(R.invb));
-        GA_CHECK(R.constraints(R.invb, i));
+        for (int p = 0; p < R.np; p++) GA_CHECK(R.eval_on_coset(i, p, R.work_of(p)));
+        GA_CHECK(R.inv_x_minus_one(i, R.invb));
+        GA_CHECK(R.constraints(i, R.invb));
     }
     return R.finish(A, h_out);
 }
@@ -580,138 +743,11 @@ int plonk_fixed_create(Domain* d0, Domain* d1, const PlonkQuotientArgs& A, Plonk
     }
     for (int p : fixed) GA_CHECK(R.to_canonical(A, p));
     for (uint64_t i = 0; i < R.rho; i++) {
-        GA_CHECK(R.begin_coset(i));
-        for (int p : fixed) GA_CHECK(R.eval_on_coset(p, fx->evals_of(i, p)));
-        GA_CHECK(R.inv_x_minus_one(fx->inv_xm1_of(i)));
+        for (int p : fixed) GA_CHECK(R.eval_on_coset(i, p, fx->evals_of(i, p)));
+        GA_CHECK(R.inv_x_minus_one(i, fx->inv_xm1_of(i)));
     }
     GA_HIP_CHECK(hipStreamSynchronize(R.st));
     *out = fx.release();
-    return GA_OK;
-}
-
-// The per-proof polynomials only; the constraints read the circuit constants and 1/(x-1) from the key.
-template <class FrP>
-int plonk_quotient_pinned(PlonkFixed* fx, const PlonkQuotientArgs& A, void* h_out) {
-    PlonkRun<FrP> R;
-    GA_CHECK(R.begin(fx->d0, fx->d1, A.nb_bsb));
-    if (fx->nb_bsb != A.nb_bsb) {
-        set_error("plonk quotient: the pinned key was built for %u BSB22 gates", fx->nb_bsb);
-        return GA_ERR_INVALID;
-    }
-    const std::vector<int> fixed = plonk_ids(R.np, true), proof = plonk_ids(R.np, false);
-    for (int p : proof) GA_CHECK(R.to_canonical(A, p));
-    for (uint64_t i = 0; i < R.rho; i++) {
-        GA_CHECK(R.begin_coset(i));
-        R.proof_consts(A);
-        for (int p : proof) GA_CHECK(R.eval_on_coset(p, R.work_of(p)));
-        for (int p : fixed) R.P.p[p] = fx->evals_of(i, p);
-        GA_CHECK(R.constraints(fx->inv_xm1_of(i), i));
-    }
-    return R.finish(A, h_out);
-}
-
-// ---- kzg.Open: p(z) and the coefficients of (p(X) - p(z)) / (X - z) -----------------------------------------------------
-// gnark-crypto's dividePolyByXminusA is a sequential Horner recurrence q_{k-1} = p_k + z*q_k (call sites
-// backend/plonk/bn254/prove.go:681,788,827).  Unrolled, q_k = z^-(k+1) * sum_{j>k} p_j z^j: an element-wise scaling by z^j, a
-// suffix SUM (field additions only, three-phase scan) and an element-wise scaling by z^-(k+1); p(z) is the total sum.
-template <class FrP>
-__global__ void kzg_scale_kernel(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, const uint32_t* __restrict__ lo,
-                                 const uint32_t* __restrict__ hi, int lo_bits, uint64_t n, uint64_t shift) {
-    // out[i] = in[i + shift] * pow(i + shift)  (pow from the two-level table), i < n
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    store_fe(out + i * 8, mul(load_fe<FrP>(in + (i + shift) * 8), plonk_point<FrP>(lo, hi, lo_bits, i + shift)));
-}
-constexpr int SUM_CHUNK = 256;
-template <class FrP>
-__global__ void fr_chunk_sum_kernel(const uint32_t* __restrict__ t, uint32_t* __restrict__ chunk_sum, uint64_t n) {
-    uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t lo = c * SUM_CHUNK;
-    if (lo >= n) return;
-    uint64_t hi = lo + SUM_CHUNK < n ? lo + SUM_CHUNK : n;
-    Fe<FrP> acc = fe_zero<FrP>();
-    for (uint64_t i = lo; i < hi; i++) acc = add(acc, load_fe<FrP>(t + i * 8));
-    store_fe(chunk_sum + c * 8, acc);
-}
-template <class FrP>
-__global__ void __launch_bounds__(256) fr_chunk_suffix_scan_kernel(uint32_t* __restrict__ chunk_sum, uint64_t nchunks) {
-    // chunk_sum[c] <- sum of the chunks AFTER c (exclusive suffix sum); one block, segment per thread + LDS scan
-    __shared__ uint32_t sh[256 * 8];
-    const uint32_t tid = threadIdx.x;
-    const uint64_t seg = (nchunks + 255) / 256;
-    const uint64_t lo = (uint64_t)tid * seg < nchunks ? (uint64_t)tid * seg : nchunks;
-    const uint64_t hi = lo + seg < nchunks ? lo + seg : nchunks;
-    Fe<FrP> acc = fe_zero<FrP>();
-    for (uint64_t c = lo; c < hi; c++) acc = add(acc, load_fe<FrP>(chunk_sum + c * 8));
-    store_fe(sh + tid * 8, acc);
-    __syncthreads();
-    for (uint32_t off = 1; off < 256; off <<= 1) {   // inclusive suffix scan over the 256 segment sums
-        Fe<FrP> v = load_fe<FrP>(sh + tid * 8);
-        if (tid + off < 256) v = add(v, load_fe<FrP>(sh + (tid + off) * 8));
-        __syncthreads();
-        store_fe(sh + tid * 8, v);
-        __syncthreads();
-    }
-    acc = tid + 1 < 256 ? load_fe<FrP>(sh + (tid + 1) * 8) : fe_zero<FrP>();   // everything after this thread's segment
-    for (uint64_t c = hi; c-- > lo;) {
-        Fe<FrP> v = load_fe<FrP>(chunk_sum + c * 8);
-        store_fe(chunk_sum + c * 8, acc);
-        acc = add(acc, v);
-    }
-}
-template <class FrP>
-__global__ void fr_chunk_suffix_apply_kernel(uint32_t* __restrict__ t, const uint32_t* __restrict__ chunk_after, uint64_t n) {
-    // t[i] <- sum_{j >= i} t[j]  (inclusive suffix sum)
-    uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint64_t lo = c * SUM_CHUNK;
-    if (lo >= n) return;
-    uint64_t hi = lo + SUM_CHUNK < n ? lo + SUM_CHUNK : n;
-    Fe<FrP> acc = load_fe<FrP>(chunk_after + c * 8);
-    for (uint64_t i = hi; i-- > lo;) {
-        acc = add(acc, load_fe<FrP>(t + i * 8));
-        store_fe(t + i * 8, acc);
-    }
-}
-
-// d_quot (device, n elements: n-1 quotient coefficients then a zero) and *value (host, Montgomery) from d_poly (device, n coeffs)
-template <class FrP>
-int kzg_divide_by_linear(Ctx* ctx, const uint32_t* d_poly, uint64_t n, const void* z_mont, uint32_t* d_quot, void* value_out) {
-    typedef Fe<FrP> F;
-    hipStream_t st = ctx->stream;
-    F z;
-    memcpy(z.l, z_mont, 32);
-    if (n == 0) {
-        memset(value_out, 0, 32);
-        return GA_OK;
-    }
-    uint32_t *t, *cs;
-    const uint64_t nchunks = (n + SUM_CHUNK - 1) / SUM_CHUNK;
-    GA_CHECK(ctx->scratch_get("kzg_t", n * 32, (void**)&t));
-    GA_CHECK(ctx->scratch_get("kzg_chunks", nchunks * 32, (void**)&cs));
-    const unsigned blocks = (unsigned)((n + 255) / 256), cb = (unsigned)((nchunks + 63) / 64);
-    uint32_t *lo, *hi;
-    StageTimer tm(ctx, "kzg_divide");
-    GA_CHECK(plonk_pow_tables<FrP>(ctx, "plonk_x_tab", z, fe_one<FrP>(), n, &lo, &hi));
-    hipLaunchKernelGGL((kzg_scale_kernel<FrP>), dim3(blocks), dim3(256), 0, st, d_poly, t, lo, hi, NTT_POW_LO_BITS, n, (uint64_t)0);
-    hipLaunchKernelGGL((fr_chunk_sum_kernel<FrP>), dim3(cb), dim3(64), 0, st, t, cs, n);
-    hipLaunchKernelGGL((fr_chunk_suffix_scan_kernel<FrP>), dim3(1), dim3(256), 0, st, cs, nchunks);
-    hipLaunchKernelGGL((fr_chunk_suffix_apply_kernel<FrP>), dim3(cb), dim3(64), 0, st, t, cs, n);
-    GA_KERNEL_CHECK();
-    GA_HIP_CHECK(hipMemcpyAsync(value_out, t, 32, hipMemcpyDeviceToHost, st));   // S_0 = p(z)
-    GA_HIP_CHECK(hipMemsetAsync(d_quot + (n - 1) * 8, 0, 32, st));
-    if (n > 1) {
-        if (is_zero(z)) {
-            // q_k = p_{k+1}
-            GA_HIP_CHECK(hipMemcpyAsync(d_quot, d_poly + 8, (n - 1) * 32, hipMemcpyDeviceToDevice, st));
-        } else {
-            // q_k = S_{k+1} * z^-(k+1): table of zinv^j, element i of the output reads index i+1
-            GA_CHECK(plonk_pow_tables<FrP>(ctx, "plonk_scale_tab", inv(z), fe_one<FrP>(), n, &lo, &hi));
-            hipLaunchKernelGGL((kzg_scale_kernel<FrP>), dim3((unsigned)((n - 1 + 255) / 256)), dim3(256), 0, st, t, d_quot, lo, hi,
-                               NTT_POW_LO_BITS, n - 1, (uint64_t)1);
-            GA_KERNEL_CHECK();
-        }
-    }
-    GA_HIP_CHECK(hipStreamSynchronize(st));
     return GA_OK;
 }
 
@@ -778,8 +814,7 @@ int fr_batch_inverse(Ctx* ctx, void* v, uint64_t n, bool on_device) {
     if (!on_device) GA_HIP_CHECK(hipMemcpyAsync(buf, v, n * 32, hipMemcpyHostToDevice, st));
     {
         StageTimer tm(ctx, "plonk_batch_inverse");
-        const uint64_t threads = n < 65536 ? (n + 63) / 64 : n / 64;
-        hipLaunchKernelGGL((fr_batch_inverse_kernel<FrP>), dim3((unsigned)((threads + 63) / 64)), dim3(64), 0, st, d, tmp, n);
+        hipLaunchKernelGGL((fr_batch_inverse_kernel<FrP>), dim3((unsigned)((plonk_inverse_threads(n) + 63) / 64)), dim3(64), 0, st, d, tmp, n);
         GA_KERNEL_CHECK();
     }
     if (!on_device) GA_HIP_CHECK(hipMemcpyAsync(v, buf, n * 32, hipMemcpyDeviceToHost, st));
@@ -791,78 +826,6 @@ int fr_batch_inverse(Ctx* ctx, void* v, uint64_t n, bool on_device) {
 static __global__ void plonk_perm_check_kernel(const int64_t* __restrict__ perm, uint64_t n3, uint32_t* __restrict__ bad) {
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n3 && (perm[i] < 0 || (uint64_t)perm[i] >= n3)) atomicAdd(bad, 1u);
-}
-
-// iop.BuildRatioCopyConstraint: Z in Lagrange form (regular layout) from L, R, O (Lagrange regular) and the permutation.
-template <class FrP>
-int plonk_build_z(Domain* d0, const void* L, const void* R, const void* O, const int64_t* perm, const void* beta, const void* gamma,
-                  bool on_device, void* z_out) {
-    typedef Fe<FrP> F;
-    Ctx* ctx = d0->ctx;
-    const uint64_t n = d0->n;
-    hipStream_t st = ctx->stream;
-    uint32_t *lro, *num, *den, *tmp, *z, *cp;
-    int64_t* dperm;
-    const uint64_t nchunks = (n + PROD_CHUNK - 1) / PROD_CHUNK;
-    GA_CHECK(ctx->scratch_get("plonk_z_lro", 3 * n * 32, (void**)&lro));
-    GA_CHECK(ctx->scratch_get("plonk_z_num", n * 32, (void**)&num));
-    GA_CHECK(ctx->scratch_get("plonk_z_den", n * 32, (void**)&den));
-    GA_CHECK(ctx->scratch_get("plonk_tmp", n * 32, (void**)&tmp));
-    GA_CHECK(ctx->scratch_get("plonk_z_out", n * 32, (void**)&z));
-    GA_CHECK(ctx->scratch_get("plonk_z_chunks", nchunks * 32, (void**)&cp));
-    GA_CHECK(ctx->scratch_get("plonk_z_perm", 3 * n * 8, (void**)&dperm));
-    const hipMemcpyKind kin = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    const void* src[3] = {L, R, O};
-    for (int k = 0; k < 3; k++) GA_HIP_CHECK(hipMemcpyAsync(lro + (size_t)k * n * 8, src[k], n * 32, kin, st));
-    GA_HIP_CHECK(hipMemcpyAsync(dperm, perm, 3 * n * 8, kin, st));
-    if (on_device) {   // a host permutation was range-checked by the entry point
-        uint32_t* d_bad;
-        GA_CHECK(ctx->scratch_get("plonk_perm_bad", 256, (void**)&d_bad));
-        GA_HIP_CHECK(hipMemsetAsync(d_bad, 0, 4, st));
-        hipLaunchKernelGGL(plonk_perm_check_kernel, dim3((unsigned)((3 * n + 255) / 256)), dim3(256), 0, st, (const int64_t*)dperm, 3 * n, d_bad);
-        GA_KERNEL_CHECK();
-        uint32_t bad = 0;
-        GA_HIP_CHECK(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st));
-        GA_HIP_CHECK(hipStreamSynchronize(st));
-        if (bad) {
-            set_error("ga_plonk_build_z: %u entries of the device-resident permutation are outside [0, 3n)", bad);
-            return GA_ERR_INVALID;
-        }
-    }
-    PlonkConsts K;
-    memset(&K, 0, sizeof(K));
-    memcpy(K.beta, beta, 32);
-    memcpy(K.gamma, gamma, 32);
-    const F g = fe_const<FrP>(FrP::GEN);
-    memcpy(K.cs, g.l, 32);
-    F gg = sqr(g);
-    memcpy(K.css, gg.l, 32);
-    uint32_t *w_lo, *w_hi;
-    GA_CHECK(plonk_pow_tables<FrP>(ctx, "plonk_x_tab", plonk_ld<FrP>(d0->w), fe_one<FrP>(), n, &w_lo, &w_hi));
-    const unsigned blocks = (unsigned)((n + 255) / 256);
-    {
-        StageTimer tm(ctx, "plonk_z_terms");
-        hipLaunchKernelGGL((plonk_ratio_terms_kernel<FrP>), dim3(blocks), dim3(256), 0, st, lro, lro + n * 8, lro + 2 * n * 8, dperm, w_lo,
-                           w_hi, NTT_POW_LO_BITS, K, num, den, n);
-        GA_KERNEL_CHECK();
-    }
-    {
-        StageTimer tm(ctx, "plonk_batch_inverse");
-        const uint64_t threads = n < 65536 ? (n + 63) / 64 : n / 64;
-        hipLaunchKernelGGL((fr_batch_inverse_kernel<FrP>), dim3((unsigned)((threads + 63) / 64)), dim3(64), 0, st, den, tmp, n);
-        GA_KERNEL_CHECK();
-    }
-    {
-        StageTimer tm(ctx, "plonk_z_prefix_product");
-        const unsigned cb = (unsigned)((nchunks + 63) / 64);
-        hipLaunchKernelGGL((fr_chunk_product_kernel<FrP>), dim3(cb), dim3(64), 0, st, num, den, cp, n);
-        hipLaunchKernelGGL((fr_chunk_scan_kernel<FrP>), dim3(1), dim3(256), 0, st, cp, nchunks);
-        hipLaunchKernelGGL((fr_chunk_apply_kernel<FrP>), dim3(cb), dim3(64), 0, st, num, den, cp, z, n);
-        GA_KERNEL_CHECK();
-    }
-    GA_HIP_CHECK(hipMemcpyAsync(z_out, z, n * 32, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
-    GA_HIP_CHECK(hipStreamSynchronize(st));
-    return GA_OK;
 }
 
 }  // namespace ga

@@ -20,6 +20,7 @@ against in tests/test_oracle_fixtures.py).
 """
 from __future__ import annotations
 
+import functools
 import hashlib
 from dataclasses import dataclass, field
 
@@ -416,14 +417,19 @@ def plonk_numerator_at(c: Curve, n: int, x: dict, qcp, pi2, bp: dict, alpha, bet
     return (((z - 1) * lone % mod * alpha + (ll - rr)) % mod * alpha + gate) % mod
 
 
+@functools.lru_cache(maxsize=4)
+def _plonk_identity_evals(mod, w0, g, n):
+    """the identity permutation over the three cosets {1, g, g^2} * w0^i (a tuple: callers that check many proofs of one circuit share it)"""
+    return tuple(pow(g, k, mod) * pow(w0, i, mod) % mod for k in range(3) for i in range(n))
+
+
 def plonk_build_z(c: Curve, n: int, L, R, O, perm, beta, gamma):
     """iop.BuildRatioCopyConstraint (gnark-crypto [EXT], call site backend/plonk/bn254/prove.go:645-655): the grand-product
     polynomial in Lagrange form.  L,R,O: evaluations on the domain; perm: permutation of [0,3n) (s.trace.S).
     Z[0] = 1, Z[i+1] = Z[i] * prod_k (e_k[i] + beta*id_k(i) + gamma) / prod_k (e_k[i] + beta*id(perm[k*n+i]) + gamma)
     with id over the three cosets {1, g, g^2} * w^i."""
     mod = c.r
-    w0, g = c.fr_root_of_unity(n), c.fr_gen
-    ids = [pow(g, k, mod) * pow(w0, i, mod) % mod for k in range(3) for i in range(n)]
+    ids = _plonk_identity_evals(mod, c.fr_root_of_unity(n), c.fr_gen, n)
     ev = [L, R, O]
     Z = [1] * n
     for i in range(n - 1):

@@ -1,6 +1,8 @@
 """ga_plonk_build_z_batch, ga_plonk_quotient_pinned_batch and ga_kzg_open_batch under the functional HIP emulation: `count` proofs of
-one circuit per call.  Every batch output is compared byte for byte with the existing single call on item j (H after
-ga_jac_to_affine), and with an oracle that is no library call: proof 0 always, every proof at the smallest size.  One synthetic
+one circuit per call, and the single calls, which are the one-proof case of the same drivers.  Every batch output is compared byte
+for byte with the single call on item j (H after ga_jac_to_affine) -- that checks the splitting into passes, not a second
+implementation -- and with an oracle that is no library call: every proof wherever the oracle takes a few seconds at the most (each
+case function says where), proof 0 otherwise.  One synthetic
 circuit per case (pyref.plonk_synthetic_instance: the fixed polynomials, the permutation and proof 0); the other proofs are
 independent random field vectors with random challenges -- the three routines are total functions of their inputs, so a witness need
 not satisfy the circuit for the comparison to mean something.  The case functions take the context first;
@@ -27,6 +29,12 @@ def rand_fr(rng, *shape):
     a = rng.integers(0, 1 << 64, size=shape + (4,), dtype=np.uint64)
     a[..., 3] &= np.uint64((1 << 60) - 1)
     return a
+
+
+def fr_ints(c, a):
+    """arr_to_fr for long vectors: the Montgomery factor is inverted once, not per element"""
+    rinv = pow(1 << 256, -1, c.r)
+    return [int.from_bytes(row.tobytes(), "little") * rinv % c.r for row in np.ascontiguousarray(a, dtype="<u8").reshape(-1, 4)]
 
 
 def guarded(shape):
@@ -84,8 +92,9 @@ def z_inputs(c, n, count):
 
 
 def case_build_z(ctx, c, n, count, on_device=False):
-    """row j of ga_plonk_build_z_batch == ga_plonk_build_z on item j; proof 0 (every proof at n <= 8) == pyref.plonk_build_z; the
-    inputs are unchanged and the words after the output untouched"""
+    """row j of ga_plonk_build_z_batch == ga_plonk_build_z on item j (one implementation: this tests the splitting into passes);
+    EVERY row == pyref.plonk_build_z (linear in n: 0.4 s per row at n = 2^13, the largest size a test uses); the inputs are unchanged
+    and the words after the output untouched"""
     lib = ctx.lib
     T, L, R, O, betas, gammas = z_inputs(c, n, count)
     d0 = fft.Domain(ctx, c.name, n)
@@ -114,10 +123,10 @@ def case_build_z(ctx, c, n, count, on_device=False):
         for j in range(count):
             single = plonk.BuildRatioCopyConstraint(d0, L[j], R[j], O[j], T["perm"], betas[j], gammas[j])
             assert np.array_equal(got[j], single), (n, count, j)
-        for j in range(count if n <= 8 else 1):
-            want = pyref.plonk_build_z(c, n, arr_to_fr(c, L[j]), arr_to_fr(c, R[j]), arr_to_fr(c, O[j]), [int(x) for x in T["perm"]],
-                                       arr_to_fr(c, betas[j:j + 1])[0], arr_to_fr(c, gammas[j:j + 1])[0])
-            assert arr_to_fr(c, got[j]) == want, (n, count, j, "oracle")
+        perm = [int(x) for x in T["perm"]]
+        for j in range(count):
+            want = pyref.plonk_build_z(c, n, fr_ints(c, L[j]), fr_ints(c, R[j]), fr_ints(c, O[j]), perm, fr_ints(c, betas[j])[0], fr_ints(c, gammas[j])[0])
+            assert fr_ints(c, got[j]) == want, (n, count, j, "oracle")
     finally:
         d0.close()
 
@@ -189,9 +198,11 @@ def oracle_quotient(c, n, T, pr, lagrange):
 
 
 def case_quotient(ctx, c, n, nb_bsb, count, lagrange, on_device=False):
-    """block j of ga_plonk_quotient_pinned_batch == ga_plonk_quotient_pinned on proof j; proof 0 (every proof at n = 4) == the oracle
-    (pyref.plonk_quotient accepts a witness that does not satisfy the circuit: it is the same total function); two proofs with equal
-    inputs give equal blocks; the words after the output are untouched"""
+    """block j of ga_plonk_quotient_pinned_batch == ga_plonk_quotient_pinned on proof j (one implementation: this tests the splitting
+    into passes); every proof up to n = 2^11, proof 0 above (the C oracle takes 1.1 s per proof at 2^13, under 0.1 s up to 2^10: that
+    covers every emulation case and the GPU cases of 2^10 and 2^11) == the oracle (pyref.plonk_quotient accepts a witness that does
+    not satisfy the circuit: it is the same total function); two proofs with equal inputs give equal blocks; the words after the
+    output are untouched"""
     lib = ctx.lib
     T, proofs = quotient_inputs(c, n, nb_bsb, count, lagrange)
     rho = plonk.Rho(n)
@@ -209,7 +220,7 @@ def case_quotient(ctx, c, n, nb_bsb, count, lagrange, on_device=False):
         for j, pr in enumerate(proofs):
             single = pk.ComputeQuotient(pr["polys"], pr["pi2"], bp=pr["bp"], alpha=pr["alpha"], beta=pr["beta"], gamma=pr["gamma"], lagrange=lagr)
             assert np.array_equal(got[j], single), (n, nb_bsb, count, j)
-        for j in range(count if n == 4 else 1):
+        for j in range(count if n <= 1 << 11 else 1):
             assert np.array_equal(got[j], oracle_quotient(c, n, T, proofs[j], lagrange)), (n, nb_bsb, j, "oracle")
         if count >= 3:
             assert np.array_equal(got[1], got[count - 1])
@@ -332,8 +343,10 @@ def open_inputs(c, length, count):
 def case_open(ctx, c, length, srs_len, count, on_device=False):
     """item j of ga_kzg_open_batch == ga_kzg_open on (polys[j], points[j]): the claimed value byte for byte, H after
     ga_jac_to_affine.  Oracle: every claimed value == Horner in Python integers; every H == [sum_i q_i k_i]G with q from the sequential
-    recurrence of pyref.kzg_open's division and the known discrete logs k_i of the SRS; for short polynomials (<= 67 coefficients: item
-    0, <= 2: every item) H == pyref.kzg_open over the SRS points themselves"""
+    recurrence of pyref.kzg_open's division and the known discrete logs k_i of the SRS; for short polynomials (<= 67 coefficients) H
+    == pyref.kzg_open over the SRS points themselves -- item 0 always, every item where length * count <= 200 (its MSM in Python
+    integers takes 0.1 s per item at 11 coefficients and 1.2 s at 67: that covers lengths 1, 2 and 11 at every count, and 67 at
+    count 1)"""
     lib, mod = ctx.lib, c.r
     ks, pts = srs_of(c, srs_len)
     polys, points = open_inputs(c, length, count)
@@ -373,7 +386,7 @@ def case_open(ctx, c, length, srs_len, count, on_device=False):
             assert arr_to_fr(c, vals[j:j + 1])[0] == (p[0] + zs[j] * acc) % mod, (length, j, "value")
             e = sum(qi * int(ki) for qi, ki in zip(q, ks)) % mod
             assert np.array_equal(oracle.jac_to_affine(c.cid, 0, H[j]), oracle.jac_to_affine(c.cid, 0, oracle.generator_mul(c.cid, 0, e))), (length, j, "H")
-            if srs_pts is not None and (j == 0 or length <= 2):
+            if srs_pts is not None and (j == 0 or length * count <= 200):
                 want = pyref.kzg_open(c, srs_pts, p, zs[j])
                 assert want[0] == arr_to_fr(c, vals[j:j + 1])[0] and jac_to_affine_py(c, 0, H[j]) == want[1], (length, j, "pyref")
     finally:
@@ -468,6 +481,95 @@ def test_chunks_uneven_passes_and_scan_widths(emu_ctx, monkeypatch, scan_threads
     threads more chunk products (8 and 16) than the first pass reserved (6 and 12), the overrun this case guards; the suffix sums of
     67 coefficients run over wide, middling and 8-element chunks"""
     case_chunks(emu_ctx, monkeypatch, c, 64, 67, 5, 3, scan_threads)
+
+
+# ---- the single calls: the one-proof case of the same drivers ---------------------------------------------------------------------------
+def case_single_build_z(ctx, c, n):
+    """ga_plonk_build_z == pyref.plonk_build_z on the synthetic trace and on random wires with beta = 0"""
+    T, L, R, O, betas, gammas = z_inputs(c, n, 2)
+    d0 = fft.Domain(ctx, c.name, n)
+    try:
+        for j in range(2):
+            got = plonk.BuildRatioCopyConstraint(d0, L[j], R[j], O[j], T["perm"], betas[j], gammas[j])
+            want = pyref.plonk_build_z(c, n, arr_to_fr(c, L[j]), arr_to_fr(c, R[j]), arr_to_fr(c, O[j]), [int(x) for x in T["perm"]],
+                                       arr_to_fr(c, betas[j:j + 1])[0], arr_to_fr(c, gammas[j:j + 1])[0])
+            assert arr_to_fr(c, got) == want, (n, j)
+    finally:
+        d0.close()
+
+
+def case_single_open(ctx, c, length, with_open=True):
+    """ga_kzg_open and ga_fr_poly_evaluate on a polynomial of `length` coefficients at a random point and at the point 0: the claimed
+    value and the evaluation == Horner in Python integers, H == [sum_i q_i k_i]G with q from the sequential recurrence and the known
+    discrete logs of the SRS (case_open's check), and up to two coefficients H == pyref.kzg_open over the SRS points.
+    with_open=False: the evaluation alone"""
+    mod = c.r
+    ks, pts = srs_of(c, length + 2)
+    polys, points = open_inputs(c, length, 2)   # item 1: the point 0
+    zs = arr_to_fr(c, points)
+    table = ecc.PrecomputedBases(ctx, c.name, 0, pts) if with_open else None
+    try:
+        for j in range(2):
+            p, q, acc = arr_to_fr(c, polys[j]), [0] * (length - 1), 0
+            for k in range(length - 1, 0, -1):
+                acc = (p[k] + zs[j] * acc) % mod
+                q[k - 1] = acc
+            want = (p[0] + zs[j] * acc) % mod
+            assert arr_to_fr(c, plonk.Evaluate(ctx, c.name, polys[j], points[j]).reshape(1, 4))[0] == want, (length, j, "evaluate")
+            if not with_open:
+                continue
+            val, H = table.KzgOpen(polys[j], points[j])
+            assert arr_to_fr(c, val.reshape(1, 4))[0] == want, (length, j, "value")
+            e = sum(qi * int(ki) for qi, ki in zip(q, ks)) % mod
+            assert np.array_equal(oracle.jac_to_affine(c.cid, 0, H), oracle.jac_to_affine(c.cid, 0, oracle.generator_mul(c.cid, 0, e))), (length, j, "H")
+            if length <= 2:
+                ref = pyref.kzg_open(c, [arr_to_g1_affine(c, x) for x in pts[:length]], p, zs[j])
+                assert ref[0] == want and jac_to_affine_py(c, 0, H) == ref[1], (length, j, "pyref")
+    finally:
+        if table:
+            table.free()
+
+
+def case_single_quotient(ctx, c, n, nb_bsb):
+    """ga_plonk_quotient_pinned with R, Z and every Pi2 as evaluations and the rest as coefficients == the oracle, on the satisfying
+    trace and on a random proof"""
+    T, proofs = quotient_inputs(c, n, nb_bsb, 2, "mixed")
+    rho = plonk.Rho(n)
+    d0, d1 = fft.Domain(ctx, c.name, n), fft.Domain(ctx, c.name, rho * n)
+    pk = None
+    try:
+        pk = plonk.ProvingKey(d0, d1, {k: T["lag"][k] for k in plonk.FIXED_IDS}, T["qcp"],
+                              lagrange=plonk.FIXED_IDS + tuple("Qcp%d" % i for i in range(nb_bsb)))
+        for j, pr in enumerate(proofs):
+            got = pk.ComputeQuotient(pr["polys"], pr["pi2"], bp=pr["bp"], alpha=pr["alpha"], beta=pr["beta"], gamma=pr["gamma"],
+                                     lagrange=lagrange_names("mixed", nb_bsb))
+            assert np.array_equal(got, oracle_quotient(c, n, T, pr, "mixed")), (n, nb_bsb, j)
+    finally:
+        if pk:
+            pk.close()
+        d0.close()
+        d1.close()
+
+
+@pytest.mark.parametrize("scan_threads", [1, 8, 20])
+@pytest.mark.parametrize("c", CURVES, ids=lambda c: c.name)
+def test_single_calls_scan_widths(emu_ctx, monkeypatch, c, scan_threads):
+    """GA_PLONK_SCAN_THREADS governs the single calls too.  ga_plonk_build_z at n = 2 (the chunk is clamped to n) and n = 512 (two
+    chunks of 256 at 1 thread, 64 chunks of 8 at 20); ga_kzg_open and ga_fr_poly_evaluate at 1, 2, 67 and 2^12 + 3 coefficients (no
+    quotient coefficient, one, an uneven last chunk, a second upper entry of the power tables), each also at the point 0.  At the
+    longest length BLS12-381 runs the evaluation only (the same division over its field): the table MSM of the opening takes seconds
+    under the emulation there, and test_open_above_one_table_block opens at that length on BN254 alone as well"""
+    monkeypatch.setenv("GA_PLONK_SCAN_THREADS", str(scan_threads))
+    for n in (2, 512):
+        case_single_build_z(emu_ctx, c, n)
+    for length in (1, 2, 67, (1 << 12) + 3):
+        case_single_open(emu_ctx, c, length, with_open=c is BN254 or length <= 67)
+
+
+@pytest.mark.parametrize("n,nb_bsb", [(4, 0), (4, 1), (8, 0), (8, 1)])
+def test_single_quotient_mixed_mask(emu_ctx, n, nb_bsb):
+    """n = 4 (rho = 8) and n = 8 (rho = 4), without and with a BSB22 gate"""
+    case_single_quotient(emu_ctx, BN254, n, nb_bsb)
 
 
 # ---- refusals --------------------------------------------------------------------------------------------------------------------------

@@ -21,7 +21,12 @@ file records
     is decided by that;
   * one stage breakdown of the three batched calls from the stage profiler, taken in a separate pass.
 The condition: at count 16 the median per-proof time of each batched call is no larger than the parent build's loop for that call,
-within the recorded spread.  A configuration that misses it stays in the table and is reported as a finding."""
+within the recorded spread.  A configuration that misses it stays in the table and is reported as a finding.
+
+--single times the SINGLE entry points of this build (ga_plonk_build_z, ga_plonk_quotient_pinned, ga_kzg_open: the one-proof case of
+the batched drivers) against the parent build's single entry points, in the same way, and writes profiles/plonk_single_fold.json:
+    python tools/plonk_batch_bench.py --single --configs bn254:10 bn254:16 bn254:22 bls12-381:16
+The condition there: every call at every size and count is no slower than the parent's, within the recorded spread."""
 import argparse
 import ctypes as C
 import json
@@ -172,7 +177,7 @@ class Side:
         self.d1.close()
 
 
-def run_config(curve, logn, counts, reps, parent_lib):
+def run_config(curve, logn, counts, reps, parent_lib, single=False):
     import numpy as np
     import gnark_amd
     import oracle
@@ -197,8 +202,9 @@ def run_config(curve, logn, counts, reps, parent_lib):
         for count in counts:
             for s in sides:
                 s.prepare(count)
+            run_new = sides[0].loop if single else sides[0].batch   # what is measured against the parent build's loop
             for call in CALLS:
-                sides[0].batch(call, count)
+                run_new(call, count)
                 sides[1].loop(call, count)
             got, ref = sides[0].outputs(count), sides[1].outputs(count)
             eq = [bool(np.array_equal(a, b)) for a, b in zip(got, ref)]
@@ -207,7 +213,7 @@ def run_config(curve, logn, counts, reps, parent_lib):
                    "claimed_values_equal_horner": {"batch": all(horner[0]), "parent_loop": all(horner[1])}}
             tot = {"batch": 0.0, "parent": 0.0}
             for call in CALLS:
-                (b, bmin, bmax), (l, lmin, lmax) = interleaved(reps, [(new, lambda: sides[0].batch(call, count)),
+                (b, bmin, bmax), (l, lmin, lmax) = interleaved(reps, [(new, lambda: run_new(call, count)),
                                                                        (par, lambda: sides[1].loop(call, count))])
                 spread = max((bmax - bmin) / b, (lmax - lmin) / l)
                 row[call] = {"batch_ms_per_proof": round(b / count, 4), "parent_loop_ms_per_proof": round(l / count, 4),
@@ -217,12 +223,12 @@ def run_config(curve, logn, counts, reps, parent_lib):
                 tot["parent"] += l
             row["sum"] = {"batch_ms_per_proof": round(tot["batch"] / count, 4), "parent_loop_ms_per_proof": round(tot["parent"] / count, 4),
                           "parent_over_batch": round(tot["parent"] / tot["batch"], 3)}
-            row["batch_stages_ms"] = stage_profile(new, lambda: [sides[0].batch(call, count) for call in CALLS])
+            row["batch_stages_ms"] = stage_profile(new, lambda: [run_new(call, count) for call in CALLS])
             rows.append(row)
     finally:
         for s in sides:
             s.close()
-    res = {"curve": curve, "log_n": logn, "nb_bsb": 1, "reps": reps, "device": new.info()["name"].strip(), "counts": rows}
+    res = {"curve": curve, "log_n": logn, "nb_bsb": 1, "reps": reps, "batch_side": "loop of single calls" if single else "batched calls", "device": new.info()["name"].strip(), "counts": rows}
     new.close()
     par.close()
     print(TAG + json.dumps(res), flush=True)
@@ -235,33 +241,44 @@ def main():
     ap.add_argument("--log-n", type=int, nargs="+", default=[10, 12, 14, 16])
     ap.add_argument("--counts", type=int, nargs="+", default=[4, 16])
     ap.add_argument("--curves", nargs="+", default=list(CURVES))
+    ap.add_argument("--configs", nargs="+", metavar="CURVE:LOGN", help="these configurations instead of every --curves x --log-n")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--step-timeout", type=int, default=240, help="seconds per configuration")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "plonk_batch.json"))
+    ap.add_argument("--single", action="store_true", help="time this build's single entry points (the `batch` columns then hold them)")
+    ap.add_argument("--out", default=None, help="default: profiles/plonk_batch.json, or profiles/plonk_single_fold.json with --single")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "plonk_single_fold.json" if args.single else "plonk_batch.json")
+    if args.single and args.counts == [4, 16]:
+        args.counts = [1]
     if not os.path.exists(args.parent_lib):
         sys.stderr.write("%s not found: build the parent commit's library first (see the top of this file)\n" % args.parent_lib)
         return 2
     if args.one:
-        run_config(args.one[0], int(args.one[1]), args.counts, args.reps, args.parent_lib)
+        run_config(args.one[0], int(args.one[1]), args.counts, args.reps, args.parent_lib, args.single)
         return 0
     results = []
-    for logn in args.log_n:
-        for curve in args.curves:
-            cmd = ["timeout", "-k", "10", str(args.step_timeout), sys.executable, os.path.abspath(__file__), "--one", curve, str(logn),
-                   "--parent-lib", args.parent_lib, "--reps", str(args.reps), "--counts"] + [str(k) for k in args.counts]
-            r = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT)
-            line = [ln for ln in r.stdout.splitlines() if ln.startswith(TAG)]
-            if r.returncode != 0 or not line:   # a failed step ends the run: nothing more is started on the device
-                sys.stderr.write("step %s failed (exit %d)\n%s\n%s\n" % ((curve, logn), r.returncode, r.stdout[-2000:], r.stderr[-2000:]))
-                return 1
-            results.append(json.loads(line[0][len(TAG):]))
-            print(line[0][:300], flush=True)
+    configs = [(curve, logn) for logn in args.log_n for curve in args.curves]
+    if args.configs:
+        configs = [(c.rsplit(":", 1)[0], int(c.rsplit(":", 1)[1])) for c in args.configs]
+    for curve, logn in configs:
+        cmd = ["timeout", "-k", "10", str(args.step_timeout), sys.executable, os.path.abspath(__file__), "--one", curve, str(logn),
+               "--parent-lib", args.parent_lib, "--reps", str(args.reps)] + (["--single"] if args.single else [])
+        r = subprocess.run(cmd + ["--counts"] + [str(k) for k in args.counts], capture_output=True, text=True, cwd=ROOT)
+        line = [ln for ln in r.stdout.splitlines() if ln.startswith(TAG)]
+        if r.returncode != 0 or not line:   # a failed step ends the run: nothing more is started on the device
+            sys.stderr.write("step %s failed (exit %d)\n%s\n%s\n" % ((curve, logn), r.returncode, r.stdout[-2000:], r.stderr[-2000:]))
+            return 1
+        results.append(json.loads(line[0][len(TAG):]))
+        print(line[0][:300], flush=True)
     cond = {"what": "count = 16, n <= 2^16, both curves: the median per-proof time of each batched call is no larger than the parent build's "
                     "loop of the single call, within the recorded run-to-run spread", "missed": []}
+    if args.single:
+        cond["what"] = ("every size and count, both curves: the median time of each single call of this build is no larger than the parent "
+                        "build's single call, within the recorded run-to-run spread")
     for r in results:
         for row in r["counts"]:
-            if row["count"] == 16:
+            if args.single or row["count"] == 16:
                 for call in CALLS:
                     if not row[call]["no_slower"]:
                         cond["missed"].append({"curve": r["curve"], "log_n": r["log_n"], "call": call, **row[call]})
@@ -272,6 +289,8 @@ def main():
                      "pinned key with nb_bsb = 1, an SRS table of n + 3 points, polynomials of n + 3 coefficients opened; inputs and outputs "
                      "in device memory (evaluation points, claimed values and H are host arguments of the ABI); spread = (max - min) / median",
            "configurations": results, "condition": cond}
+    if args.single:
+        doc["method"] = doc["method"].replace("the baseline is a loop", "the `batch` columns are a loop over proofs of this build's SINGLE call; the baseline is a loop")
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(doc, f, indent=1)
