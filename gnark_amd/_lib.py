@@ -13,6 +13,7 @@ DEFAULT_PATH = os.path.join(_HERE, "libgnark_amd.so")
 
 GA_OK = 0
 BN254, BLS12_381 = 0, 1
+BLS12_377 = 2   # G1 and Fr calls only (include/gnark_amd.h): no G2, pairing or Groth16
 G1, G2 = 0, 1
 BASES_ON_DEVICE, SCALARS_ON_DEVICE, SCALARS_MONTGOMERY, TABLE_BATCHED = 0x1, 0x2, 0x4, 0x10
 RESULT_ON_DEVICE, RESULT_BITREVERSED, CHECK_CURVE_ONLY = 0x20, 0x40, 0x80

@@ -41,6 +41,22 @@ static thread_local const char* g_entry = "";
 EntryScope::EntryScope(const char* name) : prev(g_entry) { g_entry = name; }
 EntryScope::~EntryScope() { g_entry = prev; }
 const char* current_entry() { return g_entry; }
+
+int curve_not_dispatched(int curve) {
+    if (curve == GA_BLS12_377)
+        set_error("%s is not built for bls12-377 (curve id %d): that curve has the G1 and Fr calls only, its Fp2 is Fp[u]/(u^2 + 5)", current_entry(), curve);
+    else
+        set_error("unknown curve id %d", curve);
+    return GA_ERR_INVALID;
+}
+// a (curve, group) pair of a G1 / Fr call that is not built: G2 of bls12-377, or a group id that does not exist
+static int group_not_built(int curve, int group) {
+    if (curve == GA_BLS12_377 && group == GA_G2)
+        set_error("%s: G2 is not built for bls12-377 (curve id %d): that curve has the G1 and Fr calls only, its Fp2 is Fp[u]/(u^2 + 5)", current_entry(), curve);
+    else
+        set_error("unknown group id %d", group);
+    return GA_ERR_INVALID;
+}
 static uint64_t fnv1a(const char* s) {
     uint64_t h = 1469598103934665603ull;
     for (; *s; s++) h = (h ^ (uint8_t)*s) * 1099511628211ull;
@@ -251,14 +267,22 @@ static uint32_t env_segment(const char* name) {   // the two segment knobs, capp
 }
 
 // ---- argument checks the entry points share: each sets the error under the entry point's name and returns false -------------------
-static bool abi_curve_ok(int curve) {
-    if (curve == GA_BN254 || curve == GA_BLS12_381) return true;
-    set_error("%s: unknown curve id %d", current_entry(), curve);
+// g1_fr: the entry point is one of the G1 / Fr calls, which BLS12-377 has too (include/gnark_amd.h lists them); without it only the
+// two curves built in full pass, and BLS12-377 is refused by name (curve_not_dispatched), never as an unknown curve
+static bool abi_curve_ok(int curve, bool g1_fr = false) {
+    if (curve == GA_BN254 || curve == GA_BLS12_381 || (g1_fr && curve == GA_BLS12_377)) return true;
+    if (curve == GA_BLS12_377) curve_not_dispatched(curve);
+    else set_error("%s: unknown curve id %d", current_entry(), curve);
     return false;
 }
-static bool abi_curve_group_ok(int curve, int group) {
+static bool abi_curve_group_ok(int curve, int group, bool g1_fr = false) {
     if ((curve == GA_BN254 || curve == GA_BLS12_381) && (group == GA_G1 || group == GA_G2)) return true;
-    set_error("%s: unknown curve id %d or group id %d", current_entry(), curve, group);
+    if (g1_fr && curve == GA_BLS12_377 && group == GA_G1) return true;
+    if (curve == GA_BLS12_377 && (group == GA_G1 || group == GA_G2)) {
+        if (g1_fr) group_not_built(curve, group);
+        else curve_not_dispatched(curve);
+    } else
+        set_error("%s: unknown curve id %d or group id %d", current_entry(), curve, group);
     return false;
 }
 // n elements whose first has index `first`: at most 2^32 of them, and no index above 2^64 - 1
@@ -372,6 +396,16 @@ using namespace ga;
             set_error("unknown group id %d", (int)(group));     \
             return GA_ERR_INVALID;                              \
     }
+
+// every (curve, group) that is built: both groups of the curves built in full, G1 of BLS12-377
+#define GA_DISPATCH_CURVE_GROUP(curve, group, ...)                  \
+    if ((curve) == GA_BLS12_377) {                                  \
+        if ((group) != GA_G1) return group_not_built((int)(curve), (int)(group)); \
+        using C = ::ga::Bls12377;                                   \
+        constexpr int G = GA_G1;                                    \
+        __VA_ARGS__;                                                \
+    } else                                                          \
+        GA_DISPATCH_CURVE(curve, GA_DISPATCH_GROUP(group, __VA_ARGS__))
 
 extern "C" {
 
@@ -523,7 +557,7 @@ int ga_msm(ga_ctx* h, int curve, int group, const void* bases, const void* scala
         return GA_ERR_INVALID;
     }
     Lock l(c);
-    GA_DISPATCH_CURVE(curve, GA_DISPATCH_GROUP(group, return (msm_impl<C, G>(c, bases, scalars, n, flags, 0, -1, out_jac, nullptr, nullptr, false))));
+    GA_DISPATCH_CURVE_GROUP(curve, group, return (msm_impl<C, G>(c, bases, scalars, n, flags, 0, -1, out_jac, nullptr, nullptr, false)));
     return GA_OK;
 } GA_ABI_CATCH
 
@@ -536,8 +570,8 @@ int ga_msm_windows(ga_ctx* h, int curve, int group, const void* bases, const voi
         return GA_ERR_INVALID;
     }
     Lock l(c);
-    GA_DISPATCH_CURVE(curve, GA_DISPATCH_GROUP(group, return (msm_impl<C, G>(c, bases, scalars, n, flags, win_lo, win_hi, out_windows,
-                                                                            window_bits, num_windows, true))));
+    GA_DISPATCH_CURVE_GROUP(curve, group, return (msm_impl<C, G>(c, bases, scalars, n, flags, win_lo, win_hi, out_windows,
+                                                                            window_bits, num_windows, true)));
     return GA_OK;
 } GA_ABI_CATCH
 
@@ -546,7 +580,7 @@ int ga_batch_scalar_mul(ga_ctx* h, int curve, int group, const void* base_affine
                         void* out_affine) try {
     GA_ABI_ENTRY();
     Ctx* c = reinterpret_cast<Ctx*>(h);
-    if (!abi_curve_group_ok(curve, group)) return GA_ERR_INVALID;
+    if (!abi_curve_group_ok(curve, group, true)) return GA_ERR_INVALID;
     if (n == 0) return GA_OK;
     if (!c || !base_affine || !scalars || !out_affine) {
         set_error("ga_batch_scalar_mul: null argument");
@@ -559,7 +593,7 @@ int ga_batch_scalar_mul(ga_ctx* h, int curve, int group, const void* base_affine
     Lock l(c);
     const int forced_c = env_int("GA_FIXED_BASE_C", 0);
     const uint64_t forced_chunk = env_u64("GA_FIXED_BASE_CHUNK", 0);
-    GA_DISPATCH_CURVE(curve, GA_DISPATCH_GROUP(group, return (fixed_base_run<C, G>(c, base_affine, scalars, n, flags, out_affine, forced_c, forced_chunk))));
+    GA_DISPATCH_CURVE_GROUP(curve, group, return (fixed_base_run<C, G>(c, base_affine, scalars, n, flags, out_affine, forced_c, forced_chunk)));
     return GA_OK;
 } GA_ABI_CATCH
 
@@ -570,7 +604,7 @@ int ga_batch_scalar_mul_plan(int curve, size_t n, int* window_bits, int* num_win
         return GA_ERR_INVALID;
     }
     const int forced_c = env_int("GA_FIXED_BASE_C", 0);
-    GA_DISPATCH_CURVE(curve, return fixed_base_plan_abi<C>(n, forced_c, window_bits, num_windows));
+    GA_DISPATCH_CURVE_FR(curve, return fixed_base_plan_abi<C>(n, forced_c, window_bits, num_windows));
     return GA_OK;
 } GA_ABI_CATCH
 
@@ -578,7 +612,7 @@ int ga_batch_scalar_mul_plan(int curve, size_t n, int* window_bits, int* num_win
 int ga_kzg_to_lagrange_g1(ga_ctx* h, int curve, const void* powers_affine, size_t n, unsigned flags, void* out_affine) try {
     GA_ABI_ENTRY();
     Ctx* c = reinterpret_cast<Ctx*>(h);
-    if (!abi_curve_ok(curve)) return GA_ERR_INVALID;
+    if (!abi_curve_ok(curve, true)) return GA_ERR_INVALID;
     if (n == 0) return GA_OK;
     if (!c || !powers_affine || !out_affine) {
         set_error("ga_kzg_to_lagrange_g1: null argument");
@@ -586,7 +620,7 @@ int ga_kzg_to_lagrange_g1(ga_ctx* h, int curve, const void* powers_affine, size_
     }
     Lock l(c);
     const int uniform = env_flag("GA_EC_NTT_UNIFORM", 1);
-    GA_DISPATCH_CURVE(curve, return (ec_ntt_to_lagrange<C, GA_G1>(c, powers_affine, n, flags, out_affine, uniform)));
+    GA_DISPATCH_CURVE_FR(curve, return (ec_ntt_to_lagrange<C, GA_G1>(c, powers_affine, n, flags, out_affine, uniform)));
     return GA_OK;
 } GA_ABI_CATCH
 
@@ -644,7 +678,7 @@ int ga_scale_points(ga_ctx* h, int curve, int group, const void* points_affine, 
 int ga_check_points(ga_ctx* h, int curve, int group, const void* points_affine, size_t n, unsigned flags, uint8_t* status, uint64_t* out4) try {
     GA_ABI_ENTRY();
     Ctx* c = reinterpret_cast<Ctx*>(h);
-    if (!abi_curve_group_ok(curve, group)) return GA_ERR_INVALID;
+    if (!abi_curve_group_ok(curve, group, true)) return GA_ERR_INVALID;
     if ((uint64_t)n > (1ull << 32)) {
         set_error("ga_check_points: n = %zu above 2^32", n);
         return GA_ERR_INVALID;
@@ -661,7 +695,7 @@ int ga_check_points(ga_ctx* h, int curve, int group, const void* points_affine, 
     Lock l(c);
     const int naive = check_naive_knob();
     const uint64_t forced_chunk = env_u64("GA_CHECK_CHUNK", 0);
-    GA_DISPATCH_CURVE(curve, GA_DISPATCH_GROUP(group, return (check_points_run<C, G>(c, points_affine, n, flags, status, out4, naive, forced_chunk))));
+    GA_DISPATCH_CURVE_GROUP(curve, group, return (check_points_run<C, G>(c, points_affine, n, flags, status, out4, naive, forced_chunk)));
     return GA_OK;
 } GA_ABI_CATCH
 
@@ -827,7 +861,8 @@ int ga_fr_powers(ga_ctx* h, int curve, const void* scalars, uint64_t first, size
 
 int ga_msm_plan(int curve, int group, size_t n, int* window_bits, int* num_windows) try {
     GA_ABI_ENTRY();
-    GA_DISPATCH_CURVE(curve, return msm_plan<C>(group, n, window_bits, num_windows));
+    if (curve == GA_BLS12_377 && group != GA_G1) return group_not_built(curve, group);
+    GA_DISPATCH_CURVE_FR(curve, return msm_plan<C>(group, n, window_bits, num_windows));
     return GA_OK;
 } GA_ABI_CATCH
 
@@ -837,13 +872,13 @@ int ga_msm_combine_windows(int curve, int group, const void* windows, int num_wi
         set_error("ga_msm_combine_windows: bad argument");
         return GA_ERR_INVALID;
     }
-    GA_DISPATCH_CURVE(curve, GA_DISPATCH_GROUP(group, {
+    GA_DISPATCH_CURVE_GROUP(curve, group, {
                           typedef typename GroupField<C, G>::F F;
                           std::vector<XYZZ<F>> W(num_windows);
                           for (int w = 0; w < num_windows; w++)
                               W[w] = host_load_jac<F>(reinterpret_cast<const char*>(windows) + (size_t)w * sizeof(Jac<F>));
                           host_store_jac<F>(out_jac, host_horner(W.data(), num_windows, window_bits));
-                      }));
+                      });
     return GA_OK;
 } GA_ABI_CATCH
 
@@ -875,7 +910,7 @@ int ga_msm_table_create(ga_ctx* h, int curve, int group, const void* bases, size
     } own{new MsmTable{c, curve, group, 0, 0, n, nullptr, 0}};
     MsmTable* t = own.t;
     int rc = GA_OK;
-    GA_DISPATCH_CURVE(curve, GA_DISPATCH_GROUP(group, {
+    GA_DISPATCH_CURVE_GROUP(curve, group, {
                           typedef typename GroupField<C, G>::F F;
                           rc = msm_plan_table<C>(n, &t->c, &t->nwin, (flags & GA_TABLE_BATCHED) != 0);
                           t->bytes = (uint64_t)t->nwin * n * msm_table_point_bytes<C, G>();
@@ -890,7 +925,7 @@ int ga_msm_table_create(ga_ctx* h, int curve, int group, const void* bases, size
                               set_error("ga_msm_table_create: table kernel failed");
                               rc = GA_ERR_HIP;
                           }
-                      }));
+                      });
     if (rc != GA_OK) return rc;
     own.t = nullptr;
     *out = reinterpret_cast<ga_msm_table*>(t);
@@ -927,14 +962,14 @@ int ga_msm_table_run(ga_msm_table* th, const void* scalars, unsigned flags, void
     }
     Ctx* c = t->ctx;
     LaneLock l(c);   // a second caller (the PLONK prover commits from several goroutines) runs beside the first on lane 1
-    GA_DISPATCH_CURVE(t->curve, GA_DISPATCH_GROUP(t->group, {
+    GA_DISPATCH_CURVE_GROUP(t->curve, t->group, {
                           typedef typename GroupField<C, G>::F F;
                           Staged ss{c};
                           GA_CHECK(ss.stage(scalars, t->n * 32, flags & GA_SCALARS_ON_DEVICE));
                           XYZZ<F> sum;
                           GA_CHECK((msm_table_device<C, G>(c, t->d_table, ss.dev, t->n, (flags & GA_SCALARS_MONTGOMERY) != 0, t->c, &sum)));
                           host_store_jac<F>(out_jac, sum);
-                      }));
+                      });
     return GA_OK;
 } GA_ABI_CATCH
 
@@ -957,7 +992,7 @@ int ga_msm_table_run_batch(ga_msm_table* th, const void* const* scalars, uint32_
     }
     Ctx* c = t->ctx;
     LaneLock l(c);   // a second caller (the PLONK prover commits from several goroutines) runs beside the first on lane 1
-    GA_DISPATCH_CURVE(t->curve, GA_DISPATCH_GROUP(t->group, {
+    GA_DISPATCH_CURVE_GROUP(t->curve, t->group, {
                           typedef typename GroupField<C, G>::F F;
                           std::vector<std::unique_ptr<Staged>> st;
                           std::vector<const void*> dev(k);
@@ -970,7 +1005,7 @@ int ga_msm_table_run_batch(ga_msm_table* th, const void* const* scalars, uint32_
                           GA_CHECK((msm_table_device_batch<C, G>(c, t->d_table, dev.data(), (int)k, t->n, (flags & GA_SCALARS_MONTGOMERY) != 0,
                                                                  t->c, sums.data())));
                           for (uint32_t j = 0; j < k; j++) host_store_jac<F>((char*)out_jacs + j * sizeof(Jac<F>), sums[j]);
-                      }));
+                      });
     return GA_OK;
 } GA_ABI_CATCH
 
@@ -987,7 +1022,7 @@ int ga_msm_table_run_windows(ga_msm_table* th, const void* scalars, unsigned fla
     }
     Ctx* c = t->ctx;
     LaneLock l(c);   // a second caller (the PLONK prover commits from several goroutines) runs beside the first on lane 1
-    GA_DISPATCH_CURVE(t->curve, GA_DISPATCH_GROUP(t->group, {
+    GA_DISPATCH_CURVE_GROUP(t->curve, t->group, {
                           typedef typename GroupField<C, G>::F F;
                           Staged ss{c};
                           GA_CHECK(ss.stage(scalars, t->n * 32, flags & GA_SCALARS_ON_DEVICE));
@@ -995,7 +1030,7 @@ int ga_msm_table_run_windows(ga_msm_table* th, const void* scalars, unsigned fla
                           GA_CHECK((msm_table_device<C, G>(c, t->d_table, ss.dev, t->n, (flags & GA_SCALARS_MONTGOMERY) != 0, t->c, &sum, win_lo,
                                                            win_hi)));
                           host_store_jac<F>(out_jac, sum);
-                      }));
+                      });
     return GA_OK;
 } GA_ABI_CATCH
 
@@ -1013,7 +1048,7 @@ int ga_fr_linear_combination(ga_ctx* h, int curve, uint64_t n, int k, const void
             return GA_ERR_INVALID;
         }
     Lock l(c);
-    GA_DISPATCH_CURVE(curve, GA_CHECK(fr_vec_lincomb<C>(c, n, k, vecs, scalars, out, on_device != 0)));
+    GA_DISPATCH_CURVE_FR(curve, GA_CHECK(fr_vec_lincomb<C>(c, n, k, vecs, scalars, out, on_device != 0)));
     return GA_OK;
 } GA_ABI_CATCH
 
@@ -1035,7 +1070,7 @@ int ga_fr_poly_evaluate(ga_ctx* h, int curve, const void* poly, uint64_t n, cons
     void* q;
     GA_CHECK(c->scratch_get("kzg_quotient", n * 32, &q));
     const uint64_t scan_threads = env_plonk_batch_knobs().scan_threads;
-    GA_DISPATCH_CURVE(curve, GA_CHECK(kzg_domain_divide<C>(c, sp.dev, n, point, q, value_out, scan_threads)));
+    GA_DISPATCH_CURVE_FR(curve, GA_CHECK(kzg_domain_divide<C>(c, sp.dev, n, point, q, value_out, scan_threads)));
     return GA_OK;
 } GA_ABI_CATCH
 
@@ -1054,7 +1089,7 @@ int ga_kzg_open(ga_msm_table* th, const void* poly, size_t n, unsigned flags, co
     Ctx* c = t->ctx;
     Lock l(c);
     const uint64_t scan_threads = env_plonk_batch_knobs().scan_threads;
-    GA_DISPATCH_CURVE(t->curve, {
+    GA_DISPATCH_CURVE_FR(t->curve, {
         typedef typename GroupField<C, GA_G1>::F F;
         Staged sp{c};
         GA_CHECK(sp.stage(poly, n * 32, flags & GA_SCALARS_ON_DEVICE));
@@ -1101,7 +1136,7 @@ int ga_kzg_open_batch(ga_msm_table* th, const void* const* polys, size_t n, uint
     }
     const bool on_device = (flags & GA_SCALARS_ON_DEVICE) != 0;
     const size_t qn = n > t->n ? n : t->n;   // a row of quotients: the table's n scalars (zero beyond the n - 1 coefficients)
-    GA_DISPATCH_CURVE(t->curve, {
+    GA_DISPATCH_CURVE_FR(t->curve, {
         typedef typename GroupField<C, GA_G1>::F F;
         char *in = nullptr, *q = nullptr, *vals = nullptr;
         auto reserve = [&](uint32_t cnt) -> int {
@@ -1143,30 +1178,30 @@ int ga_kzg_open_batch(ga_msm_table* th, const void* const* polys, size_t n, uint
 // ---- host group helpers ---------------------------------------------------------------------------------
 int ga_jac_add(int curve, int group, const void* a, const void* b, void* out) try {
     GA_ABI_ENTRY();
-    GA_DISPATCH_CURVE(curve, GA_DISPATCH_GROUP(group, {
+    GA_DISPATCH_CURVE_GROUP(curve, group, {
                           typedef typename GroupField<C, G>::F F;
                           host_store_jac<F>(out, add(host_load_jac<F>(a), host_load_jac<F>(b)));
-                      }));
+                      });
     return GA_OK;
 } GA_ABI_CATCH
 
 int ga_jac_to_affine(int curve, int group, const void* a, void* out) try {
     GA_ABI_ENTRY();
-    GA_DISPATCH_CURVE(curve, GA_DISPATCH_GROUP(group, {
+    GA_DISPATCH_CURVE_GROUP(curve, group, {
                           typedef typename GroupField<C, G>::F F;
                           host_store_affine<F>(out, host_load_jac<F>(a));
-                      }));
+                      });
     return GA_OK;
 } GA_ABI_CATCH
 
 int ga_jac_scalar_mul(int curve, int group, const void* a, const void* k, void* out) try {
     GA_ABI_ENTRY();
-    GA_DISPATCH_CURVE(curve, GA_DISPATCH_GROUP(group, {
+    GA_DISPATCH_CURVE_GROUP(curve, group, {
                           typedef typename GroupField<C, G>::F F;
                           uint32_t kw[8];
                           memcpy(kw, k, 32);
                           host_store_jac<F>(out, scalar_mul(host_load_jac<F>(a), kw, 8));
-                      }));
+                      });
     return GA_OK;
 } GA_ABI_CATCH
 
@@ -1180,7 +1215,7 @@ int ga_domain_create(ga_ctx* h, int curve, uint64_t cardinality, ga_domain** out
     }
     Lock l(c);
     Domain* d = nullptr;
-    GA_DISPATCH_CURVE(curve, GA_CHECK(ntt_domain_new<C>(c, cardinality, &d)));
+    GA_DISPATCH_CURVE_FR(curve, GA_CHECK(ntt_domain_new<C>(c, cardinality, &d)));
     *out = reinterpret_cast<ga_domain*>(d);
     return GA_OK;
 } GA_ABI_CATCH
@@ -1209,7 +1244,7 @@ int ga_fft(ga_domain* dh, void* data, int direction, int decimation, int on_cose
         GA_CHECK(c->scratch_get("fft_io", bytes, &dev));
         GA_HIP_CHECK(hipMemcpyAsync(dev, data, bytes, hipMemcpyHostToDevice, c->stream));
     }
-    GA_DISPATCH_CURVE(ntt_domain_curve(d), GA_CHECK(ntt_domain_fft<C>(d, dev, direction, decimation, on_coset)));
+    GA_DISPATCH_CURVE_FR(ntt_domain_curve(d), GA_CHECK(ntt_domain_fft<C>(d, dev, direction, decimation, on_coset)));
     if (!on_device) GA_HIP_CHECK(hipMemcpyAsync(data, dev, bytes, hipMemcpyDeviceToHost, c->stream));
     GA_HIP_CHECK(hipStreamSynchronize(c->stream));
     return GA_OK;
@@ -1234,7 +1269,7 @@ int ga_fft_batch(ga_domain* dh, void* data, uint32_t count, int direction, int d
         GA_CHECK(c->scratch_get("fft_batch_io", bytes, &dev));
         GA_HIP_CHECK(hipMemcpyAsync(dev, data, bytes, hipMemcpyHostToDevice, c->stream));
     }
-    GA_DISPATCH_CURVE(ntt_domain_curve(d), GA_CHECK(ntt_domain_fft<C>(d, dev, direction, decimation, on_coset, count)));
+    GA_DISPATCH_CURVE_FR(ntt_domain_curve(d), GA_CHECK(ntt_domain_fft<C>(d, dev, direction, decimation, on_coset, count)));
     if (!on_device) GA_HIP_CHECK(hipMemcpyAsync(data, dev, bytes, hipMemcpyDeviceToHost, c->stream));
     GA_HIP_CHECK(hipStreamSynchronize(c->stream));
     return GA_OK;
@@ -1286,7 +1321,7 @@ int ga_plonk_quotient(ga_domain* dh0, ga_domain* dh1, const ga_plonk_quotient_in
     Lock l(c);
     PlonkQuotientArgs a;
     GA_CHECK(plonk_args_from(in, true, true, &a));
-    GA_DISPATCH_CURVE(ntt_domain_curve(d0), GA_CHECK(plonk_domain_quotient<C>(d0, d1, a, h_out)));
+    GA_DISPATCH_CURVE_FR(ntt_domain_curve(d0), GA_CHECK(plonk_domain_quotient<C>(d0, d1, a, h_out)));
     return GA_OK;
 } GA_ABI_CATCH
 
@@ -1302,7 +1337,7 @@ int ga_plonk_pk_create(ga_domain* dh0, ga_domain* dh1, const ga_plonk_quotient_i
     PlonkQuotientArgs a;
     GA_CHECK(plonk_args_from(in, true, false, &a));
     PlonkFixed* fx = nullptr;
-    GA_DISPATCH_CURVE(ntt_domain_curve(d0), GA_CHECK(plonk_domain_fixed_create<C>(d0, d1, a, &fx)));
+    GA_DISPATCH_CURVE_FR(ntt_domain_curve(d0), GA_CHECK(plonk_domain_fixed_create<C>(d0, d1, a, &fx)));
     *out = reinterpret_cast<ga_plonk_pk*>(fx);
     return GA_OK;
 } GA_ABI_CATCH
@@ -1330,7 +1365,7 @@ int ga_plonk_quotient_pinned(ga_plonk_pk* p, const ga_plonk_quotient_in* in, voi
     PlonkQuotientArgs a;
     GA_CHECK(plonk_args_from(in, false, true, &a));
     const uint64_t scan_threads = env_plonk_batch_knobs().scan_threads;
-    GA_DISPATCH_CURVE(ntt_domain_curve(d0), GA_CHECK(plonk_domain_quotient_pinned<C>(fx, a, scan_threads, h_out)));
+    GA_DISPATCH_CURVE_FR(ntt_domain_curve(d0), GA_CHECK(plonk_domain_quotient_pinned<C>(fx, a, scan_threads, h_out)));
     return GA_OK;
 } GA_ABI_CATCH
 
@@ -1346,7 +1381,7 @@ int ga_plonk_build_z(ga_domain* dh0, const void* lv, const void* rv, const void*
     Lock l(c);
     if (!on_device && !abi_permutation_ok(permutation, 3 * ntt_domain_size(d0))) return GA_ERR_INVALID;
     const uint64_t scan_threads = env_plonk_batch_knobs().scan_threads;
-    GA_DISPATCH_CURVE(ntt_domain_curve(d0),
+    GA_DISPATCH_CURVE_FR(ntt_domain_curve(d0),
                       GA_CHECK(plonk_domain_build_z<C>(d0, lv, rv, ov, permutation, beta, gamma, scan_threads, on_device != 0, z_out)));
     return GA_OK;
 } GA_ABI_CATCH
@@ -1364,7 +1399,7 @@ int ga_plonk_build_z_batch(ga_domain* dh0, const void* lv, const void* rv, const
     Lock l(c);
     if (!on_device && !abi_permutation_ok(permutation, 3 * ntt_domain_size(d0))) return GA_ERR_INVALID;
     const PlonkBatchKnobs knobs = env_plonk_batch_knobs();
-    GA_DISPATCH_CURVE(ntt_domain_curve(d0), GA_CHECK(plonk_domain_build_z_batch<C>(d0, lv, rv, ov, permutation, betas, gammas, count, knobs,
+    GA_DISPATCH_CURVE_FR(ntt_domain_curve(d0), GA_CHECK(plonk_domain_build_z_batch<C>(d0, lv, rv, ov, permutation, betas, gammas, count, knobs,
                                                                                   on_device != 0, z_out)));
     return GA_OK;
 } GA_ABI_CATCH
@@ -1389,7 +1424,7 @@ int ga_plonk_quotient_pinned_batch(ga_plonk_pk* p, const ga_plonk_quotient_in* i
         GA_CHECK(plonk_args_from(&ins[j], false, true, &a[j]));
     }
     const PlonkBatchKnobs knobs = env_plonk_batch_knobs();
-    GA_DISPATCH_CURVE(ntt_domain_curve(d0), GA_CHECK(plonk_domain_quotient_pinned_batch<C>(fx, a.data(), count, knobs, h_out)));
+    GA_DISPATCH_CURVE_FR(ntt_domain_curve(d0), GA_CHECK(plonk_domain_quotient_pinned_batch<C>(fx, a.data(), count, knobs, h_out)));
     return GA_OK;
 } GA_ABI_CATCH
 
@@ -1401,7 +1436,7 @@ int ga_fr_batch_invert(ga_ctx* h, int curve, void* v, uint64_t n, int on_device)
         return GA_ERR_INVALID;
     }
     Lock l(c);
-    GA_DISPATCH_CURVE(curve, GA_CHECK(fr_vec_batch_inverse<C>(c, v, n, on_device != 0)));
+    GA_DISPATCH_CURVE_FR(curve, GA_CHECK(fr_vec_batch_inverse<C>(c, v, n, on_device != 0)));
     return GA_OK;
 } GA_ABI_CATCH
 
@@ -1426,7 +1461,7 @@ int ga_compute_h(ga_domain* dh, const void* a, const void* b, const void* cc, ui
         GA_HIP_CHECK(hipMemcpyAsync(dst[k], src[k], part, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
         if (full > part) GA_HIP_CHECK(hipMemsetAsync(reinterpret_cast<char*>(dst[k]) + part, 0, full - part, c->stream));
     }
-    GA_DISPATCH_CURVE(ntt_domain_curve(d), GA_CHECK(ntt_domain_compute_h<C>(d, da, db, dc)));
+    GA_DISPATCH_CURVE_FR(ntt_domain_curve(d), GA_CHECK(ntt_domain_compute_h<C>(d, da, db, dc)));
     GA_HIP_CHECK(hipMemcpyAsync(h_out, da, full, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
     GA_HIP_CHECK(hipStreamSynchronize(c->stream));
     return GA_OK;
@@ -1461,9 +1496,9 @@ int ga_compute_h_batch(ga_domain* dh, const void* a, const void* b, const void* 
             for (uint32_t j = 0; j < count; j++)
                 GA_HIP_CHECK(hipMemcpyAsync((char*)dst[k] + j * full, (const char*)src[k] + j * part, part, in, c->stream));
         }
-        GA_DISPATCH_CURVE(ntt_domain_curve(d), GA_CHECK(util_pad_fr_batch<C>(c, dst[k], n_constraints, n, count, c->stream)));
+        GA_DISPATCH_CURVE_FR(ntt_domain_curve(d), GA_CHECK(util_pad_fr_batch<C>(c, dst[k], n_constraints, n, count, c->stream)));
     }
-    GA_DISPATCH_CURVE(ntt_domain_curve(d), GA_CHECK(ntt_domain_compute_h<C>(d, da, db, dc, count)));
+    GA_DISPATCH_CURVE_FR(ntt_domain_curve(d), GA_CHECK(ntt_domain_compute_h<C>(d, da, db, dc, count)));
     GA_HIP_CHECK(hipMemcpyAsync(h_out, da, (size_t)count * full, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
     GA_HIP_CHECK(hipStreamSynchronize(c->stream));
     return GA_OK;
@@ -1514,7 +1549,7 @@ int ga_gen_bases(ga_ctx* h, int curve, int group, uint64_t seed, size_t n, void*
     GA_ABI_ENTRY();
     Ctx* c = reinterpret_cast<Ctx*>(h);
     Lock l(c);
-    GA_DISPATCH_CURVE(curve, GA_DISPATCH_GROUP(group, GA_CHECK((util_gen_bases<C, G>(c, seed, n, bases_dev, dlogs_dev)))));
+    GA_DISPATCH_CURVE_GROUP(curve, group, GA_CHECK((util_gen_bases<C, G>(c, seed, n, bases_dev, dlogs_dev))));
     GA_HIP_CHECK(hipStreamSynchronize(c->stream));
     return GA_OK;
 } GA_ABI_CATCH
@@ -1523,7 +1558,7 @@ int ga_gen_bases_at(ga_ctx* h, int curve, int group, uint64_t seed, uint64_t fir
     GA_ABI_ENTRY();
     Ctx* c = reinterpret_cast<Ctx*>(h);
     Lock l(c);
-    GA_DISPATCH_CURVE(curve, GA_DISPATCH_GROUP(group, GA_CHECK((util_gen_bases<C, G>(c, seed, n, bases_dev, dlogs_dev, first)))));
+    GA_DISPATCH_CURVE_GROUP(curve, group, GA_CHECK((util_gen_bases<C, G>(c, seed, n, bases_dev, dlogs_dev, first))));
     GA_HIP_CHECK(hipStreamSynchronize(c->stream));
     return GA_OK;
 } GA_ABI_CATCH
@@ -1532,7 +1567,7 @@ int ga_gen_scalars(ga_ctx* h, int curve, uint64_t seed, size_t n, void* scalars_
     GA_ABI_ENTRY();
     Ctx* c = reinterpret_cast<Ctx*>(h);
     Lock l(c);
-    GA_DISPATCH_CURVE(curve, GA_CHECK(util_gen_scalars<C>(c, seed, n, scalars_dev)));
+    GA_DISPATCH_CURVE_FR(curve, GA_CHECK(util_gen_scalars<C>(c, seed, n, scalars_dev)));
     GA_HIP_CHECK(hipStreamSynchronize(c->stream));
     return GA_OK;
 } GA_ABI_CATCH
@@ -1541,7 +1576,7 @@ int ga_fr_dot(ga_ctx* h, int curve, const void* a_dev, const void* b_dev, size_t
     GA_ABI_ENTRY();
     Ctx* c = reinterpret_cast<Ctx*>(h);
     Lock l(c);
-    GA_DISPATCH_CURVE(curve, GA_CHECK(util_fr_dot<C>(c, a_dev, b_dev, n, out_host)));
+    GA_DISPATCH_CURVE_FR(curve, GA_CHECK(util_fr_dot<C>(c, a_dev, b_dev, n, out_host)));
     return GA_OK;
 } GA_ABI_CATCH
 
@@ -1559,7 +1594,7 @@ int ga_fr_vec_mul(ga_ctx* h, int curve, const void* a, const void* b, size_t n, 
     GA_CHECK(sb.stage(b, n * 32, on_device));
     void* d_out = out;
     if (!on_device) GA_CHECK(c->scratch_get("fr_vec_out", n * 32, &d_out));
-    GA_DISPATCH_CURVE(curve, GA_CHECK(util_fr_vec_mul<C>(c, sa.dev, sb.dev, n, d_out)));
+    GA_DISPATCH_CURVE_FR(curve, GA_CHECK(util_fr_vec_mul<C>(c, sa.dev, sb.dev, n, d_out)));
     if (!on_device) GA_HIP_CHECK(hipMemcpyAsync(out, d_out, n * 32, hipMemcpyDeviceToHost, c->stream));
     GA_HIP_CHECK(hipStreamSynchronize(c->stream));
     return GA_OK;
@@ -1567,12 +1602,12 @@ int ga_fr_vec_mul(ga_ctx* h, int curve, const void* a, const void* b, size_t n, 
 
 int ga_generator_mul(int curve, int group, const void* k, void* out_jac) try {
     GA_ABI_ENTRY();
-    GA_DISPATCH_CURVE(curve, GA_DISPATCH_GROUP(group, {
+    GA_DISPATCH_CURVE_GROUP(curve, group, {
                           typedef typename GroupField<C, G>::F F;
                           uint32_t kw[8];
                           memcpy(kw, k, 32);
                           host_store_jac<F>(out_jac, scalar_mul(to_xyzz(Generator<C, G>::get()), kw, 8));
-                      }));
+                      });
     return GA_OK;
 } GA_ABI_CATCH
 

@@ -3,7 +3,8 @@
 // GA_POINT_NOT_IN_SUBGROUP; the truth is "on the curve and [r]P = O", decided per group by an identity in the curve's 64-bit seed x0
 // (constants: tools/gen_constants.py endo_constants, which asserts each identity on the generator):
 //   BN254 G1      cofactor 1: the curve equation alone.
-//   BLS12-381 G1  P + [x0^2] phi(P) = O,  phi(x, y) = (BETA x, y): two ladders by |x0|, then BETA X2 = x ZZ2, Y2 = -y ZZZ2.
+//   BLS12-381 G1, BLS12-377 G1
+//                 P + [x0^2] phi(P) = O,  phi(x, y) = (BETA x, y): two ladders by |x0|, then BETA X2 = x ZZ2, Y2 = -y ZZZ2.
 //   BLS12-381 G2  psi(P) = [x0] P,  x0 = -|x0|: one ladder, then psi(P) = -[|x0|]P.
 //   BN254 G2      [x0 + 1]P + psi([x0]P) + psi^2([x0]P) = psi^3([2 x0]P): one ladder, five complete additions, one comparison.
 //
@@ -50,6 +51,10 @@ template <> struct CheckRule<Fe<BLS12_381_Fp>> {
 template <> struct CheckRule<Fe2<BLS12_381_Fp>> {
     static constexpr int RULE = CHECK_RULE_BLS_G2;
     static constexpr uint64_t SEED = 0xd201000000010000ull;
+};
+template <> struct CheckRule<Fe<BLS12_377_Fp>> {               // (G1 only: no rule over Fe2 of this field, common.hip.h HAS_G2)
+    static constexpr int RULE = CHECK_RULE_BLS_G1;
+    static constexpr uint64_t SEED = 0x8508c00000000001ull;    // x0 > 0: 64 bits, weight 7
 };
 
 // waves per SIMD asked of the two ladder kernels (DESIGN.md 4.12 has the register figures).  The fast kernel over Fp2 takes the whole

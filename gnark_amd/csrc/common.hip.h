@@ -105,19 +105,33 @@ inline hipError_t device_malloc(T** p, size_t bytes) {
 #define GA_KERNEL_CHECK() GA_HIP_CHECK(hipGetLastError())
 
 // ---- curve tags ----------------------------------------------------------------------------------
+// HAS_G2: the curve's Fp2 is Fp[u]/(u^2 + 1), the only quadratic extension Fe2 / F29x2 implement, so G2, the pairing and Groth16
+// are built for it.  BLS12-377's is u^2 + 5: that curve is G1 and Fr only, and GroupField refuses to name an Fe2 over its Fp (the
+// u^2 + 1 arithmetic would compile and be wrong); its constants carry no G2*, PSI*, FROB* or FP2Z either.
 struct Bn254 {
     static constexpr int ID = GA_BN254;
+    static constexpr bool HAS_G2 = true;
     using FpP = BN254_Fp;
     using FrP = BN254_Fr;
 };
 struct Bls12381 {
     static constexpr int ID = GA_BLS12_381;
+    static constexpr bool HAS_G2 = true;
     using FpP = BLS12_381_Fp;
     using FrP = BLS12_381_Fr;
 };
+struct Bls12377 {
+    static constexpr int ID = GA_BLS12_377;
+    static constexpr bool HAS_G2 = false;
+    using FpP = BLS12_377_Fp;
+    using FrP = BLS12_377_Fr;
+};
 template <class C, int G> struct GroupField;
 template <class C> struct GroupField<C, GA_G1> { using F = Fe<typename C::FpP>; };
-template <class C> struct GroupField<C, GA_G2> { using F = Fe2<typename C::FpP>; };
+template <class C> struct GroupField<C, GA_G2> {
+    static_assert(C::HAS_G2, "no G2 for this curve: its Fp2 is not Fp[u]/(u^2 + 1)");
+    using F = Fe2<typename C::FpP>;
+};
 
 GA_HD uint64_t splitmix64(uint64_t x) {
     x += 0x9E3779B97F4A7C15ull;
@@ -647,6 +661,13 @@ template <class C> int util_pad_fr_batch(Ctx* ctx, void* d_v, uint64_t from, uin
 int util_microbench(Ctx* ctx, char* buf, size_t cap);
 int util_clock_probe(Ctx* ctx, uint32_t micros, double* mhz_out);
 
+// The answer to a curve id no case of a dispatch takes: a curve that is built in part (BLS12-377: G1 and Fr) is named, with the
+// entry point that is not built for it; anything else is an unknown id.  Returns GA_ERR_INVALID.
+int curve_not_dispatched(int curve);
+
+// GA_DISPATCH_CURVE: the curves built in full -- its body may name G2, the pairing, Groth16 and the setup calls.
+// GA_DISPATCH_CURVE_FR: every curve -- the body may use C::FrP and Fe<C::FpP> (G1) only.
+// GA_DISPATCH_CURVE_GROUP(curve, group, body): every (curve, group) that is built, G bound like GA_DISPATCH_GROUP does.
 #define GA_DISPATCH_CURVE(curve, ...)                                \
     switch (curve) {                                                 \
         case GA_BN254: {                                             \
@@ -658,8 +679,24 @@ int util_clock_probe(Ctx* ctx, uint32_t micros, double* mhz_out);
             __VA_ARGS__;                                             \
         } break;                                                     \
         default:                                                     \
-            ::ga::set_error("unknown curve id %d", (int)(curve));    \
-            return GA_ERR_INVALID;                                   \
+            return ::ga::curve_not_dispatched((int)(curve));         \
+    }
+#define GA_DISPATCH_CURVE_FR(curve, ...)                             \
+    switch (curve) {                                                 \
+        case GA_BN254: {                                             \
+            using C = ::ga::Bn254;                                   \
+            __VA_ARGS__;                                             \
+        } break;                                                     \
+        case GA_BLS12_381: {                                         \
+            using C = ::ga::Bls12381;                                \
+            __VA_ARGS__;                                             \
+        } break;                                                     \
+        case GA_BLS12_377: {                                         \
+            using C = ::ga::Bls12377;                                \
+            __VA_ARGS__;                                             \
+        } break;                                                     \
+        default:                                                     \
+            return ::ga::curve_not_dispatched((int)(curve));         \
     }
 
 }  // namespace ga

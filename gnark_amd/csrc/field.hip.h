@@ -91,6 +91,12 @@ GA_HD void reduce_once(uint32_t* a) {
     for (int i = 0; i < P::N; i++) a[i] = keep ? t[i] : a[i];
 }
 
+// reduce_once steps that bring ANY 32N-bit integer below the modulus (a caller's canonical scalar, a big.Int's bytes): at least
+// 2^(32N) / p - 1.  The 254- and 255-bit scalar fields need 5 and 2 and have always taken 6; BLS12-377's 253-bit r = 1.17 * 2^252
+// needs 13.
+template <class P>
+constexpr int canonical_steps() { return P::BITS + 2 >= 32 * P::N ? 6 : (1 << (32 * P::N - P::BITS + 1)); }
+
 // ---- field API --------------------------------------------------------------------------------
 
 template <class P>

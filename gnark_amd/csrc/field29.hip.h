@@ -271,6 +271,8 @@ GA_HD_BIG Fe<P> f29_to_mem(const F29<P>& a) {
 // one step towards [0, p): v - q*p with q = floor(v / 2^BITS), for any normalized v < 2^(NL*L).  The result is >= 0 and below
 // 2^BITS + q*(2^BITS - p).  It is below 4p only for inputs v < 2^(BITS+3) (q <= 7; all four moduli exceed 8/11 * 2^BITS), which is
 // what every caller passes; a larger v is still reduced correctly but may leave more (tests/field_cases.py case_lazy_reductions).
+// (Its callers are the Fp2 formulas, so the four moduli are those of the two curves built with G2; BLS12-377 never comes here, and its
+// r = 0.58 * 2^BITS would not keep the 4p.)
 template <class P>
 GA_HD F29<P> f29_partial_reduce(const F29<P>& a) {
     typedef Radix<P> R;
@@ -299,6 +301,11 @@ GA_HD F29<P> f29_partial_reduce(const F29<P>& a) {
 // at most 1 too small: the result is in [0, 1.35 p) for all four fields (below 1.3496 p BN254 Fp/Fr, 1.2607 p BLS12-381 Fp,
 // 1.2152 p BLS12-381 Fr; every top-limb estimate enumerated in tests/field_cases.py reduce_3p_bound).  Its consumers need only [0, 3p) and a
 // result that fits 32N bits -- 3p itself would not for BLS12-381 Fr.  Used where sums keep doubling (NTT butterflies).
+// BLS12-377 (tools/lazy_bounds.py check_reduce_3p, tests/test_bls12_377.py): the 12 fraction bits of MU12 lose up to one unit of q per
+// 4096 of the estimate, which the four fields above never feel (2^(BITS+8) / p is within 0.05 of an integer for three of them).  Its
+// Fr: 438.8 -> 438, residue below 1.87 r for any normalized v -- inside [0, 3r) and 32N bits.  Its Fp: 304.7 -> 304 with 15 spare bits
+// above p, so the residue stays below 3p only for v < 2^386.5; every lazy value of the G1 formulas is below 2^380 (lazy_bounds), where
+// it is below 1.1 p.
 template <class P>
 GA_HD F29<P> f29_reduce_3p(const F29<P>& a) {
     typedef Radix<P> R;

@@ -11,7 +11,7 @@ template <class FrP>
 GA_HD Fe<FrP> fr_canonical(Fe<FrP> s, int mont) {
     if (mont) return from_mont(s);
 #pragma unroll 1
-    for (int k = 0; k < 6; k++) reduce_once<FrP>(s.l);   // any 256-bit integer: below r after at most 2^256 / r < 6 steps
+    for (int k = 0; k < canonical_steps<FrP>(); k++) reduce_once<FrP>(s.l);   // any 256-bit integer: below r (field.hip.h)
     return s;
 }
 

@@ -796,6 +796,7 @@ static bool key_points_present(const ga_g16_key* key) {
 // that this function starts before it returns -- plain vectors only (no tables), the whole key on one device; the caller must keep
 // the host vectors alive until the thread has been joined (pk_free does).
 static int pk_create_from_struct(Ctx* ctx, const ga_g16_key* key, G16Pk** out, bool defer_uploads = false) {
+    if (key->curve == GA_BLS12_377) return curve_not_dispatched(key->curve);   // G1 / Fr only: refused before anything is staged
     if (!key_points_present(key)) {
         set_error("ga_g16_pk_create: null pointer inside ga_g16_key");
         return GA_ERR_INVALID;

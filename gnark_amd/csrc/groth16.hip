@@ -999,6 +999,7 @@ int ga_g16_builder_create(ga_ctx* h, int curve, uint64_t domain_cardinality, uin
                           uint32_t shard_count, ga_g16_builder** out) try {
     GA_ABI_ENTRY();
     Ctx* ctx = reinterpret_cast<Ctx*>(h);
+    if (curve == GA_BLS12_377) return curve_not_dispatched(curve);   // G1 / Fr only: no Groth16 key on that curve
     if (!ctx || !out || (curve != GA_BN254 && curve != GA_BLS12_381) || domain_cardinality == 0) {
         set_error("ga_g16_builder_create: bad argument");
         return GA_ERR_INVALID;

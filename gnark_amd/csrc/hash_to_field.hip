@@ -114,7 +114,7 @@ static int expand_message_xmd(const uint8_t* msg, size_t msg_len, const uint8_t*
 template <class C>
 static int hash_to_field(const uint8_t* msg, size_t msg_len, const uint8_t* dst, size_t dst_len, uint32_t count, void* out) {
     typedef typename C::FrP FrP;
-    const size_t L = 16 + (FrP::BITS + 7) / 8;   // 48 for both scalar fields
+    const size_t L = 16 + (FrP::BITS + 7) / 8;   // 48 for the three scalar fields (253 .. 255 bits)
     std::vector<uint8_t> bytes;
     GA_CHECK(expand_message_xmd(msg, msg_len, dst, dst_len, (size_t)count * L, &bytes));
     Fe<FrP> c256 = fe_zero<FrP>();
@@ -142,7 +142,7 @@ extern "C" int ga_hash_to_field(int curve, const uint8_t* msg, size_t msg_len, c
         set_error("ga_hash_to_field: null argument");
         return GA_ERR_INVALID;
     }
-    GA_DISPATCH_CURVE(curve, return hash_to_field<C>(msg, msg_len, dst, dst_len, count, out));
+    GA_DISPATCH_CURVE_FR(curve, return hash_to_field<C>(msg, msg_len, dst, dst_len, count, out));
     return GA_OK;
 } GA_ABI_CATCH
 

@@ -57,10 +57,12 @@ struct DigitWalk {
         s = raw;
         if (mont) s = from_mont(s);
         else {
-            // canonical input may be any 256-bit integer (a caller's big.Int bytes): bring it below r, at most 2^256 / r < 6 steps,
+            // canonical input may be any 256-bit integer (a caller's big.Int bytes): bring it below r (canonical_steps, field.hip.h),
             // so that only (BITS mod c) bits are live in the top window as the digit loop assumes
+            // (BITS mod c == 0 -- c = 15, 17 for the 255-bit field, c = 11, 23 for BLS12-377's 253 bits -- leaves the top window of
+            // BITS / c + 1 with the signed-digit carry alone: digit 0 or 1, never negative, so nothing carries out of it)
 #pragma unroll 1
-            for (int k = 0; k < 6; k++) reduce_once<FrP>(s.l);
+            for (int k = 0; k < canonical_steps<FrP>(); k++) reduce_once<FrP>(s.l);
         }
     }
     __device__ __forceinline__ void next(int c, int w, int win_lo, uint64_t n, uint64_t i, int table, uint32_t key_base, uint32_t skip,

@@ -8,17 +8,18 @@ import numpy as np
 
 from . import _lib
 
-FP_LIMBS = {_lib.BN254: 4, _lib.BLS12_381: 6}
+FP_LIMBS = {_lib.BN254: 4, _lib.BLS12_381: 6, _lib.BLS12_377: 6}
 FR_LIMBS = 4
 CURVE_IDS = {"bn254": _lib.BN254, "bls12-381": _lib.BLS12_381, "bls12_381": _lib.BLS12_381,
-             _lib.BN254: _lib.BN254, _lib.BLS12_381: _lib.BLS12_381}
+             "bls12-377": _lib.BLS12_377, "bls12_377": _lib.BLS12_377,
+             _lib.BN254: _lib.BN254, _lib.BLS12_381: _lib.BLS12_381, _lib.BLS12_377: _lib.BLS12_377}
 
 
 def curve_id(curve) -> int:
     try:
         return CURVE_IDS[curve]
     except KeyError:
-        raise ValueError(f"unsupported curve {curve!r} (built: bn254, bls12-381)") from None
+        raise ValueError(f"unsupported curve {curve!r} (built: bn254, bls12-381; bls12-377 for the G1 and Fr calls)") from None
 
 
 def affine_words(curve: int, group: int) -> int:

@@ -96,7 +96,7 @@ def ToLagrangeG1(ctx: Context, curve, powers, n: int | None = None, out_device: 
     """kzg.ToLagrangeG1 (gnark-crypto ecc/<curve>/kzg): powers[i] = [tau^i]G1 -> [l_i(tau)]G1 over the size-n domain, natural order.
 
     powers : (n, affine_words) uint64 array of G1Affine images or a DeviceBuffer of n points (then n is required); never modified
-    n must be a power of two (at most 2^28 for BN254, 2^32 for BLS12-381).  The points are not validated.
+    n must be a power of two (at most 2^28 for BN254, 2^32 for BLS12-381, 2^47 for BLS12-377).  The points are not validated.
     Returns an (n, affine_words) array, or with out_device=True a DeviceBuffer of n affine points (the caller frees it) that
     MultiExp and PrecomputedBases take as they are.
     """
@@ -296,7 +296,7 @@ def LagrangeCoeffs(ctx: Context, curve, group: int, powers, n: int | None = None
     FFT over n points of G1 or G2, natural order in and out (ga_lagrange_coeffs).  group = G1 gives the bytes of ToLagrangeG1.
 
     powers : (n, affine_words) uint64 array of G1Affine / G2Affine images or a DeviceBuffer of n points (then n is required); never
-    modified.  n must be a power of two (at most 2^28 for BN254, 2^32 for BLS12-381).  The points are not validated.
+    modified.  n must be a power of two (at most 2^28 for BN254, 2^32 for BLS12-381, 2^47 for BLS12-377).  The points are not validated.
     Returns an (n, affine_words) array, or with out_device=True a DeviceBuffer of n affine points (the caller frees it).
     """
     cid = curve_id(curve)

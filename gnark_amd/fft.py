@@ -14,7 +14,8 @@ DIF, DIT = _lib.DIF, _lib.DIT
 
 class Domain:
     def __init__(self, ctx: Context, curve, cardinality: int):
-        """fft.NewDomain(m): cardinality is rounded up to the next power of two, as gnark-crypto does."""
+        """fft.NewDomain(m): cardinality is rounded up to the next power of two, as gnark-crypto does (at most 2^28 for BN254, 2^32 for
+        BLS12-381, 2^47 for BLS12-377: the 2-adicity of r - 1)."""
         n = 1
         while n < cardinality:
             n *= 2

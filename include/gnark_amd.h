@@ -6,7 +6,7 @@
  *
  * Conventions
  *  - All field elements / points are gnark-crypto memory images: little-endian 64-bit limbs in Montgomery
- *    form (fr.Element = [4]uint64; fp.Element = [4]uint64 BN254 / [6]uint64 BLS12-381); G1Affine = {X,Y};
+ *    form (fr.Element = [4]uint64; fp.Element = [4]uint64 BN254 / [6]uint64 BLS12-381 and BLS12-377); G1Affine = {X,Y};
  *    G2Affine = {X{A0,A1}, Y{A0,A1}}; point at infinity = all-zero coordinates; G1Jac/G2Jac = {X,Y,Z}.
  *    A Go slice `[]fr.Element` / `[]curve.G1Affine` can be passed as `unsafe.Pointer(&s[0])` unchanged.
  *  - No pointer passed in is retained after the call returns (cgo pointer rules): inputs are copied to
@@ -46,9 +46,17 @@ extern "C" {
                                  error the context and its keys stay usable. */
 #define GA_ERR_STATE (-4)     /* object used in the wrong state */
 
-/* curve ids (ecc.ID analogue; only the two curves of BASELINE.json are built) */
+/* curve ids (ecc.ID analogue).  BN254 and BLS12-381, the two curves of BASELINE.json, are built in full.  BLS12-377 is built for
+ * GA_G1 and the scalar field only -- what the PLONK / KZG prover needs (backend/plonk/bls12-377): ga_msm, ga_msm_windows, ga_msm_plan,
+ * ga_msm_combine_windows, the ga_msm_table_* calls, ga_jac_add / _to_affine / _scalar_mul, ga_generator_mul, ga_gen_bases(_at),
+ * ga_gen_scalars, ga_fr_dot, ga_domain_create with ga_fft(_batch) and ga_compute_h(_batch), the ga_plonk_* calls, ga_kzg_open(_batch),
+ * ga_fr_linear_combination, ga_fr_poly_evaluate, ga_fr_vec_mul, ga_fr_batch_invert, ga_hash_to_field, ga_batch_scalar_mul(_plan),
+ * ga_kzg_to_lagrange_g1 and ga_check_points.  Every other call that takes a curve id, and every call with GA_G2, answers
+ * GA_ERR_INVALID for it with a message that names the curve: its Fp2 is Fp[u]/(u^2 + 5), the library's is u^2 + 1, so G2, the
+ * pairing and Groth16 are not built for it. */
 #define GA_BN254 0
 #define GA_BLS12_381 1
+#define GA_BLS12_377 2
 
 /* group ids */
 #define GA_G1 0
@@ -155,7 +163,7 @@ int ga_batch_scalar_mul_plan(int curve, size_t n, int* window_bits, int* num_win
  *            ga_msm_table_create(..., GA_BASES_ON_DEVICE).  The bytes are bit-identical to gnark's.
  * `powers` and `out` must not overlap.  The points are NOT validated (gnark does not validate them either): for points off the
  * curve or outside the subgroup the result is whatever the group law's formulas give.
- * GA_ERR_INVALID: unknown curve, a null pointer with n > 0, n not a power of two, n above 2^28 (BN254) / 2^32 (BLS12-381), the
+ * GA_ERR_INVALID: unknown curve, a null pointer with n > 0, n not a power of two, n above 2^28 (BN254) / 2^32 (BLS12-381) / 2^47 (BLS12-377), the
  * two-adicity of r.  n = 0 is GA_OK and touches nothing; n = 1 copies the point.
  * Device scratch, kept by the context: n extended points (128 B each for BN254, 192 B for BLS12-381), n/2 twiddle scalars (32 B each),
  * n/2 + 4 words of redo list, and n affine points (64 / 96 B) of staging when `powers` or `out` is on the host.  GA_ERR_NOMEM when
@@ -213,7 +221,7 @@ int ga_scale_points(ga_ctx* ctx, int curve, int group, const void* points_affine
  * The return value says whether the check RAN, not whether the points are good: GA_OK for any mixture of points.  (0,0) is infinity
  * and OK, as in gnark-crypto.  A coordinate whose image is not below p is GA_POINT_OFF_CURVE, decided before any arithmetic (a dump
  * is raw memory).  The truth is "on the curve and [r]P = O"; it is decided by an identity in the curve's seed x0 -- BN254 G1: the
- * curve equation alone (cofactor 1); BLS12-381 G1: P + [x0^2] phi(P) = O; BLS12-381 G2: psi(P) = [x0]P; BN254 G2:
+ * curve equation alone (cofactor 1); BLS12-381 and BLS12-377 G1: P + [x0^2] phi(P) = O; BLS12-381 G2: psi(P) = [x0]P; BN254 G2:
  * [x0 + 1]P + psi([x0]P) + psi^2([x0]P) = psi^3([2 x0]P) -- one or two 64-bit ladders per point instead of a 255-bit one.
  * `redone` counts points that met an exceptional step of the fast formulas (points of small order) and were decided by [r]P with
  * the complete formulas: 0 on honest input, never an error.  GA_CHECK_NAIVE=1 runs the definition instead ([r - 1]P = -P, same bytes;
@@ -374,7 +382,7 @@ int ga_domain_create(ga_ctx* ctx, int curve, uint64_t cardinality, ga_domain** o
 void ga_domain_destroy(ga_domain* d);
 /* In-place transform of `cardinality` fr elements (Montgomery).  direction: GA_FFT_FORWARD / GA_FFT_INVERSE
  * (inverse includes the 1/n factor); decimation: GA_DIF / GA_DIT; on_coset: fft.OnCoset() with the domain's
- * FrMultiplicativeGen (5 for BN254, 7 for BLS12-381).  data is a host pointer unless on_device != 0. */
+ * FrMultiplicativeGen (5 for BN254, 7 for BLS12-381, 22 for BLS12-377).  data is a host pointer unless on_device != 0. */
 int ga_fft(ga_domain* d, void* data, int direction, int decimation, int on_coset, int on_device);
 /* `count` transforms of one size in one call: data = count vectors of `cardinality` fr elements, contiguous; the other arguments
  * as ga_fft's, the same for every vector.  Replaces a loop of fft.Domain.FFT / FFTInverse over vectors of one domain (the three

@@ -5,7 +5,7 @@
   oracle/oracle_constants.h    oracle header, 64-bit limbs (plain C, unsigned __int128)
 
 Moduli sources in the reference: backend/groth16/bn254/solidity.go:64-65,
-std/math/emulated/emparams/emparams.go:142-157,225-241.  Everything else (R, R^2, -p^-1,
+std/math/emulated/emparams/emparams.go:142-157,225-241; BLS12-377 (product header only, G1 / Fr): tools/bls12_377_params.py.  Everything else (R, R^2, -p^-1,
 roots of unity) is derived here from the moduli.
 """
 import os
@@ -14,6 +14,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 from pyref import BN254, BLS12_381, Fp2Ops, Fp12Ops, g1_group, g2_group  # noqa: E402
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import bls12_377_params as BLS12_377  # noqa: E402
 
 # the curves' seeds (x0 of the BN / BLS12 families): p, r and the cofactors are polynomials in them
 BN254_SEED = 4965661367192848881
@@ -58,7 +60,7 @@ def fp2_lazy_offset(mod, n64, K=FP2_LAZY_K):
     return Z, zint, -(-zint // R)     # the offset adds less than this to a reduced value
 
 
-def field_block(name, mod, n64, w, extra=None):
+def field_block(name, mod, n64, w, extra=None, fp2=True):
     n = n64 * (64 // w)
     R = 1 << (64 * n64)
     ty = "uint32_t" if w == 32 else "uint64_t"
@@ -73,12 +75,16 @@ def field_block(name, mod, n64, w, extra=None):
     out.append(f"    static constexpr {ty} R2[{n}] = {arr(R * R % mod, n, w)};    // R^2 mod p")
     out.append(f"    static constexpr {ty} PM2[{n}] = {arr(mod - 2, n, w)};   // p-2 (Fermat inverse exponent)")
     out.append(f"    static constexpr uint32_t MU12 = {(1 << (mod.bit_length() + 8)) // mod}u;   // floor(2^(BITS+8) / p): Barrett quotient estimate (field29.hip.h)")
-    if w == 32 and name.endswith("_Fp"):
+    if w == 32 and name.endswith("_Fp") and fp2:
         Z, zint, add = fp2_lazy_offset(mod, n64)
         out.append(f"    // lazy Fp2 product (field29.hip.h): redundant-digit columns of a multiple of p dominating a1*b1 for operands < {FP2_LAZY_K}p;")
         out.append(f"    // it adds < {add / mod:.3f} p to the reduced real part")
         out.append(f"    static constexpr int FP2Z_K = {FP2_LAZY_K};")
         out.append(f"    static constexpr uint64_t FP2Z[{len(Z)}] = {{" + ", ".join(f"0x{v:x}ull" for v in Z) + "};")
+    elif w == 32 and name.endswith("_Fp"):
+        # the G1 kernels name the constant in `Lazy<F>::FP2 ? P::FP2Z_K : 8` and never select it; the column table FP2Z, which the Fp2
+        # product needs, stays out: an Fe2 over this field does not compile
+        out.append(f"    static constexpr int FP2Z_K = {FP2_LAZY_K};   // named, never selected: there is no Fp2 over this field (no FP2Z)")
     for k, v in (extra or {}).items():
         if isinstance(v, int) and k.isupper() and k.startswith("I_"):
             out.append(f"    static constexpr int {k[2:]} = {v};")
@@ -181,7 +187,8 @@ def pairing_constants(c):
     return out
 
 
-def main():
+def main(prod_path=None, oracle_path=None):
+    """writes the two headers in place; the tests pass other paths and compare"""
     hdr = ["// GENERATED by tools/gen_constants.py -- do not edit.", "#pragma once", "#include <stdint.h>", ""]
     prod = list(hdr) + ["namespace ga {", ""]
     orc = list(hdr)
@@ -199,10 +206,19 @@ def main():
         orc.append("")
         orc.append(c_field_block(f"{tag}_FR", c.r, c.fr_limbs, fr_extra))
         orc.append("")
+    # BLS12-377, product header only, G1 and Fr only: no G2*, B2*, PSI*, FROB* and no FP2Z -- the library's Fp2 is Fp[u]/(u^2 + 1) and this
+    # curve's is u^2 + 5, so no Fe2 / G2 / pairing template may be instantiated over BLS12_377_Fp (a missing constant is a compile error)
+    q = BLS12_377
+    wmax = pow(q.FR_GEN, (q.R - 1) >> q.FR_ADICITY, q.R)
+    prod.append(field_block("BLS12_377_Fp", q.P, q.FP_LIMBS, 32, {"G1X": q.G1[0], "G1Y": q.G1[1], "B1": q.B, "BETA": q.beta()}, fp2=False))
+    prod.append("")
+    prod.append(field_block("BLS12_377_Fr", q.R, q.FR_LIMBS, 32, {"ROOT": wmax, "ROOT_INV": pow(wmax, -1, q.R), "GEN": q.FR_GEN,
+                                                                  "GEN_INV": pow(q.FR_GEN, -1, q.R), "I_ADICITY": q.FR_ADICITY}))
+    prod.append("")
     prod.append("}  // namespace ga")
-    with open(os.path.join(ROOT, "gnark_amd", "csrc", "constants.h"), "w") as f:
+    with open(prod_path or os.path.join(ROOT, "gnark_amd", "csrc", "constants.h"), "w") as f:
         f.write("\n".join(prod) + "\n")
-    with open(os.path.join(ROOT, "oracle", "oracle_constants.h"), "w") as f:
+    with open(oracle_path or os.path.join(ROOT, "oracle", "oracle_constants.h"), "w") as f:
         f.write("\n".join(orc) + "\n")
     print("wrote constants.h, oracle_constants.h")
 

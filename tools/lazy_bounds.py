@@ -6,12 +6,18 @@ Every value is tracked by an upper bound.  The representation needs (NL limbs of
   * for every  a - b + K*p :  b < K*p  (with a margin of one top-limb unit, 2^(L*(NL-1)));
   * Fp2 operands below FP2Z_K*p (the negation constant of the schoolbook-on-columns product).
 `check(...)` iterates the mixed-addition formulas to a fixed point of the accumulator bounds and asserts all of the
-above with exactly the constants the kernels use.  tests/test_lazy_bounds.py runs it for both curves."""
+above with exactly the constants the kernels use.  tests/test_lazy_bounds.py runs it for both curves, tests/test_bls12_377.py for the
+G1 side of BLS12-377 (the fp2 = True rows of that curve are arithmetic on its modulus only: no Fp2 kernel is built for it)."""
+import os
+import sys
 from math import log2
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import bls12_377_params  # noqa: E402
 
 BN254_P = 0x30644E72E131A029B85045B68181585D97816A916871CA8D3C208C16D87CFD47
 BLS12_381_P = 0x1A0111EA397FE69A4B1BA7B6434BACD764774B84F38512BF6730D2A0F6B0F6241EABFFFEB153FFFFB9FEFFFFFFFFAAAB
-CURVES = {"bn254": (BN254_P, 29, 9, 254), "bls12-381": (BLS12_381_P, 28, 14, 381)}
+CURVES = {"bn254": (BN254_P, 29, 9, 254), "bls12-381": (BLS12_381_P, 28, 14, 381), "bls12-377": bls12_377_params.LAZY}
 
 # constants used by msm_bucket.hip.h::madd29 (G1) and its Fp2 overload (G2), and by field29.hip.h's Fp2 product / square
 G1 = dict(Kx=8, Ky=8, K3=4, Kq=8, Ky3=2)
@@ -484,6 +490,7 @@ if __name__ == "__main__":
 # ---- plonk.hip.h::plonk_constraints29_kernel (round 5): the PLONK constraint expression on unreduced limbs, BN254's Fr -------------
 BN254_R = 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001
 BLS12_381_R = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
+BLS12_377_R = bls12_377_params.R
 PLONK_SUB = dict(ord=8, zm1=2)   # f29_sub<8>(ll, rr), f29_sub<2>(z, 1)
 
 
@@ -532,3 +539,23 @@ def check_plonk_constraints(r=BN254_R, nb_bsb=16, L=29, NL=9):
 
 if __name__ == "__main__" and False:
     print(check_plonk_constraints())
+
+
+# ---- field29.hip.h::f29_reduce_3p on a field whose Barrett constant loses precision (BLS12-377) ---------------------------------------
+def check_reduce_3p(p, L, NL, below_log2=None):
+    """Largest residue f29_reduce_3p leaves, in units of p, over every top-limb estimate t = v >> (BITS - 4) of a normalized value
+    v < 2^below_log2 (default: any v < 2^(NL*L)): q = (t * MU12) >> 12 with MU12 = floor(2^(BITS+8) / p), residue below
+    (t + 1) 2^(BITS-4) - q p.  The estimate is never too large (asserted).  Its consumers -- f29_pack_canonical, f29_is_zero_mod_p -- need
+    a residue below 3p that fits the 32N-bit words.  Returns (worst / p, log2 of the first v whose residue can reach 3p, or None)."""
+    bits = p.bit_length()
+    mu, sh = (1 << (bits + 8)) // p, bits - 4
+    top = 1 << (L * NL) if below_log2 is None else min(1 << (L * NL), int(2 ** below_log2) + 1)
+    worst, first_bad = 0, None
+    for t in range((top >> sh) + 1):
+        q = (t * mu) >> 12
+        assert q * p <= t << sh, "the estimate is too large"
+        res = ((t + 1) << sh) - q * p
+        worst = max(worst, res)
+        if first_bad is None and res > 3 * p:
+            first_bad = log2(t << sh)
+    return worst / p, first_bad
