@@ -6,6 +6,7 @@ The reference is plain Python integers: R = 2^(32N) (the memory format's Montgom
 pyref's group law for points.  Nothing here is computed with the code under test."""
 import ctypes
 import functools
+import math
 import os
 import sys
 
@@ -15,6 +16,7 @@ import pyref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+import bls12_377_params  # noqa: E402
 import lazy_bounds  # noqa: E402
 
 # op codes of tests/probe/field_probe.hip
@@ -26,11 +28,11 @@ import lazy_bounds  # noqa: E402
 (OP_PT_ADD29, OP_PT_DBL29, OP_PT_MADD29, OP_PT_MDBL29, OP_PT_MADD29_COMPLETE) = range(50, 55)
 OP_DIGIT_WALK, DIGIT_WINDOWS = 70, 64
 OP_PT2 = 10   # added to a point op: the same formula over Fp2
-FP2Z_K = 16   # constants.h: the negation constant of the lazy Fp2 product, both curves
+FP2Z_K = 16   # constants.h: the negation constant of the lazy Fp2 product, both curves that have an Fp2
 
 
 class Field:
-    def __init__(self, idx, name, p, curve=None):
+    def __init__(self, idx, name, p, curve=None, has_fp2=None):
         self.idx, self.name, self.p, self.curve = idx, name, p, curve
         self.bits = p.bit_length()
         self.N = (self.bits + 63) // 64 * 2                 # 32-bit words of the memory image
@@ -42,6 +44,9 @@ class Field:
         self.mask = (1 << self.L) - 1
         self.unit = 1 << (self.L * (self.NL - 1))           # one unit of the top limb
         self.is_base = curve is not None
+        # Fp2 = Fp[u]/(u^2 + 1) is built over the field: F29x2, the G2 point formulas, FP2Z_K (not over BLS12-377's Fp)
+        self.has_fp2 = self.is_base if has_fp2 is None else has_fp2
+        assert self.is_base or not self.has_fp2
 
     def __repr__(self):
         return self.name
@@ -52,8 +57,27 @@ FIELDS = {
     "bn254_fr": Field(1, "bn254_fr", pyref.BN254.r),
     "bls12_381_fp": Field(2, "bls12_381_fp", pyref.BLS12_381.p, "bls12-381"),
     "bls12_381_fr": Field(3, "bls12_381_fr", pyref.BLS12_381.r),
+    "bls12_377_fp": Field(4, "bls12_377_fp", bls12_377_params.P, "bls12-377", has_fp2=False),
+    "bls12_377_fr": Field(5, "bls12_377_fr", bls12_377_params.R),
 }
 BASE_FIELDS = [n for n, f in FIELDS.items() if f.is_base]
+FP2_FIELDS = [n for n, f in FIELDS.items() if f.has_fp2]
+# (field, fp2) of every point-formula run: G1 over each base field, G2 where the field has an Fp2
+POINT_FIELDS = [(n, fp2) for n in BASE_FIELDS for fp2 in (False, True) if not fp2 or FIELDS[n].has_fp2]
+
+# pyref.CURVES knows the oracle's two curves; BLS12-377 is built outside it (tools/bls12_377_params.py), G1 / Fr side only
+BLS12_377 = bls12_377_params.curve()
+CURVE_BY_NAME = dict(pyref.CURVES, **{BLS12_377.name: BLS12_377})
+
+
+def fp_of(c):
+    """the base field of a curve"""
+    return next(f for f in FIELDS.values() if f.curve == c.name)
+
+
+def fr_of(c):
+    """the scalar field of a curve"""
+    return next(f for f in FIELDS.values() if not f.is_base and f.p == c.r)
 
 
 # ---- the probe ------------------------------------------------------------------------------------------------------------------
@@ -228,7 +252,10 @@ def case_conversions(pr, f):
     got = pr.run(f, OP_F29_PACK_CANONICAL, [limbs(f, v) for v in pc], f.N)
     for v, g in zip(pc, got):
         assert wval(g) == v % p, (f, "pack_canonical", hex(v), hex(wval(g)))
-    # pack_hat: any normalized value below R' -> canonical words of the same domain
+    # pack_hat: any normalized value below R' -> canonical words of the same domain; where the Barrett step does not reach that far
+    # (BLS12-377 Fp), any value below hat_limit
+    top = min(f.Rp, hat_limit(f))
+    lz = [x for v in cn for x in lifts(f, v, limit=min(f.Rp // 4, top)) + [lifts(f, v, limit=top)[-1]]]
     got = pr.run(f, OP_F29_PACK_HAT, [limbs(f, v) for v in lz], f.N)
     for v, g in zip(lz, got):
         assert wval(g) == v % p, (f, "pack_hat", hex(v), hex(wval(g)))
@@ -336,7 +363,7 @@ def case_lazy_mul_sub(pr, f):
     addition passes them (limbs below 3*2^L)"""
     p, Rp = f.p, f.Rp
     Rpi = pow(Rp, -1, p)
-    for K in ((8, FP2Z_K) if f.is_base else (8,)):
+    for K in ((8, FP2Z_K) if f.has_fp2 else (8,)):
         ex = extremes(f)
         hi = lambda v: lifts(f, v)[-1]
         cmax = lambda v: v + (K - 1) * p                     # c < K*p
@@ -372,14 +399,22 @@ def case_lazy_mul_sub(pr, f):
             assert v < (a * b + (K * p - c) * d) // Rp + p + 1 <= (a * b + K * p * d) // Rp + p + 1, (f, K, "f29_mul_sub bound", hex(v))
 
 
-def reduce_3p_bound(f):
+def reduce_3p_quotient(f, v):
+    """the quotient estimate of f29_reduce_3p, from its definition: q = ((v >> (BITS-4)) * MU12) >> 12, MU12 = floor(2^(BITS+8) / p)"""
+    return ((v >> (f.bits - 4)) * ((1 << (f.bits + 8)) // f.p)) >> 12
+
+
+def reduce_3p_bound(f, below=None):
     """The largest residue f29_reduce_3p can leave, from its definition alone: q = ((v >> (BITS-4)) * MU12) >> 12 with
     MU12 = floor(2^(BITS+8) / p) (constants.h), so for the top-limb estimate t = v >> (BITS-4) the residue is at most
-    (t+1)*2^(BITS-4) - 1 - q(t)*p.  Maximised over every t a normalized v < 2^(NL*L) can have.  Returns (bound, max quotient deficit)."""
+    (t+1)*2^(BITS-4) - 1 - q(t)*p.  Maximised over every t a normalized v < below (default: 2^(NL*L)) can have; below is a multiple of
+    2^(BITS-4).  Returns (bound, max quotient deficit)."""
     mu = (1 << (f.bits + 8)) // f.p
     sh = f.bits - 4
+    below = f.Rp if below is None else below
+    assert below % (1 << sh) == 0
     worst, deficit = 0, 0
-    for t in range(f.Rp >> sh):
+    for t in range(below >> sh):
         q = (t * mu) >> 12
         hi = ((t + 1) << sh) - 1
         assert q * f.p <= (t << sh), "the estimate is too large"
@@ -388,41 +423,108 @@ def reduce_3p_bound(f):
     return worst + 1, deficit
 
 
+@functools.lru_cache(maxsize=None)
+def hat_limit(f):
+    """The largest V <= R' such that f29_reduce_3p leaves every normalized v < V below 3p and within the 32N-bit words -- the
+    precondition of its consumers f29_is_zero_mod_p (candidates 0, p, 2p), f29_pack_canonical (two conditional subtractions) and
+    f29_pack_hat.  By the enumeration of reduce_3p_bound: the first top-limb estimate t whose largest residue leaves that range ends it.
+    R' for every field but BLS12-377 Fp, whose MU12 = 304 stands for 304.7."""
+    mu = (1 << (f.bits + 8)) // f.p
+    sh = f.bits - 4
+    for t in range(f.Rp >> sh):
+        if ((t + 1) << sh) - 1 - ((t * mu) >> 12) * f.p >= min(3 * f.p, f.R):
+            return t << sh
+    return f.Rp
+
+
+# how far the exhaustive part of the operand set reaches where R' / p is too large for all of it (BLS12-377 Fp: 38996), and the size
+# of the seeded samples above it
+REDUCTION_DENSE_LOG2, REDUCTION_SAMPLE = 388, 1000
+
+
+@functools.lru_cache(maxsize=None)
 def reduction_operands(f):
     """k*p - 1, k*p, k*p + 1 for EVERY k that fits R', t*2^(BITS-4) - 1 and t*2^(BITS-4) for every top-limb estimate t, and the lifts
-    of the canonical set up to R'"""
+    of the canonical set up to R'.  BLS12-377 Fp (R' / p = 38996, 2^19 estimates): every k and every t below 2^388 -- which covers
+    hat_limit and the range every consumer lives in -- and above it a seeded sample of both up to R'.  Every field with a hat_limit
+    below R' also gets the values around it: the last estimate that is good, the first that is not and its largest value."""
     p, sh = f.p, f.bits - 4
-    vs = [x for k in range(f.Rp // p + 1) for x in (k * p - 1, k * p, k * p + 1)]
-    vs += [x for t in range((f.Rp >> sh) + 1) for x in ((t << sh) - 1, t << sh)]
+    nk, nt = f.Rp // p + 1, (f.Rp >> sh) + 1
+    ks, ts = range(nk), range(nt)
+    if 3 * nk + 2 * nt > 80000:
+        dense = 1 << REDUCTION_DENSE_LOG2
+        assert hat_limit(f) + (1 << sh) < dense < f.Rp
+        rng = pyref.Xoshiro(0x3E0 + f.idx)
+        dk, dt = dense // p + 1, (dense >> sh) + 1
+        ks = list(range(dk)) + sorted({dk + rng.next() % (nk - dk) for _ in range(REDUCTION_SAMPLE)}) + [nk - 1]
+        ts = list(range(dt)) + sorted({dt + rng.next() % (nt - dt) for _ in range(REDUCTION_SAMPLE)}) + [nt - 2, nt - 1]
+    vs = [x for k in ks for x in (k * p - 1, k * p, k * p + 1)]
+    vs += [x for t in ts for x in ((t << sh) - 1, t << sh)]
     vs += [x for v in canon(f) for x in lifts(f, v) + [lifts(f, v, limit=f.Rp)[-1]]]
-    return [v for v in dict.fromkeys(vs) if 0 <= v < f.Rp]
+    hl = hat_limit(f)
+    if hl < f.Rp:
+        vs += [hl - (1 << sh), hl - 1, hl, hl + (1 << sh) - 1] + [x for v in canon(f)[:64] for x in lifts(f, v, limit=hl)[-1:]]
+    vs = [v for v in dict.fromkeys(vs) if 0 <= v < f.Rp]
+    assert len(vs) < 80000, (f, len(vs))
+    return tuple(vs)
 
 
 def case_lazy_reductions(pr, f):
     p = f.p
     vs = reduction_operands(f)
-    bound, deficit = reduce_3p_bound(f)
+    hl = hat_limit(f)
+    bound, deficit = reduce_3p_bound(f, hl)
     # what the consumers of f29_reduce_3p need: the three candidates 0, p, 2p of f29_is_zero_mod_p and the two conditional subtractions
     # of f29_pack_canonical cover [0, 3p), and the residue must fit the 32N-bit words
     assert bound <= 3 * p and bound <= f.R and deficit <= 2, (f, bound / p, deficit)
-    # ... and what the definition gives for these four moduli: the estimate is at most 1 short, the residue below 1.35 p
-    assert deficit <= 1 and 100 * bound < 135 * p, (f, bound / p, deficit)
+    # where that holds, from the definition: for any normalized value but on BLS12-377 Fp, where lazy_bounds.check_reduce_3p finds the
+    # same first value that leaves it -- above 2^386.5 as field29.hip.h says, below the 2^390 the lazy representation allows
+    fb = lazy_bounds.check_reduce_3p(p, f.L, f.NL)[1]
+    if f.name == "bls12_377_fp":
+        assert fb == math.log2(hl) and (1 << 773) < hl * hl and hl < f.Rp // 4, (f, math.log2(hl), fb)
+    else:
+        assert hl == f.Rp and (fb is None or 2 ** fb >= f.Rp), (f, hl.bit_length(), fb)
+    if f.name == "bls12_377_fr":
+        # ... and what the definition gives for this modulus (MU12 = 438 stands for 438.8): at most 1 short, the residue below 1.87 r
+        assert deficit <= 1 and 100 * bound < 187 * p, (f, bound / p, deficit)
+    elif f.name != "bls12_377_fp":
+        # ... and what the definition gives for these four moduli: the estimate is at most 1 short, the residue below 1.35 p
+        assert deficit <= 1 and 100 * bound < 135 * p, (f, bound / p, deficit)
+    if f.is_base:
+        # every coordinate the point formulas can hold (the exact fixed points of the interval analysis) is below hat_limit: what
+        # f29_is_zero_mod_p and f29_pack_hat are given in the kernels is inside their precondition
+        for fp2 in ((False, True) if f.has_fp2 else (False,)):
+            for fn in (lazy_bounds.check, lazy_bounds.check_add, lazy_bounds.check_dbl, lazy_bounds.check_mdbl, lazy_bounds.check_ladder):
+                B = exact_bounds(fn, f, fp2)
+                assert set(B) == {"X", "Y", "ZZ", "ZZZ"} and all(v < hl for v in B.values()), (f, fn.__name__, fp2, B)
     for lo in range(0, len(vs), 30000):
         chunk = vs[lo:lo + 30000]
         rows = [limbs(f, v) for v in chunk]
         r3 = pr.run(f, OP_F29_REDUCE_3P, rows, f.NL)
         prd = pr.run(f, OP_F29_PARTIAL_REDUCE, rows, f.NL)
         zz = pr.run(f, OP_F29_IS_ZERO_MOD_P, rows, 1)
-        for v, g, h, z in zip(chunk, r3, prd, zz):
+        ph = pr.run(f, OP_F29_PACK_HAT, rows, f.N)
+        # f29_pack_canonical after the step, on the step's own output where that is inside its precondition (below: checked exactly)
+        ok = [i for i, v in enumerate(chunk) if v < hl]
+        pc = dict(zip(ok, pr.run(f, OP_F29_PACK_CANONICAL, [r3[i] for i in ok], f.N)))
+        for i, (v, g, h, z, c) in enumerate(zip(chunk, r3, prd, zz, ph)):
             assert_normalized(f, g, "f29_reduce_3p")
             r = lval(f, g)
-            assert r % p == v % p and r <= v and r < bound, (f, "f29_reduce_3p", hex(v), hex(r), r / p)
+            # the exact pin, for ANY normalized value: v - q*p with the q of the definition
+            assert r == v - reduce_3p_quotient(f, v) * p, (f, "f29_reduce_3p", hex(v), hex(r), r / p)
             assert_normalized(f, h, "f29_partial_reduce")
-            r = lval(f, h)
+            rr = lval(f, h)
             q = v >> f.bits
-            assert r == v - q * p and r < (1 << f.bits) + q * ((1 << f.bits) - p), (f, "f29_partial_reduce", hex(v), hex(r))
-            assert v >= (1 << (f.bits + 3)) or r < 4 * p, (f, "f29_partial_reduce: not below 4p", hex(v))
-            assert z[0] == (1 if v % p == 0 else 0), (f, "f29_is_zero_mod_p", hex(v), z)
+            assert rr == v - q * p and rr < (1 << f.bits) + q * ((1 << f.bits) - p), (f, "f29_partial_reduce", hex(v), hex(rr))
+            # below 4p for v < 2^(BITS+3) needs 2^BITS + 7 (2^BITS - p) <= 4p, a modulus above 8/11 * 2^BITS: every field but BLS12-377's
+            # Fr (0.58 * 2^BITS; field29.hip.h: no caller of f29_partial_reduce is built over it), which keeps the bound above alone
+            assert 11 * p >= (8 << f.bits) or f.name == "bls12_377_fr"
+            assert v >= (1 << (f.bits + 3)) or rr < 4 * p or 11 * p < (8 << f.bits), (f, "f29_partial_reduce: not below 4p", hex(v))
+            if v < hl:
+                assert r % p == v % p and r <= v and r < bound, (f, "f29_reduce_3p", hex(v), hex(r), r / p)
+                assert z[0] == (1 if v % p == 0 else 0), (f, "f29_is_zero_mod_p", hex(v), z)
+                assert wval(pc[i]) == v % p, (f, "f29_pack_canonical after f29_reduce_3p", hex(v), hex(wval(pc[i])))
+                assert wval(c) == v % p, (f, "f29_pack_hat", hex(v), hex(wval(c)))
 
 
 def case_lazy_inv(pr, f):
@@ -504,7 +606,8 @@ class PointCtx:
 
     def __init__(self, f, fp2):
         self.f, self.fp2 = f, fp2
-        self.c = pyref.CURVES[f.curve]
+        self.c = CURVE_BY_NAME[f.curve]
+        assert f.has_fp2 or not fp2
         self.G = pyref.g2_group(self.c) if fp2 else pyref.g1_group(self.c)
         self.F = self.G.F
         self.gen = self.c.g2 if fp2 else self.c.g1
@@ -712,11 +815,34 @@ def crafted_scalars(r, c):
     return list(dict.fromkeys(out))
 
 
+def sqrt_fp(a, p):
+    """a square root of a mod p, or None: the exponentiation for p = 3 (mod 4); Tonelli-Shanks for BLS12-377's p (p - 1 = 2^46 * odd)"""
+    a %= p
+    if a == 0:
+        return 0
+    if pow(a, (p - 1) // 2, p) != 1:
+        return None
+    if p % 4 == 3:
+        return pow(a, (p + 1) // 4, p)
+    e, q = 0, p - 1
+    while q % 2 == 0:
+        e, q = e + 1, q // 2
+    z = next(z for z in range(2, 1000) if pow(z, (p - 1) // 2, p) == p - 1)
+    m, c, t, x = e, pow(z, q, p), pow(a, q, p), pow(a, (q + 1) // 2, p)
+    while t != 1:
+        i, u = 0, t
+        while u != 1:
+            i, u = i + 1, u * u % p
+        b = pow(c, 1 << (m - i - 1), p)
+        m, c, t, x = i, b * b % p, t * b * b % p, x * b % p
+    return x
+
+
 def crafted_bases(c):
     """G1 points whose Montgomery-image x carries the limb patterns of the operand set: x = pattern * R^-1, the pattern's lowest word
-    stepped upward (at most 64 steps) until x^3 + b is a square; both signs of y.  On BLS12-381 these lie outside the r-torsion:
-    the reference is pyref's curve arithmetic, never a discrete logarithm."""
-    f = FIELDS["bn254_fp" if c.name == "bn254" else "bls12_381_fp"]
+    stepped upward (at most 64 steps) until x^3 + b is a square; both signs of y.  On the two BLS12 curves these lie outside the
+    r-torsion: the reference is pyref's curve arithmetic, never a discrete logarithm."""
+    f = fp_of(c)
     p, Ri = f.p, pow(f.R, -1, f.p)
     pats = [1, 0xFFFFFFFF << 32, 0xFFFFFFFF << (32 * (f.N - 2)), f.mask << f.L, f.mask << (f.L * (f.NL - 2)), (1 << (f.bits - 1)) - 1 - 64,
             p - 1 - 64, 1 << (32 * (f.N - 1))]
@@ -725,7 +851,7 @@ def crafted_bases(c):
         for step in range(65):
             assert step < 64, ("no curve point within 64 steps of the pattern", hex(pat))
             x = (pat + step) % p * Ri % p
-            y = pyref._sqrt_fp((x * x * x + c.b) % p, p)
+            y = sqrt_fp((x * x * x + c.b) % p, p)
             if y is not None and y * y % p == (x * x * x + c.b) % p:
                 pts += [(x, y), (x, p - y)]
                 break
@@ -764,7 +890,7 @@ def case_fr_vector_ops(ctx, c):
     """ga_fr_vec_mul and ga_fr_batch_invert (zeros interleaved) over the canonical operand set, host and device pointers;
     ga_fr_linear_combination (1 and 16 terms) and ga_fr_poly_evaluate over it, host and device pointers as well"""
     from helpers import arr_to_fr, fr_to_arr
-    f = FIELDS["bn254_fr" if c.name == "bn254" else "bls12_381_fr"]
+    f = fr_of(c)
     r = c.r
     vals = [v for v in canon(f)]
     a = vals
@@ -823,30 +949,59 @@ def case_fr_vector_ops(ctx, c):
                 dP.free()
 
 
+def fft_boundary_input(r, n, name):
+    return {"all r-1": lambda: [r - 1] * n, "all 1": lambda: [1] * n, "r-1 first": lambda: [r - 1] + [0] * (n - 1),
+            "r-1 last": lambda: [0] * (n - 1) + [r - 1], "alternating": lambda: [0 if i % 2 == 0 else r - 1 for i in range(n)]}[name]()
+
+
+FFT_INPUTS = ("all r-1", "all 1", "r-1 first", "r-1 last", "alternating")
+# a curve the C oracle does not know compares with pyref.fft, 2.3 s per transform at 2^17: there the grid is two inputs and the four
+# modes (DIF, forward), (DIT, inverse), each on and off the coset; computed once per session, whatever the knob set
+FFT_2P17_PYREF_INPUTS = ("all r-1", "alternating")
+FFT_2P17_PYREF_MODES = ((pyref.DIF, False), (pyref.DIT, True))
+
+
+@functools.lru_cache(maxsize=None)
+def pyref_fft_image(cname, logn, name, dec, coset, inv):
+    """pyref.fft of a boundary input as the memory image the library returns"""
+    from helpers import fr_to_arr
+    c = CURVE_BY_NAME[cname]
+    a = fr_to_arr(c, pyref.fft(c, fft_boundary_input(c.r, 1 << logn, name), dec, on_coset=coset, inverse=inv))
+    a.setflags(write=False)
+    return a
+
+
 def case_fft_boundary_inputs(ctx, c, logn):
-    """all r-1, all 1, a single r-1 first / last, alternating 0 / r-1 through every (inverse, decimation, coset) mode vs the C oracle"""
+    """all r-1, all 1, a single r-1 first / last, alternating 0 / r-1 through every (inverse, decimation, coset) mode vs the C oracle;
+    BLS12-377, which the oracle does not know, vs pyref.fft / pyref.compute_h (at 2^17 on the reduced grid above, without compute_h)"""
     import oracle
     from gnark_amd import fft
     from helpers import fr_to_arr
     n, r = 1 << logn, c.r
-    inputs = {"all r-1": [r - 1] * n, "all 1": [1] * n, "r-1 first": [r - 1] + [0] * (n - 1), "r-1 last": [0] * (n - 1) + [r - 1],
-              "alternating": [0 if i % 2 == 0 else r - 1 for i in range(n)]}
+    by_oracle = c.name in pyref.CURVES
+    reduced = not by_oracle and logn >= 17
     d = fft.Domain(ctx, c.name, n)
     try:
-        for name, v in inputs.items():
+        for name in (FFT_2P17_PYREF_INPUTS if reduced else FFT_INPUTS):
+            v = fft_boundary_input(r, n, name)
             row = {x: fr_to_arr(c, [x])[0] for x in set(v)}
             a = np.array([row[x] for x in v], dtype=np.uint64)
             for dec in (pyref.DIF, pyref.DIT):
                 for coset in (False, True):
                     for inv in (False, True):
-                        want = oracle.fft(c.cid, a, 1 if inv else 0, dec, coset, nthreads=2)
+                        if reduced and (dec, inv) not in FFT_2P17_PYREF_MODES:
+                            continue
+                        want = oracle.fft(c.cid, a, 1 if inv else 0, dec, coset, nthreads=2) if by_oracle else \
+                            pyref_fft_image(c.name, logn, name, dec, coset, inv)
                         got = (d.FFTInverse if inv else d.FFT)(a, dec, coset)
                         assert np.array_equal(got, want), (c.name, logn, name, dec, coset, inv)
-        if logn >= 2:   # compute_h with A = B = r-1, C = A*B
+        if logn >= 2 and not reduced:   # compute_h with A = B = r-1, C = A*B
             m = n - 1
             A = fr_to_arr(c, [r - 1] * m)
             Cc = fr_to_arr(c, [1] * m)
-            assert np.array_equal(d.compute_h(A, A, Cc), oracle.compute_h(c.cid, A, A, Cc, d.Cardinality)), (c.name, logn, "compute_h")
+            want = oracle.compute_h(c.cid, A, A, Cc, d.Cardinality) if by_oracle else \
+                fr_to_arr(c, pyref.compute_h(c, [r - 1] * m, [r - 1] * m, [1] * m, d.Cardinality))
+            assert np.array_equal(d.compute_h(A, A, Cc), want), (c.name, logn, "compute_h")
     finally:
         d.close()
 
@@ -905,12 +1060,39 @@ def case_plonk_constant_inputs(ctx, c, n):
         d1.close()
 
 
+def signed_digits(s, cbits, ref):
+    """the (key, value) pairs of the raw-bases recoding of s < r, window by window; ref: the probe's row, whose value of a skipped pair
+    is taken over (never read: a digit of 2^c - 1 plus a carry gives 0 with the sign set)"""
+    half = 1 << (cbits - 1)
+    carry, want = 0, []
+    for w in range(DIGIT_WINDOWS):
+        d = ((s >> (cbits * w)) & (2 * half - 1)) + carry
+        carry = 1 if d > half else 0
+        d -= carry << cbits
+        want += [0xFFFFFFFF, ref[2 * w + 1]] if d == 0 else [w * half + abs(d) - 1, 0x80000000 if d < 0 else 0]
+    assert carry == 0
+    return want
+
+
+def unreduced_scalars(r, sc):
+    """canonical scalars at and above r, any 256-bit integer being allowed: k*r - 1, k*r, k*r + 1 for every k up to 2^256 // r (the
+    count of conditional subtractions DigitWalk needs: 5, 2 and 13 for the three curves), 2^256 - 1, the largest multiple of r less
+    one, and each of sc plus the largest multiple of r that keeps it below 2^256"""
+    top = (1 << 256) // r
+    out = [k * r + d for k in range(1, top + 1) for d in (-1, 0, 1)]
+    out += [(1 << 256) - 1, (1 << 256) - 1 - (1 << 256) % r]
+    out += [s + ((1 << 256) - 1 - s) // r * r for s in sc]
+    assert all(r - 1 <= x < (1 << 256) for x in out) and max(x // r for x in out) == top
+    return list(dict.fromkeys(out))
+
+
 def case_digit_walk(pr, c, cbits):
     """DigitWalk (msm_sort.hip.h) on the crafted scalars, Montgomery and canonical: the recoding is pinned to signed digits in
     (-2^(c-1), 2^(c-1)] -- a digit of exactly 2^(c-1) stays POSITIVE and carries nothing.  (-2^(c-1) with a carry is the same scalar
     and gives the same MSM, so only this test tells the two apart.)  Raw-bases keys: window * 2^(c-1) + |digit| - 1, ~0 for digit 0;
-    value: point index (0 here) | sign << 31."""
-    f = FIELDS["bn254_fr" if c.name == "bn254" else "bls12_381_fr"]
+    value: point index (0 here) | sign << 31.  Then canonical scalars that are NOT below r (unreduced_scalars): the digits are those
+    of s mod r."""
+    f = fr_of(c)
     r, half = c.r, 1 << (cbits - 1)
     sc = crafted_scalars(r, cbits)
     assert any((s >> (cbits * w)) & (2 * half - 1) == half for s in sc for w in range(4)), "no digit at 2^(c-1)"
@@ -918,23 +1100,20 @@ def case_digit_walk(pr, c, cbits):
         rows = [words(f, s * f.R % r if mont else s) + [mont] for s in sc]
         got = pr.run(f, OP_DIGIT_WALK, rows, 2 * DIGIT_WINDOWS, k=cbits)
         for s, g in zip(sc, got):
-            carry, want = 0, []
-            for w in range(DIGIT_WINDOWS):
-                d = ((s >> (cbits * w)) & (2 * half - 1)) + carry
-                carry = 1 if d > half else 0
-                d -= carry << cbits
-                # (the value of a skipped pair is never read: a digit of 2^c - 1 plus a carry gives 0 with the sign set)
-                want += [0xFFFFFFFF, g[2 * w + 1]] if d == 0 else [w * half + abs(d) - 1, 0x80000000 if d < 0 else 0]
-            assert carry == 0 and g == want, (c.name, cbits, mont, hex(s))
+            assert g == signed_digits(s, cbits, g), (c.name, cbits, mont, hex(s))
+    big = unreduced_scalars(r, sc)
+    got = pr.run(f, OP_DIGIT_WALK, [words(f, s) + [0] for s in big], 2 * DIGIT_WINDOWS, k=cbits)
+    for s, g in zip(big, got):
+        assert g == signed_digits(s % r, cbits, g), (c.name, cbits, "canonical, not below r", hex(s), s // r)
 
 
 # ---- what the two test modules share ---------------------------------------------------------------------------------------------
-CURVES = [pyref.BN254, pyref.BLS12_381]
+CURVES = [pyref.BN254, pyref.BLS12_381, BLS12_377]
 # window widths forced on a pinned table (the raw call's planned width is found by planned_width); for BLS12-381's 255-bit Fr, 15 and
-# 17 divide 255, so the top window holds nothing but the carry
-TABLE_C = {"bn254": [4, 13, 16], "bls12-381": [5, 15, 17]}
+# 17 divide 255, so the top window holds nothing but the carry; 11 and 23 divide the 253 bits of BLS12-377's
+TABLE_C = {"bn254": [4, 13, 16], "bls12-381": [5, 15, 17], "bls12-377": [4, 11, 23]}
 TABLE_CASES = [(c, w) for c in CURVES for w in TABLE_C[c.name]]
-DIGIT_CASES = TABLE_CASES + [(CURVES[0], 8), (CURVES[1], 8), (CURVES[0], 22), (CURVES[1], 22)]
+DIGIT_CASES = TABLE_CASES + [(c, w) for w in (8, 22) for c in CURVES]
 FFT_LOGN = [1, 2, 3, 6, 10, 12]
 # the knob sets of test_fft_wave_local_rounds (device: default, no-direct, round3) and of its emulation twin (no-wave-local as well)
 FFT_2P17_KNOBS = {"default": {}, "no-direct": {"GA_NTT_DIRECT": "0"}, "no-wave-local": {"GA_NTT_WAVE_LOCAL": "0"},

@@ -23,7 +23,7 @@ enum {
     // lazy F29<P>: NL raw limbs per operand
     OP_F29_NORMALIZE = 20, OP_F29_ADD, OP_F29_ADD_RAW, OP_F29_SUB, OP_F29_SUB_RAW, OP_F29_SUB_WIDE, OP_F29_MUL, OP_F29_SQR,
     OP_F29_MUL_SUB, OP_F29_PARTIAL_REDUCE, OP_F29_REDUCE_3P, OP_F29_IS_ZERO_MOD_P, OP_F29_INV,
-    // F29x2<P>: c0 | c1, NL limbs each (base fields only)
+    // F29x2<P>: c0 | c1, NL limbs each (base fields with an Fp2 only)
     OP_F29X2_MUL = 40, OP_F29X2_SQR, OP_F29X2_MUL_SUB, OP_F29X2_INV,
     // point formulas over Fe<Fp> (50..) and Fe2<Fp> (60..): coordinates of Lazy<F>::NW words, k = number of chained applications
     OP_PT_ADD29 = 50, OP_PT_DBL29, OP_PT_MADD29, OP_PT_MDBL29, OP_PT_MADD29_COMPLETE,
@@ -34,9 +34,15 @@ enum {
 constexpr int MAX_CHAIN = 64;
 constexpr int DIGIT_WINDOWS = 64;   // every window of a 256-bit scalar for c >= 4
 
-template <class P> struct IsBaseField { static constexpr bool value = false; };
-template <> struct IsBaseField<BN254_Fp> { static constexpr bool value = true; };
-template <> struct IsBaseField<BLS12_381_Fp> { static constexpr bool value = true; };
+// HasG1: a base field, the G1 point formulas run over Fe<P>.  HasFp2: Fe2<P>, F29x2<P> and P::FP2Z_K exist (not for BLS12-377, whose
+// Fp2 would be u^2 + 5: Fe2 over it does not compile).  A scalar field has neither and gets the digit recoding instead.
+template <class P> struct HasG1 { static constexpr bool value = false; };
+template <> struct HasG1<BN254_Fp> { static constexpr bool value = true; };
+template <> struct HasG1<BLS12_381_Fp> { static constexpr bool value = true; };
+template <> struct HasG1<BLS12_377_Fp> { static constexpr bool value = true; };
+template <class P> struct HasFp2 { static constexpr bool value = false; };
+template <> struct HasFp2<BN254_Fp> { static constexpr bool value = true; };
+template <> struct HasFp2<BLS12_381_Fp> { static constexpr bool value = true; };
 
 template <class P>
 __device__ __forceinline__ Fe<P> ld_fe(const uint32_t* p) {
@@ -299,7 +305,7 @@ int run_field(int op, int k, const uint32_t* in, size_t n, size_t in_words, uint
     case OP_F29_SQR: GA_PROBE_FIELD_OP(OP_F29_SQR, 0);
     case OP_F29_MUL_SUB:
         if (k == 8) GA_PROBE_FIELD_OP(OP_F29_MUL_SUB, 8);
-        if constexpr (IsBaseField<P>::value) {
+        if constexpr (HasFp2<P>::value) {
             if (k == P::FP2Z_K) GA_PROBE_FIELD_OP(OP_F29_MUL_SUB, P::FP2Z_K);
         }
         return PROBE_BAD_ARGS;
@@ -308,11 +314,11 @@ int run_field(int op, int k, const uint32_t* in, size_t n, size_t in_words, uint
     case OP_F29_IS_ZERO_MOD_P: GA_PROBE_FIELD_OP(OP_F29_IS_ZERO_MOD_P, 0);
     case OP_F29_INV: GA_PROBE_FIELD_OP(OP_F29_INV, 0);
     }
-    if constexpr (!IsBaseField<P>::value) {
+    if constexpr (!HasG1<P>::value) {
         if (op == OP_DIGIT_WALK)
             return k >= 4 && k <= 24 ? launch(probe_digits_kernel<P>, 64, 9, 2 * DIGIT_WINDOWS, k, GA_PROBE_ARGS) : PROBE_BAD_ARGS;
     }
-    if constexpr (IsBaseField<P>::value) {
+    if constexpr (HasFp2<P>::value) {
         switch (op) {
         case OP_F29X2_MUL: GA_PROBE_FIELD_OP(OP_F29X2_MUL, 0);
         case OP_F29X2_SQR: GA_PROBE_FIELD_OP(OP_F29X2_SQR, 0);
@@ -321,15 +327,18 @@ int run_field(int op, int k, const uint32_t* in, size_t n, size_t in_words, uint
             return PROBE_BAD_ARGS;
         case OP_F29X2_INV: GA_PROBE_FIELD_OP(OP_F29X2_INV, 0);
         }
-        if (op >= OP_PT_ADD29 && op <= OP_PT_MADD29_COMPLETE) return run_point<Fe<P>>(op, k, GA_PROBE_ARGS);
         if (op >= OP_PT2_BASE && op <= OP_PT2_BASE + 4) return run_point<Fe2<P>>(op - OP_PT2_BASE + OP_PT_ADD29, k, GA_PROBE_ARGS);
+    }
+    if constexpr (HasG1<P>::value) {
+        if (op >= OP_PT_ADD29 && op <= OP_PT_MADD29_COMPLETE) return run_point<Fe<P>>(op, k, GA_PROBE_ARGS);
     }
     return PROBE_BAD_ARGS;
 }
 
 }  // namespace
 
-// field: 0 BN254 Fp, 1 BN254 Fr, 2 BLS12-381 Fp, 3 BLS12-381 Fr.  in: n elements of in_words words, out: n elements of out_words
+// field: 0 BN254 Fp, 1 BN254 Fr, 2 BLS12-381 Fp, 3 BLS12-381 Fr, 4 BLS12-377 Fp (G1 point formulas, no Fp2: the ops 40..43, the
+// point ops 60..64 and f29_mul_sub with k = FP2Z_K are refused), 5 BLS12-377 Fr.  in: n elements of in_words words, out: n elements of out_words
 // words, both host memory; the word counts must be the op's (a mismatch is refused, nothing is launched).  k: the template constant
 // of the subtractions, the factor of mul_small, the number of chained applications of a point formula, the window width of the digits.  Returns 0, 1 (bad
 // arguments) or 2 (a HIP call failed).
@@ -340,6 +349,8 @@ extern "C" __attribute__((visibility("default"))) int ga_probe_run(int field, in
     case 1: return run_field<BN254_Fr>(op, k, GA_PROBE_ARGS);
     case 2: return run_field<BLS12_381_Fp>(op, k, GA_PROBE_ARGS);
     case 3: return run_field<BLS12_381_Fr>(op, k, GA_PROBE_ARGS);
+    case 4: return run_field<BLS12_377_Fp>(op, k, GA_PROBE_ARGS);
+    case 5: return run_field<BLS12_377_Fr>(op, k, GA_PROBE_ARGS);
     }
     return PROBE_BAD_ARGS;
 }

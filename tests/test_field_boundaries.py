@@ -26,14 +26,14 @@ def test_field_primitive(emu_probe, case, field):
     fc.FIELD_CASES[case](emu_probe, fc.FIELDS[field])
 
 
-@pytest.mark.parametrize("field", fc.BASE_FIELDS)
+@pytest.mark.parametrize("field", fc.FP2_FIELDS)
 @pytest.mark.parametrize("case", sorted(fc.BASE_FIELD_CASES))
 def test_fp2_primitive(emu_probe, case, field):
     fc.BASE_FIELD_CASES[case](emu_probe, fc.FIELDS[field])
 
 
-@pytest.mark.parametrize("field", fc.BASE_FIELDS)
-@pytest.mark.parametrize("fp2", [False, True], ids=["G1", "G2"])
+# (G2 only over a field that has an Fp2: not BLS12-377's)
+@pytest.mark.parametrize("fp2,field", [pytest.param(fp2, n, id=("G2-" if fp2 else "G1-") + n) for n, fp2 in fc.POINT_FIELDS])
 @pytest.mark.parametrize("case", sorted(fc.POINT_CASES))
 def test_point_formula(emu_probe, case, fp2, field):
     fc.POINT_CASES[case](emu_probe, fc.FIELDS[field], fp2)
@@ -52,6 +52,14 @@ def test_probe_refuses_bad_arguments(emu_probe):
     assert f(1, fc.OP_F29X2_MUL, 0, buf, 1, 36, buf, 18) == 1     # Fp2 over a scalar field
     assert f(0, fc.OP_PT_ADD29, 65, buf, 0, 72, buf, 36) == 1     # chain longer than the probe allows
     assert f(0, fc.OP_ADD, 0, buf, 1, 16, buf, 8) == 0
+    # BLS12-377 Fp (field 4: 12 words, 14 limbs) has the G1 point formulas and no Fp2: the Fp2 ops, the point formulas over Fp2 and
+    # the Fp2 negation constant of f29_mul_sub are refused, with the word counts they would have; n = 0 launches nothing either way
+    assert f(4, fc.OP_F29X2_MUL, 0, buf, 0, 56, buf, 28) == 1
+    assert f(4, fc.OP_PT_ADD29 + fc.OP_PT2, 1, buf, 0, 224, buf, 112) == 1
+    assert f(4, fc.OP_F29_MUL_SUB, fc.FP2Z_K, buf, 0, 56, buf, 14) == 1
+    assert f(4, fc.OP_F29_MUL_SUB, 8, buf, 0, 56, buf, 14) == 0
+    assert f(4, fc.OP_PT_ADD29, 1, buf, 0, 112, buf, 56) == 0
+    assert f(2, fc.OP_PT_ADD29 + fc.OP_PT2, 1, buf, 0, 224, buf, 112) == 0
 
 
 @pytest.mark.parametrize("c,cbits", fc.DIGIT_CASES, ids=lambda v: getattr(v, "name", str(v)))

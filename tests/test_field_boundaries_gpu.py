@@ -24,14 +24,14 @@ def test_field_primitive(gpu_probe, case, field):
     fc.FIELD_CASES[case](gpu_probe, fc.FIELDS[field])
 
 
-@pytest.mark.parametrize("field", fc.BASE_FIELDS)
+@pytest.mark.parametrize("field", fc.FP2_FIELDS)
 @pytest.mark.parametrize("case", sorted(fc.BASE_FIELD_CASES))
 def test_fp2_primitive(gpu_probe, case, field):
     fc.BASE_FIELD_CASES[case](gpu_probe, fc.FIELDS[field])
 
 
-@pytest.mark.parametrize("field", fc.BASE_FIELDS)
-@pytest.mark.parametrize("fp2", [False, True], ids=["G1", "G2"])
+# (G2 only over a field that has an Fp2: not BLS12-377's)
+@pytest.mark.parametrize("fp2,field", [pytest.param(fp2, n, id=("G2-" if fp2 else "G1-") + n) for n, fp2 in fc.POINT_FIELDS])
 @pytest.mark.parametrize("case", sorted(fc.POINT_CASES))
 def test_point_formula(gpu_probe, case, fp2, field):
     fc.POINT_CASES[case](gpu_probe, fc.FIELDS[field], fp2)

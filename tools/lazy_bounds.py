@@ -371,7 +371,7 @@ def check_dbl(curve: str, fp2: bool, verbose=False, exact=False):
 
 
 # ---- double-and-add on general XYZZ points (ec_ntt.hip.h::ec_ntt_scalar_mul29: the butterflies of kzg.ToLagrangeG1; scale_points.hip.h) ----
-def check_ladder(curve: str, fp2: bool = False, verbose=False):
+def check_ladder(curve: str, fp2: bool = False, verbose=False, exact=False):
     """A butterfly of the point FFT feeds add29 with canonical points (one of them with a negated y, 2p - y) and then
     alternates dbl29 and add29 on the results without ever normalising: acc = dbl29(acc); acc = add29(acc, D) where D is an earlier
     add29 output.  One set of bounds covers every point either function may see there -- a canonical point, a negated one, any
@@ -463,6 +463,8 @@ def check_ladder(curve: str, fp2: bool = False, verbose=False):
         b = nb
     else:
         raise AssertionError("bounds of the double-and-add ladder do not converge")
+    if exact:
+        return dict(zip(("X", "Y", "ZZ", "ZZZ"), b))
     out = {"X": log2(b[0]), "Y": log2(b[1]), "ZZ": log2(b[2]), "ZZZ": log2(b[3]), "limit": L * NL}
     if verbose:
         print(curve, "ladder G2" if fp2 else "ladder G1", {a: round(v, 2) for a, v in out.items()})
