@@ -42,19 +42,41 @@ EntryScope::EntryScope(const char* name) : prev(g_entry) { g_entry = name; }
 EntryScope::~EntryScope() { g_entry = prev; }
 const char* current_entry() { return g_entry; }
 
-int curve_not_dispatched(int curve) {
-    if (curve == GA_BLS12_377)
-        set_error("%s is not built for bls12-377 (curve id %d): that curve has the G1 and Fr calls only, its Fp2 is Fp[u]/(u^2 + 5)", current_entry(), curve);
-    else
-        set_error("unknown curve id %d", curve);
-    return GA_ERR_INVALID;
+// ---- which (curve, group) pairs are built, and the answer for one that is not (common.hip.h: dispatch) ----------------------------
+// what the two functions below need of a curve id at run time, read from the tags of GA_CURVES; name == nullptr: no such curve
+struct CurveInfo {
+    const char* name;
+    bool has_g2;
+    const char* no_g2;
+};
+template <class C>
+static constexpr const char* no_g2_reason() {
+    if constexpr (C::HAS_G2) return "";
+    else return C::NO_G2;
 }
-// a (curve, group) pair of a G1 / Fr call that is not built: G2 of bls12-377, or a group id that does not exist
-static int group_not_built(int curve, int group) {
-    if (curve == GA_BLS12_377 && group == GA_G2)
-        set_error("%s: G2 is not built for bls12-377 (curve id %d): that curve has the G1 and Fr calls only, its Fp2 is Fp[u]/(u^2 + 5)", current_entry(), curve);
-    else
-        set_error("unknown group id %d", group);
+static CurveInfo curve_info(int curve) {
+#define GA_CURVE_INFO(T) \
+    if (curve == T::ID) return CurveInfo{T::NAME, T::HAS_G2, no_g2_reason<T>()};
+    GA_CURVES(GA_CURVE_INFO)
+#undef GA_CURVE_INFO
+    return CurveInfo{nullptr, false, ""};
+}
+static bool group_exists(GroupArg group) { return !group.given || group.id == GA_G1 || group.id == GA_G2; }
+bool dispatch_built(Scope scope, int curve, GroupArg group) {
+    const CurveInfo ci = curve_info(curve);
+    return ci.name && (scope == Scope::G1_FR || ci.has_g2) && group_exists(group) && (group.id != GA_G2 || ci.has_g2);
+}
+int dispatch_refuse(Scope scope, int curve, GroupArg group) {
+    const CurveInfo ci = curve_info(curve);
+    const char* entry = current_entry();
+    if (!ci.name)   // (asked first: with both ids unknown the curve is reported)
+        set_error("%s: unknown curve id %d", entry, curve);
+    else if (scope == Scope::FULL && !ci.has_g2)
+        set_error("%s is not built for %s (curve id %d): that curve has the G1 and Fr calls only, %s", entry, ci.name, curve, ci.no_g2);
+    else if (!group_exists(group))
+        set_error("%s: unknown group id %d", entry, group.id);
+    else   // G2 of a curve without it
+        set_error("%s: G2 is not built for %s (curve id %d): that curve has the G1 and Fr calls only, %s", entry, ci.name, curve, ci.no_g2);
     return GA_ERR_INVALID;
 }
 static uint64_t fnv1a(const char* s) {
@@ -267,24 +289,8 @@ static uint32_t env_segment(const char* name) {   // the two segment knobs, capp
 }
 
 // ---- argument checks the entry points share: each sets the error under the entry point's name and returns false -------------------
-// g1_fr: the entry point is one of the G1 / Fr calls, which BLS12-377 has too (include/gnark_amd.h lists them); without it only the
-// two curves built in full pass, and BLS12-377 is refused by name (curve_not_dispatched), never as an unknown curve
-static bool abi_curve_ok(int curve, bool g1_fr = false) {
-    if (curve == GA_BN254 || curve == GA_BLS12_381 || (g1_fr && curve == GA_BLS12_377)) return true;
-    if (curve == GA_BLS12_377) curve_not_dispatched(curve);
-    else set_error("%s: unknown curve id %d", current_entry(), curve);
-    return false;
-}
-static bool abi_curve_group_ok(int curve, int group, bool g1_fr = false) {
-    if ((curve == GA_BN254 || curve == GA_BLS12_381) && (group == GA_G1 || group == GA_G2)) return true;
-    if (g1_fr && curve == GA_BLS12_377 && group == GA_G1) return true;
-    if (curve == GA_BLS12_377 && (group == GA_G1 || group == GA_G2)) {
-        if (g1_fr) group_not_built(curve, group);
-        else curve_not_dispatched(curve);
-    } else
-        set_error("%s: unknown curve id %d or group id %d", current_entry(), curve, group);
-    return false;
-}
+// (the curve and group ids: an entry point that answers n = 0 before it dispatches names its scope S once, asks
+// dispatch_check(S, curve, group) first and dispatches under the same S -- a bad id is never answered with GA_OK)
 // n elements whose first has index `first`: at most 2^32 of them, and no index above 2^64 - 1
 static bool abi_range_ok(size_t n, uint64_t first) {
     if ((uint64_t)n <= (1ull << 32) && (n == 0 || first <= UINT64_MAX - (uint64_t)n + 1)) return true;
@@ -381,31 +387,6 @@ static int msm_impl(Ctx* ctx, const void* bases, const void* scalars, size_t n, 
 }  // namespace ga
 
 using namespace ga;
-
-#define GA_DISPATCH_GROUP(group, ...)                           \
-    switch (group) {                                            \
-        case GA_G1: {                                           \
-            constexpr int G = GA_G1;                            \
-            __VA_ARGS__;                                        \
-        } break;                                                \
-        case GA_G2: {                                           \
-            constexpr int G = GA_G2;                            \
-            __VA_ARGS__;                                        \
-        } break;                                                \
-        default:                                                \
-            set_error("unknown group id %d", (int)(group));     \
-            return GA_ERR_INVALID;                              \
-    }
-
-// every (curve, group) that is built: both groups of the curves built in full, G1 of BLS12-377
-#define GA_DISPATCH_CURVE_GROUP(curve, group, ...)                  \
-    if ((curve) == GA_BLS12_377) {                                  \
-        if ((group) != GA_G1) return group_not_built((int)(curve), (int)(group)); \
-        using C = ::ga::Bls12377;                                   \
-        constexpr int G = GA_G1;                                    \
-        __VA_ARGS__;                                                \
-    } else                                                          \
-        GA_DISPATCH_CURVE(curve, GA_DISPATCH_GROUP(group, __VA_ARGS__))
 
 extern "C" {
 
@@ -557,8 +538,7 @@ int ga_msm(ga_ctx* h, int curve, int group, const void* bases, const void* scala
         return GA_ERR_INVALID;
     }
     Lock l(c);
-    GA_DISPATCH_CURVE_GROUP(curve, group, return (msm_impl<C, G>(c, bases, scalars, n, flags, 0, -1, out_jac, nullptr, nullptr, false)));
-    return GA_OK;
+    return GA_DISPATCH(Scope::G1_FR, curve, group, return (msm_impl<C, G>(c, bases, scalars, n, flags, 0, -1, out_jac, nullptr, nullptr, false)));
 } GA_ABI_CATCH
 
 int ga_msm_windows(ga_ctx* h, int curve, int group, const void* bases, const void* scalars, size_t n, unsigned flags, int win_lo,
@@ -570,9 +550,8 @@ int ga_msm_windows(ga_ctx* h, int curve, int group, const void* bases, const voi
         return GA_ERR_INVALID;
     }
     Lock l(c);
-    GA_DISPATCH_CURVE_GROUP(curve, group, return (msm_impl<C, G>(c, bases, scalars, n, flags, win_lo, win_hi, out_windows,
-                                                                            window_bits, num_windows, true)));
-    return GA_OK;
+    return GA_DISPATCH(Scope::G1_FR, curve, group,
+                       return (msm_impl<C, G>(c, bases, scalars, n, flags, win_lo, win_hi, out_windows, window_bits, num_windows, true)));
 } GA_ABI_CATCH
 
 // ---- fixed-base batch scalar multiplication (fixed_base.hip.h) ---------------------------------------------
@@ -580,7 +559,8 @@ int ga_batch_scalar_mul(ga_ctx* h, int curve, int group, const void* base_affine
                         void* out_affine) try {
     GA_ABI_ENTRY();
     Ctx* c = reinterpret_cast<Ctx*>(h);
-    if (!abi_curve_group_ok(curve, group, true)) return GA_ERR_INVALID;
+    constexpr Scope S = Scope::G1_FR;
+    GA_CHECK(dispatch_check(S, curve, group));
     if (n == 0) return GA_OK;
     if (!c || !base_affine || !scalars || !out_affine) {
         set_error("ga_batch_scalar_mul: null argument");
@@ -593,8 +573,7 @@ int ga_batch_scalar_mul(ga_ctx* h, int curve, int group, const void* base_affine
     Lock l(c);
     const int forced_c = env_int("GA_FIXED_BASE_C", 0);
     const uint64_t forced_chunk = env_u64("GA_FIXED_BASE_CHUNK", 0);
-    GA_DISPATCH_CURVE_GROUP(curve, group, return (fixed_base_run<C, G>(c, base_affine, scalars, n, flags, out_affine, forced_c, forced_chunk)));
-    return GA_OK;
+    return GA_DISPATCH(S, curve, group, return (fixed_base_run<C, G>(c, base_affine, scalars, n, flags, out_affine, forced_c, forced_chunk)));
 } GA_ABI_CATCH
 
 int ga_batch_scalar_mul_plan(int curve, size_t n, int* window_bits, int* num_windows) try {
@@ -604,15 +583,15 @@ int ga_batch_scalar_mul_plan(int curve, size_t n, int* window_bits, int* num_win
         return GA_ERR_INVALID;
     }
     const int forced_c = env_int("GA_FIXED_BASE_C", 0);
-    GA_DISPATCH_CURVE_FR(curve, return fixed_base_plan_abi<C>(n, forced_c, window_bits, num_windows));
-    return GA_OK;
+    return GA_DISPATCH(Scope::G1_FR, curve, GA_NO_GROUP, return fixed_base_plan_abi<C>(n, forced_c, window_bits, num_windows));
 } GA_ABI_CATCH
 
 // ---- kzg.ToLagrangeG1 (ec_ntt.hip.h) -----------------------------------------------------------------------
 int ga_kzg_to_lagrange_g1(ga_ctx* h, int curve, const void* powers_affine, size_t n, unsigned flags, void* out_affine) try {
     GA_ABI_ENTRY();
     Ctx* c = reinterpret_cast<Ctx*>(h);
-    if (!abi_curve_ok(curve, true)) return GA_ERR_INVALID;
+    constexpr Scope S = Scope::G1_FR;
+    GA_CHECK(dispatch_check(S, curve, GA_NO_GROUP));
     if (n == 0) return GA_OK;
     if (!c || !powers_affine || !out_affine) {
         set_error("ga_kzg_to_lagrange_g1: null argument");
@@ -620,14 +599,14 @@ int ga_kzg_to_lagrange_g1(ga_ctx* h, int curve, const void* powers_affine, size_
     }
     Lock l(c);
     const int uniform = env_flag("GA_EC_NTT_UNIFORM", 1);
-    GA_DISPATCH_CURVE_FR(curve, return (ec_ntt_to_lagrange<C, GA_G1>(c, powers_affine, n, flags, out_affine, uniform)));
-    return GA_OK;
+    return GA_DISPATCH(S, curve, GA_NO_GROUP, return (ec_ntt_to_lagrange<C, GA_G1>(c, powers_affine, n, flags, out_affine, uniform)));
 } GA_ABI_CATCH
 
 int ga_lagrange_coeffs(ga_ctx* h, int curve, int group, const void* powers_affine, size_t n, unsigned flags, void* out_affine) try {
     GA_ABI_ENTRY();
     Ctx* c = reinterpret_cast<Ctx*>(h);
-    if (!abi_curve_group_ok(curve, group)) return GA_ERR_INVALID;
+    constexpr Scope S = Scope::FULL;
+    GA_CHECK(dispatch_check(S, curve, group));
     if (n == 0) return GA_OK;
     if (!c || !powers_affine || !out_affine) {
         set_error("ga_lagrange_coeffs: null argument");
@@ -635,8 +614,7 @@ int ga_lagrange_coeffs(ga_ctx* h, int curve, int group, const void* powers_affin
     }
     Lock l(c);
     const int uniform = env_flag("GA_EC_NTT_UNIFORM", 1);
-    GA_DISPATCH_CURVE(curve, GA_DISPATCH_GROUP(group, return (ec_ntt_to_lagrange<C, G>(c, powers_affine, n, flags, out_affine, uniform))));
-    return GA_OK;
+    return GA_DISPATCH(S, curve, group, return (ec_ntt_to_lagrange<C, G>(c, powers_affine, n, flags, out_affine, uniform)));
 } GA_ABI_CATCH
 
 // ---- per-point scalar multiplication (scale_points.hip.h) ---------------------------------------------------
@@ -644,7 +622,8 @@ int ga_scale_points(ga_ctx* h, int curve, int group, const void* points_affine, 
                     unsigned flags, void* out_affine, uint64_t* redone) try {
     GA_ABI_ENTRY();
     Ctx* c = reinterpret_cast<Ctx*>(h);
-    if (!abi_curve_group_ok(curve, group)) return GA_ERR_INVALID;
+    constexpr Scope S = Scope::FULL;
+    GA_CHECK(dispatch_check(S, curve, group));
     if (mode != GA_SCALE_EACH && mode != GA_SCALE_ONE && mode != GA_SCALE_POWERS) {
         set_error("ga_scale_points: unknown mode %d", mode);
         return GA_ERR_INVALID;
@@ -669,16 +648,16 @@ int ga_scale_points(ga_ctx* h, int curve, int group, const void* points_affine, 
     Lock l(c);
     const int windowed = env_flag("GA_SCALE_WINDOW", 1);
     const uint64_t forced_chunk = env_u64("GA_SCALE_CHUNK", 0);
-    GA_DISPATCH_CURVE(curve, GA_DISPATCH_GROUP(group, return (scale_points_run<C, G>(c, points_affine, n, mode, scalars, first, flags, out_affine, redone,
-                                                                                    windowed, forced_chunk))));
-    return GA_OK;
+    return GA_DISPATCH(S, curve, group,
+                       return (scale_points_run<C, G>(c, points_affine, n, mode, scalars, first, flags, out_affine, redone, windowed, forced_chunk)));
 } GA_ABI_CATCH
 
 // ---- batch curve and subgroup checks (check_points.hip.h) ---------------------------------------------------
 int ga_check_points(ga_ctx* h, int curve, int group, const void* points_affine, size_t n, unsigned flags, uint8_t* status, uint64_t* out4) try {
     GA_ABI_ENTRY();
     Ctx* c = reinterpret_cast<Ctx*>(h);
-    if (!abi_curve_group_ok(curve, group, true)) return GA_ERR_INVALID;
+    constexpr Scope S = Scope::G1_FR;
+    GA_CHECK(dispatch_check(S, curve, group));
     if ((uint64_t)n > (1ull << 32)) {
         set_error("ga_check_points: n = %zu above 2^32", n);
         return GA_ERR_INVALID;
@@ -695,8 +674,7 @@ int ga_check_points(ga_ctx* h, int curve, int group, const void* points_affine, 
     Lock l(c);
     const int naive = check_naive_knob();
     const uint64_t forced_chunk = env_u64("GA_CHECK_CHUNK", 0);
-    GA_DISPATCH_CURVE_GROUP(curve, group, return (check_points_run<C, G>(c, points_affine, n, flags, status, out4, naive, forced_chunk)));
-    return GA_OK;
+    return GA_DISPATCH(S, curve, group, return (check_points_run<C, G>(c, points_affine, n, flags, status, out4, naive, forced_chunk)));
 } GA_ABI_CATCH
 
 // ---- products of pairings (pairing.hip.h) -----------------------------------------------------------------
@@ -704,7 +682,8 @@ int ga_pairing_check(ga_ctx* h, int curve, const void* p_affine, const void* q_a
                      uint8_t* ok, void* gt, uint64_t* out2) try {
     GA_ABI_ENTRY();
     Ctx* c = reinterpret_cast<Ctx*>(h);
-    if (!abi_curve_ok(curve)) return GA_ERR_INVALID;
+    constexpr Scope S = Scope::FULL;
+    GA_CHECK(dispatch_check(S, curve, GA_NO_GROUP));
     if (n_groups == 0) return GA_OK;
     if ((uint64_t)n > (1ull << 32) || (uint64_t)n_groups >= (1ull << 31)) {
         set_error("ga_pairing_check: n = %zu above 2^32 or n_groups = %zu above 2^31 - 1", n, n_groups);
@@ -733,8 +712,7 @@ int ga_pairing_check(ga_ctx* h, int curve, const void* p_affine, const void* q_a
     }
     Lock l(c);
     const uint64_t forced_chunk = env_u64("GA_PAIRING_CHUNK", 0);
-    GA_DISPATCH_CURVE(curve, return (pairing_run<C>(c, p_affine, q_affine, n, group_start, n_groups, flags, ok, gt, out2, forced_chunk)));
-    return GA_OK;
+    return GA_DISPATCH(S, curve, GA_NO_GROUP, return (pairing_run<C>(c, p_affine, q_affine, n, group_start, n_groups, flags, ok, gt, out2, forced_chunk)));
 } GA_ABI_CATCH
 
 // ---- sparse point sums (sparse_sums.hip.h) ----------------------------------------------------------------
@@ -742,7 +720,8 @@ int ga_sparse_point_sums(ga_ctx* h, int curve, int group, const void* points_aff
                          const uint32_t* terms, const void* coeffs, size_t n_coeffs, unsigned flags, void* out_affine, uint64_t* redone) try {
     GA_ABI_ENTRY();
     Ctx* c = reinterpret_cast<Ctx*>(h);
-    if (!abi_curve_group_ok(curve, group)) return GA_ERR_INVALID;
+    constexpr Scope S = Scope::FULL;
+    GA_CHECK(dispatch_check(S, curve, group));
     if (n_rows == 0) {
         if (redone) *redone = 0;
         return GA_OK;
@@ -764,18 +743,19 @@ int ga_sparse_point_sums(ga_ctx* h, int curve, int group, const void* points_aff
     const uint64_t forced_chunk = env_u64("GA_SPARSE_CHUNK", 0);
     const uint32_t segment = env_segment("GA_SPARSE_SEGMENT");
     const int cid_order = env_u64("GA_SPARSE_ORDER", 0) != 0;
-    GA_DISPATCH_CURVE(curve, GA_DISPATCH_GROUP(group, return (sparse_sums_run<C, G>(c, points_affine, n_points, row_start, n_rows, terms, coeffs, n_coeffs, flags,
-                                                                                   out_affine, redone, forced_chunk, segment, cid_order))));
-    return GA_OK;
+    return GA_DISPATCH(S, curve, group,
+                       return (sparse_sums_run<C, G>(c, points_affine, n_points, row_start, n_rows, terms, coeffs, n_coeffs, flags, out_affine, redone,
+                                                     forced_chunk, segment, cid_order)));
 } GA_ABI_CATCH
 
 // ---- the scalar side of groth16.Setup (fr_sparse.hip.h, fr_setup.hip.h) -----------------------------------
 int ga_fr_lagrange_at(ga_ctx* h, int curve, uint64_t n, const void* tau, size_t m, unsigned flags, void* out) try {
     GA_ABI_ENTRY();
     Ctx* c = reinterpret_cast<Ctx*>(h);
-    if (!abi_curve_ok(curve)) return GA_ERR_INVALID;
+    constexpr Scope S = Scope::FULL;
+    GA_CHECK(dispatch_check(S, curve, GA_NO_GROUP));
     int adicity = 0;
-    GA_DISPATCH_CURVE(curve, adicity = C::FrP::ADICITY);
+    GA_CHECK(GA_DISPATCH(S, curve, GA_NO_GROUP, adicity = C::FrP::ADICITY));
     if (n == 0 || (n & (n - 1)) != 0 || n > (1ull << adicity)) {
         set_error("ga_fr_lagrange_at: n = %llu is not a power of two of at most 2^%d", (unsigned long long)n, adicity);
         return GA_ERR_INVALID;
@@ -790,8 +770,7 @@ int ga_fr_lagrange_at(ga_ctx* h, int curve, uint64_t n, const void* tau, size_t 
         return GA_ERR_INVALID;
     }
     Lock l(c);
-    GA_DISPATCH_CURVE(curve, return fr_lagrange_run<C>(c, ilog2_u64(n), tau, m, flags, out));
-    return GA_OK;
+    return GA_DISPATCH(S, curve, GA_NO_GROUP, return fr_lagrange_run<C>(c, ilog2_u64(n), tau, m, flags, out));
 } GA_ABI_CATCH
 
 int ga_fr_sparse_matvec(ga_ctx* h, int curve, const void* x, size_t n_cols, const uint64_t* row_start, size_t n_rows, const uint32_t* terms,
@@ -799,7 +778,8 @@ int ga_fr_sparse_matvec(ga_ctx* h, int curve, const void* x, size_t n_cols, cons
                         void* out) try {
     GA_ABI_ENTRY();
     Ctx* c = reinterpret_cast<Ctx*>(h);
-    if (!abi_curve_ok(curve)) return GA_ERR_INVALID;
+    constexpr Scope S = Scope::FULL;
+    GA_CHECK(dispatch_check(S, curve, GA_NO_GROUP));
     if (n_rows == 0) return GA_OK;
     if ((uint64_t)n_rows >= (1ull << 31) || (uint64_t)n_cols > (1ull << 32) || (uint64_t)n_coeffs > (1ull << 32)) {
         set_error("ga_fr_sparse_matvec: n_rows = %zu (at most 2^31 - 1), n_cols = %zu or n_coeffs = %zu (at most 2^32) out of range", n_rows, n_cols, n_coeffs);
@@ -815,14 +795,15 @@ int ga_fr_sparse_matvec(ga_ctx* h, int curve, const void* x, size_t n_cols, cons
     }
     Lock l(c);
     const uint32_t segment = env_segment("GA_FR_SPARSE_SEGMENT");
-    GA_DISPATCH_CURVE(curve, return fr_sparse_run<C>(c, x, n_cols, row_start, n_rows, terms, coeffs, n_coeffs, row_class, row_scales, n_classes, flags, out, segment));
-    return GA_OK;
+    return GA_DISPATCH(S, curve, GA_NO_GROUP,
+                       return fr_sparse_run<C>(c, x, n_cols, row_start, n_rows, terms, coeffs, n_coeffs, row_class, row_scales, n_classes, flags, out, segment));
 } GA_ABI_CATCH
 
 int ga_fr_compact_nonzero(ga_ctx* h, int curve, const void* v, size_t n, unsigned flags, void* out, uint8_t* mask, uint64_t* count) try {
     GA_ABI_ENTRY();
     Ctx* c = reinterpret_cast<Ctx*>(h);
-    if (!abi_curve_ok(curve)) return GA_ERR_INVALID;
+    constexpr Scope S = Scope::FULL;
+    GA_CHECK(dispatch_check(S, curve, GA_NO_GROUP));
     if (!count) {
         set_error("ga_fr_compact_nonzero: null count");
         return GA_ERR_INVALID;
@@ -840,14 +821,14 @@ int ga_fr_compact_nonzero(ga_ctx* h, int curve, const void* v, size_t n, unsigne
         return GA_ERR_INVALID;
     }
     Lock l(c);
-    GA_DISPATCH_CURVE(curve, return fr_compact_run<C>(c, v, n, flags, out, mask, count));
-    return GA_OK;
+    return GA_DISPATCH(S, curve, GA_NO_GROUP, return fr_compact_run<C>(c, v, n, flags, out, mask, count));
 } GA_ABI_CATCH
 
 int ga_fr_powers(ga_ctx* h, int curve, const void* scalars, uint64_t first, size_t n, unsigned flags, void* out) try {
     GA_ABI_ENTRY();
     Ctx* c = reinterpret_cast<Ctx*>(h);
-    if (!abi_curve_ok(curve)) return GA_ERR_INVALID;
+    constexpr Scope S = Scope::FULL;
+    GA_CHECK(dispatch_check(S, curve, GA_NO_GROUP));
     if (!abi_range_ok(n, first)) return GA_ERR_INVALID;
     if (n == 0) return GA_OK;
     if (!c || !scalars || !out) {
@@ -855,15 +836,12 @@ int ga_fr_powers(ga_ctx* h, int curve, const void* scalars, uint64_t first, size
         return GA_ERR_INVALID;
     }
     Lock l(c);
-    GA_DISPATCH_CURVE(curve, return fr_powers_run<C>(c, scalars, first, n, flags, out));
-    return GA_OK;
+    return GA_DISPATCH(S, curve, GA_NO_GROUP, return fr_powers_run<C>(c, scalars, first, n, flags, out));
 } GA_ABI_CATCH
 
 int ga_msm_plan(int curve, int group, size_t n, int* window_bits, int* num_windows) try {
     GA_ABI_ENTRY();
-    if (curve == GA_BLS12_377 && group != GA_G1) return group_not_built(curve, group);
-    GA_DISPATCH_CURVE_FR(curve, return msm_plan<C>(group, n, window_bits, num_windows));
-    return GA_OK;
+    return GA_DISPATCH(Scope::G1_FR, curve, group, return msm_plan<C>(G, n, window_bits, num_windows));
 } GA_ABI_CATCH
 
 int ga_msm_combine_windows(int curve, int group, const void* windows, int num_windows, int window_bits, void* out_jac) try {
@@ -872,14 +850,13 @@ int ga_msm_combine_windows(int curve, int group, const void* windows, int num_wi
         set_error("ga_msm_combine_windows: bad argument");
         return GA_ERR_INVALID;
     }
-    GA_DISPATCH_CURVE_GROUP(curve, group, {
-                          typedef typename GroupField<C, G>::F F;
-                          std::vector<XYZZ<F>> W(num_windows);
-                          for (int w = 0; w < num_windows; w++)
-                              W[w] = host_load_jac<F>(reinterpret_cast<const char*>(windows) + (size_t)w * sizeof(Jac<F>));
-                          host_store_jac<F>(out_jac, host_horner(W.data(), num_windows, window_bits));
-                      });
-    return GA_OK;
+    return GA_DISPATCH(Scope::G1_FR, curve, group, {
+        typedef typename GroupField<C, G>::F F;
+        std::vector<XYZZ<F>> W(num_windows);
+        for (int w = 0; w < num_windows; w++)
+            W[w] = host_load_jac<F>(reinterpret_cast<const char*>(windows) + (size_t)w * sizeof(Jac<F>));
+        host_store_jac<F>(out_jac, host_horner(W.data(), num_windows, window_bits));
+    });
 } GA_ABI_CATCH
 
 // ---- precomputed tables ------------------------------------------------------------------------------------
@@ -910,22 +887,22 @@ int ga_msm_table_create(ga_ctx* h, int curve, int group, const void* bases, size
     } own{new MsmTable{c, curve, group, 0, 0, n, nullptr, 0}};
     MsmTable* t = own.t;
     int rc = GA_OK;
-    GA_DISPATCH_CURVE_GROUP(curve, group, {
-                          typedef typename GroupField<C, G>::F F;
-                          rc = msm_plan_table<C>(n, &t->c, &t->nwin, (flags & GA_TABLE_BATCHED) != 0);
-                          t->bytes = (uint64_t)t->nwin * n * msm_table_point_bytes<C, G>();
-                          Staged sb{c};
-                          if (rc == GA_OK) rc = sb.stage(bases, n * sizeof(Affine<F>), flags & GA_BASES_ON_DEVICE);
-                          if (rc == GA_OK && device_malloc(&t->d_table, t->bytes) != hipSuccess) {
-                              set_error("ga_msm_table_create: device_malloc(%llu) failed", (unsigned long long)t->bytes);
-                              rc = GA_ERR_NOMEM;
-                          }
-                          if (rc == GA_OK) rc = msm_table_build<C, G>(c, sb.dev, n, t->c, t->d_table);
-                          if (rc == GA_OK && hipStreamSynchronize(c->stream) != hipSuccess) {
-                              set_error("ga_msm_table_create: table kernel failed");
-                              rc = GA_ERR_HIP;
-                          }
-                      });
+    GA_CHECK(GA_DISPATCH(Scope::G1_FR, curve, group, {
+        typedef typename GroupField<C, G>::F F;
+        rc = msm_plan_table<C>(n, &t->c, &t->nwin, (flags & GA_TABLE_BATCHED) != 0);
+        t->bytes = (uint64_t)t->nwin * n * msm_table_point_bytes<C, G>();
+        Staged sb{c};
+        if (rc == GA_OK) rc = sb.stage(bases, n * sizeof(Affine<F>), flags & GA_BASES_ON_DEVICE);
+        if (rc == GA_OK && device_malloc(&t->d_table, t->bytes) != hipSuccess) {
+            set_error("ga_msm_table_create: device_malloc(%llu) failed", (unsigned long long)t->bytes);
+            rc = GA_ERR_NOMEM;
+        }
+        if (rc == GA_OK) rc = msm_table_build<C, G>(c, sb.dev, n, t->c, t->d_table);
+        if (rc == GA_OK && hipStreamSynchronize(c->stream) != hipSuccess) {
+            set_error("ga_msm_table_create: table kernel failed");
+            rc = GA_ERR_HIP;
+        }
+    }));
     if (rc != GA_OK) return rc;
     own.t = nullptr;
     *out = reinterpret_cast<ga_msm_table*>(t);
@@ -962,15 +939,14 @@ int ga_msm_table_run(ga_msm_table* th, const void* scalars, unsigned flags, void
     }
     Ctx* c = t->ctx;
     LaneLock l(c);   // a second caller (the PLONK prover commits from several goroutines) runs beside the first on lane 1
-    GA_DISPATCH_CURVE_GROUP(t->curve, t->group, {
-                          typedef typename GroupField<C, G>::F F;
-                          Staged ss{c};
-                          GA_CHECK(ss.stage(scalars, t->n * 32, flags & GA_SCALARS_ON_DEVICE));
-                          XYZZ<F> sum;
-                          GA_CHECK((msm_table_device<C, G>(c, t->d_table, ss.dev, t->n, (flags & GA_SCALARS_MONTGOMERY) != 0, t->c, &sum)));
-                          host_store_jac<F>(out_jac, sum);
-                      });
-    return GA_OK;
+    return GA_DISPATCH(Scope::G1_FR, t->curve, t->group, {
+        typedef typename GroupField<C, G>::F F;
+        Staged ss{c};
+        GA_CHECK(ss.stage(scalars, t->n * 32, flags & GA_SCALARS_ON_DEVICE));
+        XYZZ<F> sum;
+        GA_CHECK((msm_table_device<C, G>(c, t->d_table, ss.dev, t->n, (flags & GA_SCALARS_MONTGOMERY) != 0, t->c, &sum)));
+        host_store_jac<F>(out_jac, sum);
+    });
 } GA_ABI_CATCH
 
 int ga_msm_table_run_batch(ga_msm_table* th, const void* const* scalars, uint32_t k, unsigned flags, void* out_jacs) try {
@@ -992,21 +968,20 @@ int ga_msm_table_run_batch(ga_msm_table* th, const void* const* scalars, uint32_
     }
     Ctx* c = t->ctx;
     LaneLock l(c);   // a second caller (the PLONK prover commits from several goroutines) runs beside the first on lane 1
-    GA_DISPATCH_CURVE_GROUP(t->curve, t->group, {
-                          typedef typename GroupField<C, G>::F F;
-                          std::vector<std::unique_ptr<Staged>> st;
-                          std::vector<const void*> dev(k);
-                          for (uint32_t j = 0; j < k; j++) {
-                              st.emplace_back(new Staged{c});
-                              GA_CHECK(st.back()->stage(scalars[j], t->n * 32, flags & GA_SCALARS_ON_DEVICE));
-                              dev[j] = st.back()->dev;
-                          }
-                          std::vector<XYZZ<F>> sums(k);
-                          GA_CHECK((msm_table_device_batch<C, G>(c, t->d_table, dev.data(), (int)k, t->n, (flags & GA_SCALARS_MONTGOMERY) != 0,
-                                                                 t->c, sums.data())));
-                          for (uint32_t j = 0; j < k; j++) host_store_jac<F>((char*)out_jacs + j * sizeof(Jac<F>), sums[j]);
-                      });
-    return GA_OK;
+    return GA_DISPATCH(Scope::G1_FR, t->curve, t->group, {
+        typedef typename GroupField<C, G>::F F;
+        std::vector<std::unique_ptr<Staged>> st;
+        std::vector<const void*> dev(k);
+        for (uint32_t j = 0; j < k; j++) {
+            st.emplace_back(new Staged{c});
+            GA_CHECK(st.back()->stage(scalars[j], t->n * 32, flags & GA_SCALARS_ON_DEVICE));
+            dev[j] = st.back()->dev;
+        }
+        std::vector<XYZZ<F>> sums(k);
+        GA_CHECK((msm_table_device_batch<C, G>(c, t->d_table, dev.data(), (int)k, t->n, (flags & GA_SCALARS_MONTGOMERY) != 0,
+                                               t->c, sums.data())));
+        for (uint32_t j = 0; j < k; j++) host_store_jac<F>((char*)out_jacs + j * sizeof(Jac<F>), sums[j]);
+    });
 } GA_ABI_CATCH
 
 int ga_msm_table_run_windows(ga_msm_table* th, const void* scalars, unsigned flags, int win_lo, int win_hi, void* out_jac) try {
@@ -1022,16 +997,15 @@ int ga_msm_table_run_windows(ga_msm_table* th, const void* scalars, unsigned fla
     }
     Ctx* c = t->ctx;
     LaneLock l(c);   // a second caller (the PLONK prover commits from several goroutines) runs beside the first on lane 1
-    GA_DISPATCH_CURVE_GROUP(t->curve, t->group, {
-                          typedef typename GroupField<C, G>::F F;
-                          Staged ss{c};
-                          GA_CHECK(ss.stage(scalars, t->n * 32, flags & GA_SCALARS_ON_DEVICE));
-                          XYZZ<F> sum;
-                          GA_CHECK((msm_table_device<C, G>(c, t->d_table, ss.dev, t->n, (flags & GA_SCALARS_MONTGOMERY) != 0, t->c, &sum, win_lo,
-                                                           win_hi)));
-                          host_store_jac<F>(out_jac, sum);
-                      });
-    return GA_OK;
+    return GA_DISPATCH(Scope::G1_FR, t->curve, t->group, {
+        typedef typename GroupField<C, G>::F F;
+        Staged ss{c};
+        GA_CHECK(ss.stage(scalars, t->n * 32, flags & GA_SCALARS_ON_DEVICE));
+        XYZZ<F> sum;
+        GA_CHECK((msm_table_device<C, G>(c, t->d_table, ss.dev, t->n, (flags & GA_SCALARS_MONTGOMERY) != 0, t->c, &sum, win_lo,
+                                         win_hi)));
+        host_store_jac<F>(out_jac, sum);
+    });
 } GA_ABI_CATCH
 
 int ga_fr_linear_combination(ga_ctx* h, int curve, uint64_t n, int k, const void* const* vecs, const void* scalars, void* out,
@@ -1048,8 +1022,7 @@ int ga_fr_linear_combination(ga_ctx* h, int curve, uint64_t n, int k, const void
             return GA_ERR_INVALID;
         }
     Lock l(c);
-    GA_DISPATCH_CURVE_FR(curve, GA_CHECK(fr_vec_lincomb<C>(c, n, k, vecs, scalars, out, on_device != 0)));
-    return GA_OK;
+    return GA_DISPATCH(Scope::G1_FR, curve, GA_NO_GROUP, return fr_vec_lincomb<C>(c, n, k, vecs, scalars, out, on_device != 0));
 } GA_ABI_CATCH
 
 // p(point) for a polynomial in canonical form (iop.Polynomial.Evaluate / evaluateBlinded, prove.go:1186-1215)
@@ -1060,6 +1033,8 @@ int ga_fr_poly_evaluate(ga_ctx* h, int curve, const void* poly, uint64_t n, cons
         set_error("ga_fr_poly_evaluate: null argument");
         return GA_ERR_INVALID;
     }
+    constexpr Scope S = Scope::G1_FR;
+    GA_CHECK(dispatch_check(S, curve, GA_NO_GROUP));
     Lock l(c);
     if (n == 0) {
         memset(value_out, 0, 32);
@@ -1070,8 +1045,7 @@ int ga_fr_poly_evaluate(ga_ctx* h, int curve, const void* poly, uint64_t n, cons
     void* q;
     GA_CHECK(c->scratch_get("kzg_quotient", n * 32, &q));
     const uint64_t scan_threads = env_plonk_batch_knobs().scan_threads;
-    GA_DISPATCH_CURVE_FR(curve, GA_CHECK(kzg_domain_divide<C>(c, sp.dev, n, point, q, value_out, scan_threads)));
-    return GA_OK;
+    return GA_DISPATCH(S, curve, GA_NO_GROUP, return kzg_domain_divide<C>(c, sp.dev, n, point, q, value_out, scan_threads));
 } GA_ABI_CATCH
 
 // kzg.Open(p, point, pk): claimed value p(point) and the commitment to (p(X) - p(point)) / (X - point) over the pinned SRS
@@ -1089,7 +1063,7 @@ int ga_kzg_open(ga_msm_table* th, const void* poly, size_t n, unsigned flags, co
     Ctx* c = t->ctx;
     Lock l(c);
     const uint64_t scan_threads = env_plonk_batch_knobs().scan_threads;
-    GA_DISPATCH_CURVE_FR(t->curve, {
+    return GA_DISPATCH(Scope::G1_FR, t->curve, GA_NO_GROUP, {
         typedef typename GroupField<C, GA_G1>::F F;
         Staged sp{c};
         GA_CHECK(sp.stage(poly, n * 32, flags & GA_SCALARS_ON_DEVICE));
@@ -1102,7 +1076,6 @@ int ga_kzg_open(ga_msm_table* th, const void* poly, size_t n, unsigned flags, co
         GA_CHECK((msm_table_device<C, GA_G1>(c, t->d_table, q, t->n, true, t->c, &sum)));
         host_store_jac<F>(h_out, sum);
     });
-    return GA_OK;
 } GA_ABI_CATCH
 
 // kzg.Open for `count` polynomials of one length over one SRS: per pass of at most GA_PLONK_BATCH_MAX items the divisions by
@@ -1136,7 +1109,7 @@ int ga_kzg_open_batch(ga_msm_table* th, const void* const* polys, size_t n, uint
     }
     const bool on_device = (flags & GA_SCALARS_ON_DEVICE) != 0;
     const size_t qn = n > t->n ? n : t->n;   // a row of quotients: the table's n scalars (zero beyond the n - 1 coefficients)
-    GA_DISPATCH_CURVE_FR(t->curve, {
+    return GA_DISPATCH(Scope::G1_FR, t->curve, GA_NO_GROUP, {
         typedef typename GroupField<C, GA_G1>::F F;
         char *in = nullptr, *q = nullptr, *vals = nullptr;
         auto reserve = [&](uint32_t cnt) -> int {
@@ -1172,37 +1145,33 @@ int ga_kzg_open_batch(ga_msm_table* th, const void* const* polys, size_t n, uint
             return rc;
         }
     });
-    return GA_OK;
 } GA_ABI_CATCH
 
 // ---- host group helpers ---------------------------------------------------------------------------------
 int ga_jac_add(int curve, int group, const void* a, const void* b, void* out) try {
     GA_ABI_ENTRY();
-    GA_DISPATCH_CURVE_GROUP(curve, group, {
-                          typedef typename GroupField<C, G>::F F;
-                          host_store_jac<F>(out, add(host_load_jac<F>(a), host_load_jac<F>(b)));
-                      });
-    return GA_OK;
+    return GA_DISPATCH(Scope::G1_FR, curve, group, {
+        typedef typename GroupField<C, G>::F F;
+        host_store_jac<F>(out, add(host_load_jac<F>(a), host_load_jac<F>(b)));
+    });
 } GA_ABI_CATCH
 
 int ga_jac_to_affine(int curve, int group, const void* a, void* out) try {
     GA_ABI_ENTRY();
-    GA_DISPATCH_CURVE_GROUP(curve, group, {
-                          typedef typename GroupField<C, G>::F F;
-                          host_store_affine<F>(out, host_load_jac<F>(a));
-                      });
-    return GA_OK;
+    return GA_DISPATCH(Scope::G1_FR, curve, group, {
+        typedef typename GroupField<C, G>::F F;
+        host_store_affine<F>(out, host_load_jac<F>(a));
+    });
 } GA_ABI_CATCH
 
 int ga_jac_scalar_mul(int curve, int group, const void* a, const void* k, void* out) try {
     GA_ABI_ENTRY();
-    GA_DISPATCH_CURVE_GROUP(curve, group, {
-                          typedef typename GroupField<C, G>::F F;
-                          uint32_t kw[8];
-                          memcpy(kw, k, 32);
-                          host_store_jac<F>(out, scalar_mul(host_load_jac<F>(a), kw, 8));
-                      });
-    return GA_OK;
+    return GA_DISPATCH(Scope::G1_FR, curve, group, {
+        typedef typename GroupField<C, G>::F F;
+        uint32_t kw[8];
+        memcpy(kw, k, 32);
+        host_store_jac<F>(out, scalar_mul(host_load_jac<F>(a), kw, 8));
+    });
 } GA_ABI_CATCH
 
 // ---- NTT ------------------------------------------------------------------------------------------------
@@ -1215,7 +1184,7 @@ int ga_domain_create(ga_ctx* h, int curve, uint64_t cardinality, ga_domain** out
     }
     Lock l(c);
     Domain* d = nullptr;
-    GA_DISPATCH_CURVE_FR(curve, GA_CHECK(ntt_domain_new<C>(c, cardinality, &d)));
+    GA_CHECK(GA_DISPATCH(Scope::G1_FR, curve, GA_NO_GROUP, return ntt_domain_new<C>(c, cardinality, &d)));
     *out = reinterpret_cast<ga_domain*>(d);
     return GA_OK;
 } GA_ABI_CATCH
@@ -1244,7 +1213,7 @@ int ga_fft(ga_domain* dh, void* data, int direction, int decimation, int on_cose
         GA_CHECK(c->scratch_get("fft_io", bytes, &dev));
         GA_HIP_CHECK(hipMemcpyAsync(dev, data, bytes, hipMemcpyHostToDevice, c->stream));
     }
-    GA_DISPATCH_CURVE_FR(ntt_domain_curve(d), GA_CHECK(ntt_domain_fft<C>(d, dev, direction, decimation, on_coset)));
+    GA_CHECK(GA_DISPATCH(Scope::G1_FR, ntt_domain_curve(d), GA_NO_GROUP, return ntt_domain_fft<C>(d, dev, direction, decimation, on_coset)));
     if (!on_device) GA_HIP_CHECK(hipMemcpyAsync(data, dev, bytes, hipMemcpyDeviceToHost, c->stream));
     GA_HIP_CHECK(hipStreamSynchronize(c->stream));
     return GA_OK;
@@ -1269,7 +1238,7 @@ int ga_fft_batch(ga_domain* dh, void* data, uint32_t count, int direction, int d
         GA_CHECK(c->scratch_get("fft_batch_io", bytes, &dev));
         GA_HIP_CHECK(hipMemcpyAsync(dev, data, bytes, hipMemcpyHostToDevice, c->stream));
     }
-    GA_DISPATCH_CURVE_FR(ntt_domain_curve(d), GA_CHECK(ntt_domain_fft<C>(d, dev, direction, decimation, on_coset, count)));
+    GA_CHECK(GA_DISPATCH(Scope::G1_FR, ntt_domain_curve(d), GA_NO_GROUP, return ntt_domain_fft<C>(d, dev, direction, decimation, on_coset, count)));
     if (!on_device) GA_HIP_CHECK(hipMemcpyAsync(data, dev, bytes, hipMemcpyDeviceToHost, c->stream));
     GA_HIP_CHECK(hipStreamSynchronize(c->stream));
     return GA_OK;
@@ -1321,8 +1290,7 @@ int ga_plonk_quotient(ga_domain* dh0, ga_domain* dh1, const ga_plonk_quotient_in
     Lock l(c);
     PlonkQuotientArgs a;
     GA_CHECK(plonk_args_from(in, true, true, &a));
-    GA_DISPATCH_CURVE_FR(ntt_domain_curve(d0), GA_CHECK(plonk_domain_quotient<C>(d0, d1, a, h_out)));
-    return GA_OK;
+    return GA_DISPATCH(Scope::G1_FR, ntt_domain_curve(d0), GA_NO_GROUP, return plonk_domain_quotient<C>(d0, d1, a, h_out));
 } GA_ABI_CATCH
 
 int ga_plonk_pk_create(ga_domain* dh0, ga_domain* dh1, const ga_plonk_quotient_in* in, ga_plonk_pk** out) try {
@@ -1337,7 +1305,7 @@ int ga_plonk_pk_create(ga_domain* dh0, ga_domain* dh1, const ga_plonk_quotient_i
     PlonkQuotientArgs a;
     GA_CHECK(plonk_args_from(in, true, false, &a));
     PlonkFixed* fx = nullptr;
-    GA_DISPATCH_CURVE_FR(ntt_domain_curve(d0), GA_CHECK(plonk_domain_fixed_create<C>(d0, d1, a, &fx)));
+    GA_CHECK(GA_DISPATCH(Scope::G1_FR, ntt_domain_curve(d0), GA_NO_GROUP, return plonk_domain_fixed_create<C>(d0, d1, a, &fx)));
     *out = reinterpret_cast<ga_plonk_pk*>(fx);
     return GA_OK;
 } GA_ABI_CATCH
@@ -1365,8 +1333,7 @@ int ga_plonk_quotient_pinned(ga_plonk_pk* p, const ga_plonk_quotient_in* in, voi
     PlonkQuotientArgs a;
     GA_CHECK(plonk_args_from(in, false, true, &a));
     const uint64_t scan_threads = env_plonk_batch_knobs().scan_threads;
-    GA_DISPATCH_CURVE_FR(ntt_domain_curve(d0), GA_CHECK(plonk_domain_quotient_pinned<C>(fx, a, scan_threads, h_out)));
-    return GA_OK;
+    return GA_DISPATCH(Scope::G1_FR, ntt_domain_curve(d0), GA_NO_GROUP, return plonk_domain_quotient_pinned<C>(fx, a, scan_threads, h_out));
 } GA_ABI_CATCH
 
 int ga_plonk_build_z(ga_domain* dh0, const void* lv, const void* rv, const void* ov, const int64_t* permutation, const void* beta,
@@ -1381,9 +1348,8 @@ int ga_plonk_build_z(ga_domain* dh0, const void* lv, const void* rv, const void*
     Lock l(c);
     if (!on_device && !abi_permutation_ok(permutation, 3 * ntt_domain_size(d0))) return GA_ERR_INVALID;
     const uint64_t scan_threads = env_plonk_batch_knobs().scan_threads;
-    GA_DISPATCH_CURVE_FR(ntt_domain_curve(d0),
-                      GA_CHECK(plonk_domain_build_z<C>(d0, lv, rv, ov, permutation, beta, gamma, scan_threads, on_device != 0, z_out)));
-    return GA_OK;
+    return GA_DISPATCH(Scope::G1_FR, ntt_domain_curve(d0), GA_NO_GROUP,
+                       return plonk_domain_build_z<C>(d0, lv, rv, ov, permutation, beta, gamma, scan_threads, on_device != 0, z_out));
 } GA_ABI_CATCH
 
 int ga_plonk_build_z_batch(ga_domain* dh0, const void* lv, const void* rv, const void* ov, const int64_t* permutation, const void* betas,
@@ -1399,9 +1365,8 @@ int ga_plonk_build_z_batch(ga_domain* dh0, const void* lv, const void* rv, const
     Lock l(c);
     if (!on_device && !abi_permutation_ok(permutation, 3 * ntt_domain_size(d0))) return GA_ERR_INVALID;
     const PlonkBatchKnobs knobs = env_plonk_batch_knobs();
-    GA_DISPATCH_CURVE_FR(ntt_domain_curve(d0), GA_CHECK(plonk_domain_build_z_batch<C>(d0, lv, rv, ov, permutation, betas, gammas, count, knobs,
-                                                                                  on_device != 0, z_out)));
-    return GA_OK;
+    return GA_DISPATCH(Scope::G1_FR, ntt_domain_curve(d0), GA_NO_GROUP,
+                       return plonk_domain_build_z_batch<C>(d0, lv, rv, ov, permutation, betas, gammas, count, knobs, on_device != 0, z_out));
 } GA_ABI_CATCH
 
 int ga_plonk_quotient_pinned_batch(ga_plonk_pk* p, const ga_plonk_quotient_in* ins, uint32_t count, void* h_out) try {
@@ -1424,8 +1389,7 @@ int ga_plonk_quotient_pinned_batch(ga_plonk_pk* p, const ga_plonk_quotient_in* i
         GA_CHECK(plonk_args_from(&ins[j], false, true, &a[j]));
     }
     const PlonkBatchKnobs knobs = env_plonk_batch_knobs();
-    GA_DISPATCH_CURVE_FR(ntt_domain_curve(d0), GA_CHECK(plonk_domain_quotient_pinned_batch<C>(fx, a.data(), count, knobs, h_out)));
-    return GA_OK;
+    return GA_DISPATCH(Scope::G1_FR, ntt_domain_curve(d0), GA_NO_GROUP, return plonk_domain_quotient_pinned_batch<C>(fx, a.data(), count, knobs, h_out));
 } GA_ABI_CATCH
 
 int ga_fr_batch_invert(ga_ctx* h, int curve, void* v, uint64_t n, int on_device) try {
@@ -1436,8 +1400,7 @@ int ga_fr_batch_invert(ga_ctx* h, int curve, void* v, uint64_t n, int on_device)
         return GA_ERR_INVALID;
     }
     Lock l(c);
-    GA_DISPATCH_CURVE_FR(curve, GA_CHECK(fr_vec_batch_inverse<C>(c, v, n, on_device != 0)));
-    return GA_OK;
+    return GA_DISPATCH(Scope::G1_FR, curve, GA_NO_GROUP, return fr_vec_batch_inverse<C>(c, v, n, on_device != 0));
 } GA_ABI_CATCH
 
 int ga_compute_h(ga_domain* dh, const void* a, const void* b, const void* cc, uint64_t n_constraints, void* h_out, int on_device) try {
@@ -1461,7 +1424,7 @@ int ga_compute_h(ga_domain* dh, const void* a, const void* b, const void* cc, ui
         GA_HIP_CHECK(hipMemcpyAsync(dst[k], src[k], part, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
         if (full > part) GA_HIP_CHECK(hipMemsetAsync(reinterpret_cast<char*>(dst[k]) + part, 0, full - part, c->stream));
     }
-    GA_DISPATCH_CURVE_FR(ntt_domain_curve(d), GA_CHECK(ntt_domain_compute_h<C>(d, da, db, dc)));
+    GA_CHECK(GA_DISPATCH(Scope::G1_FR, ntt_domain_curve(d), GA_NO_GROUP, return ntt_domain_compute_h<C>(d, da, db, dc)));
     GA_HIP_CHECK(hipMemcpyAsync(h_out, da, full, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
     GA_HIP_CHECK(hipStreamSynchronize(c->stream));
     return GA_OK;
@@ -1496,9 +1459,9 @@ int ga_compute_h_batch(ga_domain* dh, const void* a, const void* b, const void* 
             for (uint32_t j = 0; j < count; j++)
                 GA_HIP_CHECK(hipMemcpyAsync((char*)dst[k] + j * full, (const char*)src[k] + j * part, part, in, c->stream));
         }
-        GA_DISPATCH_CURVE_FR(ntt_domain_curve(d), GA_CHECK(util_pad_fr_batch<C>(c, dst[k], n_constraints, n, count, c->stream)));
+        GA_CHECK(GA_DISPATCH(Scope::G1_FR, ntt_domain_curve(d), GA_NO_GROUP, return util_pad_fr_batch<C>(c, dst[k], n_constraints, n, count, c->stream)));
     }
-    GA_DISPATCH_CURVE_FR(ntt_domain_curve(d), GA_CHECK(ntt_domain_compute_h<C>(d, da, db, dc, count)));
+    GA_CHECK(GA_DISPATCH(Scope::G1_FR, ntt_domain_curve(d), GA_NO_GROUP, return ntt_domain_compute_h<C>(d, da, db, dc, count)));
     GA_HIP_CHECK(hipMemcpyAsync(h_out, da, (size_t)count * full, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
     GA_HIP_CHECK(hipStreamSynchronize(c->stream));
     return GA_OK;
@@ -1549,7 +1512,7 @@ int ga_gen_bases(ga_ctx* h, int curve, int group, uint64_t seed, size_t n, void*
     GA_ABI_ENTRY();
     Ctx* c = reinterpret_cast<Ctx*>(h);
     Lock l(c);
-    GA_DISPATCH_CURVE_GROUP(curve, group, GA_CHECK((util_gen_bases<C, G>(c, seed, n, bases_dev, dlogs_dev))));
+    GA_CHECK(GA_DISPATCH(Scope::G1_FR, curve, group, return util_gen_bases<C, G>(c, seed, n, bases_dev, dlogs_dev)));
     GA_HIP_CHECK(hipStreamSynchronize(c->stream));
     return GA_OK;
 } GA_ABI_CATCH
@@ -1558,7 +1521,7 @@ int ga_gen_bases_at(ga_ctx* h, int curve, int group, uint64_t seed, uint64_t fir
     GA_ABI_ENTRY();
     Ctx* c = reinterpret_cast<Ctx*>(h);
     Lock l(c);
-    GA_DISPATCH_CURVE_GROUP(curve, group, GA_CHECK((util_gen_bases<C, G>(c, seed, n, bases_dev, dlogs_dev, first))));
+    GA_CHECK(GA_DISPATCH(Scope::G1_FR, curve, group, return util_gen_bases<C, G>(c, seed, n, bases_dev, dlogs_dev, first)));
     GA_HIP_CHECK(hipStreamSynchronize(c->stream));
     return GA_OK;
 } GA_ABI_CATCH
@@ -1567,7 +1530,7 @@ int ga_gen_scalars(ga_ctx* h, int curve, uint64_t seed, size_t n, void* scalars_
     GA_ABI_ENTRY();
     Ctx* c = reinterpret_cast<Ctx*>(h);
     Lock l(c);
-    GA_DISPATCH_CURVE_FR(curve, GA_CHECK(util_gen_scalars<C>(c, seed, n, scalars_dev)));
+    GA_CHECK(GA_DISPATCH(Scope::G1_FR, curve, GA_NO_GROUP, return util_gen_scalars<C>(c, seed, n, scalars_dev)));
     GA_HIP_CHECK(hipStreamSynchronize(c->stream));
     return GA_OK;
 } GA_ABI_CATCH
@@ -1576,8 +1539,7 @@ int ga_fr_dot(ga_ctx* h, int curve, const void* a_dev, const void* b_dev, size_t
     GA_ABI_ENTRY();
     Ctx* c = reinterpret_cast<Ctx*>(h);
     Lock l(c);
-    GA_DISPATCH_CURVE_FR(curve, GA_CHECK(util_fr_dot<C>(c, a_dev, b_dev, n, out_host)));
-    return GA_OK;
+    return GA_DISPATCH(Scope::G1_FR, curve, GA_NO_GROUP, return util_fr_dot<C>(c, a_dev, b_dev, n, out_host));
 } GA_ABI_CATCH
 
 int ga_fr_vec_mul(ga_ctx* h, int curve, const void* a, const void* b, size_t n, void* out, int on_device) try {
@@ -1587,6 +1549,8 @@ int ga_fr_vec_mul(ga_ctx* h, int curve, const void* a, const void* b, size_t n, 
         set_error("ga_fr_vec_mul: null argument");
         return GA_ERR_INVALID;
     }
+    constexpr Scope S = Scope::G1_FR;
+    GA_CHECK(dispatch_check(S, curve, GA_NO_GROUP));
     Lock l(c);
     if (n == 0) return GA_OK;
     Staged sa{c}, sb{c};
@@ -1594,7 +1558,7 @@ int ga_fr_vec_mul(ga_ctx* h, int curve, const void* a, const void* b, size_t n, 
     GA_CHECK(sb.stage(b, n * 32, on_device));
     void* d_out = out;
     if (!on_device) GA_CHECK(c->scratch_get("fr_vec_out", n * 32, &d_out));
-    GA_DISPATCH_CURVE_FR(curve, GA_CHECK(util_fr_vec_mul<C>(c, sa.dev, sb.dev, n, d_out)));
+    GA_CHECK(GA_DISPATCH(S, curve, GA_NO_GROUP, return util_fr_vec_mul<C>(c, sa.dev, sb.dev, n, d_out)));
     if (!on_device) GA_HIP_CHECK(hipMemcpyAsync(out, d_out, n * 32, hipMemcpyDeviceToHost, c->stream));
     GA_HIP_CHECK(hipStreamSynchronize(c->stream));
     return GA_OK;
@@ -1602,13 +1566,12 @@ int ga_fr_vec_mul(ga_ctx* h, int curve, const void* a, const void* b, size_t n, 
 
 int ga_generator_mul(int curve, int group, const void* k, void* out_jac) try {
     GA_ABI_ENTRY();
-    GA_DISPATCH_CURVE_GROUP(curve, group, {
-                          typedef typename GroupField<C, G>::F F;
-                          uint32_t kw[8];
-                          memcpy(kw, k, 32);
-                          host_store_jac<F>(out_jac, scalar_mul(to_xyzz(Generator<C, G>::get()), kw, 8));
-                      });
-    return GA_OK;
+    return GA_DISPATCH(Scope::G1_FR, curve, group, {
+        typedef typename GroupField<C, G>::F F;
+        uint32_t kw[8];
+        memcpy(kw, k, 32);
+        host_store_jac<F>(out_jac, scalar_mul(to_xyzz(Generator<C, G>::get()), kw, 8));
+    });
 } GA_ABI_CATCH
 
 int ga_clock_probe(ga_ctx* h, uint32_t micros, double* mhz_out) try {

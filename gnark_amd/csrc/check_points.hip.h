@@ -342,4 +342,10 @@ int check_points_tally(Ctx* ctx, hipStream_t st, uint64_t* out4, int* first_stat
     return check_read_counters(s, st, out4, first_status);
 }
 
+// what check_points_<curve>_g<k>.hip instantiates
+#define GA_INSTANTIATE_CHECK_POINTS(C, G)                                                                            \
+    template int check_points_run<C, G>(Ctx*, const void*, size_t, unsigned, uint8_t*, uint64_t*, int, uint64_t);    \
+    template int check_points_resident<C, G>(Ctx*, hipStream_t, const void*, uint64_t, uint64_t, int, int);          \
+    template int check_points_tally<C, G>(Ctx*, hipStream_t, uint64_t*, int*);
+
 }  // namespace ga

@@ -13,6 +13,7 @@
 #include <mutex>
 #include <set>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/gnark_amd.h"
@@ -106,26 +107,34 @@ inline hipError_t device_malloc(T** p, size_t bytes) {
 
 // ---- curve tags ----------------------------------------------------------------------------------
 // HAS_G2: the curve's Fp2 is Fp[u]/(u^2 + 1), the only quadratic extension Fe2 / F29x2 implement, so G2, the pairing and Groth16
-// are built for it.  BLS12-377's is u^2 + 5: that curve is G1 and Fr only, and GroupField refuses to name an Fe2 over its Fp (the
-// u^2 + 1 arithmetic would compile and be wrong); its constants carry no G2*, PSI*, FROB* or FP2Z either.
+// are built for it.  A curve without it is G1 and Fr only: GroupField refuses to name an Fe2 over its Fp (the u^2 + 1 arithmetic
+// would compile and be wrong), its constants carry no G2*, PSI*, FROB* or FP2Z, and NO_G2 is the reason a refusal quotes.
+// NAME is how messages print the curve.  DESIGN.md 7 has the steps of adding a curve.
 struct Bn254 {
     static constexpr int ID = GA_BN254;
+    static constexpr const char* NAME = "bn254";
     static constexpr bool HAS_G2 = true;
     using FpP = BN254_Fp;
     using FrP = BN254_Fr;
 };
 struct Bls12381 {
     static constexpr int ID = GA_BLS12_381;
+    static constexpr const char* NAME = "bls12-381";
     static constexpr bool HAS_G2 = true;
     using FpP = BLS12_381_Fp;
     using FrP = BLS12_381_Fr;
 };
 struct Bls12377 {
     static constexpr int ID = GA_BLS12_377;
+    static constexpr const char* NAME = "bls12-377";
     static constexpr bool HAS_G2 = false;
+    static constexpr const char* NO_G2 = "its Fp2 is Fp[u]/(u^2 + 5)";
     using FpP = BLS12_377_Fp;
     using FrP = BLS12_377_Fr;
 };
+// THE list of the curves the library is built for: X(tag) once per curve.  The dispatcher at the end of this file and the refusal
+// messages (abi.hip) are generated from it; nothing else enumerates curves.
+#define GA_CURVES(X) X(Bn254) X(Bls12381) X(Bls12377)
 template <class C, int G> struct GroupField;
 template <class C> struct GroupField<C, GA_G1> { using F = Fe<typename C::FpP>; };
 template <class C> struct GroupField<C, GA_G2> {
@@ -661,42 +670,62 @@ template <class C> int util_pad_fr_batch(Ctx* ctx, void* d_v, uint64_t from, uin
 int util_microbench(Ctx* ctx, char* buf, size_t cap);
 int util_clock_probe(Ctx* ctx, uint32_t micros, double* mhz_out);
 
-// The answer to a curve id no case of a dispatch takes: a curve that is built in part (BLS12-377: G1 and Fr) is named, with the
-// entry point that is not built for it; anything else is an unknown id.  Returns GA_ERR_INVALID.
-int curve_not_dispatched(int curve);
-
-// GA_DISPATCH_CURVE: the curves built in full -- its body may name G2, the pairing, Groth16 and the setup calls.
-// GA_DISPATCH_CURVE_FR: every curve -- the body may use C::FrP and Fe<C::FpP> (G1) only.
-// GA_DISPATCH_CURVE_GROUP(curve, group, body): every (curve, group) that is built, G bound like GA_DISPATCH_GROUP does.
-#define GA_DISPATCH_CURVE(curve, ...)                                \
-    switch (curve) {                                                 \
-        case GA_BN254: {                                             \
-            using C = ::ga::Bn254;                                   \
-            __VA_ARGS__;                                             \
-        } break;                                                     \
-        case GA_BLS12_381: {                                         \
-            using C = ::ga::Bls12381;                                \
-            __VA_ARGS__;                                             \
-        } break;                                                     \
-        default:                                                     \
-            return ::ga::curve_not_dispatched((int)(curve));         \
+// ---- dispatch: from the run-time (curve, group) of the C ABI to the tags -----------------------------------------------------------
+// An entry point has one of two scopes:
+//   Scope::FULL   the curves with HAS_G2 -- the body may name G2, the pairing, Groth16 and the setup calls;
+//   Scope::G1_FR  every curve -- the body may use C::FrP and Fe<C::FpP> (G1) only, and GroupField<C, G> under a group argument.
+// The group argument is GA_G1 / GA_G2 as the caller passed it, or GA_NO_GROUP for a call without one.  A pair is built when the
+// curve is in the list, in scope, and the group is GA_G1 -- or GA_G2 on a curve with HAS_G2.  dispatch_check is what dispatch asks
+// first, and what an entry point that must refuse before its n = 0 shortcut asks itself, under the same scope.
+enum class Scope { FULL, G1_FR };
+struct NoGroup {};
+constexpr NoGroup GA_NO_GROUP{};
+struct GroupArg {   // the caller's group id (any int: it is checked), or none
+    bool given;
+    int id;
+    GroupArg(int group) : given(true), id(group) {}
+    GroupArg(NoGroup) : given(false), id(GA_G1) {}
+};
+bool dispatch_built(Scope scope, int curve, GroupArg group);    // the one predicate
+int dispatch_refuse(Scope scope, int curve, GroupArg group);    // the one refusal: every message for a pair that is not built; GA_ERR_INVALID
+inline int dispatch_check(Scope scope, int curve, GroupArg group) {
+    return dispatch_built(scope, curve, group) ? GA_OK : dispatch_refuse(scope, curve, group);
+}
+template <int G> struct GroupTag {
+    static constexpr int value = G;
+};
+template <Scope S, class C, class Grp, class Body>
+int dispatch_curve(Grp group, Body& body) {
+    if constexpr (S == Scope::FULL && !C::HAS_G2) return GA_ERR_INVALID;   // (not built: dispatch has refused)
+    else if constexpr (std::is_same<Grp, NoGroup>::value) return body(C{}, GroupTag<-1>{});
+    else {
+        if constexpr (C::HAS_G2)   // the body is never instantiated for G2 of a curve without it
+            if (group == GA_G2) return body(C{}, GroupTag<GA_G2>{});
+        return body(C{}, GroupTag<GA_G1>{});
     }
-#define GA_DISPATCH_CURVE_FR(curve, ...)                             \
-    switch (curve) {                                                 \
-        case GA_BN254: {                                             \
-            using C = ::ga::Bn254;                                   \
-            __VA_ARGS__;                                             \
-        } break;                                                     \
-        case GA_BLS12_381: {                                         \
-            using C = ::ga::Bls12381;                                \
-            __VA_ARGS__;                                             \
-        } break;                                                     \
-        case GA_BLS12_377: {                                         \
-            using C = ::ga::Bls12377;                                \
-            __VA_ARGS__;                                             \
-        } break;                                                     \
-        default:                                                     \
-            return ::ga::curve_not_dispatched((int)(curve));         \
+}
+template <Scope S, class Grp, class Body>
+int dispatch(int curve, Grp group, Body&& body) {
+    GA_CHECK(dispatch_check(S, curve, group));
+    switch (curve) {
+#define GA_CURVE_CASE(T) \
+    case T::ID:          \
+        return dispatch_curve<S, T>(group, body);
+        GA_CURVES(GA_CURVE_CASE)
+#undef GA_CURVE_CASE
     }
+    return GA_ERR_INVALID;   // (not reached: dispatch_check knows the same list)
+}
+// GA_DISPATCH(scope, curve, group, body): an int expression.  Runs `body` with C bound to the curve's tag and G to the group
+// (GA_G1 / GA_G2; nothing usable under GA_NO_GROUP) and yields what the body returns, GA_OK when it runs off its end, or the
+// refusal.  The body is the body of a lambda: `return` and GA_CHECK leave the body, not the entry point.
+#define GA_DISPATCH(scope, curve, group, ...)                                                     \
+    ::ga::dispatch<scope>((int)(curve), group, [&](auto ga_curve_tag, auto ga_group_tag) -> int { \
+        using C = decltype(ga_curve_tag);                                                         \
+        constexpr int G = decltype(ga_group_tag)::value;                                          \
+        (void)G;                                                                                  \
+        __VA_ARGS__;                                                                              \
+        return GA_OK;                                                                             \
+    })
 
 }  // namespace ga

@@ -294,4 +294,7 @@ int ec_ntt_to_lagrange(Ctx* ctx, const void* powers, size_t n, unsigned flags, v
     return GA_OK;
 }
 
+// what ec_ntt_<curve>[_g2].hip instantiates
+#define GA_INSTANTIATE_EC_NTT(C, G) template int ec_ntt_to_lagrange<C, G>(Ctx*, const void*, size_t, unsigned, void*, int);
+
 }  // namespace ga

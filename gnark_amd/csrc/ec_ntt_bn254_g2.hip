@@ -1,5 +1,5 @@
 // Explicit instantiation: mpcsetup's lagrangeCoeffsG2 (the inverse FFT over G2 points), bn254 (see ec_ntt.hip.h).
 #include "ec_ntt.hip.h"
 namespace ga {
-template int ec_ntt_to_lagrange<Bn254, GA_G2>(Ctx*, const void*, size_t, unsigned, void*, int);
+GA_INSTANTIATE_EC_NTT(Bn254, GA_G2)
 }  // namespace ga

@@ -386,4 +386,9 @@ int fixed_base_plan_abi(size_t n, int forced_c, int* c, int* nwin) {
     return GA_OK;
 }
 
+// what fixed_base_<curve>_g<k>.hip instantiates; the G1 unit of a curve has the planner as well
+#define GA_INSTANTIATE_FIXED_BASE(C, G) \
+    template int fixed_base_run<C, G>(Ctx*, const void*, const void*, size_t, unsigned, void*, int, uint64_t);
+#define GA_INSTANTIATE_FIXED_BASE_PLAN(C) template int fixed_base_plan_abi<C>(size_t, int, int*, int*);
+
 }  // namespace ga

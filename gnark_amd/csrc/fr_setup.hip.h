@@ -191,4 +191,10 @@ int fr_powers_run(Ctx* ctx, const void* scalars, uint64_t first, size_t n, unsig
     return GA_OK;
 }
 
+// what fr_setup_<curve>.hip instantiates, with GA_INSTANTIATE_FR_SPARSE (fr_sparse.hip.h)
+#define GA_INSTANTIATE_FR_SETUP(C)                                                                   \
+    template int fr_lagrange_run<C>(Ctx*, int, const void*, size_t, unsigned, void*);                \
+    template int fr_compact_run<C>(Ctx*, const void*, size_t, unsigned, void*, uint8_t*, uint64_t*); \
+    template int fr_powers_run<C>(Ctx*, const void*, uint64_t, size_t, unsigned, void*);
+
 }  // namespace ga

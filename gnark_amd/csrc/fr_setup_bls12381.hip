@@ -2,9 +2,6 @@
 #include "fr_setup.hip.h"
 #include "fr_sparse.hip.h"
 namespace ga {
-template int fr_sparse_run<Bls12381>(Ctx*, const void*, size_t, const uint64_t*, size_t, const uint32_t*, const void*, size_t, const uint8_t*, const void*, size_t,
-                               unsigned, void*, uint32_t);
-template int fr_lagrange_run<Bls12381>(Ctx*, int, const void*, size_t, unsigned, void*);
-template int fr_compact_run<Bls12381>(Ctx*, const void*, size_t, unsigned, void*, uint8_t*, uint64_t*);
-template int fr_powers_run<Bls12381>(Ctx*, const void*, uint64_t, size_t, unsigned, void*);
+GA_INSTANTIATE_FR_SPARSE(Bls12381)
+GA_INSTANTIATE_FR_SETUP(Bls12381)
 }  // namespace ga

@@ -158,4 +158,9 @@ int fr_sparse_run(Ctx* ctx, const void* x, size_t n_cols, const uint64_t* row_st
     return GA_OK;
 }
 
+// what fr_setup_<curve>.hip instantiates, with GA_INSTANTIATE_FR_SETUP (fr_setup.hip.h)
+#define GA_INSTANTIATE_FR_SPARSE(C)                                                                                                          \
+    template int fr_sparse_run<C>(Ctx*, const void*, size_t, const uint64_t*, size_t, const uint32_t*, const void*, size_t, const uint8_t*, \
+                                  const void*, size_t, unsigned, void*, uint32_t);
+
 }  // namespace ga

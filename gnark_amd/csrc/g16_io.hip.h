@@ -548,7 +548,7 @@ static int pk_read_any(ga_ctx* h, int curve, ByteSource& src, int32_t precompute
     }
     CtxLock g(ctx);
     G16Pk* pk = nullptr;
-    GA_DISPATCH_CURVE(curve, GA_CHECK(pk_read<C>(ctx, src, precompute, shard_index, shard_count, k_remove, len_k_remove, &pk, checked)));
+    GA_CHECK(GA_DISPATCH(Scope::FULL, curve, GA_NO_GROUP, return pk_read<C>(ctx, src, precompute, shard_index, shard_count, k_remove, len_k_remove, &pk, checked)));
     *out = reinterpret_cast<ga_g16_pk*>(pk);
     if (bytes_read) *bytes_read = src.consumed;
     return GA_OK;

@@ -691,8 +691,7 @@ static int stage_add_commitment_key(G16Stage* st, const void* basis, const void*
 }
 
 static int stage_finish_any(G16Stage* st, int precompute, G16Pk** out) {
-    GA_DISPATCH_CURVE(st->curve, return stage_finish<C>(st, precompute, out));
-    return GA_OK;
+    return GA_DISPATCH(Scope::FULL, st->curve, GA_NO_GROUP, return stage_finish<C>(st, precompute, out));
 }
 
 // ---- one-shot keys (ga_g16_prove_oneshot) -------------------------------------------------------------------------------------
@@ -796,7 +795,7 @@ static bool key_points_present(const ga_g16_key* key) {
 // that this function starts before it returns -- plain vectors only (no tables), the whole key on one device; the caller must keep
 // the host vectors alive until the thread has been joined (pk_free does).
 static int pk_create_from_struct(Ctx* ctx, const ga_g16_key* key, G16Pk** out, bool defer_uploads = false) {
-    if (key->curve == GA_BLS12_377) return curve_not_dispatched(key->curve);   // G1 / Fr only: refused before anything is staged
+    GA_CHECK(dispatch_check(Scope::FULL, key->curve, GA_NO_GROUP));   // before anything is staged
     if (!key_points_present(key)) {
         set_error("ga_g16_pk_create: null pointer inside ga_g16_key");
         return GA_ERR_INVALID;

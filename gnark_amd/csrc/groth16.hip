@@ -999,8 +999,8 @@ int ga_g16_builder_create(ga_ctx* h, int curve, uint64_t domain_cardinality, uin
                           uint32_t shard_count, ga_g16_builder** out) try {
     GA_ABI_ENTRY();
     Ctx* ctx = reinterpret_cast<Ctx*>(h);
-    if (curve == GA_BLS12_377) return curve_not_dispatched(curve);   // G1 / Fr only: no Groth16 key on that curve
-    if (!ctx || !out || (curve != GA_BN254 && curve != GA_BLS12_381) || domain_cardinality == 0) {
+    GA_CHECK(dispatch_check(Scope::FULL, curve, GA_NO_GROUP));   // no Groth16 key on a G1 / Fr curve
+    if (!ctx || !out || domain_cardinality == 0) {
         set_error("ga_g16_builder_create: bad argument");
         return GA_ERR_INVALID;
     }
@@ -1249,7 +1249,7 @@ int ga_g16_key_write_fd(ga_ctx* h, const ga_g16_key* key, int format, int fd, ui
     CtxLock g(ctx);
     ByteSink dst;
     dst.fd = fd;
-    GA_DISPATCH_CURVE(key->curve, GA_CHECK(key_write<C>(ctx, key, format, dst)));
+    GA_CHECK(GA_DISPATCH(Scope::FULL, key->curve, GA_NO_GROUP, return key_write<C>(ctx, key, format, dst)));
     if (bytes_written) *bytes_written = dst.written;
     return GA_OK;
 } GA_ABI_CATCH
@@ -1261,8 +1261,8 @@ int ga_g16_proof_unmarshal(int curve, const uint8_t* data, size_t len, void* pro
         set_error("ga_g16_proof_unmarshal: null argument");
         return GA_ERR_INVALID;
     }
-    GA_DISPATCH_CURVE(curve, return proof_unmarshal<C>(data, len, proof_out, commitments_out, max_commitments, n_commitments, pok_out, consumed));
-    return GA_OK;
+    return GA_DISPATCH(Scope::FULL, curve, GA_NO_GROUP,
+                       return proof_unmarshal<C>(data, len, proof_out, commitments_out, max_commitments, n_commitments, pok_out, consumed));
 } GA_ABI_CATCH
 
 int ga_point_unmarshal(int curve, int group, const uint8_t* data, size_t len, void* affine_out, size_t* consumed) try {
@@ -1275,14 +1275,7 @@ int ga_point_unmarshal(int curve, int group, const uint8_t* data, size_t len, vo
     src.mem = data;
     src.mem_len = len;
     std::vector<uint8_t> img;
-    GA_DISPATCH_CURVE(curve, {
-        if (group == GA_G1) GA_CHECK((read_header_point<C, GA_G1>(src, &img)));
-        else if (group == GA_G2) GA_CHECK((read_header_point<C, GA_G2>(src, &img)));
-        else {
-            set_error("unknown group id %d", group);
-            return GA_ERR_INVALID;
-        }
-    });
+    GA_CHECK(GA_DISPATCH(Scope::FULL, curve, group, return (read_header_point<C, G>(src, &img))));
     memcpy(affine_out, img.data(), img.size());
     if (consumed) *consumed = src.mem_pos;
     return GA_OK;
@@ -1294,8 +1287,7 @@ int ga_g16_proof_marshal(int curve, const void* proof, uint8_t* out, size_t cap,
         set_error("ga_g16_proof_marshal: null argument");
         return GA_ERR_INVALID;
     }
-    GA_DISPATCH_CURVE(curve, return marshal<C>(proof, nullptr, 0, nullptr, out, cap, len));
-    return GA_OK;
+    return GA_DISPATCH(Scope::FULL, curve, GA_NO_GROUP, return marshal<C>(proof, nullptr, 0, nullptr, out, cap, len));
 } GA_ABI_CATCH
 
 int ga_g16_proof_marshal_bsb22(int curve, const void* proof, const void* commitments, uint32_t n, const void* pok, uint8_t* out,
@@ -1305,8 +1297,7 @@ int ga_g16_proof_marshal_bsb22(int curve, const void* proof, const void* commitm
         set_error("ga_g16_proof_marshal_bsb22: null argument");
         return GA_ERR_INVALID;
     }
-    GA_DISPATCH_CURVE(curve, return marshal<C>(proof, commitments, n, pok, out, cap, len));
-    return GA_OK;
+    return GA_DISPATCH(Scope::FULL, curve, GA_NO_GROUP, return marshal<C>(proof, commitments, n, pok, out, cap, len));
 } GA_ABI_CATCH
 
 int ga_g16_proof_marshal_raw(int curve, const void* proof, const void* commitments, uint32_t n, const void* pok, uint8_t* out,
@@ -1316,8 +1307,7 @@ int ga_g16_proof_marshal_raw(int curve, const void* proof, const void* commitmen
         set_error("ga_g16_proof_marshal_raw: null argument");
         return GA_ERR_INVALID;
     }
-    GA_DISPATCH_CURVE(curve, return marshal<C>(proof, commitments, n, pok, out, cap, len, true));
-    return GA_OK;
+    return GA_DISPATCH(Scope::FULL, curve, GA_NO_GROUP, return marshal<C>(proof, commitments, n, pok, out, cap, len, true));
 } GA_ABI_CATCH
 
 int ga_g1_marshal_uncompressed(int curve, const void* affine, uint8_t* out, size_t cap, size_t* len) try {
@@ -1326,14 +1316,13 @@ int ga_g1_marshal_uncompressed(int curve, const void* affine, uint8_t* out, size
         set_error("ga_g1_marshal_uncompressed: null argument");
         return GA_ERR_INVALID;
     }
-    GA_DISPATCH_CURVE(curve, {
+    return GA_DISPATCH(Scope::FULL, curve, GA_NO_GROUP, {
         if (cap < 2 * sizeof(Fe<typename C::FpP>)) {
             set_error("ga_g1_marshal_uncompressed: buffer too small");
             return GA_ERR_INVALID;
         }
         *len = encode_point<C, GA_G1>(affine, false, out);
     });
-    return GA_OK;
 } GA_ABI_CATCH
 
 // ---- proofs ----------------------------------------------------------------------------------------------------------------------
@@ -1379,7 +1368,7 @@ static int g16_prove_impl(ga_g16_pk* p, const void* w, const void* a, const void
         {
             LaneScope on_lane(lane);
             if (lane == 0) ctx->tun.read_env();
-            GA_DISPATCH_CURVE(pk->curve, {
+            const int rc = GA_DISPATCH(Scope::FULL, pk->curve, GA_NO_GROUP, {
                 G16Partials<C> part;
                 partial_rc = prove_partial<C>(pk, slot, preloaded, w, a, b, c, n_constraints, nb_public, &part);
                 if (partial_rc == GA_OK) {
@@ -1389,6 +1378,7 @@ static int g16_prove_impl(ga_g16_pk* p, const void* w, const void* a, const void
                     return finish<C>(pk, part, r, s, proof_out);
                 }
             });
+            if (partial_rc == GA_OK) return rc;   // the proof is finished (or the dispatch refused the key's curve)
         }
         if (partial_rc != GA_ERR_NOMEM || lane != 2) return partial_rc;
         // (everything prove_partial started on lanes 2/3 has joined; hipFree synchronises with what their streams still hold)
@@ -1429,12 +1419,11 @@ int ga_g16_prove_partial(ga_g16_pk* p, const void* w, const void* a, const void*
     GA_PK_USE(pk, "ga_g16_prove_partial");
     SlotLease slot(pk->ctx);   // always slot first, device lock second (ga_g16_prove's order)
     CtxLock g(pk->ctx);
-    GA_DISPATCH_CURVE(pk->curve, {
+    return GA_DISPATCH(Scope::FULL, pk->curve, GA_NO_GROUP, {
         G16Partials<C> part;
         GA_CHECK(prove_partial<C>(pk, slot, false, w, a, b, c, n_constraints, nb_public, &part));
         part.store(partials_out);
     });
-    return GA_OK;
 } GA_ABI_CATCH
 
 int ga_g16_finish(ga_g16_pk* p, const void* partials_sum, const void* r, const void* s, void* proof_out) try {
@@ -1445,12 +1434,11 @@ int ga_g16_finish(ga_g16_pk* p, const void* partials_sum, const void* r, const v
         return GA_ERR_INVALID;
     }
     GA_PK_USE(pk, "ga_g16_finish");
-    GA_DISPATCH_CURVE(pk->curve, {
+    return GA_DISPATCH(Scope::FULL, pk->curve, GA_NO_GROUP, {
         G16Partials<C> sum;
         sum.load(partials_sum);
         return finish<C>(pk, sum, r, s, proof_out);
     });
-    return GA_OK;
 } GA_ABI_CATCH
 
 // ---- pieces of a sharded proof (multi-GPU orchestration by the caller: gnark_amd/multigpu.py over RCCL, or ga_g16_prove_multi) ----
@@ -1464,7 +1452,7 @@ int ga_g16_witness_partial(ga_g16_pk* p, const void* w, uint64_t nb_public, void
     GA_PK_USE(pk, "ga_g16_witness_partial");
     SlotLease slot(pk->ctx);
     CtxLock g(pk->ctx);
-    GA_DISPATCH_CURVE(pk->curve, {
+    return GA_DISPATCH(Scope::FULL, pk->curve, GA_NO_GROUP, {
         G16Partials<C> part;
         GA_CHECK(witness_upload(pk, slot, w, nb_public));
         WitnessShared sh;
@@ -1473,7 +1461,6 @@ int ga_g16_witness_partial(ga_g16_pk* p, const void* w, uint64_t nb_public, void
         GA_CHECK(witness_msms<C>(pk, slot, nb_public, sh, &part, &did_k));
         part.store(partials_out);
     });
-    return GA_OK;
 } GA_ABI_CATCH
 
 int ga_g16_h_chain(ga_g16_pk* p, const void* v, uint64_t n_constraints, void* out_dev) try {
@@ -1486,7 +1473,7 @@ int ga_g16_h_chain(ga_g16_pk* p, const void* v, uint64_t n_constraints, void* ou
     GA_PK_USE(pk, "ga_g16_h_chain");
     LaneLock g(pk->ctx);   // beside the witness MSMs of the same shard when the caller runs them from another thread
     GA_CHECK(h_upload(pk, v, n_constraints, out_dev, pk->ctx->work_stream()));
-    GA_DISPATCH_CURVE(pk->curve, GA_CHECK(ntt_domain_h_chain<C>(pk->dom, out_dev)));
+    GA_CHECK(GA_DISPATCH(Scope::FULL, pk->curve, GA_NO_GROUP, return ntt_domain_h_chain<C>(pk->dom, out_dev)));
     GA_HIP_CHECK(hipStreamSynchronize(pk->ctx->work_stream()));   // the buffer is handed to another stream / device next
     return GA_OK;
 } GA_ABI_CATCH
@@ -1503,7 +1490,7 @@ int ga_g16_h_chain_dev(ga_g16_pk* p, void* buf_dev, uint64_t n_constraints) try 
     LaneLock g(pk->ctx);
     hipStream_t st = pk->ctx->work_stream();
     GA_CHECK(h_pad(pk, buf_dev, n_constraints, st));
-    GA_DISPATCH_CURVE(pk->curve, GA_CHECK(ntt_domain_h_chain<C>(pk->dom, buf_dev)));
+    GA_CHECK(GA_DISPATCH(Scope::FULL, pk->curve, GA_NO_GROUP, return ntt_domain_h_chain<C>(pk->dom, buf_dev)));
     GA_HIP_CHECK(hipStreamSynchronize(st));
     return GA_OK;
 } GA_ABI_CATCH
@@ -1517,7 +1504,7 @@ int ga_g16_h_combine(ga_g16_pk* p, void* a_dev, const void* b_dev, const void* c
     }
     GA_PK_USE(pk, "ga_g16_h_combine");
     LaneLock g(pk->ctx);
-    GA_DISPATCH_CURVE(pk->curve, GA_CHECK(ntt_domain_h_combine<C>(pk->dom, a_dev, b_dev, c_dev)));
+    GA_CHECK(GA_DISPATCH(Scope::FULL, pk->curve, GA_NO_GROUP, return ntt_domain_h_combine<C>(pk->dom, a_dev, b_dev, c_dev)));
     GA_HIP_CHECK(hipStreamSynchronize(pk->ctx->work_stream()));
     return GA_OK;
 } GA_ABI_CATCH
@@ -1531,13 +1518,12 @@ int ga_g16_z_partial(ga_g16_pk* p, const void* h_slice_dev, void* partial_out) t
     }
     GA_PK_USE(pk, "ga_g16_z_partial");
     CtxLock g(pk->ctx);
-    GA_DISPATCH_CURVE(pk->curve, {
+    return GA_DISPATCH(Scope::FULL, pk->curve, GA_NO_GROUP, {
         typedef Fe<typename C::FpP> F1;
         XYZZ<F1> z;
         GA_CHECK(z_msm<C>(pk, h_slice_dev, &z));
         host_store_jac<F1>(partial_out, z);
     });
-    return GA_OK;
 } GA_ABI_CATCH
 
 int ga_g16_prove_multi(ga_g16_pk* const* keys, uint32_t n, const void* w, const void* a, const void* b, const void* c,
@@ -1586,8 +1572,7 @@ int ga_g16_prove_multi(ga_g16_pk* const* keys, uint32_t n, const void* w, const 
                 (void)hipDeviceEnablePeerAccess(pks[q]->ctx->device, 0);
                 (void)hipGetLastError();
             }
-    GA_DISPATCH_CURVE(pks[0]->curve, return (prove_multi<C>(pks, n, w, a, b, c, n_constraints, nb_public, r, s, proof_out)));
-    return GA_OK;
+    return GA_DISPATCH(Scope::FULL, pks[0]->curve, GA_NO_GROUP, return (prove_multi<C>(pks, n, w, a, b, c, n_constraints, nb_public, r, s, proof_out)));
 } GA_ABI_CATCH
 int ga_g16_commit(ga_g16_pk* p, uint32_t index, const void* values, uint64_t n_values, void* commitment_out, void* pok_out) try {
     GA_ABI_ENTRY();
@@ -1598,8 +1583,7 @@ int ga_g16_commit(ga_g16_pk* p, uint32_t index, const void* values, uint64_t n_v
     }
     GA_PK_USE(pk, "ga_g16_commit");
     CtxLock g(pk->ctx);
-    GA_DISPATCH_CURVE(pk->curve, return commit<C>(pk, index, values, n_values, commitment_out, pok_out));
-    return GA_OK;
+    return GA_DISPATCH(Scope::FULL, pk->curve, GA_NO_GROUP, return commit<C>(pk, index, values, n_values, commitment_out, pok_out));
 } GA_ABI_CATCH
 
 int ga_g16_fold_pok(int curve, const void* poks, uint64_t n, const void* challenge, void* out) try {
@@ -1608,8 +1592,7 @@ int ga_g16_fold_pok(int curve, const void* poks, uint64_t n, const void* challen
         set_error("ga_g16_fold_pok: null argument");
         return GA_ERR_INVALID;
     }
-    GA_DISPATCH_CURVE(curve, return fold_pok<C>(poks, n, challenge, out));
-    return GA_OK;
+    return GA_DISPATCH(Scope::FULL, curve, GA_NO_GROUP, return fold_pok<C>(poks, n, challenge, out));
 } GA_ABI_CATCH
 
 int ga_g16_prove(ga_g16_pk* p, const void* w, const void* a, const void* b, const void* c, uint64_t n_constraints,
@@ -1640,7 +1623,7 @@ int ga_g16_prove_batch(ga_g16_pk* p, uint32_t count, const void* const* w, const
     GA_CHECK(check_nb_constraints(pk, n_constraints));
     GA_CHECK(check_nb_public(pk, nb_public));
     Ctx* ctx = pk->ctx;
-    GA_DISPATCH_CURVE(pk->curve, {
+    return GA_DISPATCH(Scope::FULL, pk->curve, GA_NO_GROUP, {
         std::vector<G16Partials<C>> parts(count);
         {
             std::unique_lock<std::mutex> dev(ctx->mu);
@@ -1652,7 +1635,6 @@ int ga_g16_prove_batch(ga_g16_pk* p, uint32_t count, const void* const* w, const
         }
         return finish_batch<C>(pk, parts, r, s, proofs_out, /*serial=*/false);
     });
-    return GA_OK;
 } GA_ABI_CATCH
 
 // One proof on a key that is NOT kept on the device (the Go package's default, PinToGPU = false, as icicle.go:797-805): the key

@@ -142,8 +142,7 @@ extern "C" int ga_hash_to_field(int curve, const uint8_t* msg, size_t msg_len, c
         set_error("ga_hash_to_field: null argument");
         return GA_ERR_INVALID;
     }
-    GA_DISPATCH_CURVE_FR(curve, return hash_to_field<C>(msg, msg_len, dst, dst_len, count, out));
-    return GA_OK;
+    return GA_DISPATCH(Scope::G1_FR, curve, GA_NO_GROUP, return hash_to_field<C>(msg, msg_len, dst, dst_len, count, out));
 } GA_ABI_CATCH
 
 // exposed for the fixture test of the expand_test.go vectors

@@ -177,4 +177,16 @@ int msm_table_build(Ctx* ctx, const void* d_bases, size_t n, int c, void* d_tabl
     return GA_OK;
 }
 
+// what msm_<curve>_g<k>.hip instantiates; the G1 unit of a curve has the group-independent half as well
+#define GA_INSTANTIATE_MSM(C, G)                                                                                        \
+    template int msm_windows_device<C, G>(Ctx*, const void*, const void*, size_t, bool, int, int, int, void*, bool);    \
+    template int msm_table_device<C, G>(Ctx*, const void*, const void*, size_t, bool, int, void*, int, int);            \
+    template int msm_table_device_reuse<C, G>(Ctx*, const void*, const MsmPrepared&, void*);                            \
+    template int msm_table_device_reuse_multi<C, G>(Ctx*, const void* const*, int, const MsmPrepared&, void*);          \
+    template int msm_table_device_batch<C, G>(Ctx*, const void*, const void* const*, int, size_t, bool, int, void*);    \
+    template int msm_table_build<C, G>(Ctx*, const void*, size_t, int, void*);                                          \
+    template size_t msm_table_point_bytes<C, G>();
+#define GA_INSTANTIATE_MSM_SCALARS(C) \
+    template int msm_prepare_table_scalars<C>(Ctx*, const void*, size_t, bool, int, MsmPrepared*, int, int, int, int);
+
 }  // namespace ga

@@ -801,4 +801,41 @@ inline void domain_free(Domain* d) {
     hipFree(d->d_gi_hi);
 }
 
+// ---- the per-curve calls declared in common.hip.h: C::FrP for the drivers above ------------------------------------------------
+template <class C>
+int ntt_domain_new(Ctx* ctx, uint64_t n, Domain** out) {
+    Domain* d = new Domain();
+    int rc = domain_init<typename C::FrP>(ctx, d, C::ID, n);
+    if (rc != GA_OK) {
+        domain_free(d);
+        delete d;
+        return rc;
+    }
+    *out = d;
+    return GA_OK;
+}
+template <class C>
+int ntt_domain_fft(Domain* d, void* d_data, int direction, int decimation, int on_coset, uint64_t batch) {
+    return ntt_fft<typename C::FrP>(d, (uint32_t*)d_data, direction, decimation, on_coset, batch);
+}
+template <class C>
+int ntt_domain_h_chain(Domain* d, void* d_v, uint64_t batch) {
+    return ntt_compute_h_chain<typename C::FrP>(d, (uint32_t*)d_v, batch);
+}
+template <class C>
+int ntt_domain_h_combine(Domain* d, void* d_a, const void* d_b, const void* d_c, uint64_t batch) {
+    return ntt_compute_h_combine<typename C::FrP>(d, (uint32_t*)d_a, (const uint32_t*)d_b, (const uint32_t*)d_c, batch);
+}
+template <class C>
+int ntt_domain_compute_h(Domain* d, void* d_a, void* d_b, void* d_c, uint64_t batch) {
+    return ntt_compute_h<typename C::FrP>(d, (uint32_t*)d_a, (uint32_t*)d_b, (uint32_t*)d_c, batch);
+}
+// what ntt_<curve>.hip instantiates
+#define GA_INSTANTIATE_NTT(C)                                                                   \
+    template int ntt_domain_new<C>(Ctx*, uint64_t, Domain**);                                   \
+    template int ntt_domain_fft<C>(Domain*, void*, int, int, int, uint64_t);                    \
+    template int ntt_domain_h_chain<C>(Domain*, void*, uint64_t);                               \
+    template int ntt_domain_h_combine<C>(Domain*, void*, const void*, const void*, uint64_t);   \
+    template int ntt_domain_compute_h<C>(Domain*, void*, void*, void*, uint64_t);
+
 }  // namespace ga

@@ -491,4 +491,8 @@ int pairing_run(Ctx* ctx, const void* p_affine, const void* q_affine, size_t n, 
     return GA_OK;
 }
 
+// what pairing_<curve>.hip instantiates
+#define GA_INSTANTIATE_PAIRING(C) \
+    template int pairing_run<C>(Ctx*, const void*, const void*, size_t, const uint64_t*, size_t, unsigned, uint8_t*, void*, uint64_t*, uint64_t);
+
 }  // namespace ga

@@ -828,4 +828,22 @@ static __global__ void plonk_perm_check_kernel(const int64_t* __restrict__ perm,
     if (i < n3 && (perm[i] < 0 || (uint64_t)perm[i] >= n3)) atomicAdd(bad, 1u);
 }
 
+// ---- the per-curve calls declared in common.hip.h: C::FrP for the drivers above (instantiated with those of plonk_batch.hip.h) ----
+template <class C>
+int plonk_domain_quotient(Domain* d0, Domain* d1, const PlonkQuotientArgs& args, void* h_out) {
+    return plonk_quotient<typename C::FrP>(d0, d1, args, h_out);
+}
+template <class C>
+int plonk_domain_fixed_create(Domain* d0, Domain* d1, const PlonkQuotientArgs& args, PlonkFixed** out) {
+    return plonk_fixed_create<typename C::FrP>(d0, d1, args, out);
+}
+template <class C>
+int fr_vec_batch_inverse(Ctx* ctx, void* v, uint64_t n, bool on_device) {
+    return fr_batch_inverse<typename C::FrP>(ctx, v, n, on_device);
+}
+template <class C>
+int fr_vec_lincomb(Ctx* ctx, uint64_t n, int k, const void* const* vecs, const void* scalars, void* out, bool on_device) {
+    return fr_lincomb<typename C::FrP>(ctx, n, k, vecs, scalars, out, on_device);
+}
+
 }  // namespace ga

@@ -259,4 +259,31 @@ int kzg_divide_by_linear(Ctx* ctx, const void* const* d_polys, uint64_t n, uint3
     return GA_OK;
 }
 
+// ---- the per-curve calls declared in common.hip.h: C::FrP for the drivers above ------------------------------------------------
+template <class C>
+int plonk_domain_build_z_batch(Domain* d0, const void* L, const void* R, const void* O, const int64_t* perm, const void* betas, const void* gammas,
+                               uint32_t count, PlonkBatchKnobs knobs, bool on_device, void* z_out) {
+    return plonk_build_z<typename C::FrP>(d0, L, R, O, perm, betas, gammas, count, knobs, on_device, z_out);
+}
+template <class C>
+int plonk_domain_quotient_pinned_batch(PlonkFixed* fx, const PlonkQuotientArgs* args, uint32_t count, PlonkBatchKnobs knobs, void* h_out) {
+    return plonk_quotient_pinned<typename C::FrP>(fx, args, count, knobs, h_out);
+}
+template <class C>
+int kzg_domain_divide_batch(Ctx* ctx, const void* const* d_polys, uint64_t n, uint32_t count, const void* points, void* d_quot, uint64_t quot_stride,
+                            void* d_values, uint64_t scan_threads, std::vector<uint32_t>* stage) {
+    return kzg_divide_by_linear<typename C::FrP>(ctx, d_polys, n, count, points, (uint32_t*)d_quot, quot_stride, (uint32_t*)d_values, scan_threads, *stage);
+}
+// what plonk_<curve>.hip instantiates: these three and the four of plonk.hip.h
+#define GA_INSTANTIATE_PLONK(C)                                                                                                          \
+    template int plonk_domain_quotient<C>(Domain*, Domain*, const PlonkQuotientArgs&, void*);                                            \
+    template int plonk_domain_fixed_create<C>(Domain*, Domain*, const PlonkQuotientArgs&, PlonkFixed**);                                 \
+    template int fr_vec_batch_inverse<C>(Ctx*, void*, uint64_t, bool);                                                                   \
+    template int fr_vec_lincomb<C>(Ctx*, uint64_t, int, const void* const*, const void*, void*, bool);                                   \
+    template int plonk_domain_build_z_batch<C>(Domain*, const void*, const void*, const void*, const int64_t*, const void*, const void*, \
+                                               uint32_t, PlonkBatchKnobs, bool, void*);                                                  \
+    template int plonk_domain_quotient_pinned_batch<C>(PlonkFixed*, const PlonkQuotientArgs*, uint32_t, PlonkBatchKnobs, void*);         \
+    template int kzg_domain_divide_batch<C>(Ctx*, const void* const*, uint64_t, uint32_t, const void*, void*, uint64_t, void*, uint64_t, \
+                                            std::vector<uint32_t>*);
+
 }  // namespace ga

@@ -268,4 +268,8 @@ int scale_points_run(Ctx* ctx, const void* points, size_t n, int mode, const voi
     return GA_OK;
 }
 
+// what scale_points_<curve>_g<k>.hip instantiates
+#define GA_INSTANTIATE_SCALE_POINTS(C, G) \
+    template int scale_points_run<C, G>(Ctx*, const void*, size_t, int, const void*, uint64_t, unsigned, void*, uint64_t*, int, uint64_t);
+
 }  // namespace ga

@@ -1,5 +1,5 @@
 // Explicit instantiation: per-point scalar multiplication, bls12381 G2 (see scale_points.hip.h).
 #include "scale_points.hip.h"
 namespace ga {
-template int scale_points_run<Bls12381, GA_G2>(Ctx*, const void*, size_t, int, const void*, uint64_t, unsigned, void*, uint64_t*, int, uint64_t);
+GA_INSTANTIATE_SCALE_POINTS(Bls12381, GA_G2)
 }  // namespace ga

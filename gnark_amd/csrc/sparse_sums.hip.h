@@ -304,4 +304,9 @@ int sparse_sums_run(Ctx* ctx, const void* points, size_t n_points, const uint64_
     return GA_OK;
 }
 
+// what sparse_sums_<curve>_g<k>.hip instantiates
+#define GA_INSTANTIATE_SPARSE_SUMS(C, G)                                                                                                        \
+    template int sparse_sums_run<C, G>(Ctx*, const void*, size_t, const uint64_t*, size_t, const uint32_t*, const void*, size_t, unsigned, void*, \
+                                       uint64_t*, uint64_t, uint32_t, int);
+
 }  // namespace ga

@@ -1,6 +1,5 @@
 // Explicit instantiation: sparse point sums, bls12381 G2 (see sparse_sums.hip.h).
 #include "sparse_sums.hip.h"
 namespace ga {
-template int sparse_sums_run<Bls12381, GA_G2>(Ctx*, const void*, size_t, const uint64_t*, size_t, const uint32_t*, const void*, size_t, unsigned, void*, uint64_t*,
-                                           uint64_t, uint32_t, int);
+GA_INSTANTIATE_SPARSE_SUMS(Bls12381, GA_G2)
 }  // namespace ga

@@ -1,6 +1,5 @@
 // Explicit instantiation: sparse point sums, bn254 G1 (see sparse_sums.hip.h).
 #include "sparse_sums.hip.h"
 namespace ga {
-template int sparse_sums_run<Bn254, GA_G1>(Ctx*, const void*, size_t, const uint64_t*, size_t, const uint32_t*, const void*, size_t, unsigned, void*, uint64_t*,
-                                           uint64_t, uint32_t, int);
+GA_INSTANTIATE_SPARSE_SUMS(Bn254, GA_G1)
 }  // namespace ga

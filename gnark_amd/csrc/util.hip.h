@@ -256,4 +256,16 @@ int msm_plan_table(size_t n, int* c_out, int* nwin_out, bool batched) {
     return GA_OK;
 }
 
+// what util_<curve>.hip instantiates: the per-curve part, and the per-group part once per group the curve has
+#define GA_INSTANTIATE_UTIL(C)                                                                                                  \
+    template int util_gen_scalars<C>(Ctx*, uint64_t, size_t, void*);                                                            \
+    template int util_fr_dot<C>(Ctx*, const void*, const void*, size_t, void*);                                                 \
+    template int util_fr_vec_mul<C>(Ctx*, const void*, const void*, size_t, void*);                                             \
+    template int util_gather_fr<C>(Ctx*, void*, const void*, const uint32_t*, size_t);                                          \
+    template int util_gather_fr_batch<C>(Ctx*, void*, const void*, const uint32_t*, size_t, uint32_t, uint64_t, uint64_t);      \
+    template int util_pad_fr_batch<C>(Ctx*, void*, uint64_t, uint64_t, uint32_t, hipStream_t);                                  \
+    template int msm_plan<C>(int, size_t, int*, int*);                                                                          \
+    template int msm_plan_table<C>(size_t, int*, int*, bool);
+#define GA_INSTANTIATE_UTIL_GROUP(C, G) template int util_gen_bases<C, G>(Ctx*, uint64_t, size_t, void*, void*, uint64_t);
+
 }  // namespace ga
