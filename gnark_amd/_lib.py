@@ -20,6 +20,7 @@ RESULT_ON_DEVICE, RESULT_BITREVERSED, CHECK_CURVE_ONLY = 0x20, 0x40, 0x80
 POINT_OK, POINT_OFF_CURVE, POINT_NOT_IN_SUBGROUP = 0, 1, 2
 VECTOR_ON_DEVICE = BASES_ON_DEVICE
 SCALE_EACH, SCALE_ONE, SCALE_POWERS = 0, 1, 2
+PLONK_ON_DEVICE, PLONK_VERIFY_COMBINED, PLONK_VERIFY_NO_POINT_CHECK = 0x1, 0x2, 0x4
 FFT_FORWARD, FFT_INVERSE = 0, 1
 DIF, DIT = 0, 1
 
@@ -60,6 +61,17 @@ class PlonkQuotientIn(C.Structure):
         ("alpha", C.c_void_p), ("beta", C.c_void_p), ("gamma", C.c_void_p),
         ("flags", C.c_uint32),
     ]
+
+
+class PlonkVkIn(C.Structure):
+    """struct ga_plonk_vk_in"""
+    _fields_ = [("nb_public", C.c_uint64), ("nb_bsb", C.c_uint32), ("commitment_constraint_indexes", C.c_void_p)] + [
+        (k, C.c_void_p) for k in ("ql", "qr", "qm", "qo", "qk", "s1", "s2", "s3", "qcp", "kzg_g1", "kzg_g2")]
+
+
+class PlonkProofs(C.Structure):
+    """struct ga_plonk_proofs"""
+    _fields_ = [(k, C.c_void_p) for k in ("points", "evals", "challenges", "public_inputs", "bsb_hashes")]
 
 
 _P = C.c_void_p
@@ -114,6 +126,10 @@ _PROTOS = {
     "ga_plonk_build_z": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, _P]),
     "ga_plonk_build_z_batch": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_int, _P]),
     "ga_plonk_quotient_pinned_batch": (C.c_int, [_P, C.POINTER(PlonkQuotientIn), C.c_uint32, _P]),
+    "ga_plonk_vk_create": (C.c_int, [_P, C.POINTER(PlonkVkIn), C.POINTER(_P)]),
+    "ga_plonk_vk_destroy": (None, [_P]),
+    "ga_plonk_verify_scalars": (C.c_int, [_P, C.POINTER(PlonkProofs), C.c_uint32, C.c_uint, _P, _P]),
+    "ga_plonk_verify": (C.c_int, [_P, C.POINTER(PlonkProofs), C.c_uint32, C.c_uint, _P, _P, _P, C.POINTER(C.c_uint64)]),
     "ga_fr_linear_combination": (C.c_int, [_P, C.c_int, C.c_uint64, C.c_int, C.POINTER(C.c_void_p), _P, _P, C.c_int]),
     "ga_fr_poly_evaluate": (C.c_int, [_P, C.c_int, _P, C.c_uint64, _P, _P, C.c_int]),
     "ga_kzg_open": (C.c_int, [_P, _P, C.c_size_t, C.c_uint, _P, _P, _P]),

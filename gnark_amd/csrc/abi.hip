@@ -270,6 +270,8 @@ typedef CtxLock Lock;
 //     GA_SPARSE_ORDER       0: the products in row order (default); 1: sorted by coefficient id (the A/B of tools/phase2_init_bench.py)
 //   ga_pairing_check
 //     GA_PAIRING_CHUNK      pairs per pass (0 = 2^18, at most 2^30; tests force a small chunk)
+//   ga_plonk_verify           the knobs of the calls it is made of: GA_CHECK_NAIVE, GA_CHECK_CHUNK, GA_SPARSE_CHUNK, GA_SPARSE_SEGMENT,
+//                             GA_PAIRING_CHUNK (tests force small chunks so that a few proofs take several passes)
 //   ga_fr_sparse_matvec
 //     GA_FR_SPARSE_SEGMENT  terms, or partial sums, per lane: 2 .. 2^20; unset, 0 or 1 = the default (FR_SPARSE_DEFAULT_SEGMENT); a
 //                           larger value is taken as 2^20; tests force 2
@@ -1390,6 +1392,79 @@ int ga_plonk_quotient_pinned_batch(ga_plonk_pk* p, const ga_plonk_quotient_in* i
     }
     const PlonkBatchKnobs knobs = env_plonk_batch_knobs();
     return GA_DISPATCH(Scope::G1_FR, ntt_domain_curve(d0), GA_NO_GROUP, return plonk_domain_quotient_pinned_batch<C>(fx, a.data(), count, knobs, h_out));
+} GA_ABI_CATCH
+
+// ---- plonk.Verify for many proofs under one key (plonk_verify.hip.h) ---------------------------------------------------------------
+// No curve argument: the curve is the domain's.  The key is Scope::FULL (the verifier ends in a pairing).
+int ga_plonk_vk_create(ga_domain* dh0, const ga_plonk_vk_in* in, ga_plonk_vk** out) try {
+    GA_ABI_ENTRY();
+    Domain* d0 = reinterpret_cast<Domain*>(dh0);
+    if (!d0 || !in || !out) {
+        set_error("ga_plonk_vk_create: null argument");
+        return GA_ERR_INVALID;
+    }
+    constexpr Scope S = Scope::FULL;
+    GA_CHECK(dispatch_check(S, ntt_domain_curve(d0), GA_NO_GROUP));
+    Ctx* c = ntt_domain_ctx(d0);
+    Lock l(c);
+    PlonkVk* vk = nullptr;
+    GA_CHECK(GA_DISPATCH(S, ntt_domain_curve(d0), GA_NO_GROUP, return plonk_vk_new<C>(d0, in, &vk)));
+    *out = reinterpret_cast<ga_plonk_vk*>(vk);
+    return GA_OK;
+} GA_ABI_CATCH
+
+void ga_plonk_vk_destroy(ga_plonk_vk* p) try {
+    GA_ABI_ENTRY();
+    PlonkVk* vk = reinterpret_cast<PlonkVk*>(p);
+    if (!vk) return;
+    Ctx* c = ntt_domain_ctx(plonk_vk_domain0(vk));
+    Lock l(c);
+    hipStreamSynchronize(c->stream);
+    plonk_vk_delete(vk);
+} GA_ABI_CATCH_VOID
+
+int ga_plonk_verify_scalars(ga_plonk_vk* p, const ga_plonk_proofs* proofs, uint32_t count, unsigned flags, void* rows_out, uint8_t* relation_ok) try {
+    GA_ABI_ENTRY();
+    if (count == 0) return GA_OK;
+    PlonkVk* vk = reinterpret_cast<PlonkVk*>(p);
+    if (!vk || !proofs || !rows_out || !relation_ok) {
+        set_error("ga_plonk_verify_scalars: null argument");
+        return GA_ERR_INVALID;
+    }
+    if (count > PLONK_VERIFY_MAX_COUNT) {
+        set_error("ga_plonk_verify_scalars: count = %u above 2^20", count);
+        return GA_ERR_INVALID;
+    }
+    Domain* d0 = plonk_vk_domain0(vk);
+    Ctx* c = ntt_domain_ctx(d0);
+    Lock l(c);
+    return GA_DISPATCH(Scope::FULL, ntt_domain_curve(d0), GA_NO_GROUP,
+                       return plonk_verify_scalars_run<C>(vk, proofs, count, (flags & GA_PLONK_ON_DEVICE) != 0, rows_out, relation_ok));
+} GA_ABI_CATCH
+
+int ga_plonk_verify(ga_plonk_vk* p, const ga_plonk_proofs* proofs, uint32_t count, unsigned flags, const void* weights, uint8_t* ok, uint8_t* relation_ok,
+                    uint64_t* out2) try {
+    GA_ABI_ENTRY();
+    if (count == 0) return GA_OK;
+    PlonkVk* vk = reinterpret_cast<PlonkVk*>(p);
+    if (!vk || !proofs || !ok || !out2) {
+        set_error("ga_plonk_verify: null argument%s", out2 ? "" : " (out2)");
+        return GA_ERR_INVALID;
+    }
+    if ((flags & GA_PLONK_VERIFY_COMBINED) && !weights) {
+        set_error("ga_plonk_verify: GA_PLONK_VERIFY_COMBINED without weights");
+        return GA_ERR_INVALID;
+    }
+    if (count > PLONK_VERIFY_MAX_COUNT) {
+        set_error("ga_plonk_verify: count = %u above 2^20", count);
+        return GA_ERR_INVALID;
+    }
+    Domain* d0 = plonk_vk_domain0(vk);
+    Ctx* c = ntt_domain_ctx(d0);
+    Lock l(c);
+    const PlonkVerifyKnobs knobs{check_naive_knob(), env_u64("GA_CHECK_CHUNK", 0), env_u64("GA_SPARSE_CHUNK", 0), env_u64("GA_PAIRING_CHUNK", 0),
+                                 env_segment("GA_SPARSE_SEGMENT")};
+    return GA_DISPATCH(Scope::FULL, ntt_domain_curve(d0), GA_NO_GROUP, return plonk_verify_run<C>(vk, proofs, count, flags, weights, ok, relation_ok, out2, knobs));
 } GA_ABI_CATCH
 
 int ga_fr_batch_invert(ga_ctx* h, int curve, void* v, uint64_t n, int on_device) try {

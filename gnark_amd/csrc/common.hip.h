@@ -620,6 +620,23 @@ int kzg_domain_divide(Ctx* ctx, const void* d_poly, uint64_t n, const void* z_mo
     return GA_OK;
 }
 
+// plonk.Verify for `count` proofs under one key (plonk_verify.hip.h).  The knobs are those of the calls it is made of, as the entry
+// point read them (abi.hip has the table).
+struct PlonkVk;   // plonk_verify.hip.h: the key's points on the device, its shape and the constants of domain0
+struct PlonkVerifyKnobs {
+    int check_naive;
+    uint64_t check_chunk, sparse_chunk, pairing_chunk;
+    uint32_t sparse_segment;
+};
+constexpr uint32_t PLONK_VERIFY_MAX_COUNT = 1u << 20;   // proofs per call: count * row width stays far below the 2^32 coefficients of a sparse sum
+template <class C> int plonk_vk_new(Domain* d0, const ga_plonk_vk_in* in, PlonkVk** out);
+void plonk_vk_delete(PlonkVk* vk);
+Domain* plonk_vk_domain0(PlonkVk* vk);
+template <class C> int plonk_verify_scalars_run(PlonkVk* vk, const ga_plonk_proofs* p, uint32_t count, bool on_device, void* rows_out, uint8_t* relation_ok);
+template <class C>
+int plonk_verify_run(PlonkVk* vk, const ga_plonk_proofs* p, uint32_t count, unsigned flags, const void* weights, uint8_t* ok, uint8_t* relation_ok,
+                     uint64_t* out2, const PlonkVerifyKnobs& knobs);
+
 // ---- the point and Fr vector calls; explicitly instantiated in <call>_<curve>[_g<k>].hip.  Operands are host or device pointers per
 // the GA_*_ON_DEVICE flags; the trailing arguments are the run-time knobs as the entry point read them (abi.hip has the table)
 // fixed_base.hip.h: out[i] = [scalars[i]] base, one affine base on the host; and the (c, nwin) it will use for n scalars

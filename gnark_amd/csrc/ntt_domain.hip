@@ -1,8 +1,11 @@
 // Non-templated accessors of the fft.Domain analogue (see ntt.hip.h).
 #include "plonk.hip.h"
+#include "plonk_verify.hip.h"
 namespace ga {
 void plonk_fixed_delete(PlonkFixed* fx) { plonk_fixed_destroy(fx); }
 Domain* plonk_fixed_domain0(PlonkFixed* fx) { return fx->d0; }
+void plonk_vk_delete(PlonkVk* vk) { plonk_vk_free(vk); }
+Domain* plonk_vk_domain0(PlonkVk* vk) { return vk->d0; }
 void ntt_domain_delete(Domain* d) {
     if (!d) return;
     domain_free(d);

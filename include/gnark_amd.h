@@ -499,6 +499,70 @@ int ga_fr_vec_mul(ga_ctx* ctx, int curve, const void* a, const void* b, size_t n
 /* fr.BatchInvert in place (zeros stay zero): the batchInvert of prove.go:1134-1147 */
 int ga_fr_batch_invert(ga_ctx* ctx, int curve, void* v, uint64_t n, int on_device);
 
+/* ---- PLONK: verification of MANY proofs under one key ---------------------------------------------------------
+ * replaces: the arithmetic of plonk.Verify (backend/plonk/bn254/verify.go:124-318) for `count` proofs at once: PI(zeta) over the public
+ * inputs and the BSB22 hashes (:136-188), the algebraic relation constLin == ClaimedValues[0] (:206-223), the scalars of the
+ * linearised digest (:225-277), kzg.FoldProof and kzg.BatchVerifyMultiPoints (:282-318), and the subgroup tests of :61-85.
+ * NOT replaced -- the caller supplies them: the Fiat-Shamir challenges gamma, beta, alpha, zeta (gnark-crypto's fiatshamir
+ * transcript), the fold challenge v of kzg.FoldProof's transcript, the scalar u that BatchVerifyMultiPoints draws from crypto/rand,
+ * and the hashed BSB22 commitments (ga_hash_to_field with DST "BSB22-Plonk" over the marshalled commitments, :162-175).
+ *
+ * The key: the points of plonk.VerifyingKey on the device; Size, SizeInv, Generator and CosetShift are domain0's, and so is the
+ * curve (BN254 or BLS12-381; a BLS12-377 domain is refused by name: no pairing).  Everything behind `in` is host memory and is
+ * copied; the domain must outlive the key.  GA_ERR_INVALID: a null pointer (commitment_constraint_indexes and qcp may be null
+ * when nb_bsb = 0), nb_bsb above 16, nb_public + nb_bsb above the domain's size, a constraint index that puts its term at or
+ * beyond the size. */
+typedef struct ga_plonk_vk ga_plonk_vk;
+typedef struct ga_plonk_vk_in {
+    uint64_t nb_public;                              /* vk.NbPublicVariables */
+    uint32_t nb_bsb;                                 /* len(vk.Qcp), at most 16 */
+    const uint64_t* commitment_constraint_indexes;   /* nb_bsb */
+    const void *ql, *qr, *qm, *qo, *qk, *s1, *s2, *s3;   /* G1Affine each (vk.S[0..2]) */
+    const void* qcp;                                 /* nb_bsb G1Affine, contiguous */
+    const void* kzg_g1;                              /* vk.Kzg.G1 */
+    const void* kzg_g2;                              /* vk.Kzg.G2[0], G2[1]: two G2Affine, contiguous */
+} ga_plonk_vk_in;
+int ga_plonk_vk_create(ga_domain* domain0, const ga_plonk_vk_in* in, ga_plonk_vk** out);
+void ga_plonk_vk_destroy(ga_plonk_vk* vk);
+
+/* `count` proofs as five arrays; every fr is a Montgomery image below r (gnark's fr.Element), every point a G1Affine image.
+ * Host memory, or ALL device memory with GA_PLONK_ON_DEVICE (then rows_out, ok and relation_ok are device pointers too; weights
+ * and out2 are always host).  public_inputs / bsb_hashes may be null when nb_public / nb_bsb is 0. */
+typedef struct ga_plonk_proofs {
+    const void* points;        /* [count][9 + nb_bsb] G1Affine: L R O Z H0 H1 H2 W_zeta W_zeta_omega Bsb_0.. */
+    const void* evals;         /* [count][7 + nb_bsb] fr: ClaimedValues[0 .. 5 + nb_bsb], then ZShiftedOpening.ClaimedValue */
+    const void* challenges;    /* [count][6] fr: gamma beta alpha zeta v u */
+    const void* public_inputs; /* [count][nb_public] fr */
+    const void* bsb_hashes;    /* [count][nb_bsb] fr: the hashed commitments of verify.go:171-175 */
+} ga_plonk_proofs;
+#define GA_PLONK_VERIFY_COMBINED       0x2u   /* one randomised check of all proofs instead of one verdict each */
+#define GA_PLONK_VERIFY_NO_POINT_CHECK 0x4u   /* the caller has run the subgroup tests of verify.go:61-85 itself */
+/* The scalar side alone: relation_ok[j] = (constLin == ClaimedValues[0]) of proof j, and rows_out = [count][2 (9 + nb_bsb) + 2] fr,
+ * row j the coefficients of proof j's whole KZG check e(P_j, G2[0]) e(Q_j, G2[1]) = 1 with (E = sum_k v^k ClaimedValues[k], zu the
+ * shifted claimed value, D0 the linearised digest, F = D0 + v L + v^2 R + v^3 O + v^4 S1 + v^5 S2 + sum_t v^(6+t) Qcp_t)
+ *     P_j = F - E G1 + zeta W_zeta + u (Z - zu G1 + omega zeta W_zeta_omega),      Q_j = -(W_zeta + u W_zeta_omega)
+ * in the column order   G1 Ql Qr Qm Qo Qk S1 S2 S3 Qcp_0..  |  L R O Z H0 H1 H2 W_zeta W_zeta_omega Bsb_0..  |  -1, -u
+ * (key points, proof points, the two coefficients of Q_j) -- what a caller with its own MSM needs.  The inverse of 0 is 0, as
+ * fr.Inverse / BatchInvert / Div have it: zeta on the domain gives what verify.go computes.  Two launches (profiler stages
+ * plonk_vf_public, plonk_vf_rows) and one host synchronisation. */
+int ga_plonk_verify_scalars(ga_plonk_vk* vk, const ga_plonk_proofs* p, uint32_t count, unsigned flags, void* rows_out,
+                            uint8_t* relation_ok);
+/* The whole verifier.  Default: ga_check_points' tests on the count * (9 + nb_bsb) proof points (unless NO_POINT_CHECK), the rows,
+ * P_j and Q_j of every proof as the 2 count rows of one sparse point sum over [key points | proof points], and ONE pairing pass of
+ * count groups of two pairs:  ok[j] = relation_ok[j] && every point of proof j passed && the pairing product of group j is 1.
+ * out2 = {proofs rejected, index of the first one or UINT64_MAX}; relation_ok may be NULL.
+ * GA_PLONK_VERIFY_COMBINED: weights = count fr (Montgomery, host) chosen by the caller -- the randomness of the batch.  The
+ * key columns are summed over the proofs with the weights (stage plonk_vf_combine), the proof columns scaled, and
+ * P = sum_j rho_j P_j, Q = sum_j rho_j Q_j come from one MSM each; one pairing group.  ok[0] = every relation and every point
+ * check passed and e(P, G2[0]) e(Q, G2[1]) = 1; out2 = {0 or 1, 0 or UINT64_MAX}; relation_ok stays per proof.
+ * The return value says whether the check RAN, not what it found: a bad point is a rejected proof (its terms are left out of the
+ * sums), never an error and never another proof's verdict.  count = 0 is GA_OK and touches nothing.  GA_ERR_INVALID, before any
+ * launch: a null pointer, count above 2^20, combined mode without weights, a null out2.  Device scratch comes from the context;
+ * GA_ERR_NOMEM leaves nothing in flight and the context usable.  Host synchronisations: those of the point check, the sparse sum
+ * or the two MSMs, and the pairing, plus ONE for the rows (the sparse sum classifies its coefficients on the host). */
+int ga_plonk_verify(ga_plonk_vk* vk, const ga_plonk_proofs* p, uint32_t count, unsigned flags, const void* weights, uint8_t* ok,
+                    uint8_t* relation_ok, uint64_t* out2);
+
 /* ---- Groth16 -------------------------------------------------------------------------------------------
  * replaces: (*ProvingKey).setupDevicePointers (icicle.go:88-264) and Prove (icicle.go:784-1360).
  * ga_g16_key describes gnark's groth16 ProvingKey (setup.go:25-48) by pointer+length; everything is copied to
