@@ -133,7 +133,7 @@ struct Bls12377 {
     using FrP = BLS12_377_Fr;
 };
 // THE list of the curves the library is built for: X(tag) once per curve.  The dispatcher at the end of this file and the refusal
-// messages (abi.hip) are generated from it; nothing else enumerates curves.
+// messages (ctx.hip) are generated from it; nothing else enumerates curves.
 #define GA_CURVES(X) X(Bn254) X(Bls12381) X(Bls12377)
 template <class C, int G> struct GroupField;
 template <class C> struct GroupField<C, GA_G1> { using F = Fe<typename C::FpP>; };
@@ -167,8 +167,15 @@ struct StageRec {
     hipEvent_t a, b;
 };
 
+// a 64-bit knob (strtoull), an int knob (atoi), a 0 / 1 knob (anything atoi reads as non-zero is 1); the default when the variable is not set
+uint64_t env_u64(const char* name, uint64_t dflt);
+int env_int(const char* name, int dflt);
+int env_flag(const char* name, int dflt);
+
 // Run-time knobs, read from the environment ONCE per ABI entry point (Lock's constructor), never inside the launch paths:
-//   GA_MSM_MAX_CHUNK      split an MSM along the point axis into chunks of at most this many points (msmChunkedG1/G2 analogue)
+//   GA_MSM_MAX_CHUNK      split an MSM over raw bases along the point axis into chunks of at most this many points (msmChunkedG1/G2
+//                         analogue): ga_msm, ga_msm_windows, and the prover's MSMs over un-pinned vectors, the BSB22 commitments and
+//                         PLONK verify alike (msm_run is the one driver of them all)
 //   GA_REDUCE_LAZY_MIN    bucket count from which the window reduction runs in the lazy representation
 //   GA_G16_SHARE_MIN_PCT  a Groth16 base vector shares the single witness sort when it covers at least this % of the wires
 //   GA_G16_TABLE_BUDGET_PCT  % of the bytes of a key's five window tables that precompute = 0 may spend, instead of what the free HBM allows (tests: partial tables)
@@ -219,7 +226,7 @@ struct Tunables {
 //   * a second ga_g16_prove caller computes its proof CONCURRENTLY on lanes 2/3 instead of queueing behind the first: its
 //     uploads hide behind the other proof's kernels;
 //   * the table MSM entry points and the pieces of a sharded proof take lane 1 when lane 0 is busy (LaneLock).
-// The lane is a thread-local of the calling thread (abi.hip), so the launch paths pick the right stream / scratch without extra
+// The lane is a thread-local of the calling thread (ctx.hip), so the launch paths pick the right stream / scratch without extra
 // parameters.  Results never depend on the interleaving.
 constexpr int GA_NUM_LANES = 4;
 int current_lane();
@@ -457,6 +464,18 @@ int msm_windows_device(Ctx* ctx, const void* d_bases, const void* d_scalars, siz
                        int win_lo, int win_hi, void* h_window_sums, bool combine = false);
 template <class C>
 int msm_plan(int group, size_t n, int* c, int* nwin);
+// THE driver of an MSM over raw bases on the device (msm.hip.h): windows [win_lo, win_hi) of width c, win_lo < win_hi.  h_out (host,
+// XYZZ<F> images) receives ONE point, sum_w 2^(c w) W_w over the range (the shares of disjoint ranges add up), or with want_windows the
+// win_hi - win_lo window sums.  Vectors of more than max_chunk points (0 = no cap), or of more than the 2^31 (point, window) pairs of
+// one launch sequence, are split along the point axis -- the analogue of msmChunkedG1/G2, icicle.go:362-467 -- and the parts added on
+// the host.  Every caller passes ctx->tun.msm_max_chunk (GA_MSM_MAX_CHUNK, like ICICLE's chunk-cap override, icicle.go:577-584).
+template <class C, int G>
+int msm_run(Ctx* ctx, const void* d_bases, const void* d_scalars, size_t n, bool scalars_mont, int c, int win_lo, int win_hi, size_t max_chunk,
+            void* h_out, bool want_windows);
+// ga_msm / ga_msm_windows: plan, check the range (win_hi < 0 = all), stage host operands, msm_run; out = Jac<F> images
+template <class C, int G>
+int msm_abi_run(Ctx* ctx, const void* bases, const void* scalars, size_t n, unsigned flags, int win_lo, int win_hi, void* out, int* c_out,
+                int* nwin_out, bool want_windows);
 // window width for the precomputed-table mode (one shared bucket set; table = nwin x n affine points)
 template <class C>
 int msm_plan_table(size_t n, int* c, int* nwin, bool batched = false);
@@ -487,6 +506,19 @@ int msm_table_device(Ctx* ctx, const void* d_table, const void* d_scalars, size_
 template <class C, int G>
 int msm_table_device_batch(Ctx* ctx, const void* d_table, const void* const* d_scalars, int batch, size_t n, bool scalars_mont, int c,
                            void* h_sums);
+// A precomputed table as the C ABI hands it out (ga_msm_table), and its two drivers (msm.hip.h): create plans, stages host bases, builds
+// the table into t->d_table (the caller owns t and frees both on failure) and synchronises; run is the MSM of k <= 16 scalar vectors
+// (host or device per flags) over windows [win_lo, win_hi) of the table (win_hi < 0 = all; a range needs k = 1): k Jac<F> images.
+struct MsmTable {
+    Ctx* ctx;
+    int curve, group, c, nwin;
+    size_t n;
+    void* d_table;
+    uint64_t bytes;
+};
+template <class C, int G> int msm_table_create_run(MsmTable* t, const void* bases, unsigned flags);
+template <class C, int G>
+int msm_table_run(MsmTable* t, const void* const* scalars, uint32_t k, unsigned flags, int win_lo, int win_hi, void* out_jacs);
 // slot 0/1 selects one of two scratch sets (the witness sort shared by several tables stays live in set 1 while set 0 is reused)
 // batch > 1: d_scalars is a host array of `batch` device pointers (msm_prepare); every table walked with *P then gives `batch` sums
 template <class C>
@@ -506,6 +538,11 @@ template <class C> int ntt_domain_fft(Domain* d, void* d_data, int direction, in
 template <class C> int ntt_domain_compute_h(Domain* d, void* d_a, void* d_b, void* d_c, uint64_t batch = 1);
 template <class C> int ntt_domain_h_chain(Domain* d, void* d_v, uint64_t batch = 1);                                        // v <- FFT_coset(iFFT(v))
 template <class C> int ntt_domain_h_combine(Domain* d, void* d_a, const void* d_b, const void* d_c, uint64_t batch = 1);    // a <- h (bit-reversed)
+// The drivers of ga_fft[_batch] and ga_compute_h[_batch] (ntt_domain.hip; the single calls are count = 1): `count` contiguous vectors,
+// host or device, transformed in place; a, b, c = [count][n_constraints] -> h_out = [count][cardinality], bit-reversed.
+int ntt_domain_fft_run(Domain* d, void* data, uint32_t count, int direction, int decimation, int on_coset, bool on_device);
+int ntt_domain_compute_h_run(Domain* d, const void* a, const void* b, const void* c, uint32_t count, uint64_t n_constraints, void* h_out,
+                             bool on_device);
 void ntt_domain_delete(Domain* d);
 // The NTT domain of the last proving key freed on a context stays with the context (like its scratch): a caller that re-pins its key
 // for every proof -- the Go package's default, PinToGPU = false -- gets it back instead of rebuilding 3 GiB of twiddle tables (11 ms
@@ -594,31 +631,14 @@ template <class C>
 int plonk_domain_quotient_pinned(PlonkFixed* fx, const PlonkQuotientArgs& args, uint64_t scan_threads, void* h_out) {
     return plonk_domain_quotient_pinned_batch<C>(fx, &args, 1, PlonkBatchKnobs{1, scan_threads}, h_out);
 }
-// d_quot (device, n elements: n - 1 quotient coefficients then a zero) and *value_out (host, Montgomery) = p(z) from d_poly (device, n
-// coefficients); n = 0 is the zero polynomial: the value 0 and no quotient.  Synchronises.
+// kzg.Open for `count` polynomials of n >= 1 coefficients (host or device per flags) over the SRS table t, in passes of at most
+// knobs.batch_max: the divisions of a pass are one launch chain, its quotients one batched table MSM.  ga_kzg_open is count = 1.
 template <class C>
-int kzg_domain_divide(Ctx* ctx, const void* d_poly, uint64_t n, const void* z_mont, void* d_quot, void* value_out, uint64_t scan_threads) {
-    if (n == 0) {
-        memset(value_out, 0, 32);
-        return GA_OK;
-    }
-    std::vector<uint32_t> stage;   // read by an upload that the synchronisation below completes
-    auto run = [&]() -> int {
-        void* d_value;
-        GA_CHECK(ctx->scratch_get("kzg_b_values", 32, &d_value));
-        GA_HIP_CHECK(hipMemsetAsync((char*)d_quot + (n - 1) * 32, 0, 32, ctx->stream));
-        GA_CHECK(kzg_domain_divide_batch<C>(ctx, &d_poly, n, 1, z_mont, d_quot, n, d_value, scan_threads, &stage));
-        GA_HIP_CHECK(hipMemcpyAsync(value_out, d_value, 32, hipMemcpyDeviceToHost, ctx->stream));
-        return GA_OK;
-    };
-    const int rc = run();
-    if (rc != GA_OK) {
-        hipStreamSynchronize(ctx->stream);
-        return rc;
-    }
-    GA_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return GA_OK;
-}
+int kzg_open_run(MsmTable* t, const void* const* polys, size_t n, uint32_t count, unsigned flags, const void* points, void* claimed_values_out,
+                 void* h_out, PlonkBatchKnobs knobs);
+// ga_fr_poly_evaluate: *value_out (host, Montgomery) = p(z) for n >= 1 coefficients, host or device; the quotient stays in scratch.
+// Synchronises.
+template <class C> int kzg_domain_divide(Ctx* ctx, const void* poly, uint64_t n, const void* z_mont, void* value_out, bool on_device, uint64_t scan_threads);
 
 // plonk.Verify for `count` proofs under one key (plonk_verify.hip.h).  The knobs are those of the calls it is made of, as the entry
 // point read them (abi.hip has the table).
@@ -654,7 +674,7 @@ template <class C, int G>
 int check_points_run(Ctx* ctx, const void* points, size_t n, unsigned flags, uint8_t* status, uint64_t* out4, int naive, uint64_t forced_chunk);
 template <class C, int G> int check_points_resident(Ctx* ctx, hipStream_t st, const void* d_points, uint64_t n, uint64_t base, int reset, int naive);
 template <class C, int G> int check_points_tally(Ctx* ctx, hipStream_t st, uint64_t* out4, int* first_status);
-int check_naive_knob();   // GA_CHECK_NAIVE, for ga_check_points and the key reader alike (abi.hip)
+int check_naive_knob();   // GA_CHECK_NAIVE, for ga_check_points and the key reader alike (ctx.hip)
 // sparse_sums.hip.h: a sparse Fr matrix applied to a vector of points
 template <class C, int G>
 int sparse_sums_run(Ctx* ctx, const void* points, size_t n_points, const uint64_t* row_start, size_t n_rows, const uint32_t* terms, const void* coeffs,
@@ -677,6 +697,7 @@ template <class C, int G> int util_gen_bases(Ctx* ctx, uint64_t seed, size_t n, 
 template <class C> int util_gen_scalars(Ctx* ctx, uint64_t seed, size_t n, void* d_scalars);
 template <class C> int util_fr_dot(Ctx* ctx, const void* d_a, const void* d_b, size_t n, void* h_out);
 template <class C> int util_fr_vec_mul(Ctx* ctx, const void* d_a, const void* d_b, size_t n, void* d_out);
+template <class C> int util_fr_vec_mul_run(Ctx* ctx, const void* a, const void* b, size_t n, void* out, bool on_device);   // ga_fr_vec_mul: host or device
 template <class C> int util_gather_fr(Ctx* ctx, void* d_dst, const void* d_src, const uint32_t* d_idx, size_t n);
 // the same for `count` vectors in one launch (dst / src: count vectors of dst_stride / src_stride elements); and the zero padding of
 // `count` contiguous n-element vectors: elements [from, n) of each <- 0 on `st`

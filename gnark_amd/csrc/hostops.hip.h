@@ -50,6 +50,29 @@ XYZZ<F> host_horner(const XYZZ<F>* W, int nwin, int c) {
     return acc;
 }
 
+// the host group helpers of the C ABI (ga_jac_add, ga_jac_to_affine, ga_jac_scalar_mul / ga_generator_mul, ga_msm_combine_windows):
+// Jac<F> images in and out, k = 8 canonical words
+template <class F>
+inline void host_jac_add(const void* a, const void* b, void* out) {
+    host_store_jac<F>(out, add(host_load_jac<F>(a), host_load_jac<F>(b)));
+}
+template <class F>
+inline void host_jac_to_affine(const void* a, void* out) {
+    host_store_affine<F>(out, host_load_jac<F>(a));
+}
+template <class F>
+inline void host_jac_scalar_mul(const XYZZ<F>& a, const void* k, void* out) {
+    uint32_t kw[8];
+    memcpy(kw, k, 32);
+    host_store_jac<F>(out, scalar_mul(a, kw, 8));
+}
+template <class F>
+inline void host_jac_horner(const void* windows, int nwin, int c, void* out) {
+    std::vector<XYZZ<F>> W(nwin);
+    for (int w = 0; w < nwin; w++) W[w] = host_load_jac<F>(reinterpret_cast<const char*>(windows) + (size_t)w * sizeof(Jac<F>));
+    host_store_jac<F>(out, host_horner(W.data(), nwin, c));
+}
+
 // contiguous share `index` of `count` of nwin windows (same split as multigpu.shard_range)
 inline void window_share(int nwin, uint32_t index, uint32_t count, int* lo, int* hi) {
     const int base = nwin / (int)count, rem = nwin % (int)count, k = (int)index;
@@ -57,38 +80,17 @@ inline void window_share(int nwin, uint32_t index, uint32_t count, int* lo, int*
     *hi = *lo + base + (k < rem ? 1 : 0);
 }
 
-// MSM on device + Horner on host -> XYZZ.  Long vectors are split along the point axis (the (point, window) pair space of one
-// launch is 2^31): the analogue of msmChunkedG1/G2, icicle.go:362-467.  (win_index, win_count) restrict the accumulation to one
-// share of the windows (multi-GPU partition A): the other windows count as zero in the Horner sum, so shares add up.
+// An MSM over raw bases on the device -> XYZZ: msm_run (msm.hip.h) over the planned window width and share (win_index, win_count) of
+// the windows (multi-GPU partition A): the other windows count as zero in the Horner sum, so shares add up.
 template <class C, int G>
 int host_msm(Ctx* ctx, const void* d_bases, const void* d_scalars, size_t n, bool mont,
              XYZZ<typename GroupField<C, G>::F>* out, uint32_t win_index = 0, uint32_t win_count = 1) {
-    typedef typename GroupField<C, G>::F F;
-    int c, nwin;
+    int c, nwin, lo, hi;
     GA_CHECK(msm_plan<C>(G, n, &c, &nwin));
-    int lo = 0, hi = nwin;
     window_share(nwin, win_index, win_count ? win_count : 1, &lo, &hi);
-    if (hi > lo && n > 0 && n <= ((size_t)1 << 31) / (size_t)(hi - lo) - 1) {   // one launch sequence: Horner folded into the reduction's host tail
-        XYZZ<F> sum;
-        GA_CHECK((msm_windows_device<C, G>(ctx, d_bases, d_scalars, n, mont, c, lo, hi, &sum, true)));
-        for (int k = 0; k < c * lo; k++) sum = dbl(sum);
-        *out = sum;
-        return GA_OK;
-    }
-    std::vector<XYZZ<F>> W(nwin, xyzz_inf<F>());
-    if (hi > lo && n > 0) {
-        const size_t max_chunk = ((size_t)1 << 31) / (size_t)(hi - lo) - 1;
-        std::vector<XYZZ<F>> part(hi - lo);
-        for (size_t done = 0; done < n;) {
-            const size_t cn = n - done < max_chunk ? n - done : max_chunk;
-            GA_CHECK((msm_windows_device<C, G>(ctx, (const char*)d_bases + done * sizeof(Affine<F>), (const char*)d_scalars + done * 32, cn, mont, c,
-                                              lo, hi, part.data())));
-            for (int w = lo; w < hi; w++) W[w] = add(W[w], part[w - lo]);
-            done += cn;
-        }
-    }
-    *out = host_horner(W.data(), nwin, c);
-    return GA_OK;
+    *out = xyzz_inf<typename GroupField<C, G>::F>();
+    if (hi <= lo) return GA_OK;   // an empty share
+    return msm_run<C, G>(ctx, d_bases, d_scalars, n, mont, c, lo, hi, (size_t)ctx->tun.msm_max_chunk, out, false);
 }
 
 }  // namespace ga

@@ -38,8 +38,11 @@
 //                          host anyway.
 // msm_lazy.hip.h     the general-point arithmetic in the lazy representation that 5, 6 and the table build share.
 //
-// This header: msm_accumulate_reduce and the per-(curve, group) entry points that the msm_<curve>_<group>.hip units instantiate.
+// This header: msm_accumulate_reduce, the per-(curve, group) launch sequences and -- at the end -- the drivers of the MSM calls of the C
+// ABI (msm_run, msm_abi_run, msm_table_create_run, msm_table_run), all instantiated by the msm_<curve>_<group>.hip units.
 #pragma once
+#include "hostops.hip.h"
+#include "vec_call.hip.h"
 #include "msm_sort.hip.h"
 #include "msm_tasks.hip.h"
 #include "msm_bucket.hip.h"
@@ -177,8 +180,104 @@ int msm_table_build(Ctx* ctx, const void* d_bases, size_t n, int c, void* d_tabl
     return GA_OK;
 }
 
+// ---- the drivers (declared in common.hip.h) -----------------------------------------------------------------------------------------
+template <class C, int G>
+int msm_run(Ctx* ctx, const void* d_bases, const void* d_scalars, size_t n, bool scalars_mont, int c, int win_lo, int win_hi, size_t max_chunk,
+            void* h_out, bool want_windows) {
+    typedef typename GroupField<C, G>::F F;
+    XYZZ<F>* out = reinterpret_cast<XYZZ<F>*>(h_out);
+    const size_t nw = (size_t)(win_hi - win_lo), pair_cap = ((size_t)1 << 31) / nw - 1;   // (never reached up to 2^26 points)
+    if (max_chunk == 0 || max_chunk > pair_cap) max_chunk = pair_cap;
+    XYZZ<F> sum;
+    if (!want_windows && n <= max_chunk) {   // the usual case: one launch sequence, the Horner step shares the window reduction's host chain
+        GA_CHECK((msm_windows_device<C, G>(ctx, d_bases, d_scalars, n, scalars_mont, c, win_lo, win_hi, &sum, true)));
+    } else {
+        std::vector<XYZZ<F>> W(nw, xyzz_inf<F>()), part(nw);
+        for (size_t done = 0; done < n;) {
+            const size_t cn = n - done < max_chunk ? n - done : max_chunk;
+            GA_CHECK((msm_windows_device<C, G>(ctx, (const char*)d_bases + done * sizeof(Affine<F>), (const char*)d_scalars + done * 32, cn,
+                                              scalars_mont, c, win_lo, win_hi, part.data())));
+            for (size_t w = 0; w < nw; w++) W[w] = add(W[w], part[w]);
+            done += cn;
+        }
+        if (want_windows) {
+            for (size_t w = 0; w < nw; w++) out[w] = W[w];
+            return GA_OK;
+        }
+        sum = host_horner(W.data(), (int)nw, c);
+    }
+    for (int k = 0; k < c * win_lo; k++) sum = dbl(sum);   // the windows below the range count as zero
+    *out = sum;
+    return GA_OK;
+}
+
+template <class C, int G>
+int msm_abi_run(Ctx* ctx, const void* bases, const void* scalars, size_t n, unsigned flags, int win_lo, int win_hi, void* out, int* c_out,
+                int* nwin_out, bool want_windows) {
+    typedef typename GroupField<C, G>::F F;
+    int c, nwin;
+    GA_CHECK(msm_plan<C>(G, n, &c, &nwin));
+    if (c_out) *c_out = c;
+    if (nwin_out) *nwin_out = nwin;
+    if (win_hi < 0) win_hi = nwin;
+    if (win_lo < 0 || win_hi > nwin || win_lo >= win_hi) {
+        set_error("msm: window range [%d,%d) outside [0,%d)", win_lo, win_hi, nwin);
+        return GA_ERR_INVALID;
+    }
+    Staged sb{ctx}, ss{ctx};
+    GA_CHECK(sb.stage(bases, n * sizeof(Affine<F>), flags & GA_BASES_ON_DEVICE));
+    GA_CHECK(ss.stage(scalars, n * 32, flags & GA_SCALARS_ON_DEVICE));
+    std::vector<XYZZ<F>> sums(want_windows ? win_hi - win_lo : 1);
+    GA_CHECK((msm_run<C, G>(ctx, sb.dev, ss.dev, n, (flags & GA_SCALARS_MONTGOMERY) != 0, c, win_lo, win_hi, (size_t)ctx->tun.msm_max_chunk,
+                            sums.data(), want_windows)));
+    for (size_t w = 0; w < sums.size(); w++) host_store_jac<F>((char*)out + w * sizeof(Jac<F>), sums[w]);
+    return GA_OK;
+}
+
+template <class C, int G>
+int msm_table_create_run(MsmTable* t, const void* bases, unsigned flags) {
+    typedef typename GroupField<C, G>::F F;
+    Ctx* ctx = t->ctx;
+    GA_CHECK(msm_plan_table<C>(t->n, &t->c, &t->nwin, (flags & GA_TABLE_BATCHED) != 0));
+    t->bytes = (uint64_t)t->nwin * t->n * msm_table_point_bytes<C, G>();
+    Staged sb{ctx};
+    GA_CHECK(sb.stage(bases, t->n * sizeof(Affine<F>), flags & GA_BASES_ON_DEVICE));
+    if (device_malloc(&t->d_table, t->bytes) != hipSuccess) {
+        set_error("%s: device_malloc(%llu) failed", current_entry(), (unsigned long long)t->bytes);
+        return GA_ERR_NOMEM;
+    }
+    GA_CHECK((msm_table_build<C, G>(ctx, sb.dev, t->n, t->c, t->d_table)));
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) {
+        set_error("%s: table kernel failed", current_entry());
+        return GA_ERR_HIP;
+    }
+    return GA_OK;
+}
+
+template <class C, int G>
+int msm_table_run(MsmTable* t, const void* const* scalars, uint32_t k, unsigned flags, int win_lo, int win_hi, void* out_jacs) {
+    typedef typename GroupField<C, G>::F F;
+    Ctx* ctx = t->ctx;
+    const bool mont = (flags & GA_SCALARS_MONTGOMERY) != 0;
+    std::vector<Staged> st(k, Staged{ctx});   // (copies of an empty one; none is copied once it owns a buffer)
+    std::vector<const void*> dev(k);
+    for (uint32_t j = 0; j < k; j++) {
+        GA_CHECK(st[j].stage(scalars[j], t->n * 32, flags & GA_SCALARS_ON_DEVICE));
+        dev[j] = st[j].dev;
+    }
+    std::vector<XYZZ<F>> sums(k);
+    if (k == 1) GA_CHECK((msm_table_device<C, G>(ctx, t->d_table, dev[0], t->n, mont, t->c, sums.data(), win_lo, win_hi)));
+    else GA_CHECK((msm_table_device_batch<C, G>(ctx, t->d_table, dev.data(), (int)k, t->n, mont, t->c, sums.data())));
+    for (uint32_t j = 0; j < k; j++) host_store_jac<F>((char*)out_jacs + j * sizeof(Jac<F>), sums[j]);
+    return GA_OK;
+}
+
 // what msm_<curve>_g<k>.hip instantiates; the G1 unit of a curve has the group-independent half as well
 #define GA_INSTANTIATE_MSM(C, G)                                                                                        \
+    template int msm_run<C, G>(Ctx*, const void*, const void*, size_t, bool, int, int, int, size_t, void*, bool);       \
+    template int msm_abi_run<C, G>(Ctx*, const void*, const void*, size_t, unsigned, int, int, void*, int*, int*, bool); \
+    template int msm_table_create_run<C, G>(MsmTable*, const void*, unsigned);                                          \
+    template int msm_table_run<C, G>(MsmTable*, const void* const*, uint32_t, unsigned, int, int, void*);               \
     template int msm_windows_device<C, G>(Ctx*, const void*, const void*, size_t, bool, int, int, int, void*, bool);    \
     template int msm_table_device<C, G>(Ctx*, const void*, const void*, size_t, bool, int, void*, int, int);            \
     template int msm_table_device_reuse<C, G>(Ctx*, const void*, const MsmPrepared&, void*);                            \

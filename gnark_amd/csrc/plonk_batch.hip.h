@@ -1,14 +1,16 @@
 // The three PLONK-specific drivers, each for `count` proofs of one circuit per device pass: the grand product (ga_plonk_build_z,
 // ga_plonk_build_z_batch), the quotient over a pinned key (ga_plonk_quotient_pinned, ga_plonk_quotient_pinned_batch) and the
 // division of kzg.Open (ga_kzg_open, ga_fr_poly_evaluate, ga_kzg_open_batch).  The single calls are count = 1 (the wrappers of
-// common.hip.h): there is no second implementation.  The proof is the grid's y dimension (or a segment of a flat index), the per-proof
+// common.hip.h, and count = 1 of kzg_open_run at the end of this file): there is no second implementation.  The proof is the grid's y dimension (or a segment of a flat index), the per-proof
 // challenges come from a device array uploaded once per pass, every power table is built on the device, the scans are segmented per
 // proof, and a pass of up to PLONK_BATCH_LIMIT proofs of the grand product or the quotient ends in ONE synchronisation (a division
 // pass has none: its caller synchronises).  The kernels are those of plonk.hip.h.
 // Every stored field element is fully reduced, so row j of every output is the same bit for bit however the proofs are split into
 // passes and whatever the association order of the scans.
 #pragma once
+#include "hostops.hip.h"    // host_store_jac
 #include "plonk.hip.h"
+#include "vec_call.hip.h"   // Staged, StreamDrain
 
 namespace ga {
 
@@ -274,7 +276,71 @@ int kzg_domain_divide_batch(Ctx* ctx, const void* const* d_polys, uint64_t n, ui
                             void* d_values, uint64_t scan_threads, std::vector<uint32_t>* stage) {
     return kzg_divide_by_linear<typename C::FrP>(ctx, d_polys, n, count, points, (uint32_t*)d_quot, quot_stride, (uint32_t*)d_values, scan_threads, *stage);
 }
-// what plonk_<curve>.hip instantiates: these three and the four of plonk.hip.h
+// ga_fr_poly_evaluate: the division alone, for its value (the quotient lands in the batch path's quotient scratch and stays there)
+template <class C>
+int kzg_domain_divide(Ctx* ctx, const void* poly, uint64_t n, const void* z_mont, void* value_out, bool on_device, uint64_t scan_threads) {
+    Staged sp{ctx};
+    GA_CHECK(sp.stage(poly, n * 32, on_device));
+    char *q, *d_value;
+    GA_CHECK(ctx->scratch_get("kzg_b_quotient", n * 32, (void**)&q));
+    GA_CHECK(ctx->scratch_get("kzg_b_values", 32, (void**)&d_value));
+    std::vector<uint32_t> stage;   // the division's small upload: outlives the drain
+    StreamDrain drain{ctx->stream};
+    GA_HIP_CHECK(hipMemsetAsync(q + (n - 1) * 32, 0, 32, ctx->stream));
+    GA_CHECK(kzg_domain_divide_batch<C>(ctx, &sp.dev, n, 1, z_mont, q, n, d_value, scan_threads, &stage));
+    GA_HIP_CHECK(hipMemcpyAsync(value_out, d_value, 32, hipMemcpyDeviceToHost, ctx->stream));
+    GA_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return GA_OK;
+}
+
+// kzg.Open for `count` polynomials of one length over one SRS: per pass of at most knobs.batch_max items the divisions by (X - z_j)
+// are one launch chain and the quotients one batched table MSM, whose synchronisation (it returns its sums) ends the pass
+template <class C>
+int kzg_open_run(MsmTable* t, const void* const* polys, size_t n, uint32_t count, unsigned flags, const void* points, void* claimed_values_out,
+                 void* h_out, PlonkBatchKnobs knobs) {
+    typedef typename GroupField<C, GA_G1>::F F;
+    Ctx* c = t->ctx;
+    uint32_t batch_max = knobs.batch_max;
+    while (batch_max > 1 && (uint64_t)batch_max * t->nwin * t->n >= (1ull << 31)) batch_max--;   // the pair index space of one batched MSM
+    if ((uint64_t)batch_max * t->nwin * t->n >= (1ull << 31)) {
+        set_error("%s: %d windows x %zu points exceed the 2^31 pair index space of the batched table MSM", current_entry(), t->nwin, (size_t)t->n);
+        return GA_ERR_INVALID;
+    }
+    const bool on_device = (flags & GA_SCALARS_ON_DEVICE) != 0;
+    const size_t qn = n > t->n ? n : t->n;   // a row of quotients: the table's n scalars (zero beyond the n - 1 coefficients)
+    char *in = nullptr, *q = nullptr, *vals = nullptr;
+    auto reserve = [&](uint32_t cnt) -> int {
+        GA_CHECK(c->scratch_get("kzg_b_in", on_device ? 256 : (size_t)cnt * n * 32, (void**)&in));
+        GA_CHECK(c->scratch_get("kzg_b_quotient", (size_t)cnt * qn * 32, (void**)&q));
+        GA_CHECK(c->scratch_get("kzg_b_values", (size_t)cnt * 32, (void**)&vals));
+        return GA_OK;
+    };
+    std::vector<XYZZ<F>> sums(PLONK_BATCH_LIMIT);
+    std::vector<uint32_t> stage;   // the division's small upload; read before the MSM of its pass has returned
+    StreamDrain drain{c->stream};  // `stage` and the caller's polynomials: no copy from them is still queued on any way out
+    // (the division and the MSM get their own scratch inside the pass: plonk_batch_chunks halves a pass that fails there as well)
+    auto pass = [&](uint32_t first, uint32_t cnt) -> int {
+        const void *dpoly[PLONK_BATCH_LIMIT], *dquot[PLONK_BATCH_LIMIT];
+        for (uint32_t j = 0; j < cnt; j++) {
+            dpoly[j] = polys[first + j];
+            if (!on_device) {
+                GA_HIP_CHECK(hipMemcpyAsync(in + (size_t)j * n * 32, polys[first + j], n * 32, hipMemcpyHostToDevice, c->stream));
+                dpoly[j] = in + (size_t)j * n * 32;
+            }
+            dquot[j] = q + (size_t)j * qn * 32;
+        }
+        GA_HIP_CHECK(hipMemsetAsync(q, 0, (size_t)cnt * qn * 32, c->stream));
+        GA_CHECK(kzg_domain_divide_batch<C>(c, dpoly, n, cnt, (const char*)points + (size_t)first * 32, q, qn, vals, knobs.scan_threads, &stage));
+        // the claimed values leave in one copy ahead of the MSM, whose synchronisation completes it
+        GA_HIP_CHECK(hipMemcpyAsync((char*)claimed_values_out + (size_t)first * 32, vals, (size_t)cnt * 32, hipMemcpyDeviceToHost, c->stream));
+        GA_CHECK((msm_table_device_batch<C, GA_G1>(c, t->d_table, dquot, (int)cnt, t->n, true, t->c, sums.data())));
+        for (uint32_t j = 0; j < cnt; j++) host_store_jac<F>((char*)h_out + (size_t)(first + j) * sizeof(Jac<F>), sums[j]);
+        return GA_OK;
+    };
+    return plonk_batch_chunks(count, batch_max, reserve, pass);
+}
+
+// what plonk_<curve>.hip instantiates: these five and the four of plonk.hip.h
 #define GA_INSTANTIATE_PLONK(C)                                                                                                          \
     template int plonk_domain_quotient<C>(Domain*, Domain*, const PlonkQuotientArgs&, void*);                                            \
     template int plonk_domain_fixed_create<C>(Domain*, Domain*, const PlonkQuotientArgs&, PlonkFixed**);                                 \
@@ -284,6 +350,8 @@ int kzg_domain_divide_batch(Ctx* ctx, const void* const* d_polys, uint64_t n, ui
                                                uint32_t, PlonkBatchKnobs, bool, void*);                                                  \
     template int plonk_domain_quotient_pinned_batch<C>(PlonkFixed*, const PlonkQuotientArgs*, uint32_t, PlonkBatchKnobs, void*);         \
     template int kzg_domain_divide_batch<C>(Ctx*, const void* const*, uint64_t, uint32_t, const void*, void*, uint64_t, void*, uint64_t, \
-                                            std::vector<uint32_t>*);
+                                            std::vector<uint32_t>*);                                                                     \
+    template int kzg_domain_divide<C>(Ctx*, const void*, uint64_t, const void*, void*, bool, uint64_t);                                  \
+    template int kzg_open_run<C>(MsmTable*, const void* const*, size_t, uint32_t, unsigned, const void*, void*, void*, PlonkBatchKnobs);
 
 }  // namespace ga

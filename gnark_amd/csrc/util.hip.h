@@ -2,6 +2,7 @@
 // Groth16 wire filtering (prove.go:147-168) need around the MSM/NTT kernels; plus the window-size planner.
 #pragma once
 #include "common.hip.h"
+#include "vec_call.hip.h"
 
 namespace ga {
 
@@ -158,6 +159,21 @@ int util_fr_vec_mul(Ctx* ctx, const void* d_a, const void* d_b, size_t n, void* 
     return GA_OK;
 }
 
+// ga_fr_vec_mul: out[i] = a[i] b[i], the three of them on the host or on the device
+template <class C>
+int util_fr_vec_mul_run(Ctx* ctx, const void* a, const void* b, size_t n, void* out, bool on_device) {
+    Staged sa{ctx}, sb{ctx};
+    GA_CHECK(sa.stage(a, n * 32, on_device));
+    GA_CHECK(sb.stage(b, n * 32, on_device));
+    void* d_out = out;
+    if (!on_device) GA_CHECK(ctx->scratch_get("fr_vec_out", n * 32, &d_out));
+    StreamDrain drain{ctx->stream};
+    GA_CHECK(util_fr_vec_mul<C>(ctx, sa.dev, sb.dev, n, d_out));
+    if (!on_device) GA_HIP_CHECK(hipMemcpyAsync(out, d_out, n * 32, hipMemcpyDeviceToHost, ctx->stream));
+    GA_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return GA_OK;
+}
+
 template <class C>
 int util_gather_fr(Ctx* ctx, void* d_dst, const void* d_src, const uint32_t* d_idx, size_t n) {
     if (n == 0) return GA_OK;
@@ -261,6 +277,7 @@ int msm_plan_table(size_t n, int* c_out, int* nwin_out, bool batched) {
     template int util_gen_scalars<C>(Ctx*, uint64_t, size_t, void*);                                                            \
     template int util_fr_dot<C>(Ctx*, const void*, const void*, size_t, void*);                                                 \
     template int util_fr_vec_mul<C>(Ctx*, const void*, const void*, size_t, void*);                                             \
+    template int util_fr_vec_mul_run<C>(Ctx*, const void*, const void*, size_t, void*, bool);                                   \
     template int util_gather_fr<C>(Ctx*, void*, const void*, const uint32_t*, size_t);                                          \
     template int util_gather_fr_batch<C>(Ctx*, void*, const void*, const uint32_t*, size_t, uint32_t, uint64_t, uint64_t);      \
     template int util_pad_fr_batch<C>(Ctx*, void*, uint64_t, uint64_t, uint32_t, hipStream_t);                                  \

@@ -17,6 +17,32 @@ struct StreamDrain {
     ~StreamDrain() { hipStreamSynchronize(st); }
 };
 
+// A whole operand brought to the device when it is a host pointer, for the calls that do not walk their input in chunks (the MSMs,
+// the table MSMs, ga_fr_poly_evaluate, ga_fr_vec_mul): its own allocation, released at scope exit, and complete when stage() returns.
+struct Staged {
+    Ctx* ctx;
+    const void* dev = nullptr;
+    void* owned = nullptr;
+    int stage(const void* p, size_t bytes, bool on_device) {
+        if (on_device || bytes == 0) {
+            dev = p;
+            return GA_OK;
+        }
+        hipError_t e = device_malloc(&owned, bytes);
+        if (e != hipSuccess) {
+            set_error("device_malloc(%zu) failed: %s", bytes, device_malloc_error(e));
+            return GA_ERR_NOMEM;
+        }
+        GA_HIP_CHECK(hipMemcpyAsync(owned, p, bytes, hipMemcpyHostToDevice, ctx->work_stream()));
+        GA_HIP_CHECK(hipStreamSynchronize(ctx->work_stream()));   // host memory must not be referenced after return
+        dev = owned;
+        return GA_OK;
+    }
+    ~Staged() {
+        if (owned) hipFree(owned);
+    }
+};
+
 // elements per pass: the knob (0 = the call's default), at most VEC_MAX_CHUNK, at most n
 inline uint64_t clamp_chunk(uint64_t forced, uint64_t dflt, uint64_t n) {
     uint64_t chunk = forced ? forced : dflt;
