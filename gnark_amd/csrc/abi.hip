@@ -1,5 +1,5 @@
 // extern "C" surface of libgnark_amd.so (include/gnark_amd.h): context, buffers, MSM, NTT, group helpers,
-// profiling.  Groth16 lives in groth16.hip (the prover and its entry points; keys in g16_key.hip.h, key files and proof bytes in
+// profiling.  The Groth16 entry points are g16_abi.hip, under the same rule (their drivers: groth16.hip, g16_key.hip.h,
 // g16_io.hip.h).  Every entry point selects the context's device itself and takes the context mutex (one proof at a time per device,
 // as icicle.go:821-823).  An entry point checks its arguments, reads its knobs, takes the lock and makes ONE dispatch into the driver
 // of its call family, which lives beside that family's kernels; the runtime under all of them is ctx.hip.
@@ -77,18 +77,9 @@ static bool abi_permutation_ok(const int64_t* permutation, uint64_t n3) {
     return true;
 }
 
-// the entry point's own test of its pointers came out `bad`
-static bool abi_null_argument(bool bad) {
-    if (bad) set_error("%s: null argument", current_entry());
-    return bad;
-}
-
 // the arguments the single and the batched form of a call share: one check, reported under the name of the entry point that was called
 static bool abi_kzg_open_ok(const MsmTable* t, const void* polys, size_t n, const void* points, const void* values_out, const void* h_out) {
-    if (!t || !polys || !points || !values_out || !h_out || n == 0) {
-        set_error("%s: null argument or empty polynomial", current_entry());
-        return false;
-    }
+    if (abi_bad_argument(!t || !polys || !points || !values_out || !h_out || n == 0, "null argument or empty polynomial")) return false;
     if (t->group != GA_G1 || n - 1 > t->n) {
         set_error("%s: the SRS table must be G1 and hold at least len(p) - 1 = %zu points (it has %zu)", current_entry(), n - 1, t->n);
         return false;
@@ -490,10 +481,7 @@ int ga_fr_compact_nonzero(ga_ctx* h, int curve, const void* v, size_t n, unsigne
     Ctx* c = reinterpret_cast<Ctx*>(h);
     constexpr Scope S = Scope::FULL;
     GA_CHECK(dispatch_check(S, curve, GA_NO_GROUP));
-    if (!count) {
-        set_error("ga_fr_compact_nonzero: null count");
-        return GA_ERR_INVALID;
-    }
+    if (abi_bad_argument(!count, "null count")) return GA_ERR_INVALID;
     if ((uint64_t)n >= (1ull << 31)) {
         set_error("ga_fr_compact_nonzero: n = %zu, at most 2^31 - 1", n);
         return GA_ERR_INVALID;
@@ -526,10 +514,7 @@ int ga_msm_plan(int curve, int group, size_t n, int* window_bits, int* num_windo
 
 int ga_msm_combine_windows(int curve, int group, const void* windows, int num_windows, int window_bits, void* out_jac) try {
     GA_ABI_ENTRY();
-    if (!windows || !out_jac || num_windows <= 0 || window_bits <= 0) {
-        set_error("ga_msm_combine_windows: bad argument");
-        return GA_ERR_INVALID;
-    }
+    if (abi_bad_argument(!windows || !out_jac || num_windows <= 0 || window_bits <= 0, "bad argument")) return GA_ERR_INVALID;
     return GA_DISPATCH(Scope::G1_FR, curve, group, (host_jac_horner<typename GroupField<C, G>::F>(windows, num_windows, window_bits, out_jac)));
 } GA_ABI_CATCH
 
@@ -537,10 +522,7 @@ int ga_msm_combine_windows(int curve, int group, const void* windows, int num_wi
 int ga_msm_table_create(ga_ctx* h, int curve, int group, const void* bases, size_t n, unsigned flags, ga_msm_table** out) try {
     GA_ABI_ENTRY();
     Ctx* c = reinterpret_cast<Ctx*>(h);
-    if (!c || !out || !bases || n == 0) {
-        set_error("ga_msm_table_create: bad argument");
-        return GA_ERR_INVALID;
-    }
+    if (abi_bad_argument(!c || !out || !bases || n == 0, "bad argument")) return GA_ERR_INVALID;
     Lock l(c);
     struct Owner {   // (the table object and its device memory are released on every way out but the successful one)
         MsmTable* t;
@@ -698,10 +680,7 @@ int ga_jac_scalar_mul(int curve, int group, const void* a, const void* k, void* 
 int ga_domain_create(ga_ctx* h, int curve, uint64_t cardinality, ga_domain** out) try {
     GA_ABI_ENTRY();
     Ctx* c = reinterpret_cast<Ctx*>(h);
-    if (!c || !out || cardinality == 0) {
-        set_error("ga_domain_create: bad argument");
-        return GA_ERR_INVALID;
-    }
+    if (abi_bad_argument(!c || !out || cardinality == 0, "bad argument")) return GA_ERR_INVALID;
     Lock l(c);
     Domain* d = nullptr;
     GA_CHECK(GA_DISPATCH(Scope::G1_FR, curve, GA_NO_GROUP, return ntt_domain_new<C>(c, cardinality, &d)));
@@ -925,10 +904,7 @@ int ga_plonk_verify(ga_plonk_vk* p, const ga_plonk_proofs* proofs, uint32_t coun
         set_error("ga_plonk_verify: null argument%s", out2 ? "" : " (out2)");
         return GA_ERR_INVALID;
     }
-    if ((flags & GA_PLONK_VERIFY_COMBINED) && !weights) {
-        set_error("ga_plonk_verify: GA_PLONK_VERIFY_COMBINED without weights");
-        return GA_ERR_INVALID;
-    }
+    if (abi_bad_argument((flags & GA_PLONK_VERIFY_COMBINED) && !weights, "GA_PLONK_VERIFY_COMBINED without weights")) return GA_ERR_INVALID;
     if (count > PLONK_VERIFY_MAX_COUNT) {
         set_error("ga_plonk_verify: count = %u above 2^20", count);
         return GA_ERR_INVALID;
@@ -1063,10 +1039,7 @@ int ga_generator_mul(int curve, int group, const void* k, void* out_jac) try {
 int ga_clock_probe(ga_ctx* h, uint32_t micros, double* mhz_out) try {
     GA_ABI_ENTRY();
     Ctx* c = reinterpret_cast<Ctx*>(h);
-    if (!c || !mhz_out || micros == 0) {
-        set_error("ga_clock_probe: bad argument");
-        return GA_ERR_INVALID;
-    }
+    if (abi_bad_argument(!c || !mhz_out || micros == 0, "bad argument")) return GA_ERR_INVALID;
     return util_clock_probe(c, micros, mhz_out);   // (no context lock: it is meant to run BESIDE whatever holds it)
 } GA_ABI_CATCH
 

@@ -69,6 +69,9 @@ struct EntryScope {
     ~EntryScope();
 };
 const char* current_entry();         // the innermost entry point of the calling thread ("" outside the library)
+// the argument checks of the entry points (abi.hip, g16_abi.hip) and of their drivers: the test came out `bad` -> "<entry point>: <what>"
+bool abi_bad_argument(bool bad, const char* what);
+inline bool abi_null_argument(bool bad) { return abi_bad_argument(bad, "null argument"); }
 #define GA_ABI_ENTRY() ::ga::EntryScope _ga_entry_scope(__func__)
 #define GA_ABI_CATCH \
     catch (...) { return ::ga::abi_exception_code(__func__); }

@@ -38,6 +38,10 @@ static thread_local const char* g_entry = "";
 EntryScope::EntryScope(const char* name) : prev(g_entry) { g_entry = name; }
 EntryScope::~EntryScope() { g_entry = prev; }
 const char* current_entry() { return g_entry; }
+bool abi_bad_argument(bool bad, const char* what) {
+    if (bad) set_error("%s: %s", g_entry, what);
+    return bad;
+}
 
 // ---- which (curve, group) pairs are built, and the answer for one that is not (common.hip.h: dispatch) ----------------------------
 // what the two functions below need of a curve id at run time, read from the tags of GA_CURVES; name == nullptr: no such curve

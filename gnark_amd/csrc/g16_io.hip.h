@@ -2,7 +2,8 @@
 //   ProvingKey.ReadFrom / UnsafeReadFrom / ReadDump    a key file, decoded on the device into the staged builder (g16_key.hip.h)
 //   ProvingKey.WriteTo / WriteRawTo / WriteDump        the host description of a key (ga_g16_key) -> key-file bytes
 //   Proof.WriteTo / WriteRawTo / ReadFrom              proof bytes; G1Affine.Marshal (the BSB22 commitment hash input)
-// The formats and the point codec (point_encode / point_decode, host and device) are in keyio.hip.h; the entry points in groth16.hip.
+// The formats and the point codec (point_encode / point_decode, host and device) are in keyio.hip.h; the drivers of the entry points
+// (g16.hip.h: g16_pk_read_run, g16_key_write_run, g16_marshal_run, ...) are at the end of this file.
 #pragma once
 #include <string>
 #include <vector>
@@ -250,10 +251,7 @@ static int pk_read(Ctx* ctx, ByteSource& src, int32_t precompute, uint32_t shard
     st.curve = C::ID;
     st.shard_index = shard_index;
     st.shard_count = shard_count ? shard_count : 1;
-    if (st.shard_index >= st.shard_count) {
-        set_error("proving key: shard_index %u >= shard_count %u", st.shard_index, st.shard_count);
-        return GA_ERR_INVALID;
-    }
+    GA_CHECK(check_shard_index(st.shard_index, st.shard_count));
     Staging sg;
     GA_CHECK(sg.init());
     const bool dump = source_is_dump(src);
@@ -480,9 +478,7 @@ static int proof_unmarshal(const uint8_t* data, size_t len, void* proof_out, voi
                            uint32_t* n_commitments, void* pok_out, size_t* consumed) {
     typedef Fe<typename C::FpP> F1;
     typedef Fe2<typename C::FpP> F2;
-    ByteSource src;
-    src.mem = data;
-    src.mem_len = len;
+    ByteSource src{data, len};
     std::vector<uint8_t> img;
     int mode = -1;
     char* o = reinterpret_cast<char*>(proof_out);
@@ -510,8 +506,7 @@ static int proof_unmarshal(const uint8_t* data, size_t len, void* proof_out, voi
 }
 // Proof.WriteTo / WriteRawTo (marshal.go:25-58): Ar | Bs | Krs | u32 BE n | n commitments | CommitmentPok, all compressed or all raw
 template <class C>
-static int marshal(const void* proof, const void* commitments, uint32_t ncom, const void* pok, uint8_t* out, size_t cap, size_t* len,
-                   bool raw = false) {
+static int marshal(const void* proof, const void* commitments, uint32_t ncom, const void* pok, uint8_t* out, size_t cap, size_t* len, bool raw) {
     typedef Fe<typename C::FpP> F1;
     typedef Fe2<typename C::FpP> F2;
     const size_t nb = C::FpP::N * 4;
@@ -538,20 +533,53 @@ static int marshal(const void* proof, const void* commitments, uint32_t ncom, co
     return GA_OK;
 }
 
-// ga_g16_pk_read_mem / _fd and their _checked forms: a key file from either source
-static int pk_read_any(ga_ctx* h, int curve, ByteSource& src, int32_t precompute, uint32_t shard_index, uint32_t shard_count,
-                       const uint64_t* k_remove, uint64_t len_k_remove, ga_g16_pk** out, uint64_t* bytes_read, bool checked = false) {
-    Ctx* ctx = reinterpret_cast<Ctx*>(h);
-    if (!ctx || !out || (len_k_remove && !k_remove)) {
-        set_error("ga_g16_pk_read: null argument");
-        return GA_ERR_INVALID;
-    }
+// ---- the drivers of the entry points (g16.hip.h) -----------------------------------------------------------------------------------
+int g16_pk_read_run(Ctx* ctx, int curve, const uint8_t* data, size_t len, int fd, int32_t precompute, uint32_t shard_index, uint32_t shard_count,
+                    const uint64_t* k_remove, uint64_t len_k_remove, G16Pk** out, uint64_t* bytes_read, bool checked) {
+    ByteSource src{data, len, 0, fd};   // (the entry point passes fd = -1 with data, data = null with a descriptor)
     CtxLock g(ctx);
     G16Pk* pk = nullptr;
     GA_CHECK(GA_DISPATCH(Scope::FULL, curve, GA_NO_GROUP, return pk_read<C>(ctx, src, precompute, shard_index, shard_count, k_remove, len_k_remove, &pk, checked)));
-    *out = reinterpret_cast<ga_g16_pk*>(pk);
+    *out = pk;
     if (bytes_read) *bytes_read = src.consumed;
     return GA_OK;
+}
+
+int g16_key_write_run(Ctx* ctx, const ga_g16_key* key, int format, int fd, uint64_t* bytes_written) {
+    if (abi_bad_argument(!key_points_present(key) || (key->nb_commitments && (!key->ck_basis || !key->ck_basis_exp_sigma || !key->ck_len)),
+                         "null pointer inside ga_g16_key"))
+        return GA_ERR_INVALID;
+    CtxLock g(ctx);
+    ByteSink dst{fd};
+    GA_CHECK(GA_DISPATCH(Scope::FULL, key->curve, GA_NO_GROUP, return key_write<C>(ctx, key, format, dst)));
+    if (bytes_written) *bytes_written = dst.written;
+    return GA_OK;
+}
+
+int g16_proof_unmarshal_run(int curve, const uint8_t* data, size_t len, void* proof_out, void* commitments_out, uint32_t max_commitments,
+                            uint32_t* n_commitments, void* pok_out, size_t* consumed) {
+    return GA_DISPATCH(Scope::FULL, curve, GA_NO_GROUP,
+                       return proof_unmarshal<C>(data, len, proof_out, commitments_out, max_commitments, n_commitments, pok_out, consumed));
+}
+
+int g16_point_unmarshal_run(int curve, int group, const uint8_t* data, size_t len, void* affine_out, size_t* consumed) {
+    ByteSource src{data, len};
+    std::vector<uint8_t> img;
+    GA_CHECK(GA_DISPATCH(Scope::FULL, curve, group, return (read_header_point<C, G>(src, &img))));
+    memcpy(affine_out, img.data(), img.size());
+    if (consumed) *consumed = src.mem_pos;
+    return GA_OK;
+}
+
+int g16_marshal_run(int curve, const void* proof, const void* commitments, uint32_t n, const void* pok, uint8_t* out, size_t cap, size_t* len, bool raw) {
+    return GA_DISPATCH(Scope::FULL, curve, GA_NO_GROUP, return marshal<C>(proof, commitments, n, pok, out, cap, len, raw));
+}
+
+int g16_g1_marshal_uncompressed_run(int curve, const void* affine, uint8_t* out, size_t cap, size_t* len) {
+    return GA_DISPATCH(Scope::FULL, curve, GA_NO_GROUP, {
+        if (abi_bad_argument(cap < 2 * sizeof(Fe<typename C::FpP>), "buffer too small")) return GA_ERR_INVALID;
+        *len = encode_point<C, GA_G1>(affine, false, out);
+    });
 }
 
 }  // namespace ga

@@ -1,8 +1,8 @@
 // Groth16 proving key construction, part of the groth16.hip translation unit: the device-resident key (G16Pk: one G16Vec record per base
 // vector, indexed by GA_KEY_*, whose `layout` names the path of its MSM) and the guard that counts its users (PkUse); the staged builder
 // (G16Stage -> stage_finish -> G16Pk: check, move, domain, gather lists, plan_layouts, build_tables, points); the one-shot key of
-// ga_g16_prove_oneshot (its uploader thread) and the key's lifetime.  Key files are read into the same builder by g16_io.hip.h; the
-// entry points (ga_g16_pk_create, ga_g16_builder_*, ...) are in groth16.hip with the rest of the Groth16 ABI.
+// ga_g16_prove_oneshot (its uploader thread) and the key's lifetime.  Key files are read into the same builder by g16_io.hip.h.  The
+// drivers of ga_g16_pk_create, ga_g16_builder_* and the layout queries (g16.hip.h) are here, each beside the step it locks.
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -12,7 +12,7 @@
 #include <thread>
 #include <vector>
 
-#include "common.hip.h"
+#include "g16.hip.h"
 
 namespace ga {
 
@@ -122,10 +122,10 @@ struct PkUse {
     PkUse(const PkUse&) = delete;
     PkUse& operator=(const PkUse&) = delete;
 };
-#define GA_PK_USE(pk, what)                                                      \
+#define GA_PK_USE(pk)                                                            \
     PkUse _pk_use(pk);                                                           \
     if (!_pk_use.ok) {                                                           \
-        set_error(what ": the proving key is being destroyed");                  \
+        set_error("%s: the proving key is being destroyed", current_entry());    \
         return GA_ERR_STATE;                                                     \
     }
 
@@ -272,7 +272,7 @@ static void pk_free(G16Pk* pk) {
 }
 
 // waits for every entry point still using the key, then frees it
-static void pk_destroy_impl(G16Pk* pk) {
+void pk_destroy(G16Pk* pk) {
     if (!pk) return;
     {   // wait for every entry point still working on this key (provers on other lanes, epilogues outside the device lock)
         std::unique_lock<std::mutex> u(pk->use_mu);
@@ -284,7 +284,45 @@ static void pk_destroy_impl(G16Pk* pk) {
     pk_free(pk);
 }
 
+// what a key holds, for callers that orchestrate a sharded proof themselves (gnark_amd/multigpu.py)
+int pk_shard_layout(const G16Pk* pk, uint64_t* out8) {
+    const G16Vec& z = pk->vec[GA_KEY_G1_Z];   // (win_count: the plain count; which vectors carry tables is pk_table_layout's answer)
+    const uint64_t v[8] = {z.off, z.len, pk->w_lo, pk->w_hi, pk->n, pk->nb_wires, pk->win_index, pk->win_count};
+    memcpy(out8, v, sizeof v);
+    return GA_OK;
+}
+// out2[0]: which vectors carry a window table (bit GA_KEY_*: 0 G1.A, 1 G1.B, 2 G1.Z, 3 G1.K, 4 G2.B); out2[1]: which of those are laid
+// out by wire id over the shared witness sort
+int pk_table_layout(const G16Pk* pk, uint64_t* out2) {
+    out2[0] = out2[1] = 0;
+    for (int w = 0; w < GA_KEY_NB_VECTORS; w++) {
+        out2[0] |= (uint64_t)pk->vec[w].has_table() << w;
+        out2[1] |= (uint64_t)pk->vec[w].wire_indexed() << w;
+    }
+    return GA_OK;
+}
+
 // ---- the staged builder's steps ------------------------------------------------------------------------------------------------
+// (a step that is not static is the driver of its ga_g16_builder_* entry point and takes the context's lock; x_run is that form of a
+// step which pk_create_from_struct and the key readers call under the lock they hold)
+static int check_shard_index(uint32_t shard_index, uint32_t shard_count) {
+    if (shard_index < shard_count) return GA_OK;
+    set_error("proving key: shard_index %u >= shard_count %u", shard_index, shard_count);
+    return GA_ERR_INVALID;
+}
+int stage_create(Ctx* ctx, int curve, uint64_t domain_cardinality, uint64_t nb_wires, uint32_t shard_index, uint32_t shard_count, G16Stage** out) {
+    if (shard_count == 0) shard_count = 1;
+    GA_CHECK(check_shard_index(shard_index, shard_count));
+    *out = new G16Stage{ctx, curve, domain_cardinality, nb_wires, shard_index, shard_count};   // (its first six members)
+    return GA_OK;
+}
+void stage_destroy(G16Stage* st) {
+    if (!st) return;
+    Ctx* ctx = st->ctx;
+    CtxLock g(ctx);
+    hipStreamSynchronize(ctx->stream);
+    delete st;
+}
 static size_t stage_point_bytes(int curve, int which) {
     const size_t fp = curve == GA_BN254 ? 32 : 48;
     return which == GA_KEY_G2_B ? 4 * fp : 2 * fp;
@@ -317,6 +355,10 @@ static int stage_reserve(G16Stage* st, int which, uint64_t total) {
     x.reserved = true;
     return GA_OK;
 }
+int stage_reserve_run(G16Stage* st, int which, uint64_t total) {
+    CtxLock g(st->ctx);
+    return stage_reserve(st, which, total);
+}
 
 // points [seen, seen + count) of the full vector; only the part inside this shard's range is copied.  `pinned`: the source is
 // page-locked memory owned by the caller for the duration of the call (keyio's staging buffers) -- the copy is then truly
@@ -341,6 +383,26 @@ static int stage_append(G16Stage* st, int which, const void* points, uint64_t co
     }
     x.seen += count;
     return GA_OK;
+}
+// the append without a pointer: `count` points that are none of this shard's business
+static int stage_skip(G16Stage* st, int which, uint64_t count) {
+    if (which < 0 || which >= GA_KEY_NB_VECTORS || !st->v[which].reserved) {
+        set_error("%s: skip on vector %d before ga_g16_builder_reserve", current_entry(), which);
+        return GA_ERR_STATE;
+    }
+    G16Stage::Vec& x = st->v[which];
+    const bool outside = x.seen + count <= x.lo || x.seen >= x.lo + x.cnt;
+    if (!outside || x.seen + count > x.total) {
+        set_error("%s: null pointer for points [%llu, %llu) of vector %d, of which this shard keeps [%llu, %llu)", current_entry(),
+                  (unsigned long long)x.seen, (unsigned long long)(x.seen + count), which, (unsigned long long)x.lo, (unsigned long long)(x.lo + x.cnt));
+        return GA_ERR_INVALID;
+    }
+    x.seen += count;
+    return GA_OK;
+}
+int stage_append_run(G16Stage* st, int which, const void* points, uint64_t count) {
+    CtxLock g(st->ctx);
+    return count && !points ? stage_skip(st, which, count) : stage_append(st, which, points, count);
 }
 
 // ---- stage_finish: G16Stage -> G16Pk in seven steps, each called once, top to bottom ------------------------------------------------
@@ -668,6 +730,44 @@ static int stage_set_point(G16Stage* st, int which, const void* affine) {
     st->pts[which].assign((const uint8_t*)affine, (const uint8_t*)affine + bytes);
     return GA_OK;
 }
+int stage_set_point_run(G16Stage* st, int which, const void* affine) {
+    CtxLock g(st->ctx);
+    return stage_set_point(st, which, affine);
+}
+
+int stage_set_infinity(G16Stage* st, int which, const uint8_t* mask, uint64_t nb_wires) {
+    CtxLock g(st->ctx);
+    if ((which != 0 && which != 1) || !mask || nb_wires != st->nb_wires) {
+        set_error("%s: which must be 0/1 and the mask must have nbWires = %llu entries", current_entry(), (unsigned long long)st->nb_wires);
+        return GA_ERR_INVALID;
+    }
+    if (st->lists[which].job.joinable()) st->lists[which].job.join();   // (a mask set twice: the list of the old one must not outlive it)
+    st->inf[which].assign(mask, mask + nb_wires);
+    st->have_inf[which] = true;
+    st->start_list(which);   // (beside whatever the caller appends next)
+    return GA_OK;
+}
+
+int stage_set_k_remove(G16Stage* st, const uint64_t* ids, uint64_t len) {
+    CtxLock g(st->ctx);
+    if (len > st->nb_wires) {
+        set_error("%s: %llu removed wires for %llu wires", current_entry(), (unsigned long long)len, (unsigned long long)st->nb_wires);
+        return GA_ERR_INVALID;
+    }
+    st->k_remove.assign(ids, ids + len);
+    return GA_OK;
+}
+
+int stage_set_window_shard(G16Stage* st, uint32_t index, uint32_t count) {
+    CtxLock g(st->ctx);
+    if (count == 0 || index >= count) {
+        set_error("%s: index %u must be below count %u", current_entry(), index, count);
+        return GA_ERR_INVALID;
+    }
+    st->win_index = index;
+    st->win_count = count;
+    return GA_OK;
+}
 
 static int stage_add_commitment_key(G16Stage* st, const void* basis, const void* sigma, uint64_t len) {
     if (len && (!basis || !sigma)) {
@@ -689,9 +789,30 @@ static int stage_add_commitment_key(G16Stage* st, const void* basis, const void*
     st->ck_len.push_back(len);
     return GA_OK;
 }
+int stage_add_commitment_key_run(G16Stage* st, const void* basis, const void* sigma, uint64_t len) {
+    CtxLock g(st->ctx);
+    return stage_add_commitment_key(st, basis, sigma, len);
+}
 
 static int stage_finish_any(G16Stage* st, int precompute, G16Pk** out) {
     return GA_DISPATCH(Scope::FULL, st->curve, GA_NO_GROUP, return stage_finish<C>(st, precompute, out));
+}
+// ga_g16_builder_finish: the builder is consumed either way, a failed finish leaves nothing half-built behind
+int stage_finish_consume(G16Stage* st, int32_t precompute, G16Pk** out) {
+    int rc;
+    {
+        CtxLock g(st->ctx);
+        G16Pk* pk = nullptr;
+        try {
+            rc = stage_finish_any(st, precompute, &pk);
+        } catch (const std::exception& e) {   // (host allocations sized by the key: no exception crosses the C ABI)
+            set_error("%s: %s", current_entry(), e.what());
+            rc = GA_ERR_NOMEM;
+        }
+        if (rc == GA_OK) *out = pk;
+    }
+    delete st;
+    return rc;
 }
 
 // ---- one-shot keys (ga_g16_prove_oneshot) -------------------------------------------------------------------------------------
@@ -794,10 +915,10 @@ static bool key_points_present(const ga_g16_key* key) {
 // defer_uploads (ga_g16_prove_oneshot): the five base vectors get their device buffers here but are copied by an uploader thread
 // that this function starts before it returns -- plain vectors only (no tables), the whole key on one device; the caller must keep
 // the host vectors alive until the thread has been joined (pk_free does).
-static int pk_create_from_struct(Ctx* ctx, const ga_g16_key* key, G16Pk** out, bool defer_uploads = false) {
+static int pk_create_from_struct(Ctx* ctx, const ga_g16_key* key, G16Pk** out, bool defer_uploads) {
     GA_CHECK(dispatch_check(Scope::FULL, key->curve, GA_NO_GROUP));   // before anything is staged
     if (!key_points_present(key)) {
-        set_error("ga_g16_pk_create: null pointer inside ga_g16_key");
+        set_error("%s: null pointer inside ga_g16_key", current_entry());
         return GA_ERR_INVALID;
     }
     if (key->len_a + key->nb_infinity_a != key->nb_wires || key->len_b + key->nb_infinity_b != key->nb_wires) {
@@ -820,10 +941,7 @@ static int pk_create_from_struct(Ctx* ctx, const ga_g16_key* key, G16Pk** out, b
     st.nb_wires = key->nb_wires;
     st.shard_count = key->shard_count ? key->shard_count : 1;
     st.shard_index = key->shard_index;
-    if (st.shard_index >= st.shard_count) {
-        set_error("proving key: shard_index %u >= shard_count %u", st.shard_index, st.shard_count);
-        return GA_ERR_INVALID;
-    }
+    GA_CHECK(check_shard_index(st.shard_index, st.shard_count));
     st.win_count = key->window_shard_count ? key->window_shard_count : 1;
     st.win_index = key->window_shard_index;
     // the masks first: their gather lists are built by helper threads while this thread is busy with the 6-9 GiB of uploads below
@@ -835,7 +953,7 @@ static int pk_create_from_struct(Ctx* ctx, const ga_g16_key* key, G16Pk** out, b
     const void* vec[GA_KEY_NB_VECTORS] = {key->g1_a, key->g1_b, key->g1_z, key->g1_k, key->g2_b};
     const uint64_t len[GA_KEY_NB_VECTORS] = {key->len_a, key->len_b, key->len_z, key->len_k, key->len_b2};
     if (defer_uploads && (st.shard_count != 1 || st.win_count != 1)) {
-        set_error("ga_g16_prove_oneshot: the key must be whole (no base-range or window sharding)");
+        set_error("%s: the key must be whole (no base-range or window sharding)", current_entry());
         return GA_ERR_INVALID;
     }
     if (defer_uploads) adopt_spare_vectors(ctx, &st, len);
@@ -874,6 +992,10 @@ static int pk_create_from_struct(Ctx* ctx, const ga_g16_key* key, G16Pk** out, b
     }
     *out = pk;
     return GA_OK;
+}
+int pk_create_run(Ctx* ctx, const ga_g16_key* key, G16Pk** out, bool defer_uploads) {
+    CtxLock g(ctx);
+    return pk_create_from_struct(ctx, key, out, defer_uploads);
 }
 
 }  // namespace ga

@@ -1,12 +1,12 @@
-// Groth16 prover: one-call proof from the solver's output on a device-resident proving key, and the Groth16 entry points of the C
-// ABI.  The key (one record per base vector) and its builder are g16_key.hip.h, key files and proof bytes are g16_io.hip.h: one
-// translation unit.
+// Groth16 prover: one-call proof from the solver's output on a device-resident proving key, and the drivers of the proving entry
+// points (g16.hip.h; the entry points themselves are g16_abi.hip).  The key (one record per base vector) and its builder are
+// g16_key.hip.h, key files and proof bytes are g16_io.hip.h, each with the drivers of its entry points: one translation unit.
 //
 // Mirrors backend/groth16/bn254/prove.go:130-315 (CPU) and backend/accelerated/icicle/groth16/bn254/icicle.go:784-1360
 // (GPU):  computeH -> filter wire values -> 4 G1 MSMs + 1 G2 MSM -> host epilogue with the caller-supplied randomness
 // (r, s); BSB22 commitments are the two extra MSMs per commitment of ga_g16_commit (prove.go:84,114) plus the K filter.  The host
 // side is C++ because the reference's host side is compiled Go and no Go toolchain exists in the build image (INTEGRATION.md shows
-// the cgo binding that calls this file's entry points).
+// the cgo binding that calls the entry points).
 #include <algorithm>
 #include <atomic>
 #include <condition_variable>
@@ -35,7 +35,7 @@ namespace ga {
 // prove_batch    : the device part of MANY proofs under one key (ga_g16_prove_batch): chunks of <= 16 solutions, the H side as batched
 //                  transforms, one batch MSM per base vector (vector_msm_batch); finish_batch runs the epilogues side by side
 // prove_partial runs them on one device (witness_msms on the caller's lane, h_helper beside it), prove_multi / MultiProof on several;
-// finish is the host epilogue.
+// finish is the host epilogue.  The drivers (g16_*_run, at the end of the file) take the key's use count, the input slot and the locks.
 
 // nbPublic of a proof agrees with the key: nbWires - nbPublic wires feed K, some of them through the commitments' remove list
 static int check_nb_public(const G16Pk* pk, uint64_t nb_public) {
@@ -46,11 +46,11 @@ static int check_nb_public(const G16Pk* pk, uint64_t nb_public) {
     }
     return GA_OK;
 }
-// a whole proof needs the whole key (`entry`: the entry point refusing)
-static int check_unsharded(const G16Pk* pk, const char* entry) {
+// a whole proof needs the whole key
+static int check_unsharded(const G16Pk* pk) {
     if (pk->shard_count != 1 || pk->win_count != 1) {
         set_error("%s: this key holds one share of a sharded key (base range %u/%u, windows %u/%u); use ga_g16_prove_multi or "
-                  "ga_g16_prove_partial + ga_g16_finish", entry, pk->shard_index, pk->shard_count, pk->win_index, pk->win_count);
+                  "ga_g16_prove_partial + ga_g16_finish", current_entry(), pk->shard_index, pk->shard_count, pk->win_index, pk->win_count);
         return GA_ERR_STATE;
     }
     return GA_OK;
@@ -467,7 +467,7 @@ static int h_helper(G16Pk* pk, const SlotLease& slot, const void* const* src, ui
 // reaches it first.  The two halves share the device: the sorts, reduction tails, host round trips and launch gaps of one run under
 // the bucket kernels of the other.  Without a partner lane (profiling on, GA_G16_SPLIT=0, or the lane is taken) the helper only
 // uploads and the same h_side follows on the caller's lane after the join, as in round 2.  Either half's result code is returned
-// verbatim: ga_g16_prove's lane-2 fallback keys on GA_ERR_NOMEM.  Everything is joined before this function returns.
+// verbatim: g16_prove_run's lane-2 fallback keys on GA_ERR_NOMEM.  Everything is joined before this function returns.
 template <class C>
 static int prove_partial(G16Pk* pk, const SlotLease& slot, bool preloaded, const void* w, const void* a, const void* b, const void* c,
                          uint64_t n_constraints, uint64_t nb_public, G16Partials<C>* out) {
@@ -974,367 +974,12 @@ static int prove_multi(G16Pk* const* pks, uint32_t n, const void* w, const void*
     return finish<C>(pks[0], sum, r, s, proof_out);
 }
 
-}  // namespace ga
-
-using namespace ga;
-
-extern "C" {
-
-// ---- proving keys (g16_key.hip.h) ------------------------------------------------------------------------------------------------
-int ga_g16_pk_create(ga_ctx* h, const ga_g16_key* key, ga_g16_pk** out) try {
-    GA_ABI_ENTRY();
-    Ctx* ctx = reinterpret_cast<Ctx*>(h);
-    if (!ctx || !key || !out) {
-        set_error("ga_g16_pk_create: null argument");
-        return GA_ERR_INVALID;
-    }
-    CtxLock g(ctx);
-    G16Pk* pk = nullptr;
-    GA_CHECK(pk_create_from_struct(ctx, key, &pk));
-    *out = reinterpret_cast<ga_g16_pk*>(pk);
-    return GA_OK;
-} GA_ABI_CATCH
-
-int ga_g16_builder_create(ga_ctx* h, int curve, uint64_t domain_cardinality, uint64_t nb_wires, uint32_t shard_index,
-                          uint32_t shard_count, ga_g16_builder** out) try {
-    GA_ABI_ENTRY();
-    Ctx* ctx = reinterpret_cast<Ctx*>(h);
-    GA_CHECK(dispatch_check(Scope::FULL, curve, GA_NO_GROUP));   // no Groth16 key on a G1 / Fr curve
-    if (!ctx || !out || domain_cardinality == 0) {
-        set_error("ga_g16_builder_create: bad argument");
-        return GA_ERR_INVALID;
-    }
-    if (shard_count == 0) shard_count = 1;
-    if (shard_index >= shard_count) {
-        set_error("proving key: shard_index %u >= shard_count %u", shard_index, shard_count);
-        return GA_ERR_INVALID;
-    }
-    G16Stage* st = new G16Stage();
-    st->ctx = ctx;
-    st->curve = curve;
-    st->n = domain_cardinality;
-    st->nb_wires = nb_wires;
-    st->shard_index = shard_index;
-    st->shard_count = shard_count;
-    *out = reinterpret_cast<ga_g16_builder*>(st);
-    return GA_OK;
-} GA_ABI_CATCH
-
-#define GA_STAGE(b)                                     \
-    G16Stage* st = reinterpret_cast<G16Stage*>(b);      \
-    if (!st) {                                          \
-        set_error("ga_g16_builder: null builder");      \
-        return GA_ERR_INVALID;                          \
-    }                                                   \
-    CtxLock g(st->ctx)
-
-int ga_g16_builder_reserve(ga_g16_builder* b, int which, uint64_t total_len) try {
-    GA_ABI_ENTRY();
-    GA_STAGE(b);
-    return stage_reserve(st, which, total_len);
-} GA_ABI_CATCH
-
-int ga_g16_builder_append(ga_g16_builder* b, int which, const void* points, uint64_t count) try {
-    GA_ABI_ENTRY();
-    GA_STAGE(b);
-    if (count && !points) {
-        // skipping is allowed for points that are none of this shard's business
-        if (which < 0 || which >= GA_KEY_NB_VECTORS || !st->v[which].reserved) {
-            set_error("ga_g16_builder_append: skip on vector %d before ga_g16_builder_reserve", which);
-            return GA_ERR_STATE;
-        }
-        G16Stage::Vec& x = st->v[which];
-        const bool outside = x.seen + count <= x.lo || x.seen >= x.lo + x.cnt;
-        if (!outside || x.seen + count > x.total) {
-            set_error("ga_g16_builder_append: null pointer for points [%llu, %llu) of vector %d, of which this shard keeps [%llu, %llu)",
-                      (unsigned long long)x.seen, (unsigned long long)(x.seen + count), which, (unsigned long long)x.lo, (unsigned long long)(x.lo + x.cnt));
-            return GA_ERR_INVALID;
-        }
-        x.seen += count;
-        return GA_OK;
-    }
-    return stage_append(st, which, points, count);
-} GA_ABI_CATCH
-
-int ga_g16_builder_set_point(ga_g16_builder* b, int which, const void* affine) try {
-    GA_ABI_ENTRY();
-    GA_STAGE(b);
-    return stage_set_point(st, which, affine);
-} GA_ABI_CATCH
-
-int ga_g16_builder_set_infinity(ga_g16_builder* b, int which, const uint8_t* mask, uint64_t nb_wires) try {
-    GA_ABI_ENTRY();
-    GA_STAGE(b);
-    if ((which != 0 && which != 1) || !mask || nb_wires != st->nb_wires) {
-        set_error("ga_g16_builder_set_infinity: which must be 0/1 and the mask must have nbWires = %llu entries", (unsigned long long)st->nb_wires);
-        return GA_ERR_INVALID;
-    }
-    if (st->lists[which].job.joinable()) st->lists[which].job.join();   // (a mask set twice: the list of the old one must not outlive it)
-    st->inf[which].assign(mask, mask + nb_wires);
-    st->have_inf[which] = true;
-    st->start_list(which);   // (beside whatever the caller appends next)
-    return GA_OK;
-} GA_ABI_CATCH
-
-int ga_g16_builder_add_commitment_key(ga_g16_builder* b, const void* basis, const void* sigma, uint64_t len) try {
-    GA_ABI_ENTRY();
-    GA_STAGE(b);
-    return stage_add_commitment_key(st, basis, sigma, len);
-} GA_ABI_CATCH
-
-int ga_g16_builder_set_k_remove(ga_g16_builder* b, const uint64_t* ids, uint64_t len) try {
-    GA_ABI_ENTRY();
-    GA_STAGE(b);
-    if (len && !ids) {
-        set_error("ga_g16_builder_set_k_remove: null pointer");
-        return GA_ERR_INVALID;
-    }
-    if (len > st->nb_wires) {
-        set_error("ga_g16_builder_set_k_remove: %llu removed wires for %llu wires", (unsigned long long)len, (unsigned long long)st->nb_wires);
-        return GA_ERR_INVALID;
-    }
-    st->k_remove.assign(ids, ids + len);
-    return GA_OK;
-} GA_ABI_CATCH
-
-int ga_g16_builder_set_window_shard(ga_g16_builder* b, uint32_t index, uint32_t count) try {
-    GA_ABI_ENTRY();
-    GA_STAGE(b);
-    if (count == 0 || index >= count) {
-        set_error("ga_g16_builder_set_window_shard: index %u must be below count %u", index, count);
-        return GA_ERR_INVALID;
-    }
-    st->win_index = index;
-    st->win_count = count;
-    return GA_OK;
-} GA_ABI_CATCH
-
-int ga_g16_builder_finish(ga_g16_builder* b, int32_t precompute, ga_g16_pk** out) try {
-    GA_ABI_ENTRY();
-    G16Stage* st = reinterpret_cast<G16Stage*>(b);
-    if (!st || !out) {
-        set_error("ga_g16_builder_finish: null argument");
-        return GA_ERR_INVALID;
-    }
-    int rc;
-    {
-        CtxLock g(st->ctx);
-        G16Pk* pk = nullptr;
-        try {
-            rc = stage_finish_any(st, precompute, &pk);
-        } catch (const std::exception& e) {   // (host allocations sized by the key: no exception crosses the C ABI)
-            set_error("ga_g16_builder_finish: %s", e.what());
-            rc = GA_ERR_NOMEM;
-        }
-        if (rc == GA_OK) *out = reinterpret_cast<ga_g16_pk*>(pk);
-    }
-    delete st;   // consumed either way: a failed finish leaves nothing half-built behind
-    return rc;
-} GA_ABI_CATCH
-
-void ga_g16_builder_destroy(ga_g16_builder* b) try {
-    GA_ABI_ENTRY();
-    G16Stage* st = reinterpret_cast<G16Stage*>(b);
-    if (!st) return;
-    Ctx* ctx = st->ctx;
-    CtxLock g(ctx);
-    hipStreamSynchronize(ctx->stream);
-    delete st;
-} GA_ABI_CATCH_VOID
-
-void ga_g16_pk_destroy(ga_g16_pk* p) try {
-    GA_ABI_ENTRY();
-    pk_destroy_impl(reinterpret_cast<G16Pk*>(p));
-} GA_ABI_CATCH_VOID
-
-// what a key holds, for callers that orchestrate a sharded proof themselves (gnark_amd/multigpu.py)
-int ga_g16_shard_layout(ga_g16_pk* p, uint64_t* out8) try {
-    GA_ABI_ENTRY();
-    G16Pk* pk = reinterpret_cast<G16Pk*>(p);
-    if (!pk || !out8) {
-        set_error("ga_g16_shard_layout: null argument");
-        return GA_ERR_INVALID;
-    }
-    out8[0] = pk->vec[GA_KEY_G1_Z].off;
-    out8[1] = pk->vec[GA_KEY_G1_Z].len;
-    out8[2] = pk->w_lo;
-    out8[3] = pk->w_hi;
-    out8[4] = pk->n;
-    out8[5] = pk->nb_wires;
-    out8[6] = pk->win_index;
-    out8[7] = pk->win_count;   // (the plain count: which vectors carry tables is ga_g16_table_layout's answer)
-    return GA_OK;
-} GA_ABI_CATCH
-
-// out2[0]: which vectors carry a window table (bit GA_KEY_*: 0 G1.A, 1 G1.B, 2 G1.Z, 3 G1.K, 4 G2.B); out2[1]: which of those are laid
-// out by wire id over the shared witness sort
-int ga_g16_table_layout(ga_g16_pk* p, uint64_t* out2) try {
-    GA_ABI_ENTRY();
-    G16Pk* pk = reinterpret_cast<G16Pk*>(p);
-    if (!pk || !out2) {
-        set_error("ga_g16_table_layout: null argument");
-        return GA_ERR_INVALID;
-    }
-    out2[0] = out2[1] = 0;
-    for (int w = 0; w < GA_KEY_NB_VECTORS; w++) {
-        out2[0] |= (uint64_t)pk->vec[w].has_table() << w;
-        out2[1] |= (uint64_t)pk->vec[w].wire_indexed() << w;
-    }
-    return GA_OK;
-} GA_ABI_CATCH
-
-// ---- key files and proof bytes ------------------------------------------------------------------------------------------------
-int ga_g16_pk_read_mem(ga_ctx* h, int curve, const uint8_t* data, size_t len, int32_t precompute, uint32_t shard_index, uint32_t shard_count,
-                       const uint64_t* k_remove, uint64_t len_k_remove, ga_g16_pk** out, uint64_t* bytes_read) try {
-    GA_ABI_ENTRY();
-    if (!data) {
-        set_error("ga_g16_pk_read_mem: null data");
-        return GA_ERR_INVALID;
-    }
-    ByteSource src;
-    src.mem = data;
-    src.mem_len = len;
-    return pk_read_any(h, curve, src, precompute, shard_index, shard_count, k_remove, len_k_remove, out, bytes_read);
-} GA_ABI_CATCH
-
-int ga_g16_pk_read_fd(ga_ctx* h, int curve, int fd, int32_t precompute, uint32_t shard_index, uint32_t shard_count, const uint64_t* k_remove,
-                      uint64_t len_k_remove, ga_g16_pk** out, uint64_t* bytes_read) try {
-    GA_ABI_ENTRY();
-    if (fd < 0) {
-        set_error("ga_g16_pk_read_fd: bad file descriptor");
-        return GA_ERR_INVALID;
-    }
-    ByteSource src;
-    src.fd = fd;
-    return pk_read_any(h, curve, src, precompute, shard_index, shard_count, k_remove, len_k_remove, out, bytes_read);
-} GA_ABI_CATCH
-
-// ProvingKey.ReadFrom semantics: every point kept is tested for curve and subgroup membership (g16_io.hip.h, check_points.hip.h)
-int ga_g16_pk_read_mem_checked(ga_ctx* h, int curve, const uint8_t* data, size_t len, int32_t precompute, uint32_t shard_index, uint32_t shard_count,
-                               const uint64_t* k_remove, uint64_t len_k_remove, ga_g16_pk** out, uint64_t* bytes_read) try {
-    GA_ABI_ENTRY();
-    if (!data) {
-        set_error("ga_g16_pk_read_mem_checked: null data");
-        return GA_ERR_INVALID;
-    }
-    ByteSource src;
-    src.mem = data;
-    src.mem_len = len;
-    return pk_read_any(h, curve, src, precompute, shard_index, shard_count, k_remove, len_k_remove, out, bytes_read, true);
-} GA_ABI_CATCH
-
-int ga_g16_pk_read_fd_checked(ga_ctx* h, int curve, int fd, int32_t precompute, uint32_t shard_index, uint32_t shard_count, const uint64_t* k_remove,
-                              uint64_t len_k_remove, ga_g16_pk** out, uint64_t* bytes_read) try {
-    GA_ABI_ENTRY();
-    if (fd < 0) {
-        set_error("ga_g16_pk_read_fd_checked: bad file descriptor");
-        return GA_ERR_INVALID;
-    }
-    ByteSource src;
-    src.fd = fd;
-    return pk_read_any(h, curve, src, precompute, shard_index, shard_count, k_remove, len_k_remove, out, bytes_read, true);
-} GA_ABI_CATCH
-
-int ga_g16_key_write_fd(ga_ctx* h, const ga_g16_key* key, int format, int fd, uint64_t* bytes_written) try {
-    GA_ABI_ENTRY();
-    Ctx* ctx = reinterpret_cast<Ctx*>(h);
-    if (!ctx || !key || fd < 0 || format < GA_KEY_FORMAT_COMPRESSED || format > GA_KEY_FORMAT_DUMP) {
-        set_error("ga_g16_key_write_fd: bad argument");
-        return GA_ERR_INVALID;
-    }
-    if (!key_points_present(key) || (key->nb_commitments && (!key->ck_basis || !key->ck_basis_exp_sigma || !key->ck_len))) {
-        set_error("ga_g16_key_write_fd: null pointer inside ga_g16_key");
-        return GA_ERR_INVALID;
-    }
-    CtxLock g(ctx);
-    ByteSink dst;
-    dst.fd = fd;
-    GA_CHECK(GA_DISPATCH(Scope::FULL, key->curve, GA_NO_GROUP, return key_write<C>(ctx, key, format, dst)));
-    if (bytes_written) *bytes_written = dst.written;
-    return GA_OK;
-} GA_ABI_CATCH
-
-int ga_g16_proof_unmarshal(int curve, const uint8_t* data, size_t len, void* proof_out, void* commitments_out, uint32_t max_commitments,
-                           uint32_t* n_commitments, void* pok_out, size_t* consumed) try {
-    GA_ABI_ENTRY();
-    if (!data || !proof_out) {
-        set_error("ga_g16_proof_unmarshal: null argument");
-        return GA_ERR_INVALID;
-    }
-    return GA_DISPATCH(Scope::FULL, curve, GA_NO_GROUP,
-                       return proof_unmarshal<C>(data, len, proof_out, commitments_out, max_commitments, n_commitments, pok_out, consumed));
-} GA_ABI_CATCH
-
-int ga_point_unmarshal(int curve, int group, const uint8_t* data, size_t len, void* affine_out, size_t* consumed) try {
-    GA_ABI_ENTRY();
-    if (!data || !affine_out) {
-        set_error("ga_point_unmarshal: null argument");
-        return GA_ERR_INVALID;
-    }
-    ByteSource src;
-    src.mem = data;
-    src.mem_len = len;
-    std::vector<uint8_t> img;
-    GA_CHECK(GA_DISPATCH(Scope::FULL, curve, group, return (read_header_point<C, G>(src, &img))));
-    memcpy(affine_out, img.data(), img.size());
-    if (consumed) *consumed = src.mem_pos;
-    return GA_OK;
-} GA_ABI_CATCH
-
-int ga_g16_proof_marshal(int curve, const void* proof, uint8_t* out, size_t cap, size_t* len) try {
-    GA_ABI_ENTRY();
-    if (!proof || !out || !len) {
-        set_error("ga_g16_proof_marshal: null argument");
-        return GA_ERR_INVALID;
-    }
-    return GA_DISPATCH(Scope::FULL, curve, GA_NO_GROUP, return marshal<C>(proof, nullptr, 0, nullptr, out, cap, len));
-} GA_ABI_CATCH
-
-int ga_g16_proof_marshal_bsb22(int curve, const void* proof, const void* commitments, uint32_t n, const void* pok, uint8_t* out,
-                               size_t cap, size_t* len) try {
-    GA_ABI_ENTRY();
-    if (!proof || !out || !len || (n && !commitments)) {
-        set_error("ga_g16_proof_marshal_bsb22: null argument");
-        return GA_ERR_INVALID;
-    }
-    return GA_DISPATCH(Scope::FULL, curve, GA_NO_GROUP, return marshal<C>(proof, commitments, n, pok, out, cap, len));
-} GA_ABI_CATCH
-
-int ga_g16_proof_marshal_raw(int curve, const void* proof, const void* commitments, uint32_t n, const void* pok, uint8_t* out,
-                             size_t cap, size_t* len) try {
-    GA_ABI_ENTRY();
-    if (!proof || !out || !len || (n && !commitments)) {
-        set_error("ga_g16_proof_marshal_raw: null argument");
-        return GA_ERR_INVALID;
-    }
-    return GA_DISPATCH(Scope::FULL, curve, GA_NO_GROUP, return marshal<C>(proof, commitments, n, pok, out, cap, len, true));
-} GA_ABI_CATCH
-
-int ga_g1_marshal_uncompressed(int curve, const void* affine, uint8_t* out, size_t cap, size_t* len) try {
-    GA_ABI_ENTRY();
-    if (!affine || !out || !len) {
-        set_error("ga_g1_marshal_uncompressed: null argument");
-        return GA_ERR_INVALID;
-    }
-    return GA_DISPATCH(Scope::FULL, curve, GA_NO_GROUP, {
-        if (cap < 2 * sizeof(Fe<typename C::FpP>)) {
-            set_error("ga_g1_marshal_uncompressed: buffer too small");
-            return GA_ERR_INVALID;
-        }
-        *len = encode_point<C, GA_G1>(affine, false, out);
-    });
-} GA_ABI_CATCH
-
-// ---- proofs ----------------------------------------------------------------------------------------------------------------------
-static int g16_prove_impl(ga_g16_pk* p, const void* w, const void* a, const void* b, const void* c, uint64_t n_constraints,
-                 uint64_t nb_public, const void* r, const void* s, void* proof_out) {
-    G16Pk* pk = reinterpret_cast<G16Pk*>(p);
-    if (!pk || !w || !a || !b || !c || !r || !s || !proof_out) {
-        set_error("ga_g16_prove: null argument");
-        return GA_ERR_INVALID;
-    }
-    GA_PK_USE(pk, "ga_g16_prove");
-    GA_CHECK(check_unsharded(pk, "ga_g16_prove"));
+// ---- the drivers of the proving entry points (g16.hip.h; the entry points are g16_abi.hip) -------------------------------------------
+// ga_g16_prove, and the proof inside ga_g16_prove_oneshot and ga_g16_prove_multi with one key
+int g16_prove_run(G16Pk* pk, const void* w, const void* a, const void* b, const void* c, uint64_t n_constraints, uint64_t nb_public,
+                  const void* r, const void* s, void* proof_out) {
+    GA_PK_USE(pk);
+    GA_CHECK(check_unsharded(pk));
     // Two callers may be inside at once (two goroutines proving on one device).  The first holds the device lock and works on
     // lanes 0/1 (witness MSMs / H side, prove_partial).  The second finds the device busy and computes its proof on lanes 2/3 --
     // own streams, own scratch namespaces -- so the two proofs run CONCURRENTLY: uploads hide behind the other proof's kernels
@@ -1391,65 +1036,94 @@ static int g16_prove_impl(ga_g16_pk* p, const void* w, const void* a, const void
 // out[0..3] = ga_g16_prove calls of this context that ran on lanes 0/1, on lanes 2/3 beside another proof, that staged their
 // inputs and queued for the device, and proofs whose H side ran on a partner lane (any entry point); out[4..5] = device bytes
 // of scratch held by lanes 0/1 and by lanes 2/3
-int ga_g16_lane_stats(ga_ctx* h, uint64_t* out6) try {
-    GA_ABI_ENTRY();
-    Ctx* ctx = reinterpret_cast<Ctx*>(h);
-    if (!ctx || !out6) {
-        set_error("ga_g16_lane_stats: null argument");
-        return GA_ERR_INVALID;
-    }
-    out6[0] = ctx->stat_lane0;
-    out6[1] = ctx->stat_lane2;
-    out6[2] = ctx->stat_queued;
-    out6[3] = ctx->stat_split;
-    out6[4] = out6[5] = 0;
+int g16_lane_stats(Ctx* ctx, uint64_t* out6) {
+    const uint64_t stats[6] = {ctx->stat_lane0, ctx->stat_lane2, ctx->stat_queued, ctx->stat_split, 0, 0};
+    memcpy(out6, stats, sizeof stats);
     std::lock_guard<std::mutex> g(ctx->scratch_mu);
     for (const auto& kv : ctx->scratch) out6[kv.second.lane < 2 ? 4 : 5] += kv.second.bytes;
     return GA_OK;
-} GA_ABI_CATCH
+}
 
-int ga_g16_prove_partial(ga_g16_pk* p, const void* w, const void* a, const void* b, const void* c, uint64_t n_constraints,
-                         uint64_t nb_public, void* partials_out) try {
-    GA_ABI_ENTRY();
-    G16Pk* pk = reinterpret_cast<G16Pk*>(p);
-    if (!pk || !w || !a || !b || !c || !partials_out) {
-        set_error("ga_g16_prove_partial: null argument");
-        return GA_ERR_INVALID;
-    }
-    GA_PK_USE(pk, "ga_g16_prove_partial");
-    SlotLease slot(pk->ctx);   // always slot first, device lock second (ga_g16_prove's order)
+// `count` proofs under one key: a loop of groth16.Prove over one ProvingKey (prove.go:130-315; the reference has no batch entry
+// point) as one caller of the device -- prove_batch on lane 0 under the device lock, then the epilogues outside it (finish_batch).  A
+// ga_g16_prove arriving meanwhile finds the device busy and proves on lanes 2/3 as beside any other proof.
+int g16_prove_batch_run(G16Pk* pk, uint32_t count, const void* const* w, const void* const* a, const void* const* b, const void* const* c,
+                        uint64_t n_constraints, uint64_t nb_public, const void* r, const void* s, void* proofs_out) {
+    for (uint32_t j = 0; j < count; j++)
+        if (!w[j] || !a[j] || !b[j] || !c[j]) {
+            set_error("%s: null pointer in solution %u (%s[%u])", current_entry(), j, !w[j] ? "w" : !a[j] ? "a" : !b[j] ? "b" : "c", j);
+            return GA_ERR_INVALID;
+        }
+    GA_PK_USE(pk);
+    GA_CHECK(check_unsharded(pk));
+    GA_CHECK(check_nb_constraints(pk, n_constraints));
+    GA_CHECK(check_nb_public(pk, nb_public));
+    Ctx* ctx = pk->ctx;
+    return GA_DISPATCH(Scope::FULL, pk->curve, GA_NO_GROUP, {
+        std::vector<G16Partials<C>> parts(count);
+        {
+            std::unique_lock<std::mutex> dev(ctx->mu);
+            hipSetDevice(ctx->device);
+            ctx->tun.read_env();
+            GA_CHECK(prove_batch<C>(pk, count, w, a, b, c, n_constraints, nb_public, parts.data()));
+            // (the stage list of the profiler is guarded by the device lock)
+            if (ctx->profiling) return finish_batch<C>(pk, parts, r, s, proofs_out, /*serial=*/true);
+        }
+        return finish_batch<C>(pk, parts, r, s, proofs_out, /*serial=*/false);
+    });
+}
+
+// One proof on a key that is NOT kept on the device (the Go package's default, PinToGPU = false, as icicle.go:797-805): the key
+// goes up as plain vectors WHILE the proof runs -- the uploader thread of pk_create_from_struct copies A, B, K, G2.B, Z in the order
+// the MSMs consume them, every MSM waits for its own vector only -- and is dropped afterwards.  Same proof bytes as
+// ga_g16_pk_create(precompute = -1) + ga_g16_prove + ga_g16_pk_destroy, in about the time of the longer of the two (PCIe, device)
+// instead of their sum.  No host pointer is used after the call returns (the uploader is joined before the key is freed).
+int g16_prove_oneshot_run(Ctx* ctx, const ga_g16_key* key, const void* w, const void* a, const void* b, const void* c, uint64_t n_constraints,
+                          uint64_t nb_public, const void* r, const void* s, void* proof_out) {
+    trace_event("ga_g16_prove_oneshot", 0);
+    struct InFlight {   // pageable uploads of this context take turns while the key is on its way (common.hip.h)
+        Ctx* c;
+        explicit InFlight(Ctx* x) : c(x) { c->oneshot_inflight++; }
+        ~InFlight() { c->oneshot_inflight--; }
+    } inflight(ctx);
+    G16Pk* pk = nullptr;
+    GA_CHECK(pk_create_run(ctx, key, &pk, /*defer_uploads=*/true));
+    struct Drop {   // whatever happens below, the uploader is joined and the key freed before the host vectors go out of scope
+        G16Pk* pk;
+        ~Drop() {
+            pk_destroy(pk);
+            trace_event("key dropped", 0);
+        }
+    } drop{pk};
+    trace_event("key reserved, uploader started", 0);
+    const int rc = g16_prove_run(pk, w, a, b, c, n_constraints, nb_public, r, s, proof_out);
+    trace_event("proof done", rc);
+    return rc;
+}
+
+int g16_prove_partial_run(G16Pk* pk, const void* w, const void* a, const void* b, const void* c, uint64_t n_constraints, uint64_t nb_public, void* partials_out) {
+    GA_PK_USE(pk);
+    SlotLease slot(pk->ctx);   // always slot first, device lock second (g16_prove_run's order)
     CtxLock g(pk->ctx);
     return GA_DISPATCH(Scope::FULL, pk->curve, GA_NO_GROUP, {
         G16Partials<C> part;
         GA_CHECK(prove_partial<C>(pk, slot, false, w, a, b, c, n_constraints, nb_public, &part));
         part.store(partials_out);
     });
-} GA_ABI_CATCH
+}
 
-int ga_g16_finish(ga_g16_pk* p, const void* partials_sum, const void* r, const void* s, void* proof_out) try {
-    GA_ABI_ENTRY();
-    G16Pk* pk = reinterpret_cast<G16Pk*>(p);
-    if (!pk || !partials_sum || !r || !s || !proof_out) {
-        set_error("ga_g16_finish: null argument");
-        return GA_ERR_INVALID;
-    }
-    GA_PK_USE(pk, "ga_g16_finish");
+int g16_finish_run(G16Pk* pk, const void* partials_sum, const void* r, const void* s, void* proof_out) {
+    GA_PK_USE(pk);
     return GA_DISPATCH(Scope::FULL, pk->curve, GA_NO_GROUP, {
         G16Partials<C> sum;
         sum.load(partials_sum);
         return finish<C>(pk, sum, r, s, proof_out);
     });
-} GA_ABI_CATCH
+}
 
-// ---- pieces of a sharded proof (multi-GPU orchestration by the caller: gnark_amd/multigpu.py over RCCL, or ga_g16_prove_multi) ----
-int ga_g16_witness_partial(ga_g16_pk* p, const void* w, uint64_t nb_public, void* partials_out) try {
-    GA_ABI_ENTRY();
-    G16Pk* pk = reinterpret_cast<G16Pk*>(p);
-    if (!pk || !w || !partials_out) {
-        set_error("ga_g16_witness_partial: null argument");
-        return GA_ERR_INVALID;
-    }
-    GA_PK_USE(pk, "ga_g16_witness_partial");
+// ---- pieces of a sharded proof (multi-GPU orchestration by the caller: gnark_amd/multigpu.py over RCCL, or g16_prove_multi_run) ----
+int g16_witness_partial_run(G16Pk* pk, const void* w, uint64_t nb_public, void* partials_out) {
+    GA_PK_USE(pk);
     SlotLease slot(pk->ctx);
     CtxLock g(pk->ctx);
     return GA_DISPATCH(Scope::FULL, pk->curve, GA_NO_GROUP, {
@@ -1461,62 +1135,30 @@ int ga_g16_witness_partial(ga_g16_pk* p, const void* w, uint64_t nb_public, void
         GA_CHECK(witness_msms<C>(pk, slot, nb_public, sh, &part, &did_k));
         part.store(partials_out);
     });
-} GA_ABI_CATCH
+}
 
-int ga_g16_h_chain(ga_g16_pk* p, const void* v, uint64_t n_constraints, void* out_dev) try {
-    GA_ABI_ENTRY();
-    G16Pk* pk = reinterpret_cast<G16Pk*>(p);
-    if (!pk || !v || !out_dev) {
-        set_error("ga_g16_h_chain: null argument");
-        return GA_ERR_INVALID;
-    }
-    GA_PK_USE(pk, "ga_g16_h_chain");
-    LaneLock g(pk->ctx);   // beside the witness MSMs of the same shard when the caller runs them from another thread
-    GA_CHECK(h_upload(pk, v, n_constraints, out_dev, pk->ctx->work_stream()));
-    GA_CHECK(GA_DISPATCH(Scope::FULL, pk->curve, GA_NO_GROUP, return ntt_domain_h_chain<C>(pk->dom, out_dev)));
-    GA_HIP_CHECK(hipStreamSynchronize(pk->ctx->work_stream()));   // the buffer is handed to another stream / device next
-    return GA_OK;
-} GA_ABI_CATCH
-
-int ga_g16_h_chain_dev(ga_g16_pk* p, void* buf_dev, uint64_t n_constraints) try {
-    GA_ABI_ENTRY();
-    G16Pk* pk = reinterpret_cast<G16Pk*>(p);
-    if (!pk || !buf_dev) {
-        set_error("ga_g16_h_chain_dev: null argument");
-        return GA_ERR_INVALID;
-    }
-    GA_PK_USE(pk, "ga_g16_h_chain_dev");
+int g16_h_chain_run(G16Pk* pk, const void* host_v, void* dev_buf, uint64_t n_constraints) {
+    GA_PK_USE(pk);
     GA_CHECK(check_nb_constraints(pk, n_constraints));
-    LaneLock g(pk->ctx);
+    LaneLock g(pk->ctx);   // beside the witness MSMs of the same shard when the caller runs them from another thread
     hipStream_t st = pk->ctx->work_stream();
-    GA_CHECK(h_pad(pk, buf_dev, n_constraints, st));
-    GA_CHECK(GA_DISPATCH(Scope::FULL, pk->curve, GA_NO_GROUP, return ntt_domain_h_chain<C>(pk->dom, buf_dev)));
-    GA_HIP_CHECK(hipStreamSynchronize(st));
+    GA_CHECK(host_v ? h_upload(pk, host_v, n_constraints, dev_buf, st) : h_pad(pk, dev_buf, n_constraints, st));
+    GA_CHECK(GA_DISPATCH(Scope::FULL, pk->curve, GA_NO_GROUP, return ntt_domain_h_chain<C>(pk->dom, dev_buf)));
+    GA_HIP_CHECK(hipStreamSynchronize(st));   // the buffer is handed to another stream / device next
     return GA_OK;
-} GA_ABI_CATCH
+}
 
-int ga_g16_h_combine(ga_g16_pk* p, void* a_dev, const void* b_dev, const void* c_dev) try {
-    GA_ABI_ENTRY();
-    G16Pk* pk = reinterpret_cast<G16Pk*>(p);
-    if (!pk || !a_dev || !b_dev || !c_dev) {
-        set_error("ga_g16_h_combine: null argument");
-        return GA_ERR_INVALID;
-    }
-    GA_PK_USE(pk, "ga_g16_h_combine");
+int g16_h_combine_run(G16Pk* pk, void* a_dev, const void* b_dev, const void* c_dev) {
+    GA_PK_USE(pk);
     LaneLock g(pk->ctx);
     GA_CHECK(GA_DISPATCH(Scope::FULL, pk->curve, GA_NO_GROUP, return ntt_domain_h_combine<C>(pk->dom, a_dev, b_dev, c_dev)));
     GA_HIP_CHECK(hipStreamSynchronize(pk->ctx->work_stream()));
     return GA_OK;
-} GA_ABI_CATCH
+}
 
-int ga_g16_z_partial(ga_g16_pk* p, const void* h_slice_dev, void* partial_out) try {
-    GA_ABI_ENTRY();
-    G16Pk* pk = reinterpret_cast<G16Pk*>(p);
-    if (!pk || (!h_slice_dev && pk->vec[GA_KEY_G1_Z].len) || !partial_out) {
-        set_error("ga_g16_z_partial: null argument");
-        return GA_ERR_INVALID;
-    }
-    GA_PK_USE(pk, "ga_g16_z_partial");
+int g16_z_partial_run(G16Pk* pk, const void* h_slice_dev, void* partial_out) {
+    if (abi_null_argument(!h_slice_dev && pk->vec[GA_KEY_G1_Z].len)) return GA_ERR_INVALID;
+    GA_PK_USE(pk);
     CtxLock g(pk->ctx);
     return GA_DISPATCH(Scope::FULL, pk->curve, GA_NO_GROUP, {
         typedef Fe<typename C::FpP> F1;
@@ -1524,36 +1166,30 @@ int ga_g16_z_partial(ga_g16_pk* p, const void* h_slice_dev, void* partial_out) t
         GA_CHECK(z_msm<C>(pk, h_slice_dev, &z));
         host_store_jac<F1>(partial_out, z);
     });
-} GA_ABI_CATCH
+}
 
-int ga_g16_prove_multi(ga_g16_pk* const* keys, uint32_t n, const void* w, const void* a, const void* b, const void* c,
-                       uint64_t n_constraints, uint64_t nb_public, const void* r, const void* s, void* proof_out) try {
-    GA_ABI_ENTRY();
-    if (!keys || n == 0 || n > 64 || !w || !a || !b || !c || !r || !s || !proof_out) {
-        set_error("ga_g16_prove_multi: null argument or unsupported device count");
-        return GA_ERR_INVALID;
-    }
-    G16Pk* const* pks = reinterpret_cast<G16Pk* const*>(keys);
+int g16_prove_multi_run(G16Pk* const* pks, uint32_t n, const void* w, const void* a, const void* b, const void* c, uint64_t n_constraints,
+                        uint64_t nb_public, const void* r, const void* s, void* proof_out) {
     for (uint32_t t = 0; t < n; t++) {
         const bool by_range = pks[t] && pks[t]->shard_count == n && pks[t]->shard_index == t && pks[t]->win_count == 1;
         const bool by_window = pks[t] && pks[t]->win_count == n && pks[t]->win_index == t && pks[t]->shard_count == 1;
         if (!pks[t] || pks[t]->curve != pks[0]->curve || pks[t]->n != pks[0]->n || pks[t]->nb_wires != pks[0]->nb_wires ||
             !(n == 1 || by_range || by_window) || (pks[t]->win_count > 1) != (pks[0]->win_count > 1)) {
-            set_error("ga_g16_prove_multi: keys[%u] must be shard %u of %u of the same proving key (all by base range or all by windows)", t, t, n);
+            set_error("%s: keys[%u] must be shard %u of %u of the same proving key (all by base range or all by windows)", current_entry(), t, t, n);
             return GA_ERR_INVALID;
         }
         for (uint32_t q = 0; q < t; q++)
             if (pks[q]->ctx == pks[t]->ctx) {
-                set_error("ga_g16_prove_multi: keys[%u] and keys[%u] share a context; one context per shard", q, t);
+                set_error("%s: keys[%u] and keys[%u] share a context; one context per shard", current_entry(), q, t);
                 return GA_ERR_INVALID;
             }
     }
-    if (n == 1) return ga_g16_prove(keys[0], w, a, b, c, n_constraints, nb_public, r, s, proof_out);
+    if (n == 1) return g16_prove_run(pks[0], w, a, b, c, n_constraints, nb_public, r, s, proof_out);
     std::vector<std::unique_ptr<PkUse>> uses;
     for (uint32_t t = 0; t < n; t++) {
         uses.emplace_back(new PkUse(pks[t]));
         if (!uses.back()->ok) {
-            set_error("ga_g16_prove_multi: keys[%u] is being destroyed", t);
+            set_error("%s: keys[%u] is being destroyed", current_entry(), t);
             return GA_ERR_STATE;
         }
     }
@@ -1573,106 +1209,16 @@ int ga_g16_prove_multi(ga_g16_pk* const* keys, uint32_t n, const void* w, const 
                 (void)hipGetLastError();
             }
     return GA_DISPATCH(Scope::FULL, pks[0]->curve, GA_NO_GROUP, return (prove_multi<C>(pks, n, w, a, b, c, n_constraints, nb_public, r, s, proof_out)));
-} GA_ABI_CATCH
-int ga_g16_commit(ga_g16_pk* p, uint32_t index, const void* values, uint64_t n_values, void* commitment_out, void* pok_out) try {
-    GA_ABI_ENTRY();
-    G16Pk* pk = reinterpret_cast<G16Pk*>(p);
-    if (!pk || (!values && n_values) || !commitment_out || !pok_out) {
-        set_error("ga_g16_commit: null argument");
-        return GA_ERR_INVALID;
-    }
-    GA_PK_USE(pk, "ga_g16_commit");
+}
+
+int g16_commit_run(G16Pk* pk, uint32_t index, const void* values, uint64_t n_values, void* commitment_out, void* pok_out) {
+    GA_PK_USE(pk);
     CtxLock g(pk->ctx);
     return GA_DISPATCH(Scope::FULL, pk->curve, GA_NO_GROUP, return commit<C>(pk, index, values, n_values, commitment_out, pok_out));
-} GA_ABI_CATCH
+}
 
-int ga_g16_fold_pok(int curve, const void* poks, uint64_t n, const void* challenge, void* out) try {
-    GA_ABI_ENTRY();
-    if ((!poks && n) || !challenge || !out) {
-        set_error("ga_g16_fold_pok: null argument");
-        return GA_ERR_INVALID;
-    }
+int g16_fold_pok_run(int curve, const void* poks, uint64_t n, const void* challenge, void* out) {
     return GA_DISPATCH(Scope::FULL, curve, GA_NO_GROUP, return fold_pok<C>(poks, n, challenge, out));
-} GA_ABI_CATCH
+}
 
-int ga_g16_prove(ga_g16_pk* p, const void* w, const void* a, const void* b, const void* c, uint64_t n_constraints,
-                 uint64_t nb_public, const void* r, const void* s, void* proof_out) try {
-    GA_ABI_ENTRY();
-    return g16_prove_impl(p, w, a, b, c, n_constraints, nb_public, r, s, proof_out);
-} GA_ABI_CATCH
-
-// `count` proofs under one key: a loop of groth16.Prove over one ProvingKey (prove.go:130-315; the reference has no batch entry
-// point) as one caller of the device -- prove_batch on lane 0 under the device lock, then the epilogues outside it (finish_batch).  A
-// ga_g16_prove arriving meanwhile finds the device busy and proves on lanes 2/3 as beside any other proof.
-int ga_g16_prove_batch(ga_g16_pk* p, uint32_t count, const void* const* w, const void* const* a, const void* const* b, const void* const* c,
-                       uint64_t n_constraints, uint64_t nb_public, const void* r, const void* s, void* proofs_out) try {
-    GA_ABI_ENTRY();
-    if (count == 0) return GA_OK;
-    G16Pk* pk = reinterpret_cast<G16Pk*>(p);
-    if (!pk || !w || !a || !b || !c || !r || !s || !proofs_out) {
-        set_error("ga_g16_prove_batch: null argument");
-        return GA_ERR_INVALID;
-    }
-    for (uint32_t j = 0; j < count; j++)
-        if (!w[j] || !a[j] || !b[j] || !c[j]) {
-            set_error("ga_g16_prove_batch: null pointer in solution %u (%s[%u])", j, !w[j] ? "w" : !a[j] ? "a" : !b[j] ? "b" : "c", j);
-            return GA_ERR_INVALID;
-        }
-    GA_PK_USE(pk, "ga_g16_prove_batch");
-    GA_CHECK(check_unsharded(pk, "ga_g16_prove_batch"));
-    GA_CHECK(check_nb_constraints(pk, n_constraints));
-    GA_CHECK(check_nb_public(pk, nb_public));
-    Ctx* ctx = pk->ctx;
-    return GA_DISPATCH(Scope::FULL, pk->curve, GA_NO_GROUP, {
-        std::vector<G16Partials<C>> parts(count);
-        {
-            std::unique_lock<std::mutex> dev(ctx->mu);
-            hipSetDevice(ctx->device);
-            ctx->tun.read_env();
-            GA_CHECK(prove_batch<C>(pk, count, w, a, b, c, n_constraints, nb_public, parts.data()));
-            // (the stage list of the profiler is guarded by the device lock)
-            if (ctx->profiling) return finish_batch<C>(pk, parts, r, s, proofs_out, /*serial=*/true);
-        }
-        return finish_batch<C>(pk, parts, r, s, proofs_out, /*serial=*/false);
-    });
-} GA_ABI_CATCH
-
-// One proof on a key that is NOT kept on the device (the Go package's default, PinToGPU = false, as icicle.go:797-805): the key
-// goes up as plain vectors WHILE the proof runs -- the uploader thread of pk_create_from_struct copies A, B, K, G2.B, Z in the order
-// the MSMs consume them, every MSM waits for its own vector only -- and is dropped afterwards.  Same proof bytes as
-// ga_g16_pk_create(precompute = -1) + ga_g16_prove + ga_g16_pk_destroy, in about the time of the longer of the two (PCIe, device)
-// instead of their sum.  No host pointer is used after the call returns (the uploader is joined before the key is freed).
-int ga_g16_prove_oneshot(ga_ctx* h, const ga_g16_key* key, const void* w, const void* a, const void* b, const void* c, uint64_t n_constraints,
-                         uint64_t nb_public, const void* r, const void* s, void* proof_out) try {
-    GA_ABI_ENTRY();
-    Ctx* ctx = reinterpret_cast<Ctx*>(h);
-    if (!ctx || !key || !w || !a || !b || !c || !r || !s || !proof_out) {
-        set_error("ga_g16_prove_oneshot: null argument");
-        return GA_ERR_INVALID;
-    }
-    trace_event("ga_g16_prove_oneshot", 0);
-    struct InFlight {   // pageable uploads of this context take turns while the key is on its way (common.hip.h)
-        Ctx* c;
-        explicit InFlight(Ctx* x) : c(x) { c->oneshot_inflight++; }
-        ~InFlight() { c->oneshot_inflight--; }
-    } inflight(ctx);
-    G16Pk* pk = nullptr;
-    {
-        CtxLock g(ctx);
-        GA_CHECK(pk_create_from_struct(ctx, key, &pk, /*defer_uploads=*/true));
-    }
-    struct Drop {   // whatever happens below, the uploader is joined and the key freed before the host vectors go out of scope
-        G16Pk* pk;
-        ~Drop() {
-            pk_destroy_impl(pk);
-            trace_event("key dropped", 0);
-        }
-    } drop{pk};
-    trace_event("key reserved, uploader started", 0);
-    const int rc = g16_prove_impl(reinterpret_cast<ga_g16_pk*>(pk), w, a, b, c, n_constraints, nb_public, r, s, proof_out);
-    trace_event("proof done", rc);
-    return rc;
-} GA_ABI_CATCH
-
-}  // extern "C"
-
+}  // namespace ga

@@ -138,10 +138,7 @@ using namespace ga;
 
 extern "C" int ga_hash_to_field(int curve, const uint8_t* msg, size_t msg_len, const uint8_t* dst, size_t dst_len, uint32_t count, void* out) try {
     GA_ABI_ENTRY();
-    if ((!msg && msg_len) || (!dst && dst_len) || !out) {
-        set_error("ga_hash_to_field: null argument");
-        return GA_ERR_INVALID;
-    }
+    if (abi_null_argument((!msg && msg_len) || (!dst && dst_len) || !out)) return GA_ERR_INVALID;
     return GA_DISPATCH(Scope::G1_FR, curve, GA_NO_GROUP, return hash_to_field<C>(msg, msg_len, dst, dst_len, count, out));
 } GA_ABI_CATCH
 

@@ -1,7 +1,8 @@
 """The call families whose single and batched entry points share one driver, and the one driver of every MSM over raw bases, under the
 functional HIP emulation: (1) GA_MSM_MAX_CHUNK reaches the prover's MSMs over plain vectors, a window share and ga_g16_commit, and the
 proof does not change; (2) a single call is the batched call with count = 1, byte for byte, from host pointers and from device
-buffers; (3) a refusal names the entry point that was called.  The correctness anchors of the singles (pyref, the C oracle) stay in
+buffers; (3) a refusal names the entry point that was called, the Groth16 entry points included (g16_abi.hip); (4) ga_g16_h_chain_dev is
+ga_g16_h_chain without the upload (one driver).  The correctness anchors of the singles (pyref, the C oracle) stay in
 test_emu_kernels.py / test_gpu_parity.py; tests/test_abi_drivers_gpu.py runs these cases on the device at its sizes."""
 import ctypes as C
 
@@ -266,3 +267,107 @@ def case_refusal_names(ctx, c=BN254, n=8):
 
 def test_refusal_names(emu_ctx):
     case_refusal_names(emu_ctx)
+
+
+def case_g16_refusal_names(ctx, c=BN254, logn=3):
+    """the Groth16 half: one refusing call per Groth16 entry point that takes a pointer or a handle -- the argument null, or n = 0
+    keys for ga_g16_prove_multi -- gives GA_ERR_INVALID under the name that was called, and the key then proves the bytes it proved
+    before.  One tiny key: nothing here depends on size."""
+    from gnark_amd import synth
+    lib, cid, h = ctx.lib, c.cid, ctx.handle
+    inst = synth.make_instance(ctx, c.name, logn, 0x6A16, want_dlogs=False)
+    pk = inst.proving_key(ctx, precompute=1)
+    k = pk.handle
+    out, n32, sz = C.c_void_p(), C.c_uint32(), C.c_size_t()
+    v = np.zeros((1 << logn, 4), np.uint64)
+    keys0 = (C.c_void_p * 1)(k)
+    N = None
+    calls = {
+        "ga_g16_pk_create": lambda: lib.ga_g16_pk_create(h, N, C.byref(out)),
+        "ga_g16_builder_create": lambda: lib.ga_g16_builder_create(N, cid, 1 << logn, 1 << logn, 0, 1, C.byref(out)),
+        "ga_g16_builder_reserve": lambda: lib.ga_g16_builder_reserve(N, 0, 1),
+        "ga_g16_builder_append": lambda: lib.ga_g16_builder_append(N, 0, _ptr(v), 1),
+        "ga_g16_builder_set_point": lambda: lib.ga_g16_builder_set_point(N, 0, _ptr(v)),
+        "ga_g16_builder_set_infinity": lambda: lib.ga_g16_builder_set_infinity(N, 0, _ptr(v), 1),
+        "ga_g16_builder_add_commitment_key": lambda: lib.ga_g16_builder_add_commitment_key(N, _ptr(v), _ptr(v), 1),
+        "ga_g16_builder_set_k_remove": lambda: lib.ga_g16_builder_set_k_remove(N, _ptr(v), 1),
+        "ga_g16_builder_set_window_shard": lambda: lib.ga_g16_builder_set_window_shard(N, 0, 1),
+        "ga_g16_builder_finish": lambda: lib.ga_g16_builder_finish(N, 0, C.byref(out)),
+        "ga_g16_shard_layout": lambda: lib.ga_g16_shard_layout(k, N),
+        "ga_g16_table_layout": lambda: lib.ga_g16_table_layout(k, N),
+        "ga_g16_pk_read_mem": lambda: lib.ga_g16_pk_read_mem(h, cid, N, 0, 0, 0, 1, N, 0, C.byref(out), N),
+        "ga_g16_pk_read_fd": lambda: lib.ga_g16_pk_read_fd(h, cid, -1, 0, 0, 1, N, 0, C.byref(out), N),
+        "ga_g16_pk_read_mem_checked": lambda: lib.ga_g16_pk_read_mem_checked(h, cid, N, 0, 0, 0, 1, N, 0, C.byref(out), N),
+        "ga_g16_pk_read_fd_checked": lambda: lib.ga_g16_pk_read_fd_checked(h, cid, -1, 0, 0, 1, N, 0, C.byref(out), N),
+        "ga_g16_key_write_fd": lambda: lib.ga_g16_key_write_fd(h, N, 0, 1, N),
+        "ga_g16_proof_unmarshal": lambda: lib.ga_g16_proof_unmarshal(cid, N, 0, _ptr(v), N, 0, C.byref(n32), N, C.byref(sz)),
+        "ga_point_unmarshal": lambda: lib.ga_point_unmarshal(cid, 0, N, 0, _ptr(v), C.byref(sz)),
+        "ga_g16_proof_marshal": lambda: lib.ga_g16_proof_marshal(cid, N, _ptr(v), v.nbytes, C.byref(sz)),
+        "ga_g16_proof_marshal_bsb22": lambda: lib.ga_g16_proof_marshal_bsb22(cid, N, N, 0, N, _ptr(v), v.nbytes, C.byref(sz)),
+        "ga_g16_proof_marshal_raw": lambda: lib.ga_g16_proof_marshal_raw(cid, N, N, 0, N, _ptr(v), v.nbytes, C.byref(sz)),
+        "ga_g1_marshal_uncompressed": lambda: lib.ga_g1_marshal_uncompressed(cid, N, _ptr(v), v.nbytes, C.byref(sz)),
+        "ga_g16_prove": lambda: lib.ga_g16_prove(k, N, _ptr(v), _ptr(v), _ptr(v), 1, inst.nb_public, _ptr(v), _ptr(v), _ptr(v)),
+        "ga_g16_prove_batch": lambda: lib.ga_g16_prove_batch(k, 1, N, N, N, N, 1, inst.nb_public, _ptr(v), _ptr(v), _ptr(v)),
+        "ga_g16_prove_oneshot": lambda: lib.ga_g16_prove_oneshot(h, N, _ptr(v), _ptr(v), _ptr(v), _ptr(v), 1, inst.nb_public, _ptr(v), _ptr(v), _ptr(v)),
+        "ga_g16_prove_partial": lambda: lib.ga_g16_prove_partial(k, N, _ptr(v), _ptr(v), _ptr(v), 1, inst.nb_public, _ptr(v)),
+        "ga_g16_finish": lambda: lib.ga_g16_finish(k, N, _ptr(v), _ptr(v), _ptr(v)),
+        "ga_g16_witness_partial": lambda: lib.ga_g16_witness_partial(k, N, inst.nb_public, _ptr(v)),
+        "ga_g16_h_chain": lambda: lib.ga_g16_h_chain(k, _ptr(v), 1, N),
+        "ga_g16_h_chain_dev": lambda: lib.ga_g16_h_chain_dev(k, N, 1),
+        "ga_g16_h_combine": lambda: lib.ga_g16_h_combine(k, N, N, N),
+        "ga_g16_z_partial": lambda: lib.ga_g16_z_partial(k, N, _ptr(v)),
+        "ga_g16_prove_multi": lambda: lib.ga_g16_prove_multi(keys0, 0, _ptr(v), _ptr(v), _ptr(v), _ptr(v), 1, inst.nb_public, _ptr(v), _ptr(v), _ptr(v)),
+        "ga_g16_commit": lambda: lib.ga_g16_commit(k, 0, N, 1, _ptr(v), _ptr(v)),
+        "ga_g16_fold_pok": lambda: lib.ga_g16_fold_pok(cid, _ptr(v), 1, N, _ptr(v)),
+        "ga_g16_lane_stats": lambda: lib.ga_g16_lane_stats(h, N),
+    }
+    try:
+        args = (pk, inst.solution, inst.nb_public, inst.r, inst.s)
+        before = groth16.Prove(*args).WriteTo()
+        for name, call in calls.items():
+            assert call() == GA_ERR_INVALID, (name, lib.ga_last_error().decode())
+            msg = lib.ga_last_error().decode()
+            assert msg.startswith(name + ":") or msg.startswith(name + " "), (name, msg)
+        assert out.value is None
+        assert groth16.Prove(*args).WriteTo() == before
+    finally:
+        pk.FreeGPUResources()
+
+
+def test_g16_refusal_names(emu_ctx):
+    case_g16_refusal_names(emu_ctx)
+
+
+# ---- 4. ga_g16_h_chain_dev is ga_g16_h_chain without the upload ------------------------------------------------------------------
+def case_h_chain_dev_is_h_chain(ctx, c, logn, short):
+    """v of n - short elements: the chain of the host vector (upload, pad, transform) and the chain of a device buffer that holds v
+    already (pad, transform) leave the same n * 32 bytes.  Both buffers start with stale non-zero bytes everywhere, so the tails are
+    what the pads wrote; n_constraints = n + 1 is refused."""
+    from gnark_amd import synth
+    n = 1 << logn
+    m = n - short
+    pk = synth.make_instance(ctx, c.name, logn, 0x6C4A, want_dlogs=False).proving_key(ctx, precompute=1)
+    v = gb._scal(ctx, c, m, 0x6C4B)
+    stale = np.full((n, 4), 0x0123456789ABCDEF, np.uint64)
+    filled = stale.copy()
+    filled[:m] = v
+    buf_a, buf_b = ctx.to_device(stale), ctx.to_device(filled)
+    try:
+        groth16.HChain(pk, v, buf_a.ptr)
+        groth16.HChainDevice(pk, buf_b.ptr, m)
+        a, b = buf_a.to_host((n, 4)), buf_b.to_host((n, 4))
+        assert np.array_equal(a, b)
+        assert not np.array_equal(a, stale)
+        assert ctx.lib.ga_g16_h_chain_dev(pk.handle, buf_b.ptr, n + 1) == GA_ERR_INVALID
+        assert "exceed the domain cardinality" in ctx.lib.ga_last_error().decode()
+        assert np.array_equal(buf_b.to_host((n, 4)), b)   # (refused before anything was written)
+    finally:
+        buf_a.free()
+        buf_b.free()
+        pk.FreeGPUResources()
+
+
+@pytest.mark.parametrize("short", [0, 3], ids=["n", "n-3"])
+@pytest.mark.parametrize("c", CURVES, ids=lambda c: c.name)
+def test_h_chain_dev_is_h_chain(emu_ctx, c, short):
+    case_h_chain_dev_is_h_chain(emu_ctx, c, 3, short)

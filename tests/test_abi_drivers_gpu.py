@@ -43,3 +43,13 @@ def test_table_run_shapes(gpu_ctx, c, group):
 
 def test_refusal_names(gpu_ctx):
     cases.case_refusal_names(gpu_ctx)
+
+
+def test_g16_refusal_names(gpu_ctx):
+    cases.case_g16_refusal_names(gpu_ctx)
+
+
+@pytest.mark.parametrize("short", [0, 3], ids=["n", "n-3"])
+@pytest.mark.parametrize("c", CURVES, ids=lambda c: c.name)
+def test_h_chain_dev_is_h_chain(gpu_ctx, c, short):
+    cases.case_h_chain_dev_is_h_chain(gpu_ctx, c, 3, short)
