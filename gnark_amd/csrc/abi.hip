@@ -37,6 +37,9 @@ typedef CtxLock Lock;
 //     GA_SPARSE_ORDER       0: the products in row order (default); 1: sorted by coefficient id (the A/B of tools/phase2_init_bench.py)
 //   ga_pairing_check
 //     GA_PAIRING_CHUNK      pairs per pass (0 = 2^18, at most 2^30; tests force a small chunk)
+//   ga_g16_pk_read_mem / _fd (and _checked), ga_g16_key_write_fd   (read in g16_abi.hip)
+//     GA_KEY_CHUNK          points per staging pass of the key reader and writer (0 = as many as the 32 MiB staging buffers hold, a
+//                           larger value is capped there; the buffers keep their size; tests force 1 and 63 .. 65)
 //   ga_plonk_verify           the knobs of the calls it is made of: GA_CHECK_NAIVE, GA_CHECK_CHUNK, GA_SPARSE_CHUNK, GA_SPARSE_SEGMENT,
 //                             GA_PAIRING_CHUNK (tests force small chunks so that a few proofs take several passes)
 //   ga_fr_sparse_matvec

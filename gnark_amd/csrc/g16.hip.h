@@ -46,9 +46,10 @@ void stage_destroy(G16Stage* st);
 
 // ---- g16_io.hip.h: key files and proof bytes ---------------------------------------------------------------------------------------
 // a key file from memory (data != null) or from fd; checked: ProvingKey.ReadFrom semantics, every kept point tested
+// key_chunk: GA_KEY_CHUNK as the entry point read it, the points per staging pass of the reader and the writer (abi.hip has the table)
 int g16_pk_read_run(Ctx* ctx, int curve, const uint8_t* data, size_t len, int fd, int32_t precompute, uint32_t shard_index, uint32_t shard_count,
-                    const uint64_t* k_remove, uint64_t len_k_remove, G16Pk** out, uint64_t* bytes_read, bool checked);
-int g16_key_write_run(Ctx* ctx, const ga_g16_key* key, int format, int fd, uint64_t* bytes_written);
+                    const uint64_t* k_remove, uint64_t len_k_remove, G16Pk** out, uint64_t* bytes_read, bool checked, uint64_t key_chunk);
+int g16_key_write_run(Ctx* ctx, const ga_g16_key* key, int format, int fd, uint64_t* bytes_written, uint64_t key_chunk);
 int g16_proof_unmarshal_run(int curve, const uint8_t* data, size_t len, void* proof_out, void* commitments_out, uint32_t max_commitments,
                             uint32_t* n_commitments, void* pok_out, size_t* consumed);
 int g16_point_unmarshal_run(int curve, int group, const uint8_t* data, size_t len, void* affine_out, size_t* consumed);

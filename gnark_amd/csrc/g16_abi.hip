@@ -105,34 +105,34 @@ int ga_g16_pk_read_mem(ga_ctx* h, int curve, const uint8_t* data, size_t len, in
                        const uint64_t* k_remove, uint64_t len_k_remove, ga_g16_pk** out, uint64_t* bytes_read) try {
     GA_ABI_ENTRY();
     if (abi_bad_argument(!data, "null data") || abi_null_argument(!h || !out || (len_k_remove && !k_remove))) return GA_ERR_INVALID;
-    return g16_pk_read_run(as_ctx(h), curve, data, len, -1, precompute, shard_index, shard_count, k_remove, len_k_remove, as_pk_out(out), bytes_read, false);
+    return g16_pk_read_run(as_ctx(h), curve, data, len, -1, precompute, shard_index, shard_count, k_remove, len_k_remove, as_pk_out(out), bytes_read, false, env_u64("GA_KEY_CHUNK", 0));
 } GA_ABI_CATCH
 
 int ga_g16_pk_read_fd(ga_ctx* h, int curve, int fd, int32_t precompute, uint32_t shard_index, uint32_t shard_count, const uint64_t* k_remove,
                       uint64_t len_k_remove, ga_g16_pk** out, uint64_t* bytes_read) try {
     GA_ABI_ENTRY();
     if (abi_bad_argument(fd < 0, "bad file descriptor") || abi_null_argument(!h || !out || (len_k_remove && !k_remove))) return GA_ERR_INVALID;
-    return g16_pk_read_run(as_ctx(h), curve, nullptr, 0, fd, precompute, shard_index, shard_count, k_remove, len_k_remove, as_pk_out(out), bytes_read, false);
+    return g16_pk_read_run(as_ctx(h), curve, nullptr, 0, fd, precompute, shard_index, shard_count, k_remove, len_k_remove, as_pk_out(out), bytes_read, false, env_u64("GA_KEY_CHUNK", 0));
 } GA_ABI_CATCH
 
 int ga_g16_pk_read_mem_checked(ga_ctx* h, int curve, const uint8_t* data, size_t len, int32_t precompute, uint32_t shard_index, uint32_t shard_count,
                                const uint64_t* k_remove, uint64_t len_k_remove, ga_g16_pk** out, uint64_t* bytes_read) try {
     GA_ABI_ENTRY();
     if (abi_bad_argument(!data, "null data") || abi_null_argument(!h || !out || (len_k_remove && !k_remove))) return GA_ERR_INVALID;
-    return g16_pk_read_run(as_ctx(h), curve, data, len, -1, precompute, shard_index, shard_count, k_remove, len_k_remove, as_pk_out(out), bytes_read, true);
+    return g16_pk_read_run(as_ctx(h), curve, data, len, -1, precompute, shard_index, shard_count, k_remove, len_k_remove, as_pk_out(out), bytes_read, true, env_u64("GA_KEY_CHUNK", 0));
 } GA_ABI_CATCH
 
 int ga_g16_pk_read_fd_checked(ga_ctx* h, int curve, int fd, int32_t precompute, uint32_t shard_index, uint32_t shard_count, const uint64_t* k_remove,
                               uint64_t len_k_remove, ga_g16_pk** out, uint64_t* bytes_read) try {
     GA_ABI_ENTRY();
     if (abi_bad_argument(fd < 0, "bad file descriptor") || abi_null_argument(!h || !out || (len_k_remove && !k_remove))) return GA_ERR_INVALID;
-    return g16_pk_read_run(as_ctx(h), curve, nullptr, 0, fd, precompute, shard_index, shard_count, k_remove, len_k_remove, as_pk_out(out), bytes_read, true);
+    return g16_pk_read_run(as_ctx(h), curve, nullptr, 0, fd, precompute, shard_index, shard_count, k_remove, len_k_remove, as_pk_out(out), bytes_read, true, env_u64("GA_KEY_CHUNK", 0));
 } GA_ABI_CATCH
 
 int ga_g16_key_write_fd(ga_ctx* h, const ga_g16_key* key, int format, int fd, uint64_t* bytes_written) try {
     GA_ABI_ENTRY();
     if (abi_bad_argument(!h || !key || fd < 0 || format < GA_KEY_FORMAT_COMPRESSED || format > GA_KEY_FORMAT_DUMP, "bad argument")) return GA_ERR_INVALID;
-    return g16_key_write_run(as_ctx(h), key, format, fd, bytes_written);
+    return g16_key_write_run(as_ctx(h), key, format, fd, bytes_written, env_u64("GA_KEY_CHUNK", 0));
 } GA_ABI_CATCH
 
 int ga_g16_proof_unmarshal(int curve, const uint8_t* data, size_t len, void* proof_out, void* commitments_out, uint32_t max_commitments,

@@ -53,7 +53,7 @@ static int decode_stream(Ctx* ctx, Staging& sg, ByteSource& src, uint64_t count,
                          uint64_t keep_cnt, const char* check_name = nullptr) {   // check_name: a checked read, and what to call the vector
     typedef typename GroupField<C, G>::F F;
     const size_t enc = compressed ? sizeof(F) : 2 * sizeof(F), psz = sizeof(Affine<F>);
-    const uint64_t per_chunk = Staging::BYTES / enc;
+    const uint64_t per_chunk = sg.per_pass(enc);
     GA_HIP_CHECK(hipMemsetAsync(sg.d_bad, 0, 4, ctx->stream));
     const int naive = check_name ? check_naive_knob() : 0;
     int k = 0, tally = 0;
@@ -157,7 +157,7 @@ static int read_dumped_vector(G16Stage* st, Staging& sg, ByteSource& src, int wh
         }
         *d_plain = plain;
     }
-    const uint64_t per_chunk = Staging::BYTES / psz;
+    const uint64_t per_chunk = sg.per_pass(psz);
     int k = 0;
     for (uint64_t done = 0; done < len; k ^= 1) {
         const uint64_t cn = len - done < per_chunk ? len - done : per_chunk;
@@ -200,7 +200,7 @@ static int read_header_point(ByteSource& src, std::vector<uint8_t>* out_image, i
     const size_t len = compressed ? sizeof(F) : 2 * sizeof(F);
     GA_CHECK(src.read(buf, len));
     Affine<F> p;
-    if (!point_decode<C, G>(buf, f.compressed, &p)) {
+    if (!point_decode<C, G>(buf, compressed, &p)) {   // (the mode of the bytes consumed: an infinity is all zeros over exactly those)
         set_error("key file: header point does not decode");
         return GA_ERR_INVALID;
     }
@@ -244,7 +244,7 @@ static bool source_is_dump(ByteSource& src) {
 
 template <class C>
 static int pk_read(Ctx* ctx, ByteSource& src, int32_t precompute, uint32_t shard_index, uint32_t shard_count, const uint64_t* k_remove,
-                   uint64_t len_k_remove, G16Pk** out, bool checked) {
+                   uint64_t len_k_remove, G16Pk** out, bool checked, uint64_t key_chunk) {
     G16Stage st;
     st.ctx = ctx;
     st.checked = checked;
@@ -253,6 +253,7 @@ static int pk_read(Ctx* ctx, ByteSource& src, int32_t precompute, uint32_t shard
     st.shard_count = shard_count ? shard_count : 1;
     GA_CHECK(check_shard_index(st.shard_index, st.shard_count));
     Staging sg;
+    sg.chunk = key_chunk;
     GA_CHECK(sg.init());
     const bool dump = source_is_dump(src);
     if (dump) {
@@ -363,7 +364,7 @@ static int write_encoded_vector(Ctx* ctx, Staging& sg, ByteSink& dst, const void
     }
     GA_CHECK(dst.u32be((uint32_t)len));
     const size_t enc = compressed ? sizeof(F) : 2 * sizeof(F), psz = sizeof(Affine<F>);
-    const uint64_t per_chunk = Staging::BYTES / psz;
+    const uint64_t per_chunk = sg.per_pass(psz);
     for (uint64_t done = 0; done < len;) {
         const uint64_t cn = len - done < per_chunk ? len - done : per_chunk;
         GA_HIP_CHECK(hipMemcpyAsync(sg.d_points, (const char*)pts + done * psz, cn * psz, hipMemcpyHostToDevice, ctx->stream));
@@ -419,11 +420,12 @@ static int write_domain(ByteSink& dst, uint64_t n) {
     return dst.write(&with_precompute, 1);
 }
 template <class C>
-static int key_write(Ctx* ctx, const ga_g16_key* key, int format, ByteSink& dst) {
+static int key_write(Ctx* ctx, const ga_g16_key* key, int format, ByteSink& dst, uint64_t key_chunk) {
     typedef Fe<typename C::FpP> F1;
     typedef Fe2<typename C::FpP> F2;
     const bool dump = format == GA_KEY_FORMAT_DUMP, compressed = format == GA_KEY_FORMAT_COMPRESSED;
     Staging sg;
+    sg.chunk = key_chunk;
     GA_CHECK(sg.init());
     if (dump) GA_CHECK(dst.u64le(0xdeadbeefull));
     GA_CHECK(write_domain<C>(dst, key->domain_cardinality));
@@ -535,23 +537,23 @@ static int marshal(const void* proof, const void* commitments, uint32_t ncom, co
 
 // ---- the drivers of the entry points (g16.hip.h) -----------------------------------------------------------------------------------
 int g16_pk_read_run(Ctx* ctx, int curve, const uint8_t* data, size_t len, int fd, int32_t precompute, uint32_t shard_index, uint32_t shard_count,
-                    const uint64_t* k_remove, uint64_t len_k_remove, G16Pk** out, uint64_t* bytes_read, bool checked) {
+                    const uint64_t* k_remove, uint64_t len_k_remove, G16Pk** out, uint64_t* bytes_read, bool checked, uint64_t key_chunk) {
     ByteSource src{data, len, 0, fd};   // (the entry point passes fd = -1 with data, data = null with a descriptor)
     CtxLock g(ctx);
     G16Pk* pk = nullptr;
-    GA_CHECK(GA_DISPATCH(Scope::FULL, curve, GA_NO_GROUP, return pk_read<C>(ctx, src, precompute, shard_index, shard_count, k_remove, len_k_remove, &pk, checked)));
+    GA_CHECK(GA_DISPATCH(Scope::FULL, curve, GA_NO_GROUP, return pk_read<C>(ctx, src, precompute, shard_index, shard_count, k_remove, len_k_remove, &pk, checked, key_chunk)));
     *out = pk;
     if (bytes_read) *bytes_read = src.consumed;
     return GA_OK;
 }
 
-int g16_key_write_run(Ctx* ctx, const ga_g16_key* key, int format, int fd, uint64_t* bytes_written) {
+int g16_key_write_run(Ctx* ctx, const ga_g16_key* key, int format, int fd, uint64_t* bytes_written, uint64_t key_chunk) {
     if (abi_bad_argument(!key_points_present(key) || (key->nb_commitments && (!key->ck_basis || !key->ck_basis_exp_sigma || !key->ck_len)),
                          "null pointer inside ga_g16_key"))
         return GA_ERR_INVALID;
     CtxLock g(ctx);
     ByteSink dst{fd};
-    GA_CHECK(GA_DISPATCH(Scope::FULL, key->curve, GA_NO_GROUP, return key_write<C>(ctx, key, format, dst)));
+    GA_CHECK(GA_DISPATCH(Scope::FULL, key->curve, GA_NO_GROUP, return key_write<C>(ctx, key, format, dst, key_chunk)));
     if (bytes_written) *bytes_written = dst.written;
     return GA_OK;
 }

@@ -164,7 +164,10 @@ GA_HD void coord_to_bytes(const Fe2<P>& v, uint8_t* out) {
     fe_to_be_bytes(v.c0, out + 4 * P::N);
 }
 
-// one point from its wire encoding; `compressed` is the mode of the stream it belongs to
+// one point from its wire encoding; `compressed` is the mode of the stream it belongs to, which fixes the length of the encoding: CB
+// bytes compressed, 2 CB raw.  Infinity has ONE encoding per mode (ZCash; gnark-crypto's ErrInvalidInfinityEncoding): the flag bits and
+// nothing else, every other bit of those bytes zero, and on BLS12-381 the flag of that mode (0xC0 compressed, 0x40 raw; BN254 has the
+// one flag 0x40 for both).  A caller that takes an infinity's length from its own flag (read_header_point) passes that length's mode.
 template <class C, int G>
 GA_HD bool point_decode(const uint8_t* b, bool compressed, Affine<typename GroupField<C, G>::F>* out) {
     typedef typename GroupField<C, G>::F F;
@@ -172,6 +175,10 @@ GA_HD bool point_decode(const uint8_t* b, bool compressed, Affine<typename Group
     PointFlags f;
     if (!point_flags<C>(b[0], &f)) return false;
     if (f.infinity) {
+        if (C::ID != GA_BN254 && f.compressed != compressed) return false;
+        uint8_t stray = b[0] & f.mask;
+        for (int i = 1; i < (compressed ? CB : 2 * CB); i++) stray |= b[i];
+        if (stray) return false;
         out->x = FieldTraits<F>::zero();
         out->y = FieldTraits<F>::zero();
         return true;
@@ -390,6 +397,12 @@ struct ByteSink {
 // two page-locked staging buffers: the file read of chunk k+1 overlaps the H2D copy (and the decode kernel) of chunk k
 struct Staging {
     static constexpr size_t BYTES = 32u << 20;
+    uint64_t chunk = 0;            // GA_KEY_CHUNK as the entry point read it: points per pass, 0 = as many as BYTES hold
+    // points of `bytes_each` bytes per staging pass: what BYTES hold, or the knob where that is less (the buffers keep their size)
+    uint64_t per_pass(size_t bytes_each) const {
+        const uint64_t fit = BYTES / bytes_each;
+        return chunk && chunk < fit ? chunk : fit;
+    }
     uint8_t* h[2] = {nullptr, nullptr};
     uint8_t* d_bytes = nullptr;    // device copy of an encoded chunk
     void* d_points = nullptr;      // decoded chunk

@@ -755,7 +755,18 @@ int ga_g16_key_write_fd(ga_ctx* ctx, const ga_g16_key* key, int format, int fd, 
  * (WriteRawTo) points.  proof_out: Ar | Bs | Krs affine (Montgomery), commitments_out: room for max_commitments G1Affine. */
 int ga_g16_proof_unmarshal(int curve, const uint8_t* data, size_t len, void* proof_out, void* commitments_out,
                            uint32_t max_commitments, uint32_t* n_commitments, void* pok_out, size_t* consumed);
-/* one G1Affine / G2Affine from its wire encoding (curve.Decoder for a single point; host arithmetic) */
+/* one G1Affine / G2Affine from its wire encoding (curve.Decoder for a single point; host arithmetic)
+ * What the decoder accepts -- here, in ga_g16_proof_unmarshal and in the key readers above, one rule:
+ *   - flag bits: BN254 00 raw, 01 infinity, 10 / 11 compressed with the smaller / larger y; BLS12-381 bit 7 compressed, bit 6 infinity,
+ *     bit 5 larger y, and 0b001, 0b011, 0b111 are malformed;
+ *   - every coordinate below p (in G2 A1 and A0 each); compressed: x^3 + b is a square, the flag picks the root ("larger" in Fp2: by A1,
+ *     by A0 only when A1 = 0); raw: y^2 = x^3 + b (stricter than an unchecked gnark read);
+ *   - infinity is its flag and nothing else: every other bit of the encoding is zero over the bytes consumed (an infinity flag followed by
+ *     anything else is GA_ERR_INVALID, as gnark-crypto's ErrInvalidInfinityEncoding); an all-zero raw point is infinity as well;
+ *   - a single point and a point of a proof take their length from their own flag (a BN254 infinity, whose flag is the same in both
+ *     modes, takes the mode of the proof's first finite point, compressed while none was seen); inside a key's vector the stream fixes
+ *     mode and stride, and a point or an infinity carrying the other mode's flag (BLS12-381: 0x40 compressed, 0xC0 raw) is refused.
+ * On GA_ERR_INVALID *consumed (and *n_commitments) are not written. */
 int ga_point_unmarshal(int curve, int group, const uint8_t* data, size_t len, void* affine_out, size_t* consumed);
 
 /* Proof.WriteTo wire format (marshal.go:33-58, no commitments): compressed Ar | Bs | Krs | u32 0 | PoK(inf).
